@@ -17,7 +17,10 @@ Started with --gpus N > 1 and no WORLD_SIZE in the environment, this script laun
 of itself as a CHILD process — decided from the arguments and the environment alone, before anything touches a GPU — and
 exits with the child's code.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure (`value`, `ms_per_step`) needs; `--full` adds,
+after the timed steps, the roofline (instrumented counting passes, committed profiler counters), the frame's sanity checks and the
+CPU baseline.  `--dump-outputs DIR` writes the frame of the last timed step to DIR/frame.npy (seeded inputs: identical from run to
+run, so two builds can be compared output for output).
 """
 import argparse
 import importlib
@@ -118,7 +121,13 @@ def main():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--bvh", default="reference", choices=["reference", "sah"])
     ap.add_argument("--spp", type=int, default=0, help="override spp (smoke runs only: the JSON then names the reduced config)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline figure does not need: the roofline "
+                         "(instrumented counting passes, committed profiler counters), the frame's sanity checks and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the frame the last timed step downloaded (float64 per-pixel sums, as rt_render returns them) "
+                         "to DIR/frame.npy")
     ap.add_argument("--gather", default="native", choices=["native", "torch"],
                     help="N > 1: the frame-end gather through the C ABI's own rt_gather_tiles_device (RCCL loaded by librt_amd; "
                          "the unique id travels over torch.distributed) or through torch.distributed.gather (RCCL behind it); "
@@ -129,6 +138,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_torchrun(args.gpus))
 
@@ -276,76 +287,16 @@ def main():
         elapsed = float(t.item())
     kernel_ms = [a.elapsed_time(b) for a, b in events]
 
-    # --- outside the timed region: work counters (instrumented kernel, reduced spp), sanity, CPU baseline ---
+    # --- outside the timed region.  A plain run stops at the headline figure (and --dump-outputs); --full adds the work
+    # counters (instrumented kernel, reduced spp), the roofline, the frame's sanity checks and the CPU baseline ---
     result = None
     if rank == 0:
-        # ALGORITHMIC work per sample (DESIGN.md "Roofline"): the events of the flat left-first walk of
-        # the reference's tree with the tight box test — counted by the instrumented kernel made to walk exactly that
-        # (it agrees with the oracle's tight-mode counters, tests/test_gpu_parity.py).  What the shipped kernel
-        # executes instead (its own trees, nearest child first, where the scene allows) is reported next to it.
-        cnt_spp = min(spp, 4)
-        scratch = torch.zeros(w * h * 3, dtype=torch.float64, device=dev)
-        cnt_params = rt.render_params(seed=RENDER_SEED, sample_end=cnt_spp)
-        executed = scene.render_device_counted(cnt_params, scratch.data_ptr(), stream.cuda_stream)
-        ref_walk = rt.DeviceScene(hs, device=local_rank, walk=rt.RT_WALK_REFERENCE_ORDER)
-        cnt = ref_walk.render_device_counted(cnt_params, scratch.data_ptr(), stream.cuda_stream)
-        del ref_walk
-        flops_ps, bytes_ps, per = algorithmic_work_per_sample(cnt)
-        executed_per = {k: v / max(1, executed["samples"]) for k, v in executed.items()}
-        samples_per_launch = w * h * spp / world
-        k_ms = sum(kernel_ms) / len(kernel_ms)
-        tflops = flops_ps * samples_per_launch / (k_ms * 1e-3) / 1e12
-        host_frame = host_frame_buf.numpy()  # what the last timed step downloaded
-        assert np.isfinite(host_frame).all() and host_frame.max() > 0.0, "rendered frame is empty or not finite"
-        assert np.array_equal(host_frame, frame.cpu().numpy()), "the timed download differs from the device frame"
-
         total_samples = float(w) * h * spp * args.steps
         value = total_samples / elapsed / 1e6
-        # HBM bytes per launch cannot be counted from inside this process: they come from the rocprofv3 PMC passes of
-        # tools/profile_round.sh (FETCH_SIZE / WRITE_SIZE, separate runs, gfx950 correction), committed per workload in
-        # profiles/hbm_traffic.json together with the tag of the build they were measured on
-        traffic, traffic_source, hbm_frac = None, "no PMC pass of this workload is committed under profiles/", None
-        traffic_parts, lane_util, valu_busy, pmc_source = None, None, None, None
-        tp = ROOT / "profiles" / "hbm_traffic.json"
-        sys.path.insert(0, str(ROOT / "tools"))
-        try:
-            from source_hash import source_hash
-            sources_now = source_hash()
-        except Exception:
-            sources_now = None
-
-        def stale(entry_hash):  # committed counters are quoted only for the kernel sources this run was built from
-            return entry_hash is None or sources_now is None or entry_hash != sources_now
-
-        if tp.exists() and world == 1 and args.spp == 0:
-            try:
-                entry = json.loads(tp.read_text()).get(args.workload)
-                if entry and stale(entry.get("source_hash")):
-                    traffic_source = (f"profiles/hbm_traffic.json holds this workload's counters for sources {entry.get('source_hash')} "
-                                      f"({entry.get('tag')}); this run is built from {sources_now}: not quoted")
-                    entry = None
-                if entry:
-                    traffic = entry.get("bytes_per_launch")  # render kernel + per-pixel summation (what the timed kernels move)
-                    traffic_parts = {k: entry[k] for k in ("render_kernel_bytes", "sum_samples_kernel_bytes") if k in entry}
-                    if traffic:  # measured bytes of one step / this run's kernel time of one step / 8 TB/s
-                        hbm_frac = round(float(traffic) / (k_ms * 1e-3) / HBM_PEAK_BYTES_PER_S, 5)
-                    traffic_source = f"profiles/hbm_traffic.json, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, build {entry.get('tag')}"
-            except Exception:
-                pass
-        # the SQ counters that explain `frac` (lanes per VALU instruction, VALU issue): the newest committed PMC summary of this workload
-        if world == 1 and args.spp == 0:
-            pmcs = sorted((ROOT / "profiles").glob(f"r[0-9][0-9]_{args.workload}_pmc.json"))
-            if pmcs:
-                try:
-                    sq = json.loads(pmcs[-1].read_text())
-                    if stale(sq.get("source_hash")):
-                        raise ValueError("counters of another build")
-                    lane_util = round(float(sq["valu_lane_utilisation"]), 4)
-                    if "valu_busy" in sq:
-                        valu_busy = round(float(sq["valu_busy"]), 4)
-                    pmc_source = f"profiles/{pmcs[-1].name}, rocprofv3 --pmc SQ passes of this command (one frame), build {sq.get('_tag', 'see file')}"
-                except Exception:
-                    pmc_source = f"profiles/{pmcs[-1].name} was measured on other kernel sources than this run's ({sources_now}): not quoted"
+        if args.dump_outputs:  # the largest workload's frame (c5) is 61.4 MB: every frame fits the dump's 64 MB whole
+            out_dir = Path(args.dump_outputs)
+            out_dir.mkdir(parents=True, exist_ok=True)
+            np.save(out_dir / "frame.npy", host_frame_buf.numpy())  # what the last timed step downloaded
         result = {
             "metric": "Msamples/sec (pixels x spp / render seconds)", "value": round(value, 3), "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -356,7 +307,74 @@ def main():
                        "parallelism": (f"tiles{world}" if world > 1 else "single") + (" [gloo rehearsal on one GPU]" if rehearsal else "")},
             "gather": gather_used,
             "timed_region": "render kernels" + (" + gather + frame reassembly" if world > 1 else "") + f" + D2H of the frame to pinned host memory ({w * h * 24 / 1e6:.1f} MB per step)",
-            "roofline": {
+        }
+        if args.full:
+            # ALGORITHMIC work per sample (DESIGN.md "Roofline"): the events of the flat left-first walk of
+            # the reference's tree with the tight box test — counted by the instrumented kernel made to walk exactly that
+            # (it agrees with the oracle's tight-mode counters, tests/test_gpu_parity.py).  What the shipped kernel
+            # executes instead (its own trees, nearest child first, where the scene allows) is reported next to it.
+            cnt_spp = min(spp, 4)
+            scratch = torch.zeros(w * h * 3, dtype=torch.float64, device=dev)
+            cnt_params = rt.render_params(seed=RENDER_SEED, sample_end=cnt_spp)
+            executed = scene.render_device_counted(cnt_params, scratch.data_ptr(), stream.cuda_stream)
+            ref_walk = rt.DeviceScene(hs, device=local_rank, walk=rt.RT_WALK_REFERENCE_ORDER)
+            cnt = ref_walk.render_device_counted(cnt_params, scratch.data_ptr(), stream.cuda_stream)
+            del ref_walk
+            flops_ps, bytes_ps, per = algorithmic_work_per_sample(cnt)
+            executed_per = {k: v / max(1, executed["samples"]) for k, v in executed.items()}
+            samples_per_launch = w * h * spp / world
+            k_ms = sum(kernel_ms) / len(kernel_ms)
+            tflops = flops_ps * samples_per_launch / (k_ms * 1e-3) / 1e12
+            host_frame = host_frame_buf.numpy()  # what the last timed step downloaded
+            assert np.isfinite(host_frame).all() and host_frame.max() > 0.0, "rendered frame is empty or not finite"
+            assert np.array_equal(host_frame, frame.cpu().numpy()), "the timed download differs from the device frame"
+
+            # HBM bytes per launch cannot be counted from inside this process: they come from the rocprofv3 PMC passes of
+            # tools/profile_round.sh (FETCH_SIZE / WRITE_SIZE, separate runs, gfx950 correction), committed per workload in
+            # profiles/hbm_traffic.json together with the tag of the build they were measured on
+            traffic, traffic_source, hbm_frac = None, "no PMC pass of this workload is committed under profiles/", None
+            traffic_parts, lane_util, valu_busy, pmc_source = None, None, None, None
+            tp = ROOT / "profiles" / "hbm_traffic.json"
+            sys.path.insert(0, str(ROOT / "tools"))
+            try:
+                from source_hash import source_hash
+                sources_now = source_hash()
+            except Exception:
+                sources_now = None
+
+            def stale(entry_hash):  # committed counters are quoted only for the kernel sources this run was built from
+                return entry_hash is None or sources_now is None or entry_hash != sources_now
+
+            if tp.exists() and world == 1 and args.spp == 0:
+                try:
+                    entry = json.loads(tp.read_text()).get(args.workload)
+                    if entry and stale(entry.get("source_hash")):
+                        traffic_source = (f"profiles/hbm_traffic.json holds this workload's counters for sources {entry.get('source_hash')} "
+                                          f"({entry.get('tag')}); this run is built from {sources_now}: not quoted")
+                        entry = None
+                    if entry:
+                        traffic = entry.get("bytes_per_launch")  # render kernel + per-pixel summation (what the timed kernels move)
+                        traffic_parts = {k: entry[k] for k in ("render_kernel_bytes", "sum_samples_kernel_bytes") if k in entry}
+                        if traffic:  # measured bytes of one step / this run's kernel time of one step / 8 TB/s
+                            hbm_frac = round(float(traffic) / (k_ms * 1e-3) / HBM_PEAK_BYTES_PER_S, 5)
+                        traffic_source = f"profiles/hbm_traffic.json, rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, build {entry.get('tag')}"
+                except Exception:
+                    pass
+            # the SQ counters that explain `frac` (lanes per VALU instruction, VALU issue): the newest committed PMC summary of this workload
+            if world == 1 and args.spp == 0:
+                pmcs = sorted((ROOT / "profiles").glob(f"r[0-9][0-9]_{args.workload}_pmc.json"))
+                if pmcs:
+                    try:
+                        sq = json.loads(pmcs[-1].read_text())
+                        if stale(sq.get("source_hash")):
+                            raise ValueError("counters of another build")
+                        lane_util = round(float(sq["valu_lane_utilisation"]), 4)
+                        if "valu_busy" in sq:
+                            valu_busy = round(float(sq["valu_busy"]), 4)
+                        pmc_source = f"profiles/{pmcs[-1].name}, rocprofv3 --pmc SQ passes of this command (one frame), build {sq.get('_tag', 'see file')}"
+                    except Exception:
+                        pmc_source = f"profiles/{pmcs[-1].name} was measured on other kernel sources than this run's ({sources_now}): not quoted"
+            result["roofline"] = {
                 "bound": "valu_f64", "achieved": round(tflops, 4), "peak": FP64_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": round(tflops / FP64_VALU_PEAK_TFLOPS, 5), "traffic": traffic, "hbm_frac": hbm_frac,
                 "traffic_parts": traffic_parts, "traffic_source": traffic_source,
@@ -371,29 +389,28 @@ def main():
                 "note": "bound: VALU issue under divergence (no MFMA: no dense contraction; not HBM: the scene is LDS / L2 "
                         "resident and `traffic` is a few per cent of 8 TB/s x kernel time); algorithmic_bytes are scene-record "
                         "bytes of the reference walk, listed for SURVEY 8(d), not an HBM figure",
-            },
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            sys.path.insert(0, str(ROOT / "tests"))
-            import oracle_lib  # the CPU restatement: timed here as the baseline, never part of the product path
-            cores = oracle_lib.default_threads()
-            # a bounded sample, about 10 s of the host's cores: the first spp of the same frame (c1: the whole workload)
-            base_spp = {"c1": 10, "c2": 64, "c3": 256, "c4": 8, "c5": 2}[args.workload]
-            base_spp = min(base_spp, spp)
-            t1 = time.perf_counter()
-            oracle_lib.render(hs, rt.render_params(seed=RENDER_SEED, sample_end=base_spp), threads=cores)
-            dt = time.perf_counter() - t1
-            # BASELINE.md's second CPU row: the same restatement with the tightened box test (flat / tight mode) — separates
-            # what the algorithmic fix buys on a CPU from what the GPU buys
-            t1 = time.perf_counter()
-            oracle_lib.render(hs, rt.render_params(seed=RENDER_SEED, sample_end=base_spp), threads=cores, aabb_mode=oracle_lib.ORC_AABB_TIGHT)
-            dt_tight = time.perf_counter() - t1
-            result["cpu_baseline"] = {
-                "value": round(w * h * base_spp / dt / 1e6, 4), "unit": "Msamples/s", "cores": cores, "kind": "port",
-                "sample": f"{w}x{h}, first {base_spp} of {spp} spp (cost is linear in spp), "
-                          f"reference-faithful mode (recursive, untightened box test), {dt:.1f} s",
-                "tight_box_test": {"value": round(w * h * base_spp / dt_tight / 1e6, 4), "unit": "Msamples/s", "cores": cores,
-                                   "sample": f"same sample, narrowing slab test (same image bit for bit), {dt_tight:.1f} s"}}
+            }
+            if world == 1 and not args.no_cpu_baseline:
+                sys.path.insert(0, str(ROOT / "tests"))
+                import oracle_lib  # the CPU restatement: timed here as the baseline, never part of the product path
+                cores = oracle_lib.default_threads()
+                # a bounded sample, about 10 s of the host's cores: the first spp of the same frame (c1: the whole workload)
+                base_spp = {"c1": 10, "c2": 64, "c3": 256, "c4": 8, "c5": 2}[args.workload]
+                base_spp = min(base_spp, spp)
+                t1 = time.perf_counter()
+                oracle_lib.render(hs, rt.render_params(seed=RENDER_SEED, sample_end=base_spp), threads=cores)
+                dt = time.perf_counter() - t1
+                # BASELINE.md's second CPU row: the same restatement with the tightened box test (flat / tight mode) — separates
+                # what the algorithmic fix buys on a CPU from what the GPU buys
+                t1 = time.perf_counter()
+                oracle_lib.render(hs, rt.render_params(seed=RENDER_SEED, sample_end=base_spp), threads=cores, aabb_mode=oracle_lib.ORC_AABB_TIGHT)
+                dt_tight = time.perf_counter() - t1
+                result["cpu_baseline"] = {
+                    "value": round(w * h * base_spp / dt / 1e6, 4), "unit": "Msamples/s", "cores": cores, "kind": "port",
+                    "sample": f"{w}x{h}, first {base_spp} of {spp} spp (cost is linear in spp), "
+                              f"reference-faithful mode (recursive, untightened box test), {dt:.1f} s",
+                    "tight_box_test": {"value": round(w * h * base_spp / dt_tight / 1e6, 4), "unit": "Msamples/s", "cores": cores,
+                                       "sample": f"same sample, narrowing slab test (same image bit for bit), {dt_tight:.1f} s"}}
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()
