@@ -349,6 +349,53 @@ int rt_resolve_rgb8_values_device(int64_t n_values, int32_t spp, const double *d
 int rt_tiles_to_frame_rgb8_device(int32_t width, int32_t height, int32_t shard_count, const uint8_t *d_gathered,
                                   uint8_t *d_frame, void *hip_stream);
 
+/* ---- adaptive sampling (opt-in; nothing above changes) --------------------------------------------------------------
+ * A path's random stream is keyed by (seed, pixel, sample) and a pixel's sum is a sequential += over its samples in order, so a
+ * pixel that stops after n samples holds, bit for bit, the sum a uniform render at spp = n gives that pixel.
+ *
+ * rt_render_pixels_device renders the samples [sample_begin, sample_end) of the listed pixels only: for each entry p of d_pixels
+ * (n_pixels entries, device memory; pixel = j * width + i) the samples are added in order onto d_sum[3 p ..] (a frame of
+ * 3 * w * h doubles; continuing its value when params->accumulate is set) and, if d_sum_sq is not NULL, each sample's c * c (the
+ * product rounded, then added) onto d_sum_sq[3 p ..] likewise.  Entries >= w * h (0xFFFFFFFF: padding) trace nothing; pixels not
+ * in the list are never written.  A pixel listed twice is the caller's error (its sums are then undefined).  Needs w * h < 2^27,
+ * shard_count 1 and out_layout RT_OUT_FRAME.  Enqueued on hip_stream.
+ *
+ * rt_render_adaptive renders every pixel from sample 0 up to max_spp = params->sample_end (camera->samples_per_pixel when that is
+ * <= 0), but stops a pixel early once its estimate has converged.  The evaluation points are n_k = min(min_spp + k * batch_spp,
+ * max_spp); at each, every still-active pixel that is converged, or has reached max_spp, gets spp = n_k and stops.  The rule, f64 in
+ * this order without FMA, for n >= 2 samples with sums S_c and squared sums Q_c:
+ *     m_c = S_c / n;  v_c = (Q_c - S_c * m_c) / (n - 1);  e2 = max(v_r, v_g, v_b) / n;  L = ((m_r + m_g) + m_b) / 3
+ *     tol = rel_threshold * L + abs_threshold;  converged <=> e2 <= tol * tol     (a non-finite S or Q never converges)
+ * Outputs: the frame's sums (each pixel's = the uniform render's at its own spp), the per-pixel spp (w * h int32), optionally the
+ * sums of squares, and the totals.  Needs sample_begin 0, accumulate 0, shard_count 1; min_spp is clipped to max_spp and must be
+ * >= 2 when max_spp >= 2.  Both forms block: the device form reads one 4-byte count of still-active pixels per batch (one
+ * synchronisation of hip_stream per batch) and returns when the last batch is done.  Resolve with rt_resolve_rgb8_spp_device. */
+typedef struct rt_adaptive_params {
+    uint32_t struct_size;   /* sizeof(rt_adaptive_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t min_spp;        /* first evaluation point (default 16) */
+    int32_t batch_spp;      /* samples between evaluation points (default 16) */
+    int32_t _pad;
+    double rel_threshold;   /* default 0.02 */
+    double abs_threshold;   /* default 1e-3 */
+} rt_adaptive_params;
+typedef struct rt_adaptive_result {
+    int64_t samples;        /* camera paths traced (= the sum of the spp map) */
+    int32_t launches;       /* evaluation points reached (render launches) */
+    int32_t converged;      /* pixels the rule stopped before max_spp */
+} rt_adaptive_result;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_adaptive_params_init_sized(rt_adaptive_params *params, uint32_t struct_size);
+int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const uint32_t *d_pixels,
+                            int32_t n_pixels, double *d_sum, double *d_sum_sq /* NULL: none */, void *hip_stream);
+int rt_render_adaptive(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const rt_adaptive_params *adaptive,
+                       double *out_rgb_sum, int32_t *out_spp, double *out_rgb_sum_sq /* NULL: none */, rt_adaptive_result *out_result);
+int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                              const rt_adaptive_params *adaptive, double *d_sum, int32_t *d_spp, double *d_sum_sq /* NULL: none */,
+                              void *hip_stream, rt_adaptive_result *out_result);
+/* color_to_rgb(sum / spp[pixel]) over a frame: a pixel with spp n gets the bytes rt_resolve_rgb8_device gives at spp = n. */
+int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8,
+                               void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

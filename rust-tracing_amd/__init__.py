@@ -187,6 +187,30 @@ def scene_options(**kw) -> "SceneCreateOptions":
     return o
 
 
+class AdaptiveParams(C.Structure):
+    """rt_adaptive_params (rt_render_adaptive)."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_spp", C.c_int32), ("batch_spp", C.c_int32), ("_pad", C.c_int32),
+                ("rel_threshold", C.c_double), ("abs_threshold", C.c_double)]
+
+
+class AdaptiveResult(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("launches", C.c_int32), ("converged", C.c_int32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def adaptive_params(**kw) -> "AdaptiveParams":
+    """rt_adaptive_params_init_sized, then the given fields (min_spp=, batch_spp=, rel_threshold=, abs_threshold=)."""
+    a = AdaptiveParams()
+    _check(amd_lib().rt_adaptive_params_init_sized(C.byref(a), C.sizeof(a)), "rt_adaptive_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(AdaptiveParams._fields_):
+            raise TypeError(f"rt_adaptive_params has no field {k}")
+        setattr(a, k, v)
+    return a
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -228,6 +252,14 @@ RT_AMD_SYMBOLS = {
     "rt_gather_tiles_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "rt_last_error": (C.c_char_p, []),
     "rt_version": (C.c_char_p, []),
+    "rt_adaptive_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_render_pixels_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_adaptive_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_resolve_rgb8_spp_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -530,6 +562,41 @@ class DeviceScene:
                "rt_render_device_counted")
         return cnt.as_dict()
 
+    def render_pixels_device(self, params: RenderParams, d_pixels_ptr: int, n_pixels: int, d_sum_ptr: int,
+                             d_sum_sq_ptr: int = 0, stream: int = 0, camera: Camera | None = None):
+        """rt_render_pixels_device: the samples of params' range for the n_pixels entries (uint32 pixel indices, device memory) onto
+        a device frame of sums (and of squared sums, if d_sum_sq_ptr is not 0)."""
+        cam = camera if camera is not None else self.host_scene.camera
+        _check(amd_lib().rt_render_pixels_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_pixels_ptr), n_pixels,
+                                                 C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr or None), C.c_void_p(stream)),
+               "rt_render_pixels_device")
+
+    def render_adaptive(self, params: RenderParams, *, min_spp=16, batch_spp=16, rel=0.02, abs=1e-3, camera: Camera | None = None):
+        """rt_render_adaptive: returns (sum (h, w, 3), spp (h, w), sum_sq (h, w, 3), result dict); the maximum spp is the
+        params' sample_end (the camera's spp when 0)."""
+        import numpy as np
+        cam = camera if camera is not None else self.host_scene.camera
+        h, w = cam.image_height, cam.image_width
+        a = adaptive_params(min_spp=min_spp, batch_spp=batch_spp, rel_threshold=rel, abs_threshold=abs)
+        total = np.zeros((h, w, 3), dtype=np.float64)
+        sq = np.zeros((h, w, 3), dtype=np.float64)
+        spp = np.zeros((h, w), dtype=np.int32)
+        res = AdaptiveResult()
+        _check(amd_lib().rt_render_adaptive(self._handle, C.byref(cam), C.byref(params), C.byref(a), C.c_void_p(total.ctypes.data),
+                                            C.c_void_p(spp.ctypes.data), C.c_void_p(sq.ctypes.data), C.byref(res)),
+               "rt_render_adaptive")
+        return total, spp, sq, res.as_dict()
+
+    def render_adaptive_device(self, params: RenderParams, adaptive: AdaptiveParams, d_sum_ptr: int, d_spp_ptr: int,
+                               d_sum_sq_ptr: int = 0, stream: int = 0, camera: Camera | None = None) -> dict:
+        """rt_render_adaptive_device: device buffers of 3 w h doubles (sums, optionally squared sums) and w h int32 (spp)."""
+        cam = camera if camera is not None else self.host_scene.camera
+        res = AdaptiveResult()
+        _check(amd_lib().rt_render_adaptive_device(self._handle, C.byref(cam), C.byref(params), C.byref(adaptive), C.c_void_p(d_sum_ptr),
+                                                   C.c_void_p(d_spp_ptr), C.c_void_p(d_sum_sq_ptr or None), C.c_void_p(stream),
+                                                   C.byref(res)), "rt_render_adaptive_device")
+        return res.as_dict()
+
     def close(self):
         if getattr(self, "_handle", None):
             amd_lib().rt_scene_destroy(self._handle)
@@ -556,6 +623,11 @@ def resolve_rgb8_device(width, height, spp, d_frame_ptr: int, d_rgb8_ptr: int, s
 def resolve_rgb8_values_device(n_values, spp, d_sum_ptr: int, d_rgb8_ptr: int, stream: int = 0):
     _check(amd_lib().rt_resolve_rgb8_values_device(n_values, spp, C.c_void_p(d_sum_ptr), C.c_void_p(d_rgb8_ptr),
                                                    C.c_void_p(stream)), "rt_resolve_rgb8_values_device")
+
+
+def resolve_rgb8_spp_device(width, height, d_sum_ptr: int, d_spp_ptr: int, d_rgb8_ptr: int, stream: int = 0):
+    _check(amd_lib().rt_resolve_rgb8_spp_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_rgb8_ptr),
+                                                C.c_void_p(stream)), "rt_resolve_rgb8_spp_device")
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

@@ -182,13 +182,26 @@ Tuning effective_tuning(const rt_scene *scene) {
 
 constexpr size_t MAX_WORKSPACES = 4; // per scene: one per stream in use; beyond that the idle ones are released
 
+// List mode (rt_render_pixels_device): the render's "local tiles" are groups of 64 entries of a pixel list, and the sums (and,
+// optionally, the sums of squares) go to the listed pixels of a frame.  Everything else — chunks, pipelining, scratch, grid — is
+// the dense render's, with n_local = the number of groups.
+struct PixelList {
+    const uint32_t *pixels;
+    int64_t n;
+    double *d_sum_sq; // or null
+};
+
 int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, double *d_out, hipStream_t stream,
-                  rt_counters *out_counters) {
+                  rt_counters *out_counters, const PixelList *list = nullptr) {
     int rc = normalise_params(camera, p);
     if (rc != RT_OK) return rc;
+    if (list && (p.shard_count != 1 || p.out_layout != RT_OUT_FRAME))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_pixels_device: a pixel list needs shard_count 1 and out_layout RT_OUT_FRAME");
+    if (list && (int64_t)camera->image_width * camera->image_height >= ((int64_t)1 << 27))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_pixels_device: a pixel list needs an image of fewer than 2^27 pixels");
     HIP_TRY(hipSetDevice(scene->device));
     const bool counted = out_counters != nullptr;
-    const int64_t n_local = tiles_local(camera->image_width, camera->image_height, p.shard_index, p.shard_count);
+    const int64_t n_local = list ? (list->n + 63) / 64 : tiles_local(camera->image_width, camera->image_height, p.shard_index, p.shard_count);
     const int64_t n_samples_total = (int64_t)p.sample_end - p.sample_begin;
     if (n_local <= 0 || n_samples_total <= 0) {
         if (out_counters) *out_counters = rt_counters{};
@@ -366,6 +379,10 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     K.tiles_x = (camera->image_width + RT_TILE_W - 1) / RT_TILE_W;
     K.inv_tiles_x = 1.0 / (double)K.tiles_x;
     K.n_local_tiles = (uint32_t)n_local;
+    if (list) {
+        K.pixel_list = list->pixels; K.n_list = (uint32_t)list->n; K.out_sq = list->d_sum_sq;
+        K.inv_width = 1.0 / (double)camera->image_width;
+    }
     K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = lds_image_bytes_for(scene, lds);
     K.lds_off_node_b = scene->lds_off_node_b;
     K.lds_off_spheres = scene->lds_off_spheres; K.lds_off_quads = scene->lds_off_quads;
@@ -430,12 +447,13 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         {
             void *args[] = {(void *)&K};
             const uint32_t kf = kernel_features_for(scene->features, lds, scene->ordered);
-            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide);
+            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, list != nullptr);
             HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, dyn_lds, s));
         }
         HIP_TRY(hipGetLastError());
         if (pipelined && k > 0) HIP_TRY(hipStreamWaitEvent(s, ws.ev_sum[h ^ 1], 0));
-        launch_sum_samples(K, sum_grid, s);
+        if (list) launch_sum_listed_samples(K, sum_grid, s);
+        else launch_sum_samples(K, sum_grid, s);
         HIP_TRY(hipGetLastError());
         if (pipelined) HIP_TRY(hipEventRecord(ws.ev_sum[h], s));
     }
@@ -463,6 +481,102 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
 } // namespace
 
 namespace rtapi {
+void adaptive_defaults(rt_adaptive_params &a) {
+    memset(&a, 0, sizeof a);
+    a.struct_size = (uint32_t)sizeof a;
+    a.min_spp = 16; a.batch_spp = 16;
+    a.rel_threshold = 0.02; a.abs_threshold = 1e-3;
+}
+
+// The adaptive parameters and the render parameters they constrain, checked before the scene handle and the device (a caller finds
+// out what is wrong without a GPU).  Fills the effective parameters, the normalised render parameters and max_spp.
+int check_adaptive(const rt_camera *camera, const rt_render_params *params, const rt_adaptive_params *adaptive, const char *who,
+                   rt_adaptive_params &a, rt_render_params &p, int32_t &max_spp) {
+    const std::string w(who);
+    if (!adaptive) return fail(RT_ERR_INVALID_ARGUMENT, w + ": adaptive is null");
+    const uint32_t size = adaptive->struct_size;
+    if (size < 8 || size > sizeof a || size % 4 != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_adaptive_params.struct_size is not one this library knows");
+    adaptive_defaults(a);
+    memcpy(&a, adaptive, size); // (an older, shorter struct: the fields it lacks keep their defaults)
+    a.struct_size = (uint32_t)sizeof a;
+    if (a.batch_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": batch_spp must be at least 1");
+    if (!(a.rel_threshold >= 0.0)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rel_threshold must be a number >= 0");
+    if (!(a.abs_threshold >= 0.0)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": abs_threshold must be a number >= 0");
+    if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, w + ": camera is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, w + ": params is null");
+    p = *params;
+    if (p.shard_count != 1 && p.shard_count > 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (adaptive sampling renders the whole frame on one device)");
+    if (p.sample_begin != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sample_begin must be 0");
+    if (p.accumulate != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": accumulate must be 0");
+    if (p.out_layout != RT_OUT_FRAME) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_layout must be RT_OUT_FRAME");
+    if (int rc = normalise_params(camera, p)) return rc;
+    if ((int64_t)camera->image_width * camera->image_height >= ((int64_t)1 << 27))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": adaptive sampling needs an image of fewer than 2^27 pixels");
+    max_spp = p.sample_end;
+    if (a.min_spp > max_spp) a.min_spp = max_spp;
+    if (max_spp >= 2 && a.min_spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": min_spp must be at least 2");
+    return RT_OK;
+}
+
+// The schedule: render the active list up to the next evaluation point, apply the rule, compact the survivors; one 4-byte read
+// of the survivor count per batch.
+int render_adaptive(rt_scene *scene, const rt_camera *camera, const rt_render_params &p, const rt_adaptive_params &a, int32_t max_spp,
+                    double *d_sum, int32_t *d_spp, double *d_sum_sq, hipStream_t stream, rt_adaptive_result *out) {
+    *out = rt_adaptive_result{};
+    HIP_TRY(hipSetDevice(scene->device));
+    const int32_t w = camera->image_width, h = camera->image_height;
+    const uint32_t n_pix = (uint32_t)w * (uint32_t)h;
+    if (max_spp <= 0) { // nothing to trace: every pixel has 0 samples
+        HIP_TRY(hipMemsetAsync(d_sum, 0, (size_t)n_pix * 3u * sizeof(double), stream));
+        if (d_sum_sq) HIP_TRY(hipMemsetAsync(d_sum_sq, 0, (size_t)n_pix * 3u * sizeof(double), stream));
+        HIP_TRY(hipMemsetAsync(d_spp, 0, (size_t)n_pix * sizeof(int32_t), stream));
+        return RT_OK;
+    }
+    const uint32_t n_list = (uint32_t)tiles_total(w, h) * 64u;
+    const uint32_t blocks = (n_list + 255u) / 256u;
+    // scratch: two lists, a ballot per wave, a count per block, the survivor count; the squared sums if the caller wants none
+    const size_t list_bytes = align16((size_t)n_list * 4u), mask_bytes = (size_t)blocks * 4u * 8u, base_bytes = align16((size_t)blocks * 4u);
+    const size_t sq_bytes = d_sum_sq ? 0u : (size_t)n_pix * 3u * sizeof(double);
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, 2u * list_bytes + mask_bytes + base_bytes + 16u + sq_bytes));
+    struct Free { char *b; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)hipFree(b); (void)hipGetLastError(); } } release{buf, stream};
+    uint32_t *list[2] = {(uint32_t *)buf, (uint32_t *)(buf + list_bytes)};
+    AdaptiveScratch x;
+    x.masks = (unsigned long long *)(buf + 2u * list_bytes);
+    x.block_base = (uint32_t *)(buf + 2u * list_bytes + mask_bytes);
+    x.count = (uint32_t *)(buf + 2u * list_bytes + mask_bytes + base_bytes);
+    double *sq = d_sum_sq ? d_sum_sq : (double *)(buf + 2u * list_bytes + mask_bytes + base_bytes + 16u);
+    launch_tile_order_list(w, h, list[0], stream);
+    HIP_TRY(hipGetLastError());
+    rt_adaptive_result r{};
+    uint32_t n_in = n_list, active = n_pix;
+    int32_t n_prev = 0;
+    for (int64_t k = 0;; ++k) {
+        const int64_t next = (int64_t)a.min_spp + k * (int64_t)a.batch_spp;
+        const int32_t n_k = next < max_spp ? (int32_t)next : max_spp;
+        rt_render_params rp = p;
+        rp.sample_begin = n_prev; rp.sample_end = n_k; rp.accumulate = n_prev > 0 ? 1 : 0;
+        const PixelList pl{list[k & 1], (int64_t)n_in, sq};
+        if (int rc = launch_render(scene, camera, rp, d_sum, stream, nullptr, &pl)) return rc;
+        r.samples += (int64_t)active * (n_k - n_prev);
+        r.launches++;
+        const bool last = n_k >= max_spp;
+        launch_adaptive_step(list[k & 1], n_in, n_pix, d_sum, sq, n_k, last ? 1 : 0, a.rel_threshold, a.abs_threshold, d_spp,
+                             list[(k + 1) & 1], x, stream);
+        HIP_TRY(hipGetLastError());
+        uint32_t survivors = 0;
+        HIP_TRY(hipMemcpyAsync(&survivors, x.count, sizeof survivors, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (!last) r.converged += (int32_t)(active - survivors);
+        active = survivors;
+        if (active == 0) break;
+        n_in = (active + 63u) & ~63u;
+        n_prev = n_k;
+    }
+    *out = r;
+    return RT_OK;
+}
+
 int resolve_scene_options(const rt_scene_options *options, rt_scene_options &opt, const char *who) {
     rt_scene_options_init(&opt);
     if (options) {
@@ -991,6 +1105,85 @@ int rt_resolve_rgb8_values_device(int64_t n_values, int32_t spp, const double *d
 int rt_resolve_rgb8_device(int32_t width, int32_t height, int32_t spp, const double *d_frame_sum, uint8_t *d_rgb8, void *hip_stream) {
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_resolve_rgb8_device: bad argument");
     return rt_resolve_rgb8_values_device((int64_t)width * height * 3, spp, d_frame_sum, d_rgb8, hip_stream);
+}
+
+
+// ---- adaptive sampling ------------------------------------------------------------------------------------------------------
+
+int rt_adaptive_params_init_sized(rt_adaptive_params *a, uint32_t struct_size) {
+    if (!a) return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive_params_init_sized: null argument");
+    if (struct_size < 8 || struct_size > sizeof(rt_adaptive_params) || struct_size % 4 != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_adaptive_params_init_sized: struct_size is not one this library knows");
+    rt_adaptive_params full;
+    adaptive_defaults(full);
+    full.struct_size = struct_size;
+    memcpy(a, &full, struct_size);
+    return RT_OK;
+}
+
+int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const uint32_t *d_pixels,
+                            int32_t n_pixels, double *d_sum, double *d_sum_sq, void *hip_stream) {
+    if (!scene || !camera || !params || !d_pixels || !d_sum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_pixels_device: null argument");
+    if (n_pixels < 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_pixels_device: n_pixels is negative");
+    if (n_pixels == 0) return RT_OK;
+    const PixelList list{d_pixels, n_pixels, d_sum_sq};
+    return launch_render(const_cast<rt_scene *>(scene), camera, *params, d_sum, (hipStream_t)hip_stream, nullptr, &list);
+}
+
+int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                              const rt_adaptive_params *adaptive, double *d_sum, int32_t *d_spp, double *d_sum_sq, void *hip_stream,
+                              rt_adaptive_result *out_result) {
+    const char *who = "rt_render_adaptive_device";
+    rt_adaptive_params a;
+    rt_render_params p;
+    int32_t max_spp = 0;
+    if (int rc = check_adaptive(camera, params, adaptive, who, a, p, max_spp)) return rc;
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_sum is null");
+    if (!d_spp) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": d_spp is null");
+    if (!out_result) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": out_result is null");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": scene is null");
+    return render_adaptive(const_cast<rt_scene *>(scene), camera, p, a, max_spp, d_sum, d_spp, d_sum_sq, (hipStream_t)hip_stream, out_result);
+}
+
+int rt_render_adaptive(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const rt_adaptive_params *adaptive,
+                       double *out_rgb_sum, int32_t *out_spp, double *out_rgb_sum_sq, rt_adaptive_result *out_result) {
+    const char *who = "rt_render_adaptive";
+    rt_adaptive_params a;
+    rt_render_params p;
+    int32_t max_spp = 0;
+    if (int rc = check_adaptive(camera, params, adaptive, who, a, p, max_spp)) return rc;
+    if (!out_rgb_sum) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": out_rgb_sum is null");
+    if (!out_spp) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": out_spp is null");
+    if (!out_result) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": out_result is null");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": scene is null");
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height;
+    const size_t sum_bytes = n_pix * 3u * sizeof(double), spp_bytes = n_pix * sizeof(int32_t);
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, 2u * sum_bytes + spp_bytes));
+    double *d_sum = (double *)buf, *d_sq = (double *)(buf + sum_bytes);
+    int32_t *d_spp = (int32_t *)(buf + 2u * sum_bytes);
+    int rc = render_adaptive(s, camera, p, a, max_spp, d_sum, d_spp, d_sq, nullptr, out_result);
+    if (rc == RT_OK) {
+        hipError_t e = hipMemcpy(out_rgb_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(out_spp, d_spp, spp_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_rgb_sum_sq) e = hipMemcpy(out_rgb_sum_sq, d_sq, sum_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    } else {
+        (void)hipDeviceSynchronize(); // (a failed batch may still be in flight on the null stream)
+    }
+    (void)hipFree(buf);
+    (void)hipGetLastError();
+    return rc;
+}
+
+int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {
+    if (!d_sum || !d_spp || !d_rgb8 || width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_resolve_rgb8_spp_device: bad argument");
+    if (int rc = select_device_of(d_rgb8, "rt_resolve_rgb8_spp_device")) return rc;
+    launch_resolve_rgb8_spp((int64_t)width * height, d_sum, d_spp, d_rgb8, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 } // extern "C"

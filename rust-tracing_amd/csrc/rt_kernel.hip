@@ -54,7 +54,7 @@ enum Terminal : uint32_t { TERM_BACKGROUND = 0, TERM_ONE = 1, TERM_ZERO = 2, TER
 // AUX: the small tables (materials, textures, frames, media, Perlin) are copied into the LDS too — for scenes whose big
 // tables do not fit there, so that a hit's material -> texture -> noise chain is not three trips to memory
 // WIDE: the ordered walk's records hold four children (rt_layout.h ONode4) instead of two
-template <bool COUNT, int LDS, int THREADS, uint32_t FEAT, bool ORDERED, bool AUX = false, bool WIDE = false>
+template <bool COUNT, int LDS, int THREADS, uint32_t FEAT, bool ORDERED, bool AUX = false, bool WIDE = false, bool LIST = false>
 __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(const KParams P) {
     constexpr bool HAS_SPHERES = (FEAT & F_SPHERES) != 0, HAS_QUADS = (FEAT & F_QUADS) != 0, HAS_FRAMES = (FEAT & F_FRAMES) != 0,
                    HAS_MEDIA = (FEAT & F_MEDIA) != 0, HAS_TEXTURES = (FEAT & F_TEXTURES) != 0;
@@ -1110,10 +1110,21 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         // n / d for n < 2^27 as trunc((n + 0.5) * (1 / d)) in f64: (n + 0.5) / d is at least 0.5 / d away from an
                         // integer, far more than the 2^-52 relative error of the product — exact, and 4 instructions, not 25
                         const uint32_t lt = (uint32_t)(((double)row + 0.5) * KP->inv_n_samples), s_rel = row - lt * KP->n_samples;
-                        const uint32_t k = lt * (uint32_t)KP->shard_count + (uint32_t)KP->shard_index;
-                        const uint32_t tile_row = (uint32_t)(((double)k + 0.5) * KP->inv_tiles_x), tile_col = k - tile_row * (uint32_t)KP->tiles_x;
-                        const int32_t i = (int32_t)tile_col * RT_TILE_W + (int32_t)(p64 & 7u);
-                        const int32_t j = (int32_t)tile_row * RT_TILE_H + (int32_t)(p64 >> 3);
+                        int32_t i, j;
+                        if constexpr (LIST) { // list mode (its own instantiations: the dense kernels keep their registers): group lt is list entries [64 lt, 64 lt + 64)
+                            const uint32_t q = lt * 64u + p64;
+                            const uint32_t e = q < KP->n_list ? KP->pixel_list[q] : 0xffffffffu;
+                            // the same exact reciprocal trick (e < w * h < 2^27); an entry outside the frame (padding) gets j = h
+                            const uint32_t er = (uint32_t)(((double)e + 0.5) * KP->inv_width);
+                            const bool in_frame = e < (uint32_t)KP->cam.image_width * (uint32_t)KP->cam.image_height;
+                            j = in_frame ? (int32_t)er : KP->cam.image_height;
+                            i = (int32_t)(e - er * (uint32_t)KP->cam.image_width);
+                        } else {
+                            const uint32_t k = lt * (uint32_t)KP->shard_count + (uint32_t)KP->shard_index;
+                            const uint32_t tile_row = (uint32_t)(((double)k + 0.5) * KP->inv_tiles_x), tile_col = k - tile_row * (uint32_t)KP->tiles_x;
+                            i = (int32_t)tile_col * RT_TILE_W + (int32_t)(p64 & 7u);
+                            j = (int32_t)tile_row * RT_TILE_H + (int32_t)(p64 >> 3);
+                        }
                         if (i < KP->cam.image_width && j < KP->cam.image_height) {
                             const uint32_t pixel = (uint32_t)j * (uint32_t)KP->cam.image_width + (uint32_t)i; // screen_pos (src/renderer.rs:32-33)
                             rng.start(KP->seed_mixed, pixel, (uint32_t)KP->sample_begin + s_rel);
@@ -1296,6 +1307,131 @@ __global__ void sum_samples_kernel(const KParams P) {
     dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
 }
 
+// sum_samples_kernel for list mode: one thread per list entry (group g, entry p of the group); a listed pixel's samples are added in
+// sample order onto out[pixel] and, when out_sq is set, their squares (each product rounded, then added: no contraction) onto
+// out_sq[pixel].  Pixels not in the list, and padding entries, are never written.
+__global__ void sum_listed_samples_kernel(const KParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t g = idx >> 6, p64 = idx & 63u;
+    if (g >= P.n_local_tiles || idx >= P.n_list) return;
+    const uint32_t e = P.pixel_list[idx];
+    if (e >= (uint32_t)P.cam.image_width * (uint32_t)P.cam.image_height) return;
+    double *dst = P.out + (size_t)e * 3u;
+    double *dsq = P.out_sq ? P.out_sq + (size_t)e * 3u : nullptr;
+    V3 acc = v3(0.0, 0.0, 0.0), sq = v3(0.0, 0.0, 0.0);
+    if (P.accumulate) {
+        acc = v3(dst[0], dst[1], dst[2]);
+        if (dsq) sq = v3(dsq[0], dsq[1], dsq[2]);
+    }
+    const double *src = P.samples + ((size_t)g * P.n_samples * 64u + p64) * 3u;
+    for (uint32_t s = 0; s < P.n_samples; ++s) {
+        const V3 c = v3(src[0], src[1], src[2]);
+        acc = acc + c;
+        sq = sq + c * c;
+        src += 64u * 3u;
+    }
+    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
+    if (dsq) { dsq[0] = sq.x; dsq[1] = sq.y; dsq[2] = sq.z; }
+}
+
+// ---- adaptive sampling (rt_render_adaptive_device) --------------------------------------------------------------
+// The first active list: every pixel in tile order (tile k's 64 entries row-major, 0xffffffff outside the frame), so that its first
+// launch has the dense render's job layout.
+__global__ void tile_order_list_kernel(int32_t w, int32_t h, int32_t tiles_x, uint32_t n, uint32_t *__restrict__ list) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const uint32_t k = idx >> 6, p64 = idx & 63u;
+    const int32_t i = (int32_t)(k % (uint32_t)tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(k / (uint32_t)tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    list[idx] = (i < w && j < h) ? (uint32_t)j * (uint32_t)w + (uint32_t)i : 0xffffffffu;
+}
+
+// One convergence step, in three passes that keep the survivors in list order:
+//   step:    the rule (rt_shared_math.h) for each active entry; a pixel that converged, or is at the last schedule point, gets spp = n;
+//            each wave's ballot of survivors is stored, and each block's survivor count (its waves' popcounts, added in LDS);
+//   scan:    one block turns the block counts into exclusive offsets, and writes the total;
+//   scatter: every survivor goes to block offset + wave offset (a scan of the block's wave popcounts in LDS) + its rank in the ballot;
+//            the tail of the new list up to a multiple of 64 is padding.
+constexpr int ADAPT_THREADS = 256, ADAPT_WAVES = ADAPT_THREADS / 64, SCAN_THREADS = 1024;
+__global__ __launch_bounds__(ADAPT_THREADS) void adaptive_step_kernel(const uint32_t *__restrict__ list_in, uint32_t n_in, uint32_t n_pixels,
+                                                                       const double *__restrict__ sum, const double *__restrict__ sum_sq, int32_t n,
+                                                                       int32_t last, double rel, double abs_t, int32_t *__restrict__ spp,
+                                                                       unsigned long long *__restrict__ masks, uint32_t *__restrict__ block_count) {
+    __shared__ uint32_t wave_count[ADAPT_WAVES];
+    const uint32_t idx = blockIdx.x * ADAPT_THREADS + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t e = idx < n_in ? list_in[idx] : 0xffffffffu;
+    bool keep = false;
+    if (e < n_pixels) {
+        const double S[3] = {sum[(size_t)e * 3u], sum[(size_t)e * 3u + 1u], sum[(size_t)e * 3u + 2u]};
+        const double Q[3] = {sum_sq[(size_t)e * 3u], sum_sq[(size_t)e * 3u + 1u], sum_sq[(size_t)e * 3u + 2u]};
+        const bool done = last || (n >= 2 && rtm::rt_adaptive_converged(S, Q, n, rel, abs_t));
+        if (done) spp[e] = n;
+        keep = !done;
+    }
+    const unsigned long long ballot = __ballot(keep ? 1 : 0);
+    if (lane == 0) {
+        masks[idx >> 6] = ballot;
+        wave_count[wave] = (uint32_t)__popcll(ballot);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < ADAPT_WAVES; ++w) t += wave_count[w];
+        block_count[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void adaptive_scan_kernel(uint32_t n_blocks, uint32_t *__restrict__ block_base, uint32_t *__restrict__ count) {
+    __shared__ uint32_t part[SCAN_THREADS];
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n_blocks; base += SCAN_THREADS) {
+        const uint32_t b = base + threadIdx.x;
+        const uint32_t v = b < n_blocks ? block_base[b] : 0u;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (uint32_t off = 1; off < SCAN_THREADS; off <<= 1) { // inclusive Hillis-Steele scan
+            const uint32_t add = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
+            __syncthreads();
+            part[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (b < n_blocks) block_base[b] = carry + part[threadIdx.x] - v;
+        carry += part[SCAN_THREADS - 1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ __launch_bounds__(ADAPT_THREADS) void adaptive_scatter_kernel(const uint32_t *__restrict__ list_in, uint32_t n_in,
+                                                                          const unsigned long long *__restrict__ masks,
+                                                                          const uint32_t *__restrict__ block_base, const uint32_t *__restrict__ count,
+                                                                          uint32_t *__restrict__ list_out) {
+    __shared__ uint32_t wave_base[ADAPT_WAVES];
+    const uint32_t idx = blockIdx.x * ADAPT_THREADS + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long ballot = masks[idx >> 6];
+    if (threadIdx.x == 0) {
+        uint32_t t = block_base[blockIdx.x];
+        for (int w = 0; w < ADAPT_WAVES; ++w) {
+            wave_base[w] = t;
+            t += (uint32_t)__popcll(masks[(size_t)blockIdx.x * ADAPT_WAVES + w]);
+        }
+    }
+    __syncthreads();
+    if (idx >= n_in) return;
+    if ((ballot >> lane) & 1ull) list_out[wave_base[wave] + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))] = list_in[idx];
+    const uint32_t total = *count, padded = (total + 63u) & ~63u;
+    if (idx >= total && idx < padded) list_out[idx] = 0xffffffffu;
+}
+
+// color_to_rgb(sum / spp[pixel]) with each pixel's own sample count: the bytes rt_resolve_rgb8_device gives at that spp
+__global__ void resolve_rgb8_spp_kernel(int64_t n_values, const double *__restrict__ sum, const int32_t *__restrict__ spp, uint8_t *__restrict__ rgb) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_values) return;
+    rgb[idx] = rtm::rt_quantise(rtm::rt_gamma_encode(sum[idx] * (1.0 / (double)spp[idx / 3])));
+}
+
 // frame-end reassembly: [shard][local tile][64][3] -> row-major frame (T = double: channel sums; uint8_t: resolved RGB8)
 template <class T>
 __global__ void tiles_to_frame_kernel(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_count, int64_t shard_stride,
@@ -1425,9 +1561,10 @@ int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered) {
     if (kernel_features == FEAT_SPHERES_QUADS_TEXTURES && !ordered) return REFERENCE_TEXTURES_THREADS;
     return kernel_features == FEAT_SPHERES_SOLID ? LDS_THREADS : LDS_THREADS_GENERAL;
 }
-const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide) {
-#define RT_PICK(L, T, F, O, A) (counted ? (const void *)path_kernel<true, L, T, F, O, A> : (const void *)path_kernel<false, L, T, F, O, A>)
-#define RT_PICK_W(L, T, F, A) (counted ? (const void *)path_kernel<true, L, T, F, true, A, true> : (const void *)path_kernel<false, L, T, F, true, A, true>)
+const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, bool list) {
+// (list mode: rt_render_pixels_device; never counted)
+#define RT_PICK(L, T, F, O, A) (list ? (const void *)path_kernel<false, L, T, F, O, A, false, true> : counted ? (const void *)path_kernel<true, L, T, F, O, A> : (const void *)path_kernel<false, L, T, F, O, A>)
+#define RT_PICK_W(L, T, F, A) (list ? (const void *)path_kernel<false, L, T, F, true, A, true, true> : counted ? (const void *)path_kernel<true, L, T, F, true, A, true> : (const void *)path_kernel<false, L, T, F, true, A, true>)
 #define RT_PICK_AUX(L, T, F) (wide ? (aux ? RT_PICK_W(L, T, F, true) : RT_PICK_W(L, T, F, false)) : (aux ? RT_PICK(L, T, F, true, true) : RT_PICK(L, T, F, true, false)))
     if (ordered) { // (AUX: the small tables in the LDS as well, wherever they fit — rt_api.cpp decides)
         if (lds == 3) {
@@ -1457,6 +1594,28 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
+void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_listed_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
+void launch_tile_order_list(int32_t w, int32_t h, uint32_t *list, hipStream_t stream) {
+    const int32_t tiles_x = (w + RT_TILE_W - 1) / RT_TILE_W, tiles_y = (h + RT_TILE_H - 1) / RT_TILE_H;
+    const uint32_t n = (uint32_t)tiles_x * (uint32_t)tiles_y * 64u;
+    hipLaunchKernelGGL(tile_order_list_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, w, h, tiles_x, n, list);
+}
+void launch_adaptive_step(const uint32_t *list_in, uint32_t n_in, uint32_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
+                          int32_t last, double rel, double abs_t, int32_t *spp, uint32_t *list_out, const AdaptiveScratch &x, hipStream_t stream) {
+    // (n_in: a multiple of 64; masks holds ADAPT_WAVES words per block, block_base one per block)
+    const uint32_t blocks = (n_in + ADAPT_THREADS - 1) / ADAPT_THREADS;
+    hipLaunchKernelGGL(adaptive_step_kernel, dim3(blocks), dim3(ADAPT_THREADS), 0, stream, list_in, n_in, n_pixels, sum, sum_sq, n, last, rel,
+                       abs_t, spp, x.masks, x.block_base);
+    hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, blocks, x.block_base, x.count);
+    hipLaunchKernelGGL(adaptive_scatter_kernel, dim3(blocks), dim3(ADAPT_THREADS), 0, stream, list_in, n_in, (const unsigned long long *)x.masks,
+                       (const uint32_t *)x.block_base, (const uint32_t *)x.count, list_out);
+}
+void launch_resolve_rgb8_spp(int64_t n_pixels, const double *sum, const int32_t *spp, uint8_t *rgb, hipStream_t stream) {
+    const int64_t n = n_pixels * 3;
+    hipLaunchKernelGGL(resolve_rgb8_spp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, sum, spp, rgb);
 }
 void launch_tiles_to_frame(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_count, int64_t shard_stride, const double *gathered,
                            double *frame, hipStream_t stream) {

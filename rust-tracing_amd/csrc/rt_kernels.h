@@ -87,6 +87,12 @@ struct KParams {
     uint32_t lds_stack_off;
     uint32_t lds_seq_off;           // the world frame's sequence, copied in by the ordered kernels (after the stacks)
     uint32_t lds_prof_off;          // COUNT kernels: per-wave profile rows (last)
+    // list mode (rt_render_pixels_device; path_kernel<..., LIST = true>): a "local tile" is a group of 64 entries of this list instead;
+    // an entry that is no pixel of the frame (0xffffffff: padding) traces nothing.  The dense instantiations never read these four.
+    const uint32_t *pixel_list;
+    uint32_t n_list;                // entries of pixel_list (the groups beyond it are padding)
+    double inv_width;               // 1 / image_width (list mode's pixel -> (i, j) decode; exact for w * h < 2^27)
+    double *out_sq;                 // list mode: per-pixel sums of the squared sample colours beside `out`, or null
 };
 
 // What a scene can contain.  A kernel instantiated without a feature has that code compiled out, which matters for
@@ -140,10 +146,23 @@ constexpr uint32_t FEAT_QUADS_FRAMES_MEDIA = F_QUADS | F_FRAMES | F_MEDIA;      
 constexpr uint32_t FEAT_SPHERES_QUADS_TEXTURES = F_SPHERES | F_QUADS | F_TEXTURES;    // two_spheres, earth, two_perlin_spheres, simple_light
 uint32_t kernel_features_for(uint32_t scene_features, int lds, bool ordered);
 int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered); // workgroup size of that instantiation
-const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide);
+const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, bool list = false);
 
 // launches of the small kernels (all asynchronous on `stream`; errors through hipGetLastError)
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream);
+void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream);
+// adaptive sampling (rt_render_adaptive_device): the list of every pixel in tile order; one convergence step over an active list
+// (spp of the pixels that leave, the survivors compacted in order into list_out, padded to a multiple of 64, their count in *count);
+// the resolve with a per-pixel sample count
+void launch_tile_order_list(int32_t w, int32_t h, uint32_t *list, hipStream_t stream);
+struct AdaptiveScratch {
+    unsigned long long *masks; // one ballot of survivors per wave of the step
+    uint32_t *block_base;      // survivors per block, then (scanned) the block's offset in list_out
+    uint32_t *count;           // survivors
+};
+void launch_adaptive_step(const uint32_t *list_in, uint32_t n_in, uint32_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
+                          int32_t last, double rel, double abs, int32_t *spp, uint32_t *list_out, const AdaptiveScratch &x, hipStream_t stream);
+void launch_resolve_rgb8_spp(int64_t n_pixels, const double *sum, const int32_t *spp, uint8_t *rgb, hipStream_t stream);
 void launch_tiles_to_frame(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_count, int64_t shard_stride, const double *gathered,
                            double *frame, hipStream_t stream);
 void launch_tiles_to_frame_rgb8(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_count, int64_t shard_stride, const uint8_t *gathered,

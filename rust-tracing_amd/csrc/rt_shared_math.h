@@ -5,6 +5,7 @@
 //   rt_exp   exponential (gamma below)
 //   rt_gamma_encode   x^(1/2.2), the output stage's linear_to_gamma (src/color.rs:3-6)
 //   rt_quantise       (256 * clamp(g, 0, 0.999)) as u8 (src/color.rs:12-19)
+//   rt_adaptive_converged   adaptive sampling's per-pixel stopping rule
 // Coefficients: FreeBSD msun e_log.c / e_exp.c (public constants of the published algorithms).
 #pragma once
 #include <stdint.h>
@@ -97,6 +98,29 @@ RT_HD uint8_t rt_quantise(double g) {
     if (g != g) return 0;
     const double c = g < 0.0 ? 0.0 : (g > 0.999 ? 0.999 : g);
     return (uint8_t)(256.0 * c);
+}
+
+// Adaptive sampling's convergence rule (include/rt_amd.h rt_render_adaptive), for a pixel with n >= 2 samples, channel sums S
+// and sums of squares Q; f64 in exactly this order, no FMA:
+//   m_c = S_c / n,  v_c = (Q_c - S_c * m_c) / (n - 1),  e2 = max(v_r, v_g, v_b) / n,  L = ((m_r + m_g) + m_b) / 3,
+//   tol = rel * L + abs,  converged <=> e2 <= tol * tol.   A non-finite S or Q (or a NaN variance) never converges.
+RT_HD bool rt_adaptive_converged(const double S[3], const double Q[3], int32_t n, double rel_threshold, double abs_threshold) {
+    for (int c = 0; c < 3; ++c)
+        if (((f2u(S[c]) >> 52) & 0x7ff) == 0x7ff || ((f2u(Q[c]) >> 52) & 0x7ff) == 0x7ff) return false;
+    const double dn = (double)n;
+    double m[3], v[3];
+    for (int c = 0; c < 3; ++c) {
+        m[c] = S[c] / dn;
+        v[c] = (Q[c] - S[c] * m[c]) / (dn - 1.0);
+        if (v[c] != v[c]) return false;
+    }
+    double vmax = v[0];
+    if (v[1] > vmax) vmax = v[1];
+    if (v[2] > vmax) vmax = v[2];
+    const double e2 = vmax / dn;
+    const double L = ((m[0] + m[1]) + m[2]) / 3.0;
+    const double tol = rel_threshold * L + abs_threshold;
+    return e2 <= tol * tol;
 }
 
 } // namespace rtm

@@ -2,7 +2,8 @@
 //   -s/--scene N, -o/--output NAME as in the reference; -l/--live is accepted and refused (no window system
 //   on a GPU node).  Added: --width/--aspect/--spp/--depth (BASELINE.json's configs change these),
 //   --seed/--scene-seed, --gpus, --earth PATH|synthetic:WxH, --bvh reference|sah, --progressive N (rewrite the PNG
-//   every N samples per pixel: what -l/--live shows in a window, written to the file instead).
+//   every N samples per pixel: what -l/--live shows in a window, written to the file instead), --adaptive REL
+//   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum).
 #include "renderer.hpp"
 #include "scenes.hpp"
 #include <chrono>
@@ -17,6 +18,7 @@ static void usage(const char *argv0) {
     fprintf(stderr,
             "Usage: %s [-s SCENE] [-o OUTPUT] [--width W] [--aspect A] [--spp N] [--depth D]\n"
             "          [--seed S] [--scene-seed S] [--gpus N] [--progressive SPP_PER_PASS] [--earth PATH|synthetic:WxH] [--bvh reference|sah]\n"
+            "          [--adaptive REL [--adaptive-abs A] [--min-spp N] [--batch-spp N]]   (one GPU; --spp is the maximum)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -48,12 +50,20 @@ int main(int argc, char **argv) {
         else if (a == "--scene-seed") scene_seed = strtoull(need("--scene-seed"), nullptr, 10);
         else if (a == "--gpus") ro.gpus = atoi(need("--gpus"));
         else if (a == "--progressive") ro.progressive_spp = atoi(need("--progressive"));
+        else if (a == "--adaptive") { ro.adaptive = true; ro.adaptive_rel = atof(need("--adaptive")); }
+        else if (a == "--adaptive-abs") ro.adaptive_abs = atof(need("--adaptive-abs"));
+        else if (a == "--min-spp") ro.min_spp = atoi(need("--min-spp"));
+        else if (a == "--batch-spp") ro.batch_spp = atoi(need("--batch-spp"));
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); usage(argv[0]); return 2; }
     }
     printf("Args: { live: %s, scene: %d, output: \"%s\" }\n", live ? "true" : "false", scene, output.c_str());
+    if (ro.adaptive && (ro.gpus > 1 || ro.progressive_spp > 0)) {
+        fprintf(stderr, "--adaptive renders on one GPU in one pass: it cannot be combined with --gpus > 1 or --progressive\n");
+        return 2;
+    }
     if (live) {
         fprintf(stderr, "live rendering needs a window system and is not available in this build\n");
         return 2;

@@ -128,11 +128,58 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
     return px;
 }
 
+// Adaptive sampling on device 0: the frame's sums and per-pixel spp stay on the device, are resolved there with each pixel's own
+// spp, and only the bytes come back.
+static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const rt_camera cam = camera.pod();
+    const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
+    rt_scene *scene = nullptr;
+    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_scene_destroy(scene); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
+    check(rt_device_malloc(0, n_pix * (int64_t)sizeof(int32_t), &d_spp));
+    check(rt_device_malloc(0, n_pix * 3, &d_rgb8));
+    rt_render_params p{};
+    p.seed = opt.seed; p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    rt_adaptive_params a;
+    check(rt_adaptive_params_init_sized(&a, sizeof a));
+    a.min_spp = opt.min_spp; a.batch_spp = opt.batch_spp; a.rel_threshold = opt.adaptive_rel; a.abs_threshold = opt.adaptive_abs;
+    rt_adaptive_result res{};
+    check(rt_render_adaptive_device(scene, &cam, &p, &a, static_cast<double *>(d_sum), static_cast<int32_t *>(d_spp), nullptr, nullptr, &res));
+    check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
+                                     static_cast<uint8_t *>(d_rgb8), nullptr));
+    std::vector<uint8_t> px((size_t)n_pix * 3u);
+    std::vector<int32_t> spp((size_t)n_pix);
+    check(rt_device_download(0, px.data(), d_rgb8, n_pix * 3, nullptr));
+    check(rt_device_download(0, spp.data(), d_spp, n_pix * (int64_t)sizeof(int32_t), nullptr));
+    cleanup();
+    int32_t lo = spp.empty() ? 0 : spp[0], hi = lo;
+    for (int32_t v : spp) { lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
+    if (!opt.quiet)
+        printf("Adaptive: mean %.2f spp, min %d, max %d, %d launches, %lld samples\n", n_pix ? (double)res.samples / (double)n_pix : 0.0, lo, hi,
+               res.launches, (long long)res.samples);
+    return px;
+}
+
 void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, const std::string &output_file_name,
             const RenderOptions &opt) {
     using clock = std::chrono::steady_clock;
     auto now = clock::now();
     const int32_t w = (int32_t)camera->image_width, h = (int32_t)camera->image_height;
+    if (opt.adaptive) {
+        const std::vector<uint8_t> px = render_adaptive_rgb8(*camera, *world, opt);
+        if (!opt.quiet) printf("Render time: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+        now = clock::now();
+        if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");
+        if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+        return;
+    }
     // progressive passes: the PNG on disk always shows the mean of the samples traced so far
     auto on_pass = [&](const std::vector<double> &partial, int done) {
         if (opt.progressive_spp <= 0 || done >= camera->samples_per_pixel) return;

@@ -21,6 +21,11 @@ struct RenderOptions {
     // counterpart of the reference's live_render (src/renderer.rs:77-137: one more sample per frame, running mean),
     // without the window.  The final image is bit-identical to a single-pass render (ranges accumulate exactly).
     int progressive_spp = 0;
+    // adaptive sampling (include/rt_amd.h rt_render_adaptive) with these thresholds; the camera's spp is the maximum.  One GPU, single pass.
+    bool adaptive = false;
+    double adaptive_rel = 0.02;
+    double adaptive_abs = 1e-3;
+    int min_spp = 16, batch_spp = 16;
 };
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
