@@ -113,6 +113,13 @@ int rt_debug_last_launch(uint32_t out[4]);
  * remainder: scheduling and the start of the next query). */
 int rt_debug_stage_profile(uint64_t out[36]);
 
+/* Profiling hook: the last rt_render_device_counted call's visits of four-child records (rt_scene_options.wide; all 0 for other
+ * walks).  out[0]: first visits of a record.  out[1 + 3 * (b - 1) + o]: revisits of a record that was set aside with b of its
+ * children still to look at (b = 1, 2, 3), by what the walk went on with: o = 0 an inner record, 1 a leaf or an instance, 2 nothing
+ * (every child culled against the interval as it had shrunk).  out[10]: entries set aside as a record with the mask of its children
+ * left; out[11]: entries set aside as the one inner child left itself (RT_WIDE_SETASIDE=1). */
+int rt_debug_visit_stats(uint64_t out[12]);
+
 /* Tuning hook: the wave scheduler's knobs (DESIGN.md "Scheduler").  A deferred stage runs once th/64 of a wave's
  * live lanes wait for it (th_new: the path-end / next-job stage); the box loop keeps running while th_box/64 of them are in
  * it; use_lds = 0 forces the

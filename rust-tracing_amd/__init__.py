@@ -273,6 +273,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_compiled_nodes": (C.c_int, [C.POINTER(SceneDesc), C.c_int32, C.POINTER(DebugNode), C.c_int64,
                                           C.POINTER(C.c_int64)]),
     "rt_debug_stage_profile": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "rt_debug_visit_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_last_launch": (C.c_int, [C.POINTER(C.c_uint32)]),
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_debug_set_traversal": (C.c_int, [C.c_int32, C.c_int32]),
@@ -387,6 +388,21 @@ def debug_stage_profile() -> dict:
                               "shade.material", "end.products", "end.newjob")):
         rounds, lanes, cycles = int(buf[3 * i]), int(buf[3 * i + 1]), int(buf[3 * i + 2])
         out[name] = {"rounds": rounds, "mean_active_lanes": lanes / rounds if rounds else 0.0, "cycles": cycles}
+    return out
+
+
+def debug_visit_stats() -> dict:
+    """rt_debug_visit_stats: the last counted render's visits of four-child records — first visits, revisits of a record set aside
+    with b = 1..3 children left by what the walk went on with (inner record / leaf or instance / nothing), and the two kinds of entry
+    set aside."""
+    buf = (C.c_uint64 * 12)()
+    _check(amd_lib().rt_debug_visit_stats(buf), "rt_debug_visit_stats")
+    out = {"first": int(buf[0])}
+    for b in (1, 2, 3):
+        for o, name in enumerate(("inner", "leaf", "none")):
+            out[f"revisit{b}.{name}"] = int(buf[1 + 3 * (b - 1) + o])
+    out["push.record"] = int(buf[10])
+    out["push.child"] = int(buf[11])
     return out
 
 

@@ -16,6 +16,7 @@ thread_local std::string g_last_error;
 thread_local uint32_t g_last_launch[4] = {0, 0, 0, 0};
 std::mutex g_stage_profile_mu;
 unsigned long long g_stage_profile[PROF_SLOTS * 3] = {0};
+unsigned long long g_visit_stats[VISIT_STATS] = {0};
 
 int fail(int status, const std::string &msg) {
     g_last_error = msg;
@@ -26,7 +27,7 @@ Tuning::Tuning() {
     auto env = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
     env("RT_TH_PRIM", forced[0]); env("RT_TH_OTHER", forced[1]); env("RT_TH_SHADE", forced[2]); env("RT_TH_BOX", forced[3]); env("RT_TH_NEW", forced[4]);
     env("RT_USE_LDS", use_lds); env("RT_REFIT", refit); env("RT_ORDERED", ordered); env("RT_JOBS_PER_GRAB", jobs_per_grab); env("RT_GRAB_TAPER", grab_taper); env("RT_DEFER", defer); env("RT_START_SHORTCUT", start_shortcut); env("RT_SEQ_LOOKAHEAD", seq_lookahead); env("RT_SLOW_MIN", slow_min); env("RT_SLOW_AGE", slow_age); env("RT_OVERLAP", overlap);
-    env("RT_WIDE", wide); env("RT_QUAD_FILTER", quad_filter); env("RT_MEDIUM_FIRST", medium_first);
+    env("RT_WIDE", wide); env("RT_WIDE_SETASIDE", wide_setaside); env("RT_QUAD_FILTER", quad_filter); env("RT_MEDIUM_FIRST", medium_first);
     if (const char *e = getenv("RT_SAH_LEAF")) ordered_options.leaf_max = (uint32_t)atoi(e);
     if (const char *e = getenv("RT_FLAT_MAX")) ordered_options.flat_max = (uint32_t)atoi(e);
     if (const char *e = getenv("RT_SAH_SPHERE")) ordered_options.cost_sphere = atof(e);
@@ -395,6 +396,14 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     K.slow_min = (uint32_t)tn.slow_min; K.slow_age = (uint32_t)tn.slow_age;
     K.o_start_stage = tn.start_shortcut ? scene->o_start_stage : 0u; K.o_start_prim = scene->o_start_prim; K.o_start_end = scene->o_start_end;
     K.o_start_rest = scene->o_start_rest; K.o_start_slot = scene->o_start_slot;
+    K.setaside_direct = tn.wide_setaside != 0 ? 1u : 0u;
+    if (scene->wide) { // the start shortcut's entry as the kernel pushes it (rt_kernel.hip W_SHIFT: 2-byte entries in the LDS kernels)
+        const uint32_t w_shift = lds != 0 ? 12u : 26u, w_full = 0xfu << w_shift;
+        if (K.setaside_direct && scene->o_start_direct != 0xffffffffu) K.o_start_rest = scene->o_start_direct | w_full;
+        else if (scene->o_start_rest != 0u) K.o_start_rest = scene->o_root | (scene->o_start_rest << w_shift);
+        // (no real entry may read as S_EXIT, all ones: a record index of all ones never exists — WIDE_MAX_LDS_RECORDS, OREF_INDEX_MASK)
+        if (K.o_start_rest == (lds != 0 ? 0xffffu : 0xffffffffu)) return fail(RT_ERR_INVALID_ARGUMENT, "start shortcut: entry reads as S_EXIT");
+    }
     K.oimage = scene->oimage.ptr; K.o_root = scene->o_root; K.oseq = scene->oseq.ptr; K.n_oseq = scene->n_oseq; K.lds_stack_off = lds_image_bytes_for(scene, lds);
     K.lds_seq_off = (uint32_t)seq_offset(scene, lds);
     K.aux_image = scene->aux_image.ptr; K.aux_bytes = scene->aux_bytes; K.lds_aux_off = (uint32_t)aux_offset(scene, lds);
@@ -469,6 +478,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         {
             std::lock_guard<std::mutex> lock(g_stage_profile_mu);
             for (uint32_t q = 0; q < PROF_SLOTS * 3u; ++q) g_stage_profile[q] = host[10 + q];
+            for (uint32_t q = 0; q < VISIT_STATS; ++q) g_visit_stats[q] = host[10 + PROF_SLOTS * 3u + q];
         }
         out_counters->samples = host[0]; out_counters->rays = host[1]; out_counters->node_visits = host[2];
         out_counters->sphere_tests = host[3]; out_counters->quad_tests = host[4]; out_counters->medium_visits = host[5];
@@ -725,11 +735,15 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
                 s->o_start_prim = ref & OREF_INDEX_MASK;
                 s->o_start_end = s->o_start_prim + ((ref >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u;
                 s->o_start_slot = slot;
-                if (s->wide) { // what is set aside: the root record with the mask of its other children
+                if (s->wide) { // what is set aside: the root record with the mask of its other children, or the one other child itself
                     uint32_t mask = 0;
                     for (uint32_t k = 0; k < 4; ++k)
                         if (k != slot && (kids[k].second >> OREF_KIND_SHIFT) != OK_EMPTY) mask |= 1u << k;
                     s->o_start_rest = mask;
+                    if (mask != 0u && (mask & (mask - 1u)) == 0u) {
+                        const uint32_t other = kids[__builtin_ctz(mask)].second;
+                        if ((other >> OREF_KIND_SHIFT) == OK_INNER) s->o_start_direct = other & OREF_INDEX_MASK;
+                    }
                 } else {
                     s->o_start_rest = kids[slot ^ 1u].second;
                 }

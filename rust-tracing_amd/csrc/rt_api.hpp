@@ -82,6 +82,7 @@ struct Tuning {
                      // (ordered_walk_pays), 2 the ordered walk wherever the scene allows it
     int jobs_per_grab = 0; // > 0: fixed grab size (RT_JOBS_PER_GRAB; tuning runs)
     int wide = -1;         // own trees with four-child records (rt_layout.h ONode4): 1 always, 0 never, -1 for scenes of 64 primitives or more (RT_WIDE)
+    int wide_setaside = 1; // four-child records: 1 = the one inner child left to look at is set aside as itself, 0 = as its record with a one-bit mask (RT_WIDE_SETASIDE)
     int quad_filter = 1;   // multi-quad leaves go through the conservative f32 filter before the exact test (RT_QUAD_FILTER; rt_scene_options.quad_filter)
     int medium_first = 1;  // a ray that starts inside a sphere-bounded medium: that medium's draw first, the tree in front of it clipped (RT_MEDIUM_FIRST)
     int overlap = 1;       // 1: a frame of several launches alternates between two scratch sets on two streams (RT_OVERLAP)
@@ -156,6 +157,7 @@ struct rt_scene {
     uint32_t aux_bytes = 0, aux_off[5] = {0, 0, 0, 0, 0};
     uint32_t o_root = 0, o_stack = 0;            // world root record; stack entries per lane
     uint32_t o_start_stage = 0, o_start_prim = 0, o_start_end = 0, o_start_rest = 0, o_start_slot = 0; // KParams::o_start_*
+    uint32_t o_start_direct = 0xffffffffu;       // wide: the root's one other child if that is an inner record (its index), else none
     rt_scene_stats stats{};
     std::mutex mu;
     std::map<hipStream_t, std::unique_ptr<rtapi::WorkspaceSlot>> workspaces; // one per stream: launches on a stream are ordered
@@ -167,4 +169,5 @@ namespace rtapi {
 // of the last counted render: per profile slot (rounds, active lanes, cycles)
 extern std::mutex g_stage_profile_mu;
 extern unsigned long long g_stage_profile[PROF_SLOTS * 3];
+extern unsigned long long g_visit_stats[VISIT_STATS]; // ... and its record visits by kind (under the same mutex)
 } // namespace rtapi

@@ -244,6 +244,14 @@ int rt_debug_stage_profile(uint64_t out[36]) {
     return RT_OK;
 }
 
+int rt_debug_visit_stats(uint64_t out[12]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_visit_stats: null argument");
+    static_assert(VISIT_STATS == 12, "rt_amd_debug.h documents 12 words");
+    std::lock_guard<std::mutex> lock(g_stage_profile_mu);
+    for (uint32_t q = 0; q < VISIT_STATS; ++q) out[q] = g_visit_stats[q];
+    return RT_OK;
+}
+
 int rt_debug_box_tests(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *out_exact_hit,
                        uint8_t *out_f32_hit, int device) {
     if (n <= 0 || !rays || !boxes || !out_exact_hit || !out_f32_hit) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_box_tests: bad argument");

@@ -156,6 +156,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     };
 
     Counts cn{};
+    uint32_t vstat[VISIT_STATS] = {}; // COUNT, wide records: visits and set-asides by kind (rt_kernels.h VISIT_STATS)
     Rng rng;
     rng.x = 0; rng.y = 0;
 
@@ -190,8 +191,9 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     constexpr uint32_t SKIP_CHILD0 = LDS != 0 ? 0x4000u : 0x40000000u, SKIP_CHILD1 = LDS != 0 ? 0x8000u : 0x80000000u,
                        NODE_INDEX = SKIP_CHILD0 - 1u;
     // wide records: an entry is a record's index and, above it, the mask of its children still to look at (all four for a record
-    // the walk comes to for the first time)
+    // the walk comes to for the first time, e.g. an inner child set aside as itself)
     constexpr uint32_t W_SHIFT = LDS != 0 ? 12u : 26u, W_INDEX = (1u << W_SHIFT) - 1u, W_FULL = WIDE ? (0xfu << W_SHIFT) : 0u;
+    static_assert(WIDE_MAX_LDS_RECORDS <= 0xfffu, "a record's own 2-byte entry (index | W_FULL) must never read as S_EXIT");
     constexpr uint32_t NODE_FRAME_EXIT = 0xffffffffu, NODE_SEQ_NEXT = 0xfffffffeu; // ST_OTHER: leave the current frame / take the next step of the world's sequence
     StackT *const stack = reinterpret_cast<StackT *>(lds_raw + P.lds_stack_off) + threadIdx.x;
     uint32_t sp = 0;
@@ -495,7 +497,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     };
     // ---- one WIDE record (rt_layout.h ONode4): four boxes at once, on with the nearest child that is hit; if others are hit too the
     // record itself is set aside with the mask of those — they are looked at again when its turn comes, against the interval as it has
-    // shrunk by then (a child missed now is missed then: it leaves the mask for good)
+    // shrunk by then (a child missed now is missed then: it leaves the mask for good) — unless the one child left is an inner record:
+    // that is set aside as itself (KParams::setaside_direct)
     auto visit_wide = [&](bool any_degenerate) { // (any_degenerate: wave-uniform, some lane's ray is — rays do not change inside the box loop)
         if constexpr (ORDERED && WIDE) {
             const uint32_t nid = node & W_INDEX;
@@ -548,8 +551,35 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             if (__uint_as_float(key[1]) == nearest) { t = 1u; ref = nd.c[1]; }
             if (__uint_as_float(key[0]) == nearest) { t = 0u; ref = nd.c[0]; }
             const uint32_t rest = hit & ~(1u << t);
+            if (COUNT) {
+                const uint32_t nb = (uint32_t)__popc(todo), went = hit == 0u ? 2u : ((ref >> OREF_KIND_SHIFT) == OK_INNER ? 0u : 1u);
+                const uint32_t slot = todo == 0xfu ? 0u : 1u + 3u * (nb - 1u) + went;
+        #pragma unroll
+                for (uint32_t k = 0; k < 10u; ++k) vstat[k] += slot == k ? 1u : 0u;
+            }
             if (rest != 0u) {
-                stack[sp * THREADS] = (StackT)(nid | (rest << W_SHIFT));
+                uint32_t entry = nid | (rest << W_SHIFT);
+                // One child left, an inner record: set aside as itself (come to later like any record, all four children to look at),
+                // not as this record again with a one-bit mask — that revisit would load and test four boxes only to pick it.  A leaf
+                // left alone keeps the record-and-mask entry: its box is tested again, against the interval as it has shrunk by then,
+                // before its primitives are.  (Same results: the closest hit does not depend on the order; and no visit more — a child
+                // whose slot box the revisit would have culled has all its own boxes inside that box, so its visit culls them all.)
+                if (P.setaside_direct != 0u) {
+                    const uint32_t k = (uint32_t)__builtin_ctz(rest); // (the child left, if it is the only one)
+                    uint32_t other;
+                    if constexpr (LDS != 0) {
+                        // its reference read again from the LDS: one load and an address, where picking one of the four in registers
+                        // costs three bit tests and three selects (the kernel is bound by VALU issue, not by the LDS)
+                        other = *reinterpret_cast<const uint32_t *>(lds_raw + 6u * P.lds_off_node_b + nid * 16u + 4u * k);
+                    } else {
+                        // (a tree of selects on bit tests, not a chain of compares of `rest` that the optimiser turns into a switch)
+                        const uint32_t lo = (rest & 1u) ? nd.c[0] : nd.c[1], hi = (rest & 4u) ? nd.c[2] : nd.c[3];
+                        other = (rest & 3u) ? lo : hi;
+                    }
+                    entry = (rest == (1u << k) && other < (1u << OREF_KIND_SHIFT)) ? (other | W_FULL) : entry;
+                }
+                if (COUNT) { vstat[10] += (entry >> W_SHIFT) == 0xfu ? 0u : 1u; vstat[11] += (entry >> W_SHIFT) == 0xfu ? 1u : 0u; }
+                stack[sp * THREADS] = (StackT)entry;
                 sp++;
             }
             o_next(hit != 0u, ref);
@@ -1187,7 +1217,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 if (P.o_start_stage != 0u) { // the root's big leaf first, its other child set aside (rt_api.cpp "start shortcut")
                     const uint32_t rest = P.o_start_rest;
                     if (WIDE ? rest != 0u : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
-                        if constexpr (WIDE) stack[0] = (StackT)((first_node & W_INDEX) | (rest << W_SHIFT)); // (rest: the mask of the root's other children)
+                        if constexpr (WIDE) stack[0] = (StackT)rest; // (rest: the entry itself, made on the host in this launch's format)
                         else stack[0] = (StackT)(rest < (1u << OREF_KIND_SHIFT) ? rest : (first_node | (P.o_start_slot ? SKIP_CHILD1 : SKIP_CHILD0)));
                         sp = 1;
                     }
@@ -1275,6 +1305,12 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
         }
         if (lane == 0) {
             for (uint32_t q = 0; q < PROF_SLOTS * 3u; ++q) atomicAdd(&P.counters[10 + q], prof[q]);
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < VISIT_STATS; ++q) {
+            unsigned long long v = vstat[q];
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+            if (lane == 0 && v) atomicAdd(&P.counters[10 + PROF_SLOTS * 3u + q], v);
         }
     }
 }

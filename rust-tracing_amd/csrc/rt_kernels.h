@@ -79,7 +79,10 @@ struct KParams {
     uint32_t o_root;
     // a query may start with the primitives of a leaf under the root instead of the root record (rt_api.cpp "start shortcut"): the stage of the
     // leaf's kind (ST_SPHERE / ST_QUAD; 0: no shortcut), its primitives [prim, end), the root's other child, which child of the root the leaf is
+    // (wide records: o_start_rest is the stack entry itself, in the launch's format — the root with the mask of its other children, or the
+    // one other child's own entry if that is an inner record (setaside_direct); 0: nothing to set aside)
     uint32_t o_start_stage, o_start_prim, o_start_end, o_start_rest, o_start_slot;
+    uint32_t setaside_direct;       // wide records: 1 = a record with one child left to look at sets that child aside itself if it is an inner record (RT_WIDE_SETASIDE)
     uint32_t inst_shortcut;         // 1: a walk that enters a frame whose tree is one leaf starts with the leaf's primitives (Instance::start_ref)
     uint32_t slow_min, slow_age;    // shade stage: lanes with a dear texture wait for this many of their kind, at most this many shade rounds
     uint32_t medium_first;          // 1: the draw of a sphere-bounded medium the ray starts inside is made before the tree in front of it is walked (path_kernel)
@@ -107,7 +110,11 @@ enum Feature : uint32_t {
 constexpr uint32_t F_ALL = 31u;
 
 constexpr uint32_t PROF_SLOTS = 12;      // COUNT kernels: profile slots per wave (6 stages + 6 parts of the shade / path-end rounds)
-constexpr uint32_t COUNTER_WORDS = 10 + PROF_SLOTS * 3; // rt_counters as 10 u64, then per profile slot: rounds, active lanes, cycles
+// COUNT kernels, wide records: visits by kind (rt_amd_debug.h rt_debug_visit_stats): [0] first visits of a record; [1 + 3 (b - 1) + o]
+// revisits of a record set aside with b children still to look at (b = 1..3), o = what the lane went on with: 0 an inner record,
+// 1 a leaf or an instance, 2 nothing (every child culled); [10] entries set aside as a record with a mask, [11] as a child's own entry
+constexpr uint32_t VISIT_STATS = 12;
+constexpr uint32_t COUNTER_WORDS = 10 + PROF_SLOTS * 3 + VISIT_STATS; // rt_counters as 10 u64, then per profile slot: rounds, active lanes, cycles, then VISIT_STATS
 // Jobs a wave reserves at a time: a multiple of 64 (one sample-row of an 8x8 tile, so the lanes a wave starts together
 // trace neighbouring pixels).  Large grabs mean few atomics; small ones a short tail (the last grab of the slowest wave
 // is all that is left running at the end): launch_render picks the size so that every wave gets at least ~32 grabs.
