@@ -102,6 +102,66 @@ int rt_debug_ordered_layout_ex(const rt_scene_desc *desc, const rt_scene_options
  * whose box a ray could enter), out[5] records on the longest chain. */
 int rt_debug_wide_layout(const rt_scene_desc *desc, const rt_scene_options *options, uint64_t out[6]);
 
+/* Test hook (no GPU needed): the four-child records a scene created from `desc` with `options` walks, as the device sees them.
+ * Set cap_records / cap_steps and the pointers (any may be null: only the counts and scalars are returned then).  wide = 0: the
+ * scene gets no four-child records under these options (n_records = 0).
+ * boxes: per record and slot the f32 box (x.lo, x.hi, y.lo, y.hi, z.lo, z.hi); refs: the four references (rt_debug_ordered's
+ * encoding; an empty slot: kind 7 and the box lo = +inf, hi = -inf).  bounds: in the same order, the f64 bound of what the slot
+ * holds — a leaf's primitives, everything below an inner record, an instance's content seen from the enclosing frame; an empty
+ * slot: (+inf, -inf).  box_extent: the B of the f32 box filter (every |plane| tested must be <= B), as scene creation computes it.
+ * step_boxes: the boxes of the world frame's sequence, which the same filter tests.
+ * global_image (256 bytes per record) and lds_image (table_bytes = 32 * n_records for each of the six plane tables X+ | X- | Y+ | Y-
+ * | Z+ | Z-, each row the four planes a ray of that sign enters the children through, then the four it leaves through; then 16
+ * bytes per record of references) are the two packed forms exactly as scene creation uploads them (the same function packs). */
+typedef struct rt_debug_wide {
+    int64_t cap_records, cap_steps;
+    int64_t n_records, n_steps;
+    uint32_t wide, table_bytes;
+    float box_extent;
+    uint32_t _pad;
+    float *boxes;          /* [n_records][4][6] */
+    uint32_t *refs;        /* [n_records][4] */
+    double *bounds;        /* [n_records][4][6] */
+    uint8_t *global_image; /* [n_records][256] */
+    uint8_t *lds_image;    /* [n_records * 208] */
+    float *step_boxes;     /* [n_steps][6] */
+} rt_debug_wide;
+int rt_debug_wide_records(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_wide *io);
+
+/* Test hook: the visit of a four-child record as the render kernels make it (rt_device_scene.h: make_ray_pair32, load_oquad,
+ * box_quad_f32 on the interval converted outward, wide_verdict with the ray's degenerate flag, wide_nearest), on n cases.
+ * Per case: rays = (origin xyz, direction xyz), the interval (tmin[i], tmax[i]), todo[i] = the mask of the slots to look at.
+ * The records come in one of two ways.
+ *   boxes != NULL: four f64 boxes per case (x.lo, x.hi, y.lo, y.hi, z.lo, z.hi; lo > hi on any axis: an empty slot) and, if
+ *   refs != NULL, their four references (an empty slot always gets the empty one; refs == NULL: a sphere leaf).  The boxes are
+ *   rounded outward as the scene compiler rounds them and packed by the function scene creation packs with.
+ *   boxes == NULL: records already packed, as rt_debug_wide_records returns them (global_image, lds_image, n_records), and
+ *   record[i] = the record case i visits.
+ * extent: the filter's B; 0: per case, the largest |coordinate| of the case's own f32 boxes.  lds = 0: load_oquad reads the
+ * 256-byte records from global memory; otherwise the plane and reference tables, staged into the LDS a batch of records at a time.
+ * Out, per case: enter / leave = box_quad_f32's distances; hit = the mask of the slots entered; chosen = the slot the walk goes
+ * on with (-1: none); degenerate = the ray's flag; exact = per slot, whether the exact f64 slab test (box_miss_f64) enters the f64
+ * box (packed records: the f32 planes widened).  tests/test_gpu_wide_visit.py holds these against a numpy reference. */
+typedef struct rt_debug_wide_cases {
+    int64_t n;
+    const double *rays;          /* [n][6] */
+    const double *tmin, *tmax;   /* [n] */
+    const uint8_t *todo;         /* [n] */
+    const double *boxes;         /* [n][4][6] or NULL */
+    const uint32_t *refs;        /* [n][4] or NULL */
+    const uint8_t *global_image, *lds_image; /* packed records (boxes == NULL) */
+    int64_t n_records;
+    const uint32_t *record;      /* [n] */
+    float extent;
+    int32_t lds;
+    float *enter, *leave;        /* [n][4] */
+    uint8_t *hit;                /* [n] */
+    int8_t *chosen;              /* [n] */
+    uint8_t *degenerate;         /* [n] */
+    uint8_t *exact;              /* [n] */
+} rt_debug_wide_cases;
+int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device);
+
 /* How the calling thread's last render was launched: out[0] = 0 (reserved), out[1] = LDS level, out[2] = workgroup threads,
  * out[3] = workgroups. */
 int rt_debug_last_launch(uint32_t out[4]);

@@ -276,6 +276,8 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_visit_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_last_launch": (C.c_int, [C.POINTER(C.c_uint32)]),
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "rt_debug_wide_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_debug_wide_visits": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_set_traversal": (C.c_int, [C.c_int32, C.c_int32]),
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_debug_ordered_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -370,6 +372,73 @@ def debug_wide_layout(host_scene, **option_fields) -> dict:
     opts = scene_options(**option_fields) if option_fields else None
     _check(amd_lib().rt_debug_wide_layout(C.addressof(host_scene.desc), C.addressof(opts) if opts is not None else None, buf), "rt_debug_wide_layout")
     return dict(zip(("records", "found", "primitives", "stack_entries", "violations", "deepest"), (int(x) for x in buf)))
+
+
+class DebugWide(C.Structure):
+    _fields_ = [("cap_records", C.c_int64), ("cap_steps", C.c_int64), ("n_records", C.c_int64), ("n_steps", C.c_int64),
+                ("wide", C.c_uint32), ("table_bytes", C.c_uint32), ("box_extent", C.c_float), ("_pad", C.c_uint32),
+                ("boxes", C.c_void_p), ("refs", C.c_void_p), ("bounds", C.c_void_p), ("global_image", C.c_void_p),
+                ("lds_image", C.c_void_p), ("step_boxes", C.c_void_p)]
+
+
+class DebugWideCases(C.Structure):
+    _fields_ = [("n", C.c_int64), ("rays", C.c_void_p), ("tmin", C.c_void_p), ("tmax", C.c_void_p), ("todo", C.c_void_p),
+                ("boxes", C.c_void_p), ("refs", C.c_void_p), ("global_image", C.c_void_p), ("lds_image", C.c_void_p),
+                ("n_records", C.c_int64), ("record", C.c_void_p), ("extent", C.c_float), ("lds", C.c_int32),
+                ("enter", C.c_void_p), ("leave", C.c_void_p), ("hit", C.c_void_p), ("chosen", C.c_void_p),
+                ("degenerate", C.c_void_p), ("exact", C.c_void_p)]
+
+
+def debug_wide_records(host_scene, **option_fields) -> dict:
+    """rt_debug_wide_records: the four-child records of the scene as the device sees them (numpy arrays; CPU only).  boxes (n, 4, 3, 2)
+    f32 and bounds (n, 4, 3, 2) f64 = [record, slot, axis, lo / hi]; refs (n, 4); the two packed images as bytes; the sequence's boxes."""
+    import numpy as np
+    io = DebugWide()
+    opts = scene_options(**option_fields) if option_fields else None
+    call = lambda: amd_lib().rt_debug_wide_records(C.addressof(host_scene.desc), C.addressof(opts) if opts is not None else None, C.addressof(io))
+    _check(call(), "rt_debug_wide_records")
+    n, ns = int(io.n_records), int(io.n_steps)
+    boxes = np.zeros((max(n, 1), 4, 3, 2), dtype=np.float32); refs = np.zeros((max(n, 1), 4), dtype=np.uint32)
+    bounds = np.zeros((max(n, 1), 4, 3, 2)); glob = np.zeros((max(n, 1), 256), dtype=np.uint8); lds = np.zeros(max(n, 1) * 208, dtype=np.uint8)
+    steps = np.zeros((max(ns, 1), 3, 2), dtype=np.float32)
+    io.cap_records, io.cap_steps = max(n, 1), max(ns, 1)
+    io.boxes, io.refs, io.bounds, io.global_image, io.lds_image, io.step_boxes = (a.ctypes.data for a in (boxes, refs, bounds, glob, lds, steps))
+    _check(call(), "rt_debug_wide_records")
+    assert (int(io.n_records), int(io.n_steps)) == (n, ns)
+    return {"wide": bool(io.wide), "box_extent": float(io.box_extent), "table_bytes": int(io.table_bytes), "boxes": boxes[:n], "refs": refs[:n],
+            "bounds": bounds[:n], "global_image": glob[:n], "lds_image": lds[:n * 208], "step_boxes": steps[:ns]}
+
+
+def debug_wide_visits(rays, tmin, tmax, todo, boxes=None, refs=None, records=None, record=None, extent=0.0, lds=0, device=0) -> dict:
+    """rt_debug_wide_visits: one visit of a four-child record per case, as the render kernels make it.  Either boxes (n, 4, 3, 2) f64
+    (+ refs (n, 4)), or records = what debug_wide_records returned and record (n,) = the record each case visits.  Returns enter,
+    leave (n, 4) f32; hit, exact (n, 4) bool; chosen (n,) int8 (-1: none); degenerate (n,) bool."""
+    import numpy as np
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    n = rays.shape[0]
+    tmin = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, dtype=np.float64), (n,)))
+    tmax = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float64), (n,)))
+    todo = np.ascontiguousarray(np.broadcast_to(np.asarray(todo, dtype=np.uint8), (n,)))
+    io = DebugWideCases(n=n, rays=rays.ctypes.data, tmin=tmin.ctypes.data, tmax=tmax.ctypes.data, todo=todo.ctypes.data, extent=extent, lds=lds)
+    keep = []
+    if boxes is not None:
+        boxes = np.ascontiguousarray(boxes, dtype=np.float64).reshape(n, 24)
+        io.boxes = boxes.ctypes.data
+        if refs is not None:
+            refs = np.ascontiguousarray(refs, dtype=np.uint32).reshape(n, 4)
+            io.refs = refs.ctypes.data
+    else:
+        glob = np.ascontiguousarray(records["global_image"], dtype=np.uint8); ldsi = np.ascontiguousarray(records["lds_image"], dtype=np.uint8)
+        record = np.ascontiguousarray(record, dtype=np.uint32).reshape(n)
+        assert ldsi.size == glob.shape[0] * 208
+        io.global_image, io.lds_image, io.n_records, io.record = glob.ctypes.data, ldsi.ctypes.data, glob.shape[0], record.ctypes.data
+        keep += [glob, ldsi]
+    enter = np.zeros((n, 4), dtype=np.float32); leave = np.zeros((n, 4), dtype=np.float32)
+    hit = np.zeros(n, dtype=np.uint8); chosen = np.zeros(n, dtype=np.int8); deg = np.zeros(n, dtype=np.uint8); exact = np.zeros(n, dtype=np.uint8)
+    io.enter, io.leave, io.hit, io.chosen, io.degenerate, io.exact = (a.ctypes.data for a in (enter, leave, hit, chosen, deg, exact))
+    _check(amd_lib().rt_debug_wide_visits(C.addressof(io), device), "rt_debug_wide_visits")
+    bits = lambda m: ((m[:, None] >> np.arange(4, dtype=np.uint8)) & 1).astype(bool)
+    return {"enter": enter, "leave": leave, "hit": bits(hit), "chosen": chosen, "degenerate": deg.astype(bool), "exact": bits(exact)}
 
 
 def debug_last_launch() -> dict:

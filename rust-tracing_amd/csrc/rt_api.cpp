@@ -600,6 +600,79 @@ int resolve_scene_options(const rt_scene_options *options, rt_scene_options &opt
     if (opt.walk < RT_WALK_DEFAULT || opt.walk > RT_WALK_OWN_TREES) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown walk");
     return RT_OK;
 }
+// Which walk for this scene?  Measured on MI355X at the in-code cameras (tools/scene_speed.py, profiles/r02_scene_speed.txt), own trees
+// vs reference order, Msamples/s: random_balls 4416 / 2128, two_spheres 8739 / 7281, earth 22557 / 22523 (one primitive: a tree and a
+// stack are pure overhead), two_perlin_spheres 4821 / 3288, quads 12860 / 12612, simple_light 5845 / 4894, cornell_box 3224 / 2102,
+// cornell_smoke 1261 / 966 (a tie until its frames' primitives went into flat leaves, rt_ordered.hpp flat_max), final_scene 983 / 643.
+static bool ordered_walk_pays(const CompiledScene &cs) {
+    return cs.spheres.size() + cs.quads.size() > 1;
+}
+
+// The scene as rt_scene_create_ex compiles it under `opt` (already resolved) and the process defaults in force now (RT_* variables,
+// rt_debug_set_*): which walk, which boxes, which records.  Shared with rt_debug_wide_records, so that the hook shows what a scene gets.
+int compile_for_scene(const rt_scene_desc &desc, const rt_scene_options &opt, CompiledScene &cs, const char *who) {
+    const Tuning tn = tuning_snapshot();
+    const int walk = opt.walk != RT_WALK_DEFAULT ? opt.walk : tn.ordered;
+    const bool refit = opt.refit >= 0 ? opt.refit != 0 : tn.refit != 0;
+    OrderedOptions oopt = tn.ordered_options;
+    if (opt.leaf_max > 0) oopt.leaf_max = (uint32_t)opt.leaf_max < OREF_MAX_LEAF ? (uint32_t)opt.leaf_max : OREF_MAX_LEAF;
+    if (opt.flat_max >= 0) oopt.flat_max = (uint32_t)opt.flat_max;
+    const int want_wide = opt.wide >= 0 ? opt.wide : tn.wide; // (-1: where it measured faster, below)
+    try {
+        cs = compile_scene(desc, refit);
+        // Four children per record where the trees are big enough for the halved number of visits to pay for the dearer visit
+        // (MI355X, Msamples/s two / four children: random-spheres 5428 / 5437, final_scene 1049 / 1088; Cornell's 4 records: 2438 / 2345)
+        oopt.wide = want_wide >= 0 ? want_wide != 0 : cs.spheres.size() + cs.quads.size() >= 64;
+        if (walk == RT_WALK_OWN_TREES || (walk == RT_WALK_AUTO && ordered_walk_pays(cs))) build_ordered(cs, oopt);
+    } catch (const CompileError &e) {
+        return fail(e.status, e.what());
+    } catch (const std::exception &e) {
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e.what());
+    }
+    return RT_OK;
+}
+
+// The largest |coordinate| of any box an ordered walk tests (box_pair_f32's and box_quad_f32's B): the children's boxes of the binary
+// records — a wide record's slots are copies of those (rt_ordered.hpp widen) — and the boxes of the world's sequence.
+float ordered_box_extent(const CompiledScene &cs) {
+    float extent = 0.0f;
+    for (const ONode &nd : cs.onodes)
+        for (int k = 0; k < 6; ++k) {
+            if ((nd.c[0] >> OREF_KIND_SHIFT) != OK_EMPTY) extent = std::fmax(extent, std::fabs(nd.b0[k]));
+            if ((nd.c[1] >> OREF_KIND_SHIFT) != OK_EMPTY) extent = std::fmax(extent, std::fabs(nd.b1[k]));
+        }
+    for (const OSeq &st : cs.oseq)
+        for (int k = 0; k < 6; ++k) extent = std::fmax(extent, std::fabs(st.box[k]));
+    return extent;
+}
+
+WideImage pack_wide_records(const std::vector<ONode4> &recs) {
+    const size_t n = recs.size(), off_b = n * 32;
+    WideImage img;
+    img.table_bytes = off_b;
+    img.tables.resize(n * 13); // 6 x 32 + 16 bytes per record
+    img.lines.resize(n * 16);
+    unsigned char *base = reinterpret_cast<unsigned char *>(img.tables.data());
+    for (size_t i = 0; i < n; ++i) {
+        const ONode4 &nd = recs[i];
+        for (int ax = 0; ax < 3; ++ax) {
+            float plus[8], minus[8];
+            for (int k = 0; k < 4; ++k) {
+                plus[k] = nd.b[k][2 * ax]; plus[4 + k] = nd.b[k][2 * ax + 1];   // enter through lo, leave through hi
+                minus[k] = nd.b[k][2 * ax + 1]; minus[4 + k] = nd.b[k][2 * ax];
+            }
+            memcpy(base + (size_t)(2 * ax) * off_b + i * 32, plus, 32);
+            memcpy(base + (size_t)(2 * ax + 1) * off_b + i * 32, minus, 32);
+        }
+        memcpy(base + 6 * off_b + i * 16, nd.c, 16);
+    }
+    unsigned char *dst = reinterpret_cast<unsigned char *>(img.lines.data());
+    for (size_t i = 0; i < n; ++i) {
+        for (size_t q = 0; q < 6; ++q) memcpy(dst + i * 256 + q * 32, base + q * off_b + i * 32, 32);
+        memcpy(dst + i * 256 + 192, base + 6 * off_b + i * 16, 16);
+    }
+    return img;
+}
 } // namespace rtapi
 
 extern "C" {
@@ -620,14 +693,6 @@ int64_t rt_out_size(int32_t width, int32_t height, int32_t out_layout, int32_t s
     if (out_layout == RT_OUT_FRAME) return (int64_t)width * height * 3;
     if (out_layout == RT_OUT_TILES) return tiles_local(width, height, shard_index, shard_count) * RT_TILE_W * RT_TILE_H * 3;
     return -1;
-}
-
-// Which walk for this scene?  Measured on MI355X at the in-code cameras (tools/scene_speed.py, profiles/r02_scene_speed.txt), own trees
-// vs reference order, Msamples/s: random_balls 4416 / 2128, two_spheres 8739 / 7281, earth 22557 / 22523 (one primitive: a tree and a
-// stack are pure overhead), two_perlin_spheres 4821 / 3288, quads 12860 / 12612, simple_light 5845 / 4894, cornell_box 3224 / 2102,
-// cornell_smoke 1261 / 966 (a tie until its frames' primitives went into flat leaves, rt_ordered.hpp flat_max), final_scene 983 / 643.
-static bool ordered_walk_pays(const CompiledScene &cs) {
-    return cs.spheres.size() + cs.quads.size() > 1;
 }
 
 void rt_scene_options_init(rt_scene_options *o) {
@@ -662,26 +727,8 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
     *out_scene = nullptr;
     rt_scene_options opt;
     if (int orc = resolve_scene_options(options, opt, "rt_scene_create_ex")) return orc;
-    // the process defaults in force now (RT_* variables, rt_debug_set_*), then the caller's options
-    const Tuning tn = tuning_snapshot();
-    const int walk = opt.walk != RT_WALK_DEFAULT ? opt.walk : tn.ordered;
-    const bool refit = opt.refit >= 0 ? opt.refit != 0 : tn.refit != 0;
-    OrderedOptions oopt = tn.ordered_options;
-    if (opt.leaf_max > 0) oopt.leaf_max = (uint32_t)opt.leaf_max < OREF_MAX_LEAF ? (uint32_t)opt.leaf_max : OREF_MAX_LEAF;
-    if (opt.flat_max >= 0) oopt.flat_max = (uint32_t)opt.flat_max;
-    const int want_wide = opt.wide >= 0 ? opt.wide : tn.wide; // (-1: where it measured faster, below)
     CompiledScene cs;
-    try {
-        cs = compile_scene(*desc, refit);
-        // Four children per record where the trees are big enough for the halved number of visits to pay for the dearer visit
-        // (MI355X, Msamples/s two / four children: random-spheres 5428 / 5437, final_scene 1049 / 1088; Cornell's 4 records: 2438 / 2345)
-        oopt.wide = want_wide >= 0 ? want_wide != 0 : cs.spheres.size() + cs.quads.size() >= 64;
-        if (walk == RT_WALK_OWN_TREES || (walk == RT_WALK_AUTO && ordered_walk_pays(cs))) build_ordered(cs, oopt);
-    } catch (const CompileError &e) {
-        return fail(e.status, e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_scene_create: ") + e.what());
-    }
+    if (int crc = compile_for_scene(*desc, opt, cs, "rt_scene_create")) return crc;
     const int ndev = rt_device_count();
     if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "rt_scene_create: no HIP device is visible (this library has no CPU path)");
     if (device < 0 || device >= ndev) return fail(RT_ERR_NO_DEVICE, "rt_scene_create: device ordinal out of range");
@@ -764,13 +811,7 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
             in.start_ref = (n == 1 && (kind == OK_SPHERES || kind == OK_QUADS)) ? only : 0u;
             if (in.start_ref) memcpy(in.start_box, box, sizeof in.start_box);
         }
-    for (const ONode &nd : cs.onodes)
-        for (int k = 0; k < 6; ++k) {
-            if ((nd.c[0] >> OREF_KIND_SHIFT) != OK_EMPTY) s->box_extent = std::fmax(s->box_extent, std::fabs(nd.b0[k]));
-            if ((nd.c[1] >> OREF_KIND_SHIFT) != OK_EMPTY) s->box_extent = std::fmax(s->box_extent, std::fabs(nd.b1[k]));
-        }
-    for (const OSeq &st : cs.oseq)
-        for (int k = 0; k < 6; ++k) s->box_extent = std::fmax(s->box_extent, std::fabs(st.box[k]));
+    s->box_extent = ordered_box_extent(cs);
     s->o_stack = cs.ordered_stack;
     // Node tables (load_node / load_opair): threaded records as two 16-byte halves, ordered records as six 16-byte plane
     // tables and an 8-byte reference table.  LDS image = node tables | spheres | quads; every LDS level copies a prefix.
@@ -779,24 +820,13 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
         const size_t n = wide ? cs.onodes4.size() : (cs.ordered ? cs.onodes.size() : cs.nodes32.size());
         const size_t off_b = wide ? n * 32 : n * 16; // bytes of one plane table (16 bytes per record; wide records: 32)
         const size_t off_sph = wide ? n * (6 * 32 + 16) : (cs.ordered ? ((n * (6 * 16 + 8) + 15u) & ~(size_t)15u) : n * 32);
-        std::vector<uint4> tables(off_sph / 16);
-        {
+        WideImage wimg;
+        if (wide) wimg = pack_wide_records(cs.onodes4); // (rt_device_scene.h load_oquad)
+        std::vector<uint4> local_tables(wide ? 0 : off_sph / 16);
+        std::vector<uint4> &tables = wide ? wimg.tables : local_tables;
+        if (!wide) {
             unsigned char *base = reinterpret_cast<unsigned char *>(tables.data());
-            if (wide) { // (rt_device_scene.h load_oquad)
-                for (size_t i = 0; i < n; ++i) {
-                    const ONode4 &nd = cs.onodes4[i];
-                    for (int ax = 0; ax < 3; ++ax) {
-                        float plus[8], minus[8];
-                        for (int k = 0; k < 4; ++k) {
-                            plus[k] = nd.b[k][2 * ax]; plus[4 + k] = nd.b[k][2 * ax + 1];   // enter through lo, leave through hi
-                            minus[k] = nd.b[k][2 * ax + 1]; minus[4 + k] = nd.b[k][2 * ax];
-                        }
-                        memcpy(base + (size_t)(2 * ax) * off_b + i * 32, plus, 32);
-                        memcpy(base + (size_t)(2 * ax + 1) * off_b + i * 32, minus, 32);
-                    }
-                    memcpy(base + 6 * off_b + i * 16, nd.c, 16);
-                }
-            } else if (cs.ordered) {
+            if (cs.ordered) {
                 for (size_t i = 0; i < n; ++i) {
                     const ONode &nd = cs.onodes[i];
                     for (int ax = 0; ax < 3; ++ax) {
@@ -814,14 +844,7 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
             }
         }
         if (wide) { // the global copy: 256 bytes per record (load_oquad<0>)
-            std::vector<uint4> lines(n * 16);
-            unsigned char *dst = reinterpret_cast<unsigned char *>(lines.data());
-            const unsigned char *tab = reinterpret_cast<const unsigned char *>(tables.data());
-            for (size_t i = 0; i < n; ++i) {
-                for (size_t q = 0; q < 6; ++q) memcpy(dst + i * 256 + q * 32, tab + q * off_b + i * 32, 32);
-                memcpy(dst + i * 256 + 192, tab + 6 * off_b + i * 16, 16);
-            }
-            int urc = upload(s->oimage, lines);
+            int urc = upload(s->oimage, wimg.lines);
             if (urc != RT_OK) { free_scene(s); return urc; }
         } else if (cs.ordered) { // the global copy: one 128-byte line per record (load_opair<0>)
             std::vector<uint4> lines(n * 8);

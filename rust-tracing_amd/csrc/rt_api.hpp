@@ -114,6 +114,19 @@ int resolve_scene_options(const rt_scene_options *options, rt_scene_options &out
 Tuning tuning_snapshot();
 void tuning_update(void (*fn)(Tuning &, const void *), const void *arg);
 
+// The node tables of a scene with four-child records as the device holds them (rt_device_scene.h load_oquad).  `tables`: the LDS form
+// — six plane tables X+ | X- | Y+ | Y- | Z+ | Z- of table_bytes each (32 bytes per record: the planes a ray of that sign enters the four
+// children through, then the four it leaves them through) and the reference table (16 bytes per record) behind them.  `lines`: the
+// global form — a record's seven pieces side by side in 256 bytes (offsets 0 .. 160, 192).  One function for rt_scene_create_ex and
+// the hooks of rt_debug.cpp, so that what a test inspects or feeds to the kernel is what a scene uploads.
+struct WideImage {
+    std::vector<uint4> tables, lines;
+    size_t table_bytes = 0; // KParams::lds_off_node_b
+};
+WideImage pack_wide_records(const std::vector<ONode4> &recs);
+int compile_for_scene(const rt_scene_desc &desc, const rt_scene_options &opt, CompiledScene &cs, const char *who); // as rt_scene_create_ex does
+float ordered_box_extent(const CompiledScene &cs); // rt_scene::box_extent, as scene creation computes it
+
 template <class T> struct DeviceArray {
     T *ptr = nullptr;
     size_t bytes = 0;

@@ -182,6 +182,190 @@ int rt_debug_wide_layout(const rt_scene_desc *desc, const rt_scene_options *opti
     return RT_OK;
 }
 
+// the f64 bound of what a wide record's slots hold (rt_debug_wide_records): leaves from their primitives, inner records and
+// instances from below, each record once
+namespace {
+struct WideBounds {
+    const CompiledScene &cs;
+    std::vector<Bound> slot;   // [record * 4 + k]
+    std::vector<uint8_t> done; // per record
+    explicit WideBounds(const CompiledScene &c) : cs(c), slot(c.onodes4.size() * 4), done(c.onodes4.size(), 0) {}
+    Bound record(uint32_t rec) { // everything below the record
+        Bound all;
+        if (rec >= cs.onodes4.size()) return all;
+        if (!done[rec]) {
+            done[rec] = 1;
+            const ONode4 &nd = cs.onodes4[rec];
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t kind = nd.c[k] >> OREF_KIND_SHIFT, index = nd.c[k] & OREF_INDEX_MASK, count = ((nd.c[k] >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u;
+                Bound b;
+                if (kind == OK_INNER) b = record(index);
+                else if (kind == OK_SPHERES) { for (uint32_t i = 0; i < count && index + i < cs.spheres.size(); ++i) b.add(sphere_bound(cs.spheres[index + i])); }
+                else if (kind == OK_QUADS) { for (uint32_t i = 0; i < count && index + i < cs.quads.size(); ++i) b.add(quad_bound(cs.quads[index + i])); }
+                else if (kind == OK_INSTANCE && index < cs.instances.size()) b = instance_bound(cs.instances[index], record(cs.instances[index].root));
+                slot[(size_t)rec * 4 + k] = b;
+            }
+        }
+        for (int k = 0; k < 4; ++k) all.add(slot[(size_t)rec * 4 + k]);
+        return all;
+    }
+};
+} // namespace
+
+int rt_debug_wide_records(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_wide *io) {
+    if (!desc || !io) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_records: null argument");
+    rt_scene_options opt;
+    if (int orc = resolve_scene_options(options, opt, "rt_debug_wide_records")) return orc;
+    CompiledScene cs;
+    if (int crc = compile_for_scene(*desc, opt, cs, "rt_debug_wide_records")) return crc;
+    const bool wide = cs.ordered && cs.wide;
+    const size_t n = wide ? cs.onodes4.size() : 0;
+    io->wide = wide ? 1u : 0u;
+    io->n_records = (int64_t)n;
+    io->n_steps = cs.ordered ? (int64_t)cs.oseq.size() : 0;
+    io->box_extent = ordered_box_extent(cs);
+    io->table_bytes = (uint32_t)(n * 32);
+    if ((io->boxes || io->refs || io->bounds || io->global_image || io->lds_image) && io->cap_records < io->n_records)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_records: record buffers too small");
+    if (io->step_boxes && io->cap_steps < io->n_steps) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_records: steps buffer too small");
+    if (io->step_boxes)
+        for (int64_t i = 0; i < io->n_steps; ++i) memcpy(io->step_boxes + i * 6, cs.oseq[(size_t)i].box, 6 * sizeof(float));
+    if (n == 0) return RT_OK;
+    for (size_t i = 0; i < n; ++i) {
+        if (io->boxes) memcpy(io->boxes + i * 24, cs.onodes4[i].b, 24 * sizeof(float));
+        if (io->refs) memcpy(io->refs + i * 4, cs.onodes4[i].c, 4 * sizeof(uint32_t));
+    }
+    if (io->bounds) {
+        WideBounds wb(cs);
+        for (size_t i = 0; i < n; ++i) {
+            wb.record((uint32_t)i);
+            for (int k = 0; k < 4; ++k) {
+                const Bound &b = wb.slot[i * 4 + k];
+                for (int ax = 0; ax < 3; ++ax) { io->bounds[(i * 4 + k) * 6 + 2 * ax] = b.lo[ax]; io->bounds[(i * 4 + k) * 6 + 2 * ax + 1] = b.hi[ax]; }
+            }
+        }
+    }
+    if (io->global_image || io->lds_image) {
+        const WideImage img = pack_wide_records(cs.onodes4);
+        if (io->global_image) memcpy(io->global_image, img.lines.data(), n * 256);
+        if (io->lds_image) memcpy(io->lds_image, img.tables.data(), n * 208);
+    }
+    return RT_OK;
+}
+
+int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device) {
+    if (!io || io->n <= 0 || !io->rays || !io->tmin || !io->tmax || !io->todo || !io->enter || !io->leave || !io->hit || !io->chosen ||
+        !io->degenerate || !io->exact)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_visits: bad argument");
+    const bool packed = io->boxes == nullptr;
+    if (packed) {
+        if (!io->global_image || !io->lds_image || !io->record || io->n_records <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_visits: neither boxes nor packed records");
+        for (int64_t i = 0; i < io->n; ++i)
+            if ((int64_t)io->record[i] >= io->n_records) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_visits: record index out of range");
+    }
+    if (rt_device_count() <= device || device < 0) return fail(RT_ERR_NO_DEVICE, "rt_debug_wide_visits: no such HIP device");
+    HIP_TRY(hipSetDevice(device));
+    const int64_t chunk_max = io->n < (1 << 18) ? io->n : (1 << 18); // cases per launch: 64 MiB of records
+    const size_t image_row = io->lds != 0 ? 208 : 256;
+    struct Buf { void *p = nullptr; size_t bytes; };
+    Buf d_rays{nullptr, (size_t)chunk_max * 48}, d_boxes{nullptr, (size_t)chunk_max * 192}, d_tmin{nullptr, (size_t)chunk_max * 8}, d_tmax{nullptr, (size_t)chunk_max * 8},
+        d_todo{nullptr, (size_t)chunk_max}, d_ext{nullptr, (size_t)chunk_max * 4}, d_image{nullptr, (size_t)chunk_max * image_row}, d_enter{nullptr, (size_t)chunk_max * 16},
+        d_leave{nullptr, (size_t)chunk_max * 16}, d_hit{nullptr, (size_t)chunk_max}, d_chosen{nullptr, (size_t)chunk_max}, d_deg{nullptr, (size_t)chunk_max}, d_exact{nullptr, (size_t)chunk_max};
+    Buf *all[] = {&d_rays, &d_boxes, &d_tmin, &d_tmax, &d_todo, &d_ext, &d_image, &d_enter, &d_leave, &d_hit, &d_chosen, &d_deg, &d_exact};
+    int rc = RT_OK;
+    for (Buf *b : all)
+        if (rc == RT_OK && hipMalloc(&b->p, b->bytes) != hipSuccess) rc = fail(RT_ERR_OUT_OF_MEMORY, "rt_debug_wide_visits: hipMalloc failed");
+    std::vector<ONode4> recs;
+    std::vector<double> boxes64;
+    std::vector<float> extents;
+    std::vector<unsigned char> gathered;
+    for (int64_t first = 0; first < io->n && rc == RT_OK; first += chunk_max) {
+        const int64_t m = io->n - first < chunk_max ? io->n - first : chunk_max;
+        recs.assign((size_t)m, ONode4{});
+        boxes64.assign((size_t)m * 24, 0.0);
+        extents.assign((size_t)m, 0.0f);
+        const unsigned char *image = nullptr;
+        WideImage img;
+        if (!packed) {
+            for (int64_t i = 0; i < m; ++i) {
+                const double *src = io->boxes + (first + i) * 24;
+                ONode4 &nd = recs[(size_t)i];
+                for (int k = 0; k < 4; ++k) {
+                    const double *b = src + 6 * k;
+                    double *b64 = &boxes64[(size_t)i * 24 + 6 * k];
+                    const bool empty = b[0] > b[1] || b[2] > b[3] || b[4] > b[5];
+                    for (int ax = 0; ax < 3; ++ax) {
+                        b64[2 * ax] = empty ? (double)INFINITY : b[2 * ax];
+                        b64[2 * ax + 1] = empty ? -(double)INFINITY : b[2 * ax + 1];
+                        nd.b[k][2 * ax] = empty ? INFINITY : round_down(b[2 * ax]); // (rt_ordered.hpp set_child, widen)
+                        nd.b[k][2 * ax + 1] = empty ? -INFINITY : round_up(b[2 * ax + 1]);
+                    }
+                    nd.c[k] = empty ? (OK_EMPTY << OREF_KIND_SHIFT) : (io->refs ? io->refs[(first + i) * 4 + k] : (OK_SPHERES << OREF_KIND_SHIFT));
+                    if (!empty && (nd.c[k] >> OREF_KIND_SHIFT) >= OK_EMPTY) rc = fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_wide_visits: an empty reference on a box");
+                }
+            }
+            if (rc != RT_OK) break;
+            img = pack_wide_records(recs);
+            image = reinterpret_cast<const unsigned char *>(io->lds != 0 ? img.tables.data() : img.lines.data());
+        } else {
+            // the rows of the caller's image that the cases visit, gathered byte for byte into an image of m records
+            gathered.assign((size_t)m * image_row, 0);
+            const size_t src_table = (size_t)io->n_records * 32, dst_table = (size_t)m * 32;
+            for (int64_t i = 0; i < m; ++i) {
+                const size_t rec = io->record[first + i];
+                if (io->lds != 0) {
+                    for (size_t q = 0; q < 6; ++q) memcpy(&gathered[q * dst_table + (size_t)i * 32], io->lds_image + q * src_table + rec * 32, 32);
+                    memcpy(&gathered[6 * dst_table + (size_t)i * 16], io->lds_image + 6 * src_table + rec * 16, 16);
+                } else {
+                    memcpy(&gathered[(size_t)i * 256], io->global_image + rec * 256, 256);
+                }
+                // the boxes back out of the record's "+" tables (enter through lo, leave through hi), for the exact test and the extent
+                const float *line = reinterpret_cast<const float *>(io->global_image + rec * 256);
+                for (int k = 0; k < 4; ++k)
+                    for (int ax = 0; ax < 3; ++ax) {
+                        recs[(size_t)i].b[k][2 * ax] = line[16 * ax + k];
+                        recs[(size_t)i].b[k][2 * ax + 1] = line[16 * ax + 4 + k];
+                        boxes64[(size_t)i * 24 + 6 * k + 2 * ax] = (double)line[16 * ax + k];
+                        boxes64[(size_t)i * 24 + 6 * k + 2 * ax + 1] = (double)line[16 * ax + 4 + k];
+                    }
+                memcpy(recs[(size_t)i].c, io->global_image + rec * 256 + 192, 16);
+            }
+            image = gathered.data();
+        }
+        for (int64_t i = 0; i < m; ++i)
+            for (int k = 0; k < 4; ++k)
+                if ((recs[(size_t)i].c[k] >> OREF_KIND_SHIFT) != OK_EMPTY)
+                    for (int q = 0; q < 6; ++q) extents[(size_t)i] = std::fmax(extents[(size_t)i], std::fabs(recs[(size_t)i].b[k][q]));
+        const bool up = hipMemcpy(d_rays.p, io->rays + first * 6, (size_t)m * 48, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_boxes.p, boxes64.data(), (size_t)m * 192, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_tmin.p, io->tmin + first, (size_t)m * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_tmax.p, io->tmax + first, (size_t)m * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_todo.p, io->todo + first, (size_t)m, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_ext.p, extents.data(), (size_t)m * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                        hipMemcpy(d_image.p, image, (size_t)m * image_row, hipMemcpyHostToDevice) == hipSuccess;
+        if (!up) { rc = fail(RT_ERR_HIP, "rt_debug_wide_visits: upload failed"); break; }
+        DebugWideArgs a{};
+        a.n = m;
+        a.rays = (const double *)d_rays.p; a.boxes = (const double *)d_boxes.p; a.tmin = (const double *)d_tmin.p; a.tmax = (const double *)d_tmax.p;
+        a.todo = (const uint8_t *)d_todo.p;
+        a.extents = io->extent > 0.0f ? nullptr : (const float *)d_ext.p;
+        a.extent = io->extent;
+        a.image = (const uint4 *)d_image.p;
+        a.enter = (float *)d_enter.p; a.leave = (float *)d_leave.p;
+        a.hit = (uint8_t *)d_hit.p; a.degenerate = (uint8_t *)d_deg.p; a.exact = (uint8_t *)d_exact.p; a.chosen = (int8_t *)d_chosen.p;
+        launch_debug_wide(a, io->lds);
+        const bool down = hipMemcpy(io->enter + first * 4, d_enter.p, (size_t)m * 16, hipMemcpyDeviceToHost) == hipSuccess &&
+                          hipMemcpy(io->leave + first * 4, d_leave.p, (size_t)m * 16, hipMemcpyDeviceToHost) == hipSuccess &&
+                          hipMemcpy(io->hit + first, d_hit.p, (size_t)m, hipMemcpyDeviceToHost) == hipSuccess &&
+                          hipMemcpy(io->chosen + first, d_chosen.p, (size_t)m, hipMemcpyDeviceToHost) == hipSuccess &&
+                          hipMemcpy(io->degenerate + first, d_deg.p, (size_t)m, hipMemcpyDeviceToHost) == hipSuccess &&
+                          hipMemcpy(io->exact + first, d_exact.p, (size_t)m, hipMemcpyDeviceToHost) == hipSuccess;
+        if (!down) { rc = fail(RT_ERR_HIP, std::string("rt_debug_wide_visits: ") + hipGetErrorString(hipGetLastError())); break; }
+    }
+    for (Buf *b : all) (void)hipFree(b->p);
+    return rc;
+}
+
 int rt_debug_compiled_nodes(const rt_scene_desc *desc, int32_t refit, rt_debug_node *out_nodes, int64_t capacity, int64_t *out_count) {
     if (!desc || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_compiled_nodes: null argument");
     CompiledScene cs;

@@ -387,6 +387,50 @@ RT_DEV void box_quad_f32(const OQuad &b, const RayPair32 &r, float tmin32, float
         leave[2 * h] = le0; leave[2 * h + 1] = le1;
     }
 }
+// What a visit of a wide record (rt_kernel.hip visit_wide; the test hook debug_wide_kernel) makes of box_quad_f32's distances, in two
+// steps — the kernel takes the world frame's instances out of `hit` and `key` between them.
+// wide_verdict: which of the children in `todo` are entered, and a key per child to choose among them by — in integer arithmetic on
+// the floats' bits (a compare-and-select per child costs two instructions and the wait states between them; these cost one each).  A
+// box is missed iff leave - enter is negative (no NaN can arise here: planes and ray constants are finite, an empty slot gives -inf);
+// the sign, spread over the word, turns the child's key — where the ray enters it — into an all-ones NaN, which the minimum ignores
+// and nothing equals; so does the complement of the entry's mask for a child that is no longer to be looked at.
+// any_degenerate: wave-uniform, some lane's ray is degenerate (tests/test_gpu_wide_visit.py checks all of this against an f64 reference)
+RT_DEV uint32_t wide_verdict(const float en[4], const float le[4], const uint32_t c[4], uint32_t todo, bool any_degenerate, bool degenerate,
+                             uint32_t key[4]) {
+    uint32_t missed[4];
+    uint32_t miss_bits = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+        missed[k] = (uint32_t)((int32_t)__float_as_uint(le[k] - en[k]) >> 31);
+        miss_bits |= missed[k] & (1u << k);
+        key[k] = __float_as_uint(en[k]) | missed[k] | (uint32_t)((int32_t)(~todo << (31u - k)) >> 31);
+    }
+    uint32_t hit = ~miss_bits & todo;
+    if (any_degenerate) { // a ray with a zero or infinite direction component: every box that exists is entered
+        if (degenerate) {
+            hit = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) hit |= c[k] < (OK_EMPTY << OREF_KIND_SHIFT) ? (1u << k) : 0u;
+            hit &= todo;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) key[k] = (hit >> k & 1u) ? 0u : 0xffffffffu; // (in any order)
+        }
+    }
+    return hit;
+}
+// wide_nearest: the slot of the nearest of the children that are entered, and its reference (v_min3 / v_min return the operand that
+// is not a NaN); slot 3 where none is — the caller looks at `hit` first
+RT_DEV uint32_t wide_nearest(const uint32_t key[4], const uint32_t c[4], uint32_t &ref) {
+    float m012, nearest;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(m012) : "v"(__uint_as_float(key[0])), "v"(__uint_as_float(key[1])), "v"(__uint_as_float(key[2])));
+    asm("v_min_f32 %0, %1, %2" : "=v"(nearest) : "v"(m012), "v"(__uint_as_float(key[3])));
+    uint32_t t = 3u;
+    ref = c[3];
+    if (__uint_as_float(key[2]) == nearest) { t = 2u; ref = c[2]; }
+    if (__uint_as_float(key[1]) == nearest) { t = 1u; ref = c[1]; }
+    if (__uint_as_float(key[0]) == nearest) { t = 0u; ref = c[0]; }
+    return t;
+}
 // one box given as (x.lo, x.hi, y.lo, y.hi, z.lo, z.hi) in both slots of a pair, as the "+" / "-" tables would hold it
 RT_DEV OPair opair_of_box(const float b[6], const RayPair32 &r) {
     OPair p;

@@ -507,30 +507,9 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             if (COUNT) cn.node_visits++;
             float en[4], le[4];
             box_quad_f32(nd, r32, tmin32, tmax32, en, le);
-            // Which children are entered, and which of them first — in integer arithmetic on the floats' bits (a compare-and-select per
-            // child costs two instructions and the wait states between them; these cost one each).  A box is missed iff leave - enter is
-            // negative (no NaN can arise here: planes and ray constants are finite, an empty slot gives -inf); the sign, spread over the
-            // word, turns the child's key — where the ray enters it — into an all-ones NaN, which the minimum ignores and nothing equals;
-            // so does the complement of the entry's mask for a child that is no longer to be looked at.
-            uint32_t missed[4], key[4];
-            uint32_t miss_bits = 0;
-        #pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) {
-                missed[k] = (uint32_t)((int32_t)__float_as_uint(le[k] - en[k]) >> 31);
-                miss_bits |= missed[k] & (1u << k);
-                key[k] = __float_as_uint(en[k]) | missed[k] | (uint32_t)((int32_t)(~todo << (31u - k)) >> 31);
-            }
-            uint32_t hit = ~miss_bits & todo;
-            if (any_degenerate) { // a ray with a zero or infinite direction component: every box that exists is entered
-                if (r32.degenerate) {
-                    hit = 0;
-        #pragma unroll
-                    for (uint32_t k = 0; k < 4u; ++k) hit |= nd.c[k] < (OK_EMPTY << OREF_KIND_SHIFT) ? (1u << k) : 0u;
-                    hit &= todo;
-        #pragma unroll
-                    for (uint32_t k = 0; k < 4u; ++k) key[k] = (hit >> k & 1u) ? 0u : 0xffffffffu; // (in any order)
-                }
-            }
+            // which children are entered, and a key per child to choose the nearest by (rt_device_scene.h)
+            uint32_t key[4];
+            uint32_t hit = wide_verdict(en, le, nd.c, todo, any_degenerate, r32.degenerate, key);
             if constexpr (DEFER) {
                 // the world frame's instances are noted, not entered (see `deferred`); rare, so behind a wave-uniform branch
                 const uint32_t c01 = nd.c[0] > nd.c[1] ? nd.c[0] : nd.c[1], c23 = nd.c[2] > nd.c[3] ? nd.c[2] : nd.c[3];
@@ -542,14 +521,9 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     }
                 }
             }
-            // the nearest of the children that are entered (v_min3 / v_min return the operand that is not a NaN)
-            float m012, nearest;
-            asm("v_min3_f32 %0, %1, %2, %3" : "=v"(m012) : "v"(__uint_as_float(key[0])), "v"(__uint_as_float(key[1])), "v"(__uint_as_float(key[2])));
-            asm("v_min_f32 %0, %1, %2" : "=v"(nearest) : "v"(m012), "v"(__uint_as_float(key[3])));
-            uint32_t t = 3u, ref = nd.c[3];
-            if (__uint_as_float(key[2]) == nearest) { t = 2u; ref = nd.c[2]; }
-            if (__uint_as_float(key[1]) == nearest) { t = 1u; ref = nd.c[1]; }
-            if (__uint_as_float(key[0]) == nearest) { t = 0u; ref = nd.c[0]; }
+            // the nearest of the children that are entered
+            uint32_t ref;
+            const uint32_t t = wide_nearest(key, nd.c, ref);
             const uint32_t rest = hit & ~(1u << t);
             if (COUNT) {
                 const uint32_t nb = (uint32_t)__popc(todo), went = hit == 0u ? 2u : ((ref >> OREF_KIND_SHIFT) == OK_INNER ? 0u : 1u);
@@ -1544,6 +1518,58 @@ __global__ void debug_quad_kernel(int64_t n, const double *__restrict__ rays, co
     keep[idx] = (uint8_t)((bits & 3u) | ((bits >> 8 & 3u) << 2) | (inside ? 16u : 0u)); // bits 0-1 keep, 2-3 certainly inside, 4: the exact alpha, beta ARE inside // (the quad sits in both slots)
 }
 
+// test hook: one visit of a four-child record per lane, as visit_wide makes it (rt_debug_wide_visits).  Case i visits record i of the
+// image.  LDS != 0: the block first stages its DEBUG_WIDE_THREADS records — a slice of each of the image's seven tables — into the LDS.
+constexpr int DEBUG_WIDE_THREADS = 256;
+template <int LDS> __global__ __launch_bounds__(DEBUG_WIDE_THREADS) void debug_wide_kernel(DebugWideArgs a) {
+    __shared__ uint4 staged[LDS != 0 ? DEBUG_WIDE_THREADS * 13 : 1]; // 6 plane tables of 32 bytes a record, one reference table of 16
+    const int64_t base = (int64_t)blockIdx.x * DEBUG_WIDE_THREADS, idx = base + threadIdx.x;
+    KParams P{};
+    uint32_t id, table_bytes;
+    if constexpr (LDS != 0) {
+        const int64_t cnt = a.n - base < DEBUG_WIDE_THREADS ? a.n - base : DEBUG_WIDE_THREADS; // records of this block (>= 1)
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(a.image);
+        const size_t src_table = (size_t)a.n * 32u;
+        for (int q = 0; q < 6; ++q) {
+            const uint4 *from = reinterpret_cast<const uint4 *>(src + (size_t)q * src_table + (size_t)base * 32u);
+            for (int64_t w = threadIdx.x; w < cnt * 2; w += DEBUG_WIDE_THREADS) staged[q * (DEBUG_WIDE_THREADS * 2) + w] = from[w];
+        }
+        const uint4 *from = reinterpret_cast<const uint4 *>(src + 6u * src_table + (size_t)base * 16u);
+        for (int64_t w = threadIdx.x; w < cnt; w += DEBUG_WIDE_THREADS) staged[6 * (DEBUG_WIDE_THREADS * 2) + w] = from[w];
+        __syncthreads();
+        table_bytes = DEBUG_WIDE_THREADS * 32u;
+        P.lds_off_node_b = table_bytes;
+        id = threadIdx.x;
+    } else {
+        P.oimage = a.image;
+        table_bytes = 32u;
+        id = (uint32_t)idx;
+    }
+    if (idx >= a.n) return;
+    const double *r = a.rays + idx * 6, *b = a.boxes + idx * 24;
+    const V3 o = v3(r[0], r[1], r[2]), d = v3(r[3], r[4], r[5]);
+    const double tmin = a.tmin[idx], tmax = a.tmax[idx];
+    uint32_t exact = 0;
+    for (int k = 0; k < 4; ++k) {
+        const double lo[3] = {b[6 * k], b[6 * k + 2], b[6 * k + 4]}, hi[3] = {b[6 * k + 1], b[6 * k + 3], b[6 * k + 5]};
+        exact |= box_miss_f64(lo, hi, o, d, tmin, tmax) ? 0u : (1u << k);
+    }
+    const RayPair32 rp = make_ray_pair32(o, d, table_bytes, a.extents ? a.extents[idx] : a.extent);
+    const bool any_degenerate = __ballot(rp.degenerate) != 0ull;
+    const OQuad nd = load_oquad<LDS>(P, reinterpret_cast<const unsigned char *>(staged), id, rp.offx, rp.offy, rp.offz);
+    float en[4], le[4];
+    box_quad_f32(nd, rp, f32_below(tmin), f32_above(tmax), en, le);
+    const uint32_t todo = a.todo[idx] & 0xfu;
+    uint32_t key[4], ref;
+    const uint32_t hit = wide_verdict(en, le, nd.c, todo, any_degenerate, rp.degenerate, key);
+    const uint32_t t = wide_nearest(key, nd.c, ref);
+    for (int k = 0; k < 4; ++k) { a.enter[idx * 4 + k] = en[k]; a.leave[idx * 4 + k] = le[k]; }
+    a.hit[idx] = (uint8_t)hit;
+    a.chosen[idx] = hit != 0u ? (int8_t)t : (int8_t)-1;
+    a.degenerate[idx] = rp.degenerate ? 1 : 0;
+    a.exact[idx] = (uint8_t)exact;
+}
+
 // test hook: evaluates one device-side scalar function over arrays (rt_debug_eval)
 __global__ void debug_eval_kernel(int32_t op, int64_t n, const double *__restrict__ a, const double *__restrict__ b,
                                   double *__restrict__ out) {
@@ -1673,6 +1699,11 @@ void launch_debug_box(int64_t n, const double *rays, const double *boxes, double
 }
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep) {
     hipLaunchKernelGGL(debug_quad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, n, rays, quads, filt, tmin, tmax, exact_hit, keep);
+}
+void launch_debug_wide(const DebugWideArgs &a, int lds) {
+    const dim3 grid((unsigned)((a.n + DEBUG_WIDE_THREADS - 1) / DEBUG_WIDE_THREADS)), block(DEBUG_WIDE_THREADS);
+    if (lds != 0) hipLaunchKernelGGL(debug_wide_kernel<1>, grid, block, 0, nullptr, a);
+    else hipLaunchKernelGGL(debug_wide_kernel<0>, grid, block, 0, nullptr, a);
 }
 void launch_debug_eval(int32_t op, int64_t n, const double *a, const double *b, double *out) {
     hipLaunchKernelGGL(debug_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, op, n, a, b, out);

@@ -177,6 +177,19 @@ void launch_tiles_to_frame_rgb8(int32_t w, int32_t h, int32_t tiles_x, int32_t s
 void launch_resolve_rgb8(int64_t n_values, double inv_spp, const double *sum, uint8_t *rgb, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
+// the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)
+struct DebugWideArgs {
+    int64_t n;
+    const double *rays, *boxes, *tmin, *tmax; // boxes: [n][4][6] f64, for the exact test
+    const uint8_t *todo;
+    const float *extents;                     // per case, or null: `extent` for all
+    float extent;
+    const uint4 *image;
+    float *enter, *leave;
+    uint8_t *hit, *degenerate, *exact;
+    int8_t *chosen;
+};
+void launch_debug_wide(const DebugWideArgs &a, int lds);
 void launch_debug_eval(int32_t op, int64_t n, const double *a, const double *b, double *out);
 
 } // namespace rtk
