@@ -162,9 +162,21 @@ typedef struct rt_debug_wide_cases {
 } rt_debug_wide_cases;
 int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device);
 
-/* How the calling thread's last render was launched: out[0] = 0 (reserved), out[1] = LDS level, out[2] = workgroup threads,
+/* How the calling thread's last render was launched: out[0] = the render-kernel launches it took (more than one when the sample
+ * range did not fit the sample buffer; of an adaptive render: its last batch's), out[1] = LDS level, out[2] = workgroup threads,
  * out[3] = workgroups. */
 int rt_debug_last_launch(uint32_t out[4]);
+
+/* Test hook: one convergence step of adaptive sampling (rt_render_adaptive) on chosen inputs — the three kernels and the scratch
+ * layout of the render's own step, nothing rendered.  Host arrays in and out.  list: n_list entries (a positive multiple of 64),
+ * pixel indices below n_pixels (< 2^27) or padding (anything else, by convention 0xffffffff); sum, sum_sq: 3 * n_pixels doubles;
+ * n: the samples they hold; last != 0: the last schedule point (every listed pixel leaves).  spp (n_pixels, in/out): a listed pixel
+ * that leaves gets n, nothing else is written.  list_out (n_list, in/out: uploaded first, so that entries the step leaves alone
+ * show): the survivors in list order, then padding up to a multiple of 64.  *out_count: the survivors.
+ * tests/test_gpu_adaptive_step.py holds these against a numpy reference. */
+int rt_debug_adaptive_step(int64_t n_list, const uint32_t *list, int64_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
+                           int32_t last, double rel_threshold, double abs_threshold, int32_t *spp, uint32_t *list_out, uint32_t *out_count,
+                           int device);
 
 /* Profiling hook: where the last rt_render_device_counted call's waves spent their time.  For each scheduler stage
  * (box, sphere, quad, other, shade, new-job): rounds run, lanes active summed over those rounds, shader cycles (s_memtime)

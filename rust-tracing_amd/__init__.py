@@ -275,6 +275,8 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_stage_profile": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_visit_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_last_launch": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "rt_debug_adaptive_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                         C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_debug_wide_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_wide_visits": (C.c_int, [C.c_void_p, C.c_int]),
@@ -442,10 +444,32 @@ def debug_wide_visits(rays, tmin, tmax, todo, boxes=None, refs=None, records=Non
 
 
 def debug_last_launch() -> dict:
-    """rt_debug_last_launch: how this thread's last render was launched (LDS level, workgroup threads, workgroups)."""
+    """rt_debug_last_launch: how this thread's last render was launched (render-kernel launches, LDS level, workgroup threads,
+    workgroups)."""
     buf = (C.c_uint32 * 4)()
     _check(amd_lib().rt_debug_last_launch(buf), "rt_debug_last_launch")
-    return {"lds_level": int(buf[1]), "threads": int(buf[2]), "grid": int(buf[3])}
+    return {"launches": int(buf[0]), "lds_level": int(buf[1]), "threads": int(buf[2]), "grid": int(buf[3])}
+
+
+def debug_adaptive_step(pixels, sums, sums_sq, n, rel, abs, *, last=False, spp=None, list_out=None, device=0):
+    """rt_debug_adaptive_step: one convergence step over `pixels` (uint32, a multiple of 64 entries) on chosen sums (n_pixels x 3).
+    `spp` (int32, n_pixels) and `list_out` (uint32, as long as the list) are the caller's pre-filled arrays (default: -1 / zeros);
+    returns (survivor count, list_out, spp) — copies, the arguments are not written."""
+    import numpy as np
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint32)
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1, 3)
+    sums_sq = np.ascontiguousarray(sums_sq, dtype=np.float64).reshape(-1, 3)
+    n_pixels = sums.shape[0]
+    assert sums_sq.shape[0] == n_pixels
+    spp = np.full(n_pixels, -1, dtype=np.int32) if spp is None else np.array(spp, dtype=np.int32)
+    list_out = np.zeros(pixels.size, dtype=np.uint32) if list_out is None else np.array(list_out, dtype=np.uint32)
+    assert spp.size == n_pixels and list_out.size == pixels.size
+    count = C.c_uint32(0)
+    _check(amd_lib().rt_debug_adaptive_step(pixels.size, C.c_void_p(pixels.ctypes.data), n_pixels, C.c_void_p(sums.ctypes.data),
+                                            C.c_void_p(sums_sq.ctypes.data), int(n), 1 if last else 0, float(rel), float(abs),
+                                            C.c_void_p(spp.ctypes.data), C.c_void_p(list_out.ctypes.data), C.byref(count), device),
+           "rt_debug_adaptive_step")
+    return int(count.value), list_out, spp
 
 
 def debug_stage_profile() -> dict:

@@ -469,7 +469,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     if (pipelined) HIP_TRY(hipStreamWaitEvent(stream, ws.ev_sum[(k - 1) & 1], 0)); // (the last sum waited for all before it)
     HIP_TRY(hipEventRecord(ws.ev_done, stream));
     release.completed = true;
-    g_last_launch[0] = 0u; g_last_launch[1] = (uint32_t)lds; g_last_launch[2] = (uint32_t)threads; g_last_launch[3] = (uint32_t)grid;
+    g_last_launch[0] = (uint32_t)k; g_last_launch[1] = (uint32_t)lds; g_last_launch[2] = (uint32_t)threads; g_last_launch[3] = (uint32_t)grid;
 
     if (counted) {
         unsigned long long host[COUNTER_WORDS];
@@ -528,6 +528,21 @@ int check_adaptive(const rt_camera *camera, const rt_render_params *params, cons
     return RT_OK;
 }
 
+// The device scratch of the convergence steps over lists of at most n_list entries (a multiple of 64), laid out in one buffer: two
+// lists, a ballot per wave of the step, a count per block, the survivor count (16 bytes).  Returns the bytes needed; with a buffer,
+// also where each part lies.  render_adaptive and the test hook rt_debug_adaptive_step size and cut their scratch with this.
+size_t adaptive_scratch_layout(uint32_t n_list, char *buf, uint32_t *list[2], AdaptiveScratch *x) {
+    const uint32_t blocks = (n_list + 255u) / 256u;
+    const size_t list_bytes = align16((size_t)n_list * 4u), mask_bytes = (size_t)blocks * 4u * 8u, base_bytes = align16((size_t)blocks * 4u);
+    if (buf) {
+        list[0] = (uint32_t *)buf; list[1] = (uint32_t *)(buf + list_bytes);
+        x->masks = (unsigned long long *)(buf + 2u * list_bytes);
+        x->block_base = (uint32_t *)(buf + 2u * list_bytes + mask_bytes);
+        x->count = (uint32_t *)(buf + 2u * list_bytes + mask_bytes + base_bytes);
+    }
+    return 2u * list_bytes + mask_bytes + base_bytes + 16u;
+}
+
 // The schedule: render the active list up to the next evaluation point, apply the rule, compact the survivors; one 4-byte read
 // of the survivor count per batch.
 int render_adaptive(rt_scene *scene, const rt_camera *camera, const rt_render_params &p, const rt_adaptive_params &a, int32_t max_spp,
@@ -543,19 +558,16 @@ int render_adaptive(rt_scene *scene, const rt_camera *camera, const rt_render_pa
         return RT_OK;
     }
     const uint32_t n_list = (uint32_t)tiles_total(w, h) * 64u;
-    const uint32_t blocks = (n_list + 255u) / 256u;
-    // scratch: two lists, a ballot per wave, a count per block, the survivor count; the squared sums if the caller wants none
-    const size_t list_bytes = align16((size_t)n_list * 4u), mask_bytes = (size_t)blocks * 4u * 8u, base_bytes = align16((size_t)blocks * 4u);
+    // scratch: the step's (adaptive_scratch_layout); behind it the squared sums if the caller wants none
+    const size_t step_bytes = adaptive_scratch_layout(n_list, nullptr, nullptr, nullptr);
     const size_t sq_bytes = d_sum_sq ? 0u : (size_t)n_pix * 3u * sizeof(double);
     char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, 2u * list_bytes + mask_bytes + base_bytes + 16u + sq_bytes));
+    HIP_TRY(hipMalloc((void **)&buf, step_bytes + sq_bytes));
     struct Free { char *b; hipStream_t s; ~Free() { (void)hipStreamSynchronize(s); (void)hipFree(b); (void)hipGetLastError(); } } release{buf, stream};
-    uint32_t *list[2] = {(uint32_t *)buf, (uint32_t *)(buf + list_bytes)};
+    uint32_t *list[2];
     AdaptiveScratch x;
-    x.masks = (unsigned long long *)(buf + 2u * list_bytes);
-    x.block_base = (uint32_t *)(buf + 2u * list_bytes + mask_bytes);
-    x.count = (uint32_t *)(buf + 2u * list_bytes + mask_bytes + base_bytes);
-    double *sq = d_sum_sq ? d_sum_sq : (double *)(buf + 2u * list_bytes + mask_bytes + base_bytes + 16u);
+    adaptive_scratch_layout(n_list, buf, list, &x);
+    double *sq = d_sum_sq ? d_sum_sq : (double *)(buf + step_bytes);
     launch_tile_order_list(w, h, list[0], stream);
     HIP_TRY(hipGetLastError());
     rt_adaptive_result r{};

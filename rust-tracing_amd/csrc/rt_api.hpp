@@ -18,7 +18,7 @@ namespace rtapi {
 using namespace rtd;
 using namespace rtk;
 
-extern thread_local uint32_t g_last_launch[4]; // of the calling thread's last render: 0 (reserved), LDS level, workgroup threads, grid
+extern thread_local uint32_t g_last_launch[4]; // of the calling thread's last render: render-kernel launches, LDS level, workgroup threads, grid
 int fail(int status, const std::string &msg); // sets rt_last_error() of the calling thread, returns `status`
 #define HIP_TRY(expr)                                                                                          \
     do {                                                                                                       \
@@ -126,6 +126,8 @@ struct WideImage {
 WideImage pack_wide_records(const std::vector<ONode4> &recs);
 int compile_for_scene(const rt_scene_desc &desc, const rt_scene_options &opt, CompiledScene &cs, const char *who); // as rt_scene_create_ex does
 float ordered_box_extent(const CompiledScene &cs); // rt_scene::box_extent, as scene creation computes it
+// the scratch of adaptive sampling's convergence steps (rt_api.cpp): bytes needed; with `buf`, where the parts lie
+size_t adaptive_scratch_layout(uint32_t n_list, char *buf, uint32_t *list[2], AdaptiveScratch *x);
 
 template <class T> struct DeviceArray {
     T *ptr = nullptr;

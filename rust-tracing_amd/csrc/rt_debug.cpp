@@ -421,6 +421,46 @@ int rt_debug_last_launch(uint32_t out[4]) {
     return RT_OK;
 }
 
+int rt_debug_adaptive_step(int64_t n_list, const uint32_t *list, int64_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
+                           int32_t last, double rel_threshold, double abs_threshold, int32_t *spp, uint32_t *list_out, uint32_t *out_count,
+                           int device) {
+    if (!list || !sum || !sum_sq || !spp || !list_out || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_step: null argument");
+    if (n_list <= 0 || n_list % 64 != 0 || n_list > ((int64_t)1 << 27))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_step: n_list must be a positive multiple of 64, at most 2^27");
+    if (n_pixels <= 0 || n_pixels >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_step: n_pixels must be positive and below 2^27");
+    if (rt_device_count() <= device || device < 0) return fail(RT_ERR_NO_DEVICE, "rt_debug_adaptive_step: no such HIP device");
+    HIP_TRY(hipSetDevice(device));
+    // the step's scratch as render_adaptive lays it out; behind it the frame's sums, squared sums and sample counts
+    const size_t step_bytes = adaptive_scratch_layout((uint32_t)n_list, nullptr, nullptr, nullptr);
+    const size_t sum_bytes = (size_t)n_pixels * 3u * sizeof(double), spp_bytes = (size_t)n_pixels * sizeof(int32_t), list_bytes = (size_t)n_list * 4u;
+    char *buf = nullptr;
+    if (hipMalloc((void **)&buf, step_bytes + 2u * sum_bytes + spp_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RT_ERR_OUT_OF_MEMORY, "rt_debug_adaptive_step: hipMalloc failed");
+    }
+    uint32_t *d_list[2];
+    AdaptiveScratch x;
+    adaptive_scratch_layout((uint32_t)n_list, buf, d_list, &x);
+    double *d_sum = (double *)(buf + step_bytes), *d_sq = (double *)(buf + step_bytes + sum_bytes);
+    int32_t *d_spp = (int32_t *)(buf + step_bytes + 2u * sum_bytes);
+    int rc = RT_OK;
+    do {
+        if (hipMemcpy(d_list[0], list, list_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_list[1], list_out, list_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_sum, sum, sum_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_sq, sum_sq, sum_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_spp, spp, spp_bytes, hipMemcpyHostToDevice) != hipSuccess) { rc = fail(RT_ERR_HIP, "rt_debug_adaptive_step: upload failed"); break; }
+        launch_adaptive_step(d_list[0], (uint32_t)n_list, (uint32_t)n_pixels, d_sum, d_sq, n, last, rel_threshold, abs_threshold, d_spp, d_list[1], x, nullptr);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(out_count, x.count, sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(list_out, d_list[1], list_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(spp, d_spp, spp_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = fail(RT_ERR_HIP, std::string("rt_debug_adaptive_step: ") + hipGetErrorString(e)); break; }
+    } while (0);
+    (void)hipFree(buf);
+    return rc;
+}
+
 int rt_debug_stage_profile(uint64_t out[36]) {
     if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_stage_profile: null argument");
     std::lock_guard<std::mutex> lock(g_stage_profile_mu);

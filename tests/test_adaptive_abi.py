@@ -140,3 +140,73 @@ def test_rtrace_refuses_adaptive_with_several_gpus_or_progressive(rt, tmp_path):
         assert r.returncode == 2, (extra, r.returncode, r.stderr)
         assert "--adaptive" in r.stderr
     assert not (tmp_path / "x.png").exists()
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_a_frame_of_2_to_the_27_pixels_is_refused_before_the_scene_is_looked_at(rt, device):
+    lib = rt.amd_lib()
+    hs = rt.HostScene(6, width=16, spp=8, depth=4)
+    p, a, res = rt.render_params(seed=1), rt.adaptive_params(), rt.AdaptiveResult()
+    one = (C.c_double * 3)()  # (never written: every call here ends in an argument check)
+    for width, height, field in ((16384, 8192, "2^27"), (8192, 16384, "2^27"), (1 << 27, 1, "2^27"), (46341, 46341, "2^31"),
+                                 (16384, 8191, "scene"), ((1 << 27) - 1, 1, "scene")):
+        cam = rt.Camera.from_buffer_copy(hs.camera)
+        cam.image_width, cam.image_height = width, height
+        args = [None, C.byref(cam), C.byref(p), C.byref(a), C.addressof(one), C.addressof(one), None]
+        rc = lib.rt_render_adaptive_device(*args, None, C.byref(res)) if device else lib.rt_render_adaptive(*args, C.byref(res))
+        msg = lib.rt_last_error().decode()
+        assert rc == -1 and field in msg, (width, height, rc, msg)
+
+
+def test_the_exact_reciprocal_decode_of_a_list_entry_is_the_integer_division():
+    """List mode finds an entry's row as trunc((e + 0.5) * (1 / w)) in f64 (rt_kernel.hip, LIST branch) for frames of fewer than 2^27
+    pixels: the same operations in numpy against e // w — every entry within 3 of a row boundary (of every row, or of 2 million rows
+    spread over the frame and its ends), and 4 million random entries, per width."""
+    import numpy as np
+    g = np.random.default_rng(1)
+    limit = 1 << 27
+    for w in (1, 3, 37, 1200, 4099, 8191, limit - 1):
+        rows_all = limit // w + 1
+        rows = np.arange(rows_all, dtype=np.int64) if rows_all <= (1 << 21) else np.unique(np.concatenate(
+            [np.arange(1 << 19), rows_all - 1 - np.arange(1 << 19), g.integers(0, rows_all, 1 << 20)]))
+        e = (rows[:, None] * w + np.arange(-3, 4)[None, :]).reshape(-1)
+        e = np.concatenate([e, g.integers(0, limit, 1 << 22), [0, limit - 1]])
+        e = e[(e >= 0) & (e < limit)]
+        inv_w = 1.0 / np.float64(w)
+        j = np.trunc((e.astype(np.float64) + 0.5) * inv_w).astype(np.int64)
+        assert np.array_equal(j, e // w), (w, int((j != e // w).sum()))
+        assert np.array_equal(e - j * w, e % w)
+
+
+def test_the_constructed_rule_families_hold_both_verdicts():
+    """The builders of tests/test_gpu_adaptive_step.py, run on the CPU under the numpy reference: a family that held one verdict only
+    would prove nothing on the device.  Ties are ties (e2 == tol^2 exactly) with a neighbour on either side; at least 10 000 cases
+    get another verdict from a fused multiply-add, in both directions."""
+    import numpy as np
+    import test_gpu_adaptive_step as t
+    for name, S, Q, n, rel, abs_ in t.random_value_groups(count=20000):
+        share = t.verdicts(S, Q, n, rel, abs_).mean()
+        assert 0.2 < share < 0.8, (name, share)
+    for name, S, Q, n, rel, abs_ in t.tie_groups():
+        v = t.verdicts(S, Q, n, rel, abs_).reshape(3, 3)  # channel x (tie, above, below)
+        assert (v == np.array([True, False, True])).all(), (name, v)
+        m = S / float(n)
+        var = (Q - S * m) / float(n - 1)
+        tol = rel * (((m[:, 0] + m[:, 1]) + m[:, 2]) / 3.0) + abs_
+        assert (var.max(axis=1)[0::3] / float(n) == (tol * tol)[0::3]).all(), name
+    for family in (t.cancellation_groups, t.edge_groups):
+        seen = set()
+        for name, S, Q, n, rel, abs_ in family():
+            seen |= set(t.verdicts(S, Q, n, rel, abs_).tolist())
+            if name.startswith("cancellation") or name in ("non-finite", "zero n=2", "zero n=3", "subnormal n=3"):
+                assert set(t.verdicts(S, Q, n, rel, abs_).tolist()) == {True, False}, name
+        assert seen == {True, False}, family.__name__
+    groups, sensitive = t.contraction_groups()
+    total = sum(int(s.sum()) for s in sensitive)
+    assert total >= 10_000, total
+    fused_stops = sum(int((s & ~t.verdicts(S, Q, n, rel, abs_)).sum()) for (name, S, Q, n, rel, abs_), s in zip(groups, sensitive))
+    assert 1000 < fused_stops < total - 1000, (fused_stops, total)  # the fused verdict errs in both directions
+    assert all(s.mean() > 0.1 for s in sensitive), [float(s.mean()) for s in sensitive]
+    # (a group's threshold sits a quarter of an ulp to one side of its two-rounding values: one verdict per group, both in the family)
+    assert {bool(t.verdicts(S, Q, n, rel, abs_).all()) for name, S, Q, n, rel, abs_ in groups} == {True, False}
+    assert all(len(set(t.verdicts(S, Q, n, rel, abs_).tolist())) == 1 for name, S, Q, n, rel, abs_ in groups)

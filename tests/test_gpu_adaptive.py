@@ -7,35 +7,12 @@ import numpy as np
 import pytest
 
 import scene_cases
+from adaptive_helpers import PAD, SENTINEL, assert_bits, bits, check_adaptive_against_oracle, tile_order
 
 pytestmark = pytest.mark.gpu
 
 CASES = ["ragged_cornell_37x37_4spp", "cornell_smoke_64x64_16spp", "c4_final_scene_64x64_8spp_d40"]
 WALKS = ["RT_WALK_REFERENCE_ORDER", "RT_WALK_OWN_TREES"]
-PAD = 0xFFFFFFFF
-SENTINEL = np.uint64(0x7FF8DEADBEEF0001)  # a NaN pattern no render writes
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def assert_bits(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, what
-    neq = bits(got) != bits(want)
-    assert not neq.any(), f"{what}: {int(neq.sum())} of {got.size} values differ (first at {int(np.flatnonzero(neq)[0])})"
-
-
-def tile_order(w, h):
-    tx, ty = (w + 7) // 8, (h + 7) // 8
-    out = np.full(tx * ty * 64, PAD, dtype=np.uint32)
-    for k in range(tx * ty):
-        for p in range(64):
-            i, j = (k % tx) * 8 + (p & 7), (k // tx) * 8 + (p >> 3)
-            if i < w and j < h:
-                out[k * 64 + p] = j * w + i
-    return out
 
 
 def setup(rt, case, walk, **kw):
@@ -144,63 +121,12 @@ def test_min_spp_equal_to_max_spp_is_the_uniform_render(rt, gpu, case):
     assert torch.equal(a, b)
 
 
-def replay(S, Q, n, rel, abs_):
-    """The rule of include/rt_amd.h in numpy, elementwise f64 in the same order (numpy does not contract)."""
-    m = S / float(n)
-    v = (Q - S * m) / float(n - 1)
-    e2 = np.maximum(np.maximum(v[:, 0], v[:, 1]), v[:, 2]) / float(n)
-    L = ((m[:, 0] + m[:, 1]) + m[:, 2]) / 3.0
-    tol = rel * L + abs_
-    finite = np.isfinite(S).all(axis=1) & np.isfinite(Q).all(axis=1) & ~np.isnan(v).any(axis=1)
-    return finite & (e2 <= tol * tol)
-
-
 @pytest.mark.parametrize("walk", WALKS)
 def test_adaptive_render_matches_the_oracle_at_every_pixels_own_spp(rt, oracle, gpu, walk):
+    """(the oracle's snapshots, the numpy replay of the rule and the assertions: adaptive_helpers.check_adaptive_against_oracle, shared
+    with the full-frame cases of tests/test_gpu_full_size.py)"""
     hs, ds = setup(rt, "simple_light_80x45_16spp", walk)
-    w, h = hs.width, hs.height
-    n_pix = w * h
-    min_spp, batch, max_spp, rel, abs_ = 4, 4, 24, 0.05, 1e-3
-    points = list(range(min_spp, max_spp, batch)) + [max_spp]
-    # the oracle: snapshots of the running sums at each schedule point (accumulate=1), squared sums from single-sample renders
-    snap, snap_q = {}, {}
-    run = np.zeros(n_pix * 3)
-    s_seq = np.zeros(n_pix * 3)
-    q_seq = np.zeros(n_pix * 3)
-    prev = 0
-    for nk in points:
-        oracle.render(hs, rt.render_params(seed=3, sample_begin=prev, sample_end=nk, accumulate=prev > 0), out=run)
-        for s in range(prev, nk):
-            c = oracle.render(hs, rt.render_params(seed=3, sample_begin=s, sample_end=s + 1))
-            s_seq = s_seq + c
-            q_seq = q_seq + c * c
-        assert_bits(s_seq, run, f"oracle: sequential single samples against the accumulated snapshot at {nk}")
-        snap[nk], snap_q[nk] = run.copy().reshape(n_pix, 3), q_seq.copy().reshape(n_pix, 3)
-        prev = nk
-    want_spp = np.zeros(n_pix, dtype=np.int32)
-    active = np.ones(n_pix, dtype=bool)
-    launches = 0
-    for nk in points:
-        launches += 1
-        leave = active & (replay(snap[nk], snap_q[nk], nk, rel, abs_) | (nk == max_spp))
-        want_spp[leave] = nk
-        active &= ~leave
-        if not active.any():
-            break
-
-    total, spp, sq, res = ds.render_adaptive(rt.render_params(seed=3, sample_end=max_spp), min_spp=min_spp, batch_spp=batch, rel=rel,
-                                             abs=abs_)
-    spp = spp.reshape(-1)
-    assert (spp == want_spp).all(), f"{int((spp != want_spp).sum())} pixels' spp differ from the replay"
-    assert (spp == min_spp).any() and (spp == max_spp).any(), np.unique(spp)
-    total, sq = total.reshape(n_pix, 3), sq.reshape(n_pix, 3)
-    for nk in points:
-        sel = spp == nk
-        assert_bits(total[sel], snap[nk][sel], f"sums of the pixels that stopped at {nk}")
-        assert_bits(sq[sel], snap_q[nk][sel], f"squared sums of the pixels that stopped at {nk}")
-    assert res["samples"] == int(spp.sum())
-    assert res["launches"] == launches
-    assert res["converged"] == int((spp < max_spp).sum())
+    check_adaptive_against_oracle(rt, oracle, hs, ds, min_spp=4, batch=4, max_spp=24, rel=0.05, abs_=1e-3)
 
 
 def test_per_pixel_spp_resolve_equals_the_uniform_resolve_per_group(rt, gpu):

@@ -201,3 +201,54 @@ def test_c5_final_scene_1600x1600_10000spp_depth50_in_full(rt, gpu):
     assert np.array_equal(t.view(np.uint64), np.ascontiguousarray(frame[rows, cols]).view(np.uint64))
     worst, rms = _fixed_block_error(f, 10000, 1600)
     assert worst < 0.06 and rms < 0.02, (worst, rms)
+
+
+# ---- adaptive sampling at full-frame list sizes ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene, width, aspect, depth, rel, abs_", [(6, 600, 1.0, 50, 0.5, 0.2), (0, 1200, 1.5, 50, 0.15, 5e-3)], ids=["c3", "c2"])
+def test_adaptive_render_matches_the_oracle_at_every_pixels_own_spp_at_full_frame_size(rt, gpu, oracle, scene, width, aspect, depth, rel, abs_):
+    """The twin of tests/test_gpu_adaptive.py's test at C3's 600x600 and C2's 1200x800 frame (lists of 360 000 and 960 000 entries: two
+    and four trips of the compaction's scan loop, survivors lists of every size below), schedule 8 : 8 : 32.  The oracle renders the
+    snapshots and the single-sample frames (2 x 31 M samples for C2, narrowing box test: the same image bit for bit).  The thresholds
+    were settled on the oracle's sums alone so that every schedule point takes its share — Cornell 89 / 3 / 3 / 4 % of the pixels
+    (three quarters of them are black after 8 samples), random-spheres 42 / 15 / 13 / 30 % — and a schedule that degenerates fails.
+    Added GPU time, measured on an MI355X: 2 s (C3) and 7 s (C2), most of it the oracle; the decode test below: 0.5 s."""
+    from adaptive_helpers import check_adaptive_against_oracle
+    hs = rt.HostScene(scene, scene_seed=1, width=width, aspect=aspect, spp=32, depth=depth)
+    check_adaptive_against_oracle(rt, oracle, hs, rt.DeviceScene(hs), min_spp=8, batch=8, max_spp=32, rel=rel, abs_=abs_, min_share=0.01,
+                                  aabb_mode=oracle.ORC_AABB_TIGHT)
+
+
+def test_list_decode_at_a_large_odd_frame_equals_the_dense_render(rt, gpu):
+    """List mode turns an entry into (i, j) with an exact-reciprocal division by the width (rt_kernel.hip, LIST branch); the dense
+    render gets its pixels from the tile arithmetic, which is held to the oracle at full size above.  8191 x 4099 (33.6 M pixels,
+    both dimensions odd and no multiple of the tile), one sphere, 1 spp, depth 2: the full tile-order list must give the dense
+    frame, and a listed subset — the frame's corners, the ends of several rows, pads — its pixels and nothing else.  Compared on
+    the device."""
+    from adaptive_helpers import PAD, SENTINEL, tile_order
+    w, h = 8191, 4099
+    hs = rt.HostScene(2, width=w, aspect=w / (h + 0.5), spp=1, depth=2, earth_image=scene_cases.EARTH_SMALL)
+    assert (hs.width, hs.height) == (w, h) and (1 << 24) < w * h < (1 << 26)
+    ds = rt.DeviceScene(hs)
+    stream = torch.cuda.current_stream().cuda_stream
+    want = render(rt, ds, hs)
+
+    def listed(pixels, fill):
+        lst = torch.from_numpy(np.ascontiguousarray(pixels, dtype=np.uint32).view(np.int32)).cuda()
+        out = torch.full((w * h * 3,), fill, dtype=torch.int64, device="cuda").view(torch.float64)
+        ds.render_pixels_device(rt.render_params(seed=1), lst.data_ptr(), len(pixels), out.data_ptr(), 0, stream)
+        torch.cuda.synchronize()
+        return out
+
+    sentinel = int(SENTINEL.astype(np.int64))
+    got = listed(tile_order(w, h), sentinel)
+    assert torch.equal(got.view(torch.int64), want.view(torch.int64))
+    del got
+    rows = np.array([0, 1, 2, 7, 8, 1023, 2048, 2049, h - 9, h - 2, h - 1], dtype=np.int64)
+    chosen = np.unique(np.concatenate([[0, w * h - 1], rows * w, rows * w + (w - 1), rows * w + 1, rows * w + (w - 2)]))
+    g = np.random.default_rng(5)
+    g.shuffle(chosen)
+    pixels = np.insert(chosen.astype(np.uint32), g.integers(0, chosen.size, 9), PAD)
+    got = listed(pixels, sentinel).view(torch.int64).reshape(w * h, 3)
+    idx = torch.from_numpy(chosen).cuda()
+    assert torch.equal(got[idx], want.view(torch.int64).reshape(w * h, 3)[idx])
+    assert int((got != sentinel).sum()) == 3 * chosen.size, "an unlisted pixel was written"
