@@ -396,6 +396,33 @@ int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, co
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8,
                                void *hip_stream);
 
+/* ---- views: many cameras of one scene in a single launch (opt-in; nothing above changes) ----------------------------------------
+ * A small frame does not fill the machine, and a caller who renders many of them — a turntable, a stereo pair, the faces of a cube map
+ * — pays launch, ramp-up, tail and summation once per frame.  rt_render_views_device renders n_views cameras of one scene as ONE job
+ * space (view v's tiles behind view v - 1's), so the machine stays full from the first view to the last.
+ *
+ * View v is, bit for bit, the frame rt_render gives under (views[v].camera, seed = views[v].seed): d_out[v * 3wh ..] equals what
+ * rt_render_device(scene, &views[v].camera, params with seed = views[v].seed, ...) writes there.  params->seed is IGNORED; sample_begin,
+ * sample_end, max_depth and accumulate mean what they mean for rt_render_device and apply to every view.  `views` is HOST memory and is
+ * copied during the call.  RT_ERR_INVALID_ARGUMENT (the message names the field), before any device work: n_views < 1; a null pointer;
+ * cameras that differ in image_width or image_height; cameras that differ in samples_per_pixel (max_depth) while params->sample_end
+ * (params->max_depth) is <= 0; shard_count > 1; an out_layout other than RT_OUT_FRAME.  RT_ERR_UNSUPPORTED, likewise before any
+ * allocation: n_views x tiles per frame >= RT_VIEWS_MAX_TILES — a job's row (tile x sample) must stay below 2^27 for the kernel's exact
+ * reciprocal decode and the job count, 64 per row, below 2^31 (the job index has 32 bits; launches keep half of them as headroom for
+ * the grabs past the end), at the one sample per launch that chunking can always fall back to —
+ * and, as for any render, a batch of which not even one sample per pixel fits the sample buffer.
+ * rt_render_views_device enqueues on hip_stream and does not synchronise; rt_render_views blocks and downloads (with accumulate set,
+ * `out` is uploaded first). */
+typedef struct rt_view {
+    rt_camera camera;
+    uint64_t seed;
+} rt_view;   /* view v is, bit for bit, the frame rt_render gives under (camera, seed) */
+#define RT_VIEWS_MAX_TILES (1 << 25) /* min(2^27 rows, 2^31 jobs / 64 per row) */
+int rt_render_views_device(const rt_scene *scene, const rt_view *views /* HOST, n_views entries, copied */, int32_t n_views,
+                           const rt_render_params *params, double *d_out /* n_views frames of 3*w*h doubles, view-major */, void *hip_stream);
+int rt_render_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params,
+                    double *out /* host */);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -35,6 +35,16 @@ void rth_scene_destroy(rth_scene *scene);
 /* Borrowed pointers, valid until rth_scene_destroy. */
 const rt_scene_desc *rth_scene_desc(const rth_scene *scene);
 const rt_camera *rth_scene_camera(const rth_scene *scene);
+/* Another view of the scene: Camera::new (src/camera.rs:54-110) over the CameraSettings the scene's builder used, with look_from and
+ * look_at replaced (NULL: the scene's own).  With both NULL, *out is byte-identical to *rth_scene_camera(scene).  What
+ * rt_render_views (rt_amd.h) takes one of per view. */
+int rth_scene_camera_look(const rth_scene *scene, const double look_from[3] /* NULL: the scene's */,
+                          const double look_at[3] /* NULL: the scene's */, rt_camera *out);
+/* The scene's own look_from, look_at and vup (each may be NULL): what a caller turns to place other views (rtrace --orbit). */
+int rth_scene_look(const rth_scene *scene, double look_from[3], double look_at[3], double vup[3]);
+/* View k of an n-view orbit (rtrace --orbit n): the scene's look_from turned about the axis through look_at along vup by 360 k / n
+ * degrees, counter-clockwise seen from vup's tip; k = 0 is look_from itself.  n >= 1. */
+int rth_scene_orbit_look_from(const rth_scene *scene, int32_t k, int32_t n, double out_look_from[3]);
 
 /* color_to_rgb(sum / spp) over a frame of per-pixel sums (src/renderer.rs:55-58, src/color.rs:12-19). */
 int rth_resolve_rgb8(int32_t width, int32_t height, int32_t spp, const double *rgb_sum, uint8_t *out_rgb8);

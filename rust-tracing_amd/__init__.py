@@ -134,6 +134,11 @@ class RenderParams(C.Structure):
                 ("shard_count", C.c_int32), ("out_layout", C.c_int32), ("device", C.c_int32)]
 
 
+class View(C.Structure):
+    """rt_view: one camera of rt_render_views with its seed."""
+    _fields_ = [("camera", Camera), ("seed", C.c_uint64)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "sphere_tests", "quad_tests",
                                           "medium_visits", "rng_draws", "noise_evals", "image_lookups",
@@ -260,6 +265,8 @@ RT_AMD_SYMBOLS = {
     "rt_render_adaptive_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_resolve_rgb8_spp_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_views_device": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
+    "rt_render_views": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -519,6 +526,9 @@ RT_HOST_SYMBOLS = {
     "rth_scene_destroy": (None, [C.c_void_p]),
     "rth_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),
     "rth_scene_camera": (C.POINTER(Camera), [C.c_void_p]),
+    "rth_scene_camera_look": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Camera)]),
+    "rth_scene_look": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rth_scene_orbit_look_from": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "rth_resolve_rgb8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
@@ -609,6 +619,58 @@ class HostScene:
             pass
 
 
+def camera_look(host_scene: HostScene, look_from=None, look_at=None) -> Camera:
+    """rth_scene_camera_look: the scene's camera with look_from and / or look_at replaced (None: the scene's own)."""
+    def vec(v):
+        return None if v is None else (C.c_double * 3)(*[float(x) for x in v])
+    cam = Camera()
+    lib = host_lib()
+    if lib.rth_scene_camera_look(host_scene._handle, vec(look_from), vec(look_at), C.byref(cam)) != 0:
+        raise RtError(lib.rth_last_error().decode(errors="replace"))
+    return cam
+
+
+def scene_look(host_scene: HostScene):
+    """rth_scene_look: the scene's own (look_from, look_at, vup), each a tuple of three floats."""
+    f, a, u = (C.c_double * 3)(), (C.c_double * 3)(), (C.c_double * 3)()
+    lib = host_lib()
+    if lib.rth_scene_look(host_scene._handle, f, a, u) != 0:
+        raise RtError(lib.rth_last_error().decode(errors="replace"))
+    return tuple(f), tuple(a), tuple(u)
+
+
+def orbit_look_from(host_scene: HostScene, k: int, n: int):
+    """rth_scene_orbit_look_from: the scene's look_from turned about the axis through look_at along vup by 360 k / n degrees (what
+    `rtrace --orbit n` gives view k)."""
+    out = (C.c_double * 3)()
+    lib = host_lib()
+    if lib.rth_scene_orbit_look_from(host_scene._handle, k, n, out) != 0:
+        raise RtError(lib.rth_last_error().decode(errors="replace"))
+    return tuple(out)
+
+
+def orbit_views(host_scene: HostScene, n: int, seed: int = 1, of: "int | None" = None):
+    """The n views of `rtrace --orbit n --seed seed`: a ctypes array of View, view k with seed + k.  With `of` > n they are the
+    first n of an `of`-view orbit, steps of 360 / of degrees: an arc, for a scene that is open to one side only."""
+    views = (View * n)()
+    for k in range(n):
+        views[k].camera = camera_look(host_scene, orbit_look_from(host_scene, k, n if of is None else of))
+        views[k].seed = seed + k
+    return views
+
+
+def _view_array(views):
+    if isinstance(views, C.Array) and views._type_ is View:
+        return views
+    arr = (View * len(views))()
+    for k, v in enumerate(views):
+        if isinstance(v, View):
+            arr[k] = v
+        else:  # (camera, seed)
+            arr[k].camera, arr[k].seed = v[0], v[1]
+    return arr
+
+
 def render_params(*, seed=1, sample_begin=0, sample_end=0, max_depth=0, accumulate=False, shard_index=0,
                   shard_count=1, out_layout=RT_OUT_FRAME, device=0) -> RenderParams:
     return RenderParams(seed=seed, sample_begin=sample_begin, sample_end=sample_end, max_depth=max_depth,
@@ -670,6 +732,30 @@ class DeviceScene:
                                                   C.c_void_p(d_out_ptr), C.c_void_p(stream), C.byref(cnt)),
                "rt_render_device_counted")
         return cnt.as_dict()
+
+    def render_views(self, params: RenderParams, views, out=None):
+        """rt_render_views: every view's frame from one launch, as an (n_views, h, w, 3) float64 array.  `views`: View records (or
+        (camera, seed) pairs); view v equals render() under that camera with seed = that seed (params.seed is ignored).  `out`: the
+        array to write (with params.accumulate: the running sums this call adds to, so it is required then); returned."""
+        import numpy as np
+        arr = _view_array(views)
+        n = len(arr)
+        h, w = (arr[0].camera.image_height, arr[0].camera.image_width) if n else (0, 0)
+        if out is None:
+            if params.accumulate:
+                raise RtError("render_views: params.accumulate adds to running sums: pass them as `out`")
+            out = np.zeros((n, h, w, 3), dtype=np.float64)
+        elif out.shape != (n, h, w, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise RtError(f"render_views: `out` must be a writable C-contiguous float64 array of shape {(n, h, w, 3)}")
+        _check(amd_lib().rt_render_views(self._handle, arr, n, C.byref(params), C.c_void_p(out.ctypes.data)), "rt_render_views")
+        return out
+
+    def render_views_device(self, params: RenderParams, views, d_out_ptr: int, stream: int = 0):
+        """rt_render_views_device: `d_out_ptr` is device memory for n_views frames of 3 w h doubles, view-major; enqueued on
+        `stream` without synchronising (the view records are copied during the call)."""
+        arr = _view_array(views)
+        _check(amd_lib().rt_render_views_device(self._handle, arr, len(arr), C.byref(params), C.c_void_p(d_out_ptr),
+                                                C.c_void_p(stream)), "rt_render_views_device")
 
     def render_pixels_device(self, params: RenderParams, d_pixels_ptr: int, n_pixels: int, d_sum_ptr: int,
                              d_sum_sq_ptr: int = 0, stream: int = 0, camera: Camera | None = None):

@@ -125,6 +125,9 @@ void free_workspace(Workspace &w) {
     if (w.ev_start) (void)hipEventDestroy(w.ev_start);
     if (w.ev_done) (void)hipEventDestroy(w.ev_done);
     (void)hipFree(w.counters);
+    (void)hipFree(w.views);
+    if (w.views_host) (void)hipHostFree(w.views_host);
+    if (w.ev_views) (void)hipEventDestroy(w.ev_views);
     w = Workspace();
 }
 } // namespace rtapi
@@ -186,14 +189,25 @@ constexpr size_t MAX_WORKSPACES = 4; // per scene: one per stream in use; beyond
 // List mode (rt_render_pixels_device): the render's "local tiles" are groups of 64 entries of a pixel list, and the sums (and,
 // optionally, the sums of squares) go to the listed pixels of a frame.  Everything else — chunks, pipelining, scratch, grid — is
 // the dense render's, with n_local = the number of groups.
+// a launch's jobs: the job index has 32 bits, and half of them stay free for the grabs past the end
+constexpr int64_t MAX_JOBS_PER_LAUNCH = (int64_t)1 << 31;
+
 struct PixelList {
     const uint32_t *pixels;
     int64_t n;
     double *d_sum_sq; // or null
 };
 
+// Views mode (rt_render_views_device): the render's "local tiles" are the tiles of view 0's frame, then view 1's, ...; `camera` is
+// view 0's (what the views share: frame size, and the defaults of the sample range and the depth); the sums go to one frame per view.
+// The records are copied to the workspace per call.  Everything else is the dense render's, with n_local = views x tiles of a frame.
+struct ViewTable {
+    const ViewRec *recs; // host
+    int64_t n;
+};
+
 int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, double *d_out, hipStream_t stream,
-                  rt_counters *out_counters, const PixelList *list = nullptr) {
+                  rt_counters *out_counters, const PixelList *list = nullptr, const ViewTable *views = nullptr) {
     int rc = normalise_params(camera, p);
     if (rc != RT_OK) return rc;
     if (list && (p.shard_count != 1 || p.out_layout != RT_OUT_FRAME))
@@ -202,7 +216,9 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_pixels_device: a pixel list needs an image of fewer than 2^27 pixels");
     HIP_TRY(hipSetDevice(scene->device));
     const bool counted = out_counters != nullptr;
-    const int64_t n_local = list ? (list->n + 63) / 64 : tiles_local(camera->image_width, camera->image_height, p.shard_index, p.shard_count);
+    const int64_t tiles_per_view = tiles_total(camera->image_width, camera->image_height);
+    const int64_t n_local = views ? views->n * tiles_per_view
+                                  : list ? (list->n + 63) / 64 : tiles_local(camera->image_width, camera->image_height, p.shard_index, p.shard_count);
     const int64_t n_samples_total = (int64_t)p.sample_end - p.sample_begin;
     if (n_local <= 0 || n_samples_total <= 0) {
         if (out_counters) *out_counters = rt_counters{};
@@ -213,7 +229,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     // samples per launch: bounded by the sample buffer and by the 32-bit job index.  A frame that needs more than one launch is
     // pipelined over two scratch sets (half the budget each) unless that is switched off or the kernel is the instrumented one.
     const int64_t bytes_per_sample_row = n_local * 64 * 3 * (int64_t)sizeof(double);
-    const int64_t max_by_index = ((int64_t)1 << 31) / (n_local * 64);
+    const int64_t max_by_index = MAX_JOBS_PER_LAUNCH / (n_local * 64);
     auto chunk_for = [&](size_t budget) {
         int64_t c = (int64_t)(budget / (size_t)bytes_per_sample_row);
         if (c > max_by_index) c = max_by_index;
@@ -358,10 +374,32 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
             if (!x.job_counter) HIP_TRY(hipMalloc((void **)&x.job_counter, sizeof(uint32_t)));
         }
         if (!w.counters) HIP_TRY(hipMalloc((void **)&w.counters, COUNTER_WORDS * sizeof(unsigned long long)));
+        if (views && w.views_bytes < (size_t)views->n * sizeof(ViewRec)) {
+            if ((rc = drain()) != RT_OK) return rc;
+            if (w.views) HIP_TRY(hipFree(w.views));
+            w.views = nullptr; w.views_bytes = 0;
+            if (w.views_host) HIP_TRY(hipHostFree(w.views_host));
+            w.views_host = nullptr;
+            HIP_TRY(hipMalloc((void **)&w.views, (size_t)views->n * sizeof(ViewRec)));
+            HIP_TRY(hipHostMalloc((void **)&w.views_host, (size_t)views->n * sizeof(ViewRec), hipHostMallocDefault));
+            w.views_bytes = (size_t)views->n * sizeof(ViewRec);
+        }
+        if (views) {
+            if (!w.ev_views) HIP_TRY(hipEventCreateWithFlags(&w.ev_views, hipEventDisableTiming));
+            // the staging copy is the slot's own pinned memory: the call's records go there once the previous call's upload has run
+            // (that upload sits ahead of its own render's kernels, so one views render may be in flight while the next is enqueued)
+            HIP_TRY(hipEventSynchronize(w.ev_views));
+            memcpy(w.views_host, views->recs, (size_t)views->n * sizeof(ViewRec));
+        }
         ws = w;
     }
     release.enqueued = true; // (from here on something may be in flight on `stream` or the internal streams)
     if (counted) HIP_TRY(hipMemsetAsync(ws.counters, 0, COUNTER_WORDS * sizeof(unsigned long long), stream));
+    // (in stream order behind the previous render's reads of the table; from pinned memory, so a true asynchronous copy)
+    if (views) {
+        HIP_TRY(hipMemcpyAsync(ws.views, ws.views_host, (size_t)views->n * sizeof(ViewRec), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(ws.ev_views, stream));
+    }
 
     KParams K{};
     K.nodes = scene->nodes.ptr; K.spheres = scene->spheres.ptr; K.quads = scene->quads.ptr; K.insts = scene->insts.ptr;
@@ -383,6 +421,9 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     if (list) {
         K.pixel_list = list->pixels; K.n_list = (uint32_t)list->n; K.out_sq = list->d_sum_sq;
         K.inv_width = 1.0 / (double)camera->image_width;
+    }
+    if (views) {
+        K.views = ws.views; K.tiles_per_view = (uint32_t)tiles_per_view; K.inv_tiles_per_view = 1.0 / (double)tiles_per_view;
     }
     K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = lds_image_bytes_for(scene, lds);
     K.lds_off_node_b = scene->lds_off_node_b;
@@ -456,12 +497,13 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         {
             void *args[] = {(void *)&K};
             const uint32_t kf = kernel_features_for(scene->features, lds, scene->ordered);
-            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, list != nullptr);
+            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, views ? JOBS_VIEWS : list ? JOBS_LIST : JOBS_DENSE);
             HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, dyn_lds, s));
         }
         HIP_TRY(hipGetLastError());
         if (pipelined && k > 0) HIP_TRY(hipStreamWaitEvent(s, ws.ev_sum[h ^ 1], 0));
-        if (list) launch_sum_listed_samples(K, sum_grid, s);
+        if (views) launch_sum_view_samples(K, sum_grid, s);
+        else if (list) launch_sum_listed_samples(K, sum_grid, s);
         else launch_sum_samples(K, sum_grid, s);
         HIP_TRY(hipGetLastError());
         if (pipelined) HIP_TRY(hipEventRecord(ws.ev_sum[h], s));
@@ -1177,6 +1219,93 @@ int rt_render_pixels_device(const rt_scene *scene, const rt_camera *camera, cons
     if (n_pixels == 0) return RT_OK;
     const PixelList list{d_pixels, n_pixels, d_sum_sq};
     return launch_render(const_cast<rt_scene *>(scene), camera, *params, d_sum, (hipStream_t)hip_stream, nullptr, &list);
+}
+
+// ---- views: many cameras, one launch ----
+namespace {
+// What the job arithmetic holds, at the one sample per launch that chunking can always fall back to: a job's row (local tile x sample)
+// below 2^27 for the exact reciprocal decode, and n_jobs = 64 rows below what launch_render puts into one launch.
+constexpr int64_t VIEWS_MAX_ROWS = (int64_t)1 << 27, VIEWS_MAX_JOBS = MAX_JOBS_PER_LAUNCH;
+constexpr int64_t VIEWS_MAX_TILES = (VIEWS_MAX_ROWS < VIEWS_MAX_JOBS / 64 ? VIEWS_MAX_ROWS : VIEWS_MAX_JOBS / 64) - 1; // n_views x tiles per frame at most
+static_assert(VIEWS_MAX_TILES + 1 == RT_VIEWS_MAX_TILES, "rt_amd.h states the bound");
+
+// every check of rt_render_views / rt_render_views_device that needs no device; fills the records
+int check_views(const rt_view *views, int32_t n_views, const rt_render_params *params, const char *who, std::vector<ViewRec> &recs) {
+    const std::string w(who);
+    if (n_views < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
+    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (views are not sharded)");
+    if (params->out_layout != RT_OUT_FRAME) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_layout must be RT_OUT_FRAME");
+    const rt_camera &c0 = views[0].camera;
+    if (c0.image_width <= 0 || c0.image_height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": empty image");
+    const int64_t tiles = tiles_total(c0.image_width, c0.image_height);
+    // (before the loop over the views: a count this large need not have that many entries behind it)
+    if ((int64_t)n_views > VIEWS_MAX_TILES / tiles)
+        return fail(RT_ERR_UNSUPPORTED, w + ": n_views x tiles per frame exceeds " + std::to_string(VIEWS_MAX_TILES) + " (the job index's 32 bits)");
+    for (int32_t v = 1; v < n_views; ++v) {
+        const rt_camera &c = views[v].camera;
+        const std::string at = w + ": views[" + std::to_string(v) + "].camera.";
+        if (c.image_width != c0.image_width) return fail(RT_ERR_INVALID_ARGUMENT, at + "image_width differs from view 0's");
+        if (c.image_height != c0.image_height) return fail(RT_ERR_INVALID_ARGUMENT, at + "image_height differs from view 0's");
+        if (params->sample_end <= 0 && c.samples_per_pixel != c0.samples_per_pixel)
+            return fail(RT_ERR_INVALID_ARGUMENT, at + "samples_per_pixel differs from view 0's and params->sample_end does not set it");
+        if (params->max_depth <= 0 && c.max_depth != c0.max_depth)
+            return fail(RT_ERR_INVALID_ARGUMENT, at + "max_depth differs from view 0's and params->max_depth does not set it");
+    }
+    recs.resize((size_t)n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        memset(&recs[(size_t)v], 0, sizeof(ViewRec));
+        recs[(size_t)v].cam = views[v].camera;
+        recs[(size_t)v].seed_mixed = host_mix64(views[v].seed + 0x9E3779B97F4A7C15ull);
+    }
+    return RT_OK;
+}
+} // namespace
+
+int rt_render_views_device(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *d_out,
+                           void *hip_stream) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: scene is null");
+    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: views is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: params is null");
+    if (!d_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: d_out is null");
+    g_last_launch[0] = 0; // (rt_debug_last_launch: a call that is refused has launched nothing)
+    std::vector<ViewRec> recs;
+    if (int rc = check_views(views, n_views, params, "rt_render_views_device", recs)) return rc;
+    rt_render_params p = *params;
+    p.shard_index = 0; p.shard_count = 1;
+    const ViewTable table{recs.data(), n_views};
+    return launch_render(const_cast<rt_scene *>(scene), &views[0].camera, p, d_out, (hipStream_t)hip_stream, nullptr, nullptr, &table);
+}
+
+int rt_render_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *out) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: scene is null");
+    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: views is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: params is null");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: out is null");
+    g_last_launch[0] = 0;
+    std::vector<ViewRec> recs;
+    if (int rc = check_views(views, n_views, params, "rt_render_views", recs)) return rc;
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    std::lock_guard<std::mutex> serial(s->host_render_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)n_views * (size_t)views[0].camera.image_width * (size_t)views[0].camera.image_height * 3u * sizeof(double);
+    double *d_out = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_out, bytes));
+    int rc = RT_OK;
+    do {
+        if (params->accumulate && hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            rc = fail(RT_ERR_HIP, "rt_render_views: upload of running sums failed");
+            break;
+        }
+        rt_render_params p = *params;
+        p.shard_index = 0; p.shard_count = 1;
+        const ViewTable table{recs.data(), n_views};
+        rc = launch_render(s, &views[0].camera, p, d_out, nullptr, nullptr, nullptr, &table);
+        if (rc != RT_OK) break;
+        const hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string("rt_render_views: ") + hipGetErrorString(e));
+    } while (0);
+    (void)hipFree(d_out);
+    return rc;
 }
 
 int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,

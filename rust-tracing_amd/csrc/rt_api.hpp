@@ -50,6 +50,10 @@ struct Workspace {
                                                   // eviction waits for (the caller's stream handle itself is never touched again)
     size_t sample_budget = 0;                     // > 0: the sample buffer size an out-of-memory back-off arrived at
     unsigned long long *counters = nullptr;
+    ViewRec *views = nullptr;                     // views mode: the call's view records (KParams::views); grows on demand
+    size_t views_bytes = 0;
+    ViewRec *views_host = nullptr;                // pinned staging copy of the same size: what the upload reads after the call returns
+    hipEvent_t ev_views = nullptr;                // recorded behind that upload: the next call waits for it before it rewrites views_host
 };
 void free_workspace(Workspace &w);
 // One per (scene, stream).  rt_scene::mu guards only the table and `in_use`; everything slow — draining the stream before a buffer

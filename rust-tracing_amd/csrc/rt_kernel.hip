@@ -48,14 +48,25 @@ enum Terminal : uint32_t { TERM_BACKGROUND = 0, TERM_ONE = 1, TERM_ZERO = 2, TER
 // frame: not worth it.  The LDS-resident every-feature kernels, whose scenes are small, do run four waves: rt_kernels.h.)
 #endif
 
+// the camera Camera::get_ray reads: the kernel arguments' (in the constant address space), or — views mode — the job's view's
+template <bool VIEWS> struct CamOf {
+    static __device__ __forceinline__ const rt_camera __attribute__((address_space(4))) &get(const KParams __attribute__((address_space(4))) *KP, const ViewRec *) { return KP->cam; }
+};
+template <> struct CamOf<true> {
+    static __device__ __forceinline__ const rt_camera &get(const KParams __attribute__((address_space(4))) *, const ViewRec *vr) { return vr->cam; }
+};
+
 // LDS: 0 = scene gathered from global memory; 1 = node table in LDS; 2 = + sphere table; 3 = + quad table
 // ORDERED: walk the compiler's own trees nearest child first (scenes without a ConstantMedium), else the threaded
 // records in the reference's order
 // AUX: the small tables (materials, textures, frames, media, Perlin) are copied into the LDS too — for scenes whose big
 // tables do not fit there, so that a hit's material -> texture -> noise chain is not three trips to memory
 // WIDE: the ordered walk's records hold four children (rt_layout.h ONode4) instead of two
-template <bool COUNT, int LDS, int THREADS, uint32_t FEAT, bool ORDERED, bool AUX = false, bool WIDE = false, bool LIST = false>
+// JOBS: what a "local tile" of the job space is (rt_kernels.h JobMode): a tile of the frame, a group of 64 entries of a pixel list, or a
+// tile of one of several views of the scene.  Only the path-end block reads it.
+template <bool COUNT, int LDS, int THREADS, uint32_t FEAT, bool ORDERED, bool AUX = false, bool WIDE = false, int JOBS = JOBS_DENSE>
 __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(const KParams P) {
+    constexpr bool LIST = JOBS == JOBS_LIST, VIEWS = JOBS == JOBS_VIEWS;
     constexpr bool HAS_SPHERES = (FEAT & F_SPHERES) != 0, HAS_QUADS = (FEAT & F_QUADS) != 0, HAS_FRAMES = (FEAT & F_FRAMES) != 0,
                    HAS_MEDIA = (FEAT & F_MEDIA) != 0, HAS_TEXTURES = (FEAT & F_TEXTURES) != 0;
     constexpr bool HAS_OTHER = HAS_FRAMES || HAS_MEDIA;
@@ -1041,6 +1052,16 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             if (here && term != TERM_STORED) {
                 V3 result = v3(0.0, 0.0, 0.0);
                 if (term != TERM_ZERO) {
+                    if constexpr (VIEWS) {
+                        // the background is the view's: the view is worked out again from `job`, which is live here anyway (it addresses
+                        // the sample store), instead of sitting in a register through every other stage
+                        result = v3(1.0, 1.0, 1.0);
+                        if (term == TERM_BACKGROUND) {
+                            const uint32_t lt = (uint32_t)(((double)(job >> 6) + 0.5) * KP->inv_n_samples);
+                            const ViewRec *vr = KP->views + (uint32_t)(((double)lt + 0.5) * KP->inv_tiles_per_view);
+                            result = v3(vr->cam.background.x, vr->cam.background.y, vr->cam.background.z);
+                        }
+                    } else
                     result = term == TERM_BACKGROUND ? v3(KP->cam.background.x, KP->cam.background.y, KP->cam.background.z) : v3(1.0, 1.0, 1.0);
                     // the parked attenuations, last parked first.  The newest four indices sit at fixed places of the two registers:
                     // their colours are fetched together and multiplied on one after the other (a level the path does not have reads
@@ -1115,7 +1136,18 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         // integer, far more than the 2^-52 relative error of the product — exact, and 4 instructions, not 25
                         const uint32_t lt = (uint32_t)(((double)row + 0.5) * KP->inv_n_samples), s_rel = row - lt * KP->n_samples;
                         int32_t i, j;
-                        if constexpr (LIST) { // list mode (its own instantiations: the dense kernels keep their registers): group lt is list entries [64 lt, 64 lt + 64)
+                        // views mode: the record of this job's view (camera, seed).  Lanes of one wave sit in different views: a per-lane
+                        // pointer into global memory, read with vector loads where Camera::get_ray needs the fields.  (Frame size, depth
+                        // and the sample range are the same for every view and stay in the kernel arguments.)
+                        const ViewRec *vr = nullptr;
+                        if constexpr (VIEWS) { // local tile lt is tile k of view lt / tiles_per_view: the same exact reciprocal (lt < 2^27)
+                            const uint32_t view = (uint32_t)(((double)lt + 0.5) * KP->inv_tiles_per_view);
+                            const uint32_t k = lt - view * KP->tiles_per_view;
+                            const uint32_t tile_row = (uint32_t)(((double)k + 0.5) * KP->inv_tiles_x), tile_col = k - tile_row * (uint32_t)KP->tiles_x;
+                            i = (int32_t)tile_col * RT_TILE_W + (int32_t)(p64 & 7u);
+                            j = (int32_t)tile_row * RT_TILE_H + (int32_t)(p64 >> 3);
+                            vr = KP->views + view;
+                        } else if constexpr (LIST) { // list mode (its own instantiations: the dense kernels keep their registers): group lt is list entries [64 lt, 64 lt + 64)
                             const uint32_t q = lt * 64u + p64;
                             const uint32_t e = q < KP->n_list ? KP->pixel_list[q] : 0xffffffffu;
                             // the same exact reciprocal trick (e < w * h < 2^27); an entry outside the frame (padding) gets j = h
@@ -1131,9 +1163,10 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         }
                         if (i < KP->cam.image_width && j < KP->cam.image_height) {
                             const uint32_t pixel = (uint32_t)j * (uint32_t)KP->cam.image_width + (uint32_t)i; // screen_pos (src/renderer.rs:32-33)
-                            rng.start(KP->seed_mixed, pixel, (uint32_t)KP->sample_begin + s_rel);
-                            // Camera::get_ray (src/camera.rs:112-137)
-                            const rt_camera __attribute__((address_space(4))) &cam = KP->cam;
+                            if constexpr (VIEWS) rng.start(vr->seed_mixed, pixel, (uint32_t)KP->sample_begin + s_rel);
+                            else rng.start(KP->seed_mixed, pixel, (uint32_t)KP->sample_begin + s_rel);
+                            // Camera::get_ray (src/camera.rs:112-137): the camera of the kernel arguments, or the view's
+                            const std::conditional_t<VIEWS, rt_camera, rt_camera __attribute__((address_space(4)))> &cam = CamOf<VIEWS>::get(KP, vr);
                             const V3 du = v3(cam.pixel_delta_u.x, cam.pixel_delta_u.y, cam.pixel_delta_u.z), dv = v3(cam.pixel_delta_v.x, cam.pixel_delta_v.y, cam.pixel_delta_v.z);
                             const V3 pixel_center = v3(cam.pixel00_loc.x, cam.pixel00_loc.y, cam.pixel00_loc.z) + du * (double)i + dv * (double)j;
                             const double px = -0.5 + rng.random();
@@ -1307,6 +1340,28 @@ __global__ void sum_samples_kernel(const KParams P) {
         if (dst) { dst[0] = 0.0; dst[1] = 0.0; dst[2] = 0.0; }
         return;
     }
+    V3 acc = v3(0.0, 0.0, 0.0);
+    if (P.accumulate) acc = v3(dst[0], dst[1], dst[2]);
+    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
+    for (uint32_t s = 0; s < P.n_samples; ++s) {
+        acc = acc + v3(src[0], src[1], src[2]);
+        src += 64u * 3u;
+    }
+    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
+}
+
+// sum_samples_kernel for views mode: local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view, whose frame starts
+// 3 * w * h doubles behind the previous view's.  One thread per (local tile, pixel of the tile); padding pixels of edge tiles are not written.
+__global__ void sum_view_samples_kernel(const KParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lt = idx >> 6, p64 = idx & 63u;
+    if (lt >= P.n_local_tiles) return;
+    const int32_t w = P.cam.image_width, h = P.cam.image_height;
+    const uint32_t view = lt / P.tiles_per_view, k = lt - view * P.tiles_per_view;
+    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    if (i >= w || j >= h) return;
+    double *dst = P.out + (size_t)view * ((size_t)w * (size_t)h * 3u) + ((size_t)j * (size_t)w + (size_t)i) * 3u;
     V3 acc = v3(0.0, 0.0, 0.0);
     if (P.accumulate) acc = v3(dst[0], dst[1], dst[2]);
     const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
@@ -1623,10 +1678,11 @@ int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered) {
     if (kernel_features == FEAT_SPHERES_QUADS_TEXTURES && !ordered) return REFERENCE_TEXTURES_THREADS;
     return kernel_features == FEAT_SPHERES_SOLID ? LDS_THREADS : LDS_THREADS_GENERAL;
 }
-const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, bool list) {
-// (list mode: rt_render_pixels_device; never counted)
-#define RT_PICK(L, T, F, O, A) (list ? (const void *)path_kernel<false, L, T, F, O, A, false, true> : counted ? (const void *)path_kernel<true, L, T, F, O, A> : (const void *)path_kernel<false, L, T, F, O, A>)
-#define RT_PICK_W(L, T, F, A) (list ? (const void *)path_kernel<false, L, T, F, true, A, true, true> : counted ? (const void *)path_kernel<true, L, T, F, true, A, true> : (const void *)path_kernel<false, L, T, F, true, A, true>)
+const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, int jobs) {
+// (list mode: rt_render_pixels_device; views mode: rt_render_views_device; neither is ever counted)
+    const bool list = jobs == JOBS_LIST, views = jobs == JOBS_VIEWS;
+#define RT_PICK(L, T, F, O, A) (views ? (const void *)path_kernel<false, L, T, F, O, A, false, JOBS_VIEWS> : list ? (const void *)path_kernel<false, L, T, F, O, A, false, JOBS_LIST> : counted ? (const void *)path_kernel<true, L, T, F, O, A> : (const void *)path_kernel<false, L, T, F, O, A>)
+#define RT_PICK_W(L, T, F, A) (views ? (const void *)path_kernel<false, L, T, F, true, A, true, JOBS_VIEWS> : list ? (const void *)path_kernel<false, L, T, F, true, A, true, JOBS_LIST> : counted ? (const void *)path_kernel<true, L, T, F, true, A, true> : (const void *)path_kernel<false, L, T, F, true, A, true>)
 #define RT_PICK_AUX(L, T, F) (wide ? (aux ? RT_PICK_W(L, T, F, true) : RT_PICK_W(L, T, F, false)) : (aux ? RT_PICK(L, T, F, true, true) : RT_PICK(L, T, F, true, false)))
     if (ordered) { // (AUX: the small tables in the LDS as well, wherever they fit — rt_api.cpp decides)
         if (lds == 3) {
@@ -1656,6 +1712,9 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
+void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_view_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
 }
 void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_listed_samples_kernel, dim3(grid), dim3(256), 0, stream, K);

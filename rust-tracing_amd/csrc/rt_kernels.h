@@ -24,6 +24,19 @@ struct DMaterial { // 64 bytes
 };
 static_assert(sizeof(DMaterial) == 64, "DMaterial must be 64 bytes");
 
+// What a "local tile" of a render's job space is (path_kernel's JOBS): a tile of the frame; a group of 64 entries of a pixel list
+// (rt_render_pixels_device); a tile of one of several views of the scene, view v's tiles behind view v - 1's (rt_render_views_device)
+enum JobMode : int { JOBS_DENSE = 0, JOBS_LIST = 1, JOBS_VIEWS = 2 };
+
+// views mode: what a lane needs of its job's view, one record per view (lanes of one wave sit in different views, so the record is read
+// from global memory per lane: 16-byte aligned and padded, for the widest vector loads)
+struct alignas(16) ViewRec {
+    rt_camera cam;
+    uint64_t seed_mixed; // mix64(seed + gamma) of the view's seed
+    uint64_t _pad;
+};
+static_assert(sizeof(ViewRec) == 208 && sizeof(ViewRec) % 16 == 0, "ViewRec: a whole number of 16-byte pieces");
+
 struct KParams {
     const Node32 *nodes;
     const Sphere *spheres;
@@ -96,6 +109,11 @@ struct KParams {
     uint32_t n_list;                // entries of pixel_list (the groups beyond it are padding)
     double inv_width;               // 1 / image_width (list mode's pixel -> (i, j) decode; exact for w * h < 2^27)
     double *out_sq;                 // list mode: per-pixel sums of the squared sample colours beside `out`, or null
+    // views mode (rt_render_views_device; path_kernel<..., JOBS_VIEWS>): local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view.
+    // `cam` then holds what the views share (frame size); camera and seed of a job come from its view's record.  No other instantiation reads these.
+    const ViewRec *views;
+    double inv_tiles_per_view;      // 1 / tiles_per_view (exact decode for lt < 2^27)
+    uint32_t tiles_per_view;
 };
 
 // What a scene can contain.  A kernel instantiated without a feature has that code compiled out, which matters for
@@ -153,11 +171,12 @@ constexpr uint32_t FEAT_QUADS_FRAMES_MEDIA = F_QUADS | F_FRAMES | F_MEDIA;      
 constexpr uint32_t FEAT_SPHERES_QUADS_TEXTURES = F_SPHERES | F_QUADS | F_TEXTURES;    // two_spheres, earth, two_perlin_spheres, simple_light
 uint32_t kernel_features_for(uint32_t scene_features, int lds, bool ordered);
 int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered); // workgroup size of that instantiation
-const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, bool list = false);
+const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, int jobs = JOBS_DENSE);
 
 // launches of the small kernels (all asynchronous on `stream`; errors through hipGetLastError)
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream);
 void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream);
+void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream);
 // adaptive sampling (rt_render_adaptive_device): the list of every pixel in tile order; one convergence step over an active list
 // (spp of the pixels that leave, the survivors compacted in order into list_out, padded to a multiple of 64, their count in *count);
 // the resolve with a per-pixel sample count

@@ -19,13 +19,29 @@ struct CameraSettings { // defaults: src/camera.rs:21-37
     Color background = Color::ZERO();
 };
 
+// look_from turned about the axis through look_at along vup by 360 k / n degrees (rtrace --orbit, rth_scene_orbit_look_from): theta = 2 pi k / n; a = vup / |vup|; p = look_from - look_at;
+// p' = p cos(theta) + (a x p) sin(theta) + a ((a . p) (1 - cos(theta))); result = look_at + p'.  k = 0 is look_from itself.
+inline Point3 orbit_look_from(const Point3 &look_from, const Point3 &look_at, const Vec3 &vup, int k, int n) {
+    if (k == 0) return look_from;
+    const FP theta = 2.0 * 3.14159265358979323846264338327950288 * (FP)k / (FP)n;
+    const FP c = std::cos(theta), s = std::sin(theta);
+    const FP len = std::sqrt(vup.x * vup.x + vup.y * vup.y + vup.z * vup.z);
+    const FP ax = vup.x / len, ay = vup.y / len, az = vup.z / len;
+    const FP px = look_from.x - look_at.x, py = look_from.y - look_at.y, pz = look_from.z - look_at.z;
+    const FP cx = ay * pz - az * py, cy = az * px - ax * pz, cz = ax * py - ay * px;
+    const FP t = (ax * px + ay * py + az * pz) * (1.0 - c);
+    return Point3(look_at.x + (px * c + cx * s + ax * t), look_at.y + (py * c + cy * s + ay * t), look_at.z + (pz * c + cz * s + az * t));
+}
+
 class Camera {
   public:
     size_t image_width, image_height;
     int32_t samples_per_pixel, max_depth;
     Color background;
+    CameraSettings settings; // what this camera was made from: another view of the scene is Camera(settings with other look points)
 
     explicit Camera(const CameraSettings &s) {
+        settings = s;
         image_width = s.image_width;
         samples_per_pixel = s.samples_per_pixel;
         max_depth = s.max_depth;

@@ -67,6 +67,33 @@ void rth_scene_destroy(rth_scene *scene) { delete scene; }
 const rt_scene_desc *rth_scene_desc(const rth_scene *scene) { return scene ? &scene->desc : nullptr; }
 const rt_camera *rth_scene_camera(const rth_scene *scene) { return scene ? &scene->cam : nullptr; }
 
+int rth_scene_camera_look(const rth_scene *scene, const double look_from[3], const double look_at[3], rt_camera *out) {
+    if (!scene || !out) return fail("rth_scene_camera_look: null argument");
+    CameraSettings s = scene->camera->settings;
+    if (look_from) s.look_from = Point3(look_from[0], look_from[1], look_from[2]);
+    if (look_at) s.look_at = Point3(look_at[0], look_at[1], look_at[2]);
+    *out = Camera(s).pod();
+    return 0;
+}
+
+int rth_scene_look(const rth_scene *scene, double look_from[3], double look_at[3], double vup[3]) {
+    if (!scene) return fail("rth_scene_look: null argument");
+    const CameraSettings &s = scene->camera->settings;
+    if (look_from) { look_from[0] = s.look_from.x; look_from[1] = s.look_from.y; look_from[2] = s.look_from.z; }
+    if (look_at) { look_at[0] = s.look_at.x; look_at[1] = s.look_at.y; look_at[2] = s.look_at.z; }
+    if (vup) { vup[0] = s.vup.x; vup[1] = s.vup.y; vup[2] = s.vup.z; }
+    return 0;
+}
+
+int rth_scene_orbit_look_from(const rth_scene *scene, int32_t k, int32_t n, double out_look_from[3]) {
+    if (!scene || !out_look_from) return fail("rth_scene_orbit_look_from: null argument");
+    if (n < 1) return fail("rth_scene_orbit_look_from: n must be at least 1");
+    const CameraSettings &s = scene->camera->settings;
+    const Point3 p = orbit_look_from(s.look_from, s.look_at, s.vup, k, n);
+    out_look_from[0] = p.x; out_look_from[1] = p.y; out_look_from[2] = p.z;
+    return 0;
+}
+
 int rth_resolve_rgb8(int32_t width, int32_t height, int32_t spp, const double *rgb_sum, uint8_t *out_rgb8) {
     if (!rgb_sum || !out_rgb8 || width <= 0 || height <= 0 || spp <= 0) return fail("rth_resolve_rgb8: bad argument");
     const size_t n = (size_t)width * (size_t)height;

@@ -3,7 +3,8 @@
 //   on a GPU node).  Added: --width/--aspect/--spp/--depth (BASELINE.json's configs change these),
 //   --seed/--scene-seed, --gpus, --earth PATH|synthetic:WxH, --bvh reference|sah, --progressive N (rewrite the PNG
 //   every N samples per pixel: what -l/--live shows in a window, written to the file instead), --adaptive REL
-//   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum).
+//   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum),
+//   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 #include "renderer.hpp"
 #include "scenes.hpp"
 #include <chrono>
@@ -19,6 +20,8 @@ static void usage(const char *argv0) {
             "Usage: %s [-s SCENE] [-o OUTPUT] [--width W] [--aspect A] [--spp N] [--depth D]\n"
             "          [--seed S] [--scene-seed S] [--gpus N] [--progressive SPP_PER_PASS] [--earth PATH|synthetic:WxH] [--bvh reference|sah]\n"
             "          [--adaptive REL [--adaptive-abs A] [--min-spp N] [--batch-spp N]]   (one GPU; --spp is the maximum)\n"
+            "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
+            "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -54,6 +57,10 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-abs") ro.adaptive_abs = atof(need("--adaptive-abs"));
         else if (a == "--min-spp") ro.min_spp = atoi(need("--min-spp"));
         else if (a == "--batch-spp") ro.batch_spp = atoi(need("--batch-spp"));
+        else if (a == "--orbit") {
+            ro.orbit = atoi(need("--orbit"));
+            if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -62,6 +69,11 @@ int main(int argc, char **argv) {
     printf("Args: { live: %s, scene: %d, output: \"%s\" }\n", live ? "true" : "false", scene, output.c_str());
     if (ro.adaptive && (ro.gpus > 1 || ro.progressive_spp > 0)) {
         fprintf(stderr, "--adaptive renders on one GPU in one pass: it cannot be combined with --gpus > 1 or --progressive\n");
+        return 2;
+    }
+    if (ro.orbit > 0 && (ro.gpus > 1 || ro.progressive_spp > 0 || ro.adaptive)) {
+        fprintf(stderr, "--orbit renders every view on one GPU in one launch: it cannot be combined with --gpus > 1, --progressive or --adaptive\n");
+        usage(argv[0]);
         return 2;
     }
     if (live) {

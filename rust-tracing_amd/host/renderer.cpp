@@ -167,11 +167,57 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     return px;
 }
 
+// An orbit on device 0: every view's frame in one rt_render_views call, one PNG per view.
+static void render_orbit(const Camera &camera, const Hittable &world, const std::string &output_file_name, const RenderOptions &opt) {
+    using clock = std::chrono::steady_clock;
+    auto now = clock::now();
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    std::vector<rt_view> views((size_t)opt.orbit);
+    for (int k = 0; k < opt.orbit; ++k) {
+        CameraSettings s = camera.settings;
+        s.look_from = orbit_look_from(camera.settings.look_from, camera.settings.look_at, camera.settings.vup, k, opt.orbit);
+        views[(size_t)k].camera = Camera(s).pod();
+        views[(size_t)k].seed = opt.seed + (uint64_t)k;
+    }
+    const rt_camera &cam = views[0].camera;
+    const size_t frame = (size_t)cam.image_width * (size_t)cam.image_height * 3u;
+    std::vector<double> sums(frame * views.size(), 0.0);
+    rt_scene *scene = nullptr;
+    rt_render_params p{};
+    p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    int rc = rt_scene_create(&desc, 0, &scene);
+    if (rc == RT_OK) rc = rt_render_views(scene, views.data(), opt.orbit, &p, sums.data());
+    const std::string msg = rc == RT_OK ? "" : rt_last_error();
+    rt_scene_destroy(scene);
+    if (rc != RT_OK) throw std::runtime_error("render: " + msg);
+    if (!opt.quiet) {
+        const double render_s = std::chrono::duration<double>(clock::now() - now).count();
+        printf("Render time: %.2fs (%d views, %.1f Msamples/s)\n", render_s, opt.orbit,
+               (double)opt.orbit * (double)cam.image_width * (double)cam.image_height * (double)cam.samples_per_pixel / 1e6 / render_s);
+    }
+    now = clock::now();
+    for (int k = 0; k < opt.orbit; ++k) {
+        const std::vector<double> one(sums.begin() + (ptrdiff_t)(frame * (size_t)k), sums.begin() + (ptrdiff_t)(frame * (size_t)(k + 1)));
+        char suffix[16];
+        snprintf(suffix, sizeof suffix, "_%03d.png", k);
+        if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, resolve_rgb8(one, cam.samples_per_pixel).data()))
+            throw std::runtime_error("Should've encoded the image into a file.");
+    }
+    if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+}
+
 void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, const std::string &output_file_name,
             const RenderOptions &opt) {
     using clock = std::chrono::steady_clock;
     auto now = clock::now();
     const int32_t w = (int32_t)camera->image_width, h = (int32_t)camera->image_height;
+    if (opt.orbit > 0) {
+        render_orbit(*camera, *world, output_file_name, opt);
+        return;
+    }
     if (opt.adaptive) {
         const std::vector<uint8_t> px = render_adaptive_rgb8(*camera, *world, opt);
         if (!opt.quiet) printf("Render time: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());

@@ -26,6 +26,10 @@ struct RenderOptions {
     double adaptive_rel = 0.02;
     double adaptive_abs = 1e-3;
     int min_spp = 16, batch_spp = 16;
+    // > 0: this many views in ONE rt_render_views call (include/rt_amd.h): view k looks from the camera's look_from turned about the
+    // axis through look_at along vup by 360 k / orbit degrees (camera.hpp orbit_look_from), with seed + k, and goes to
+    // <output_file_name>_<k as three digits>.png.  One GPU, single pass.
+    int orbit = 0;
 };
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
