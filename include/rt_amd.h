@@ -423,6 +423,33 @@ int rt_render_views_device(const rt_scene *scene, const rt_view *views /* HOST, 
 int rt_render_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params,
                     double *out /* host */);
 
+/* ---- live refinement: a running-mean frame and its RGBA8 display bytes (opt-in; nothing above changes) ----------------------------
+ * The reference's second entry point, live_render (src/renderer.rs:77-137, the CLI's -l/--live), refines the frame it shows one sample
+ * per displayed frame with a running mean,  avg += (new - avg) / num_samples  (:114), and shows color_to_rgb(avg) with alpha 0xff
+ * (:124-126).  That is a different f64 recurrence from rt_render's sum / n: a subtraction, a correctly rounded division and an addition
+ * per sample, each rounded on its own ("Arithmetic" below: no reciprocal multiply, no contraction).  The window stays with the host;
+ * these calls give it, per pass, the updated mean and the bytes to blit.
+ *
+ * rt_render_mean_device traces the samples [sample_begin, sample_end) of every pixel — the streams rt_render traces, keyed by (seed,
+ * pixel, sample) — and folds them into d_mean (a frame of 3 * w * h doubles, d_mean[(j*w + i)*3 + c]) in order:
+ *     for s = sample_begin .. sample_end - 1:   m = m + (c_s - m) / (double)(s + 1)
+ * sample_begin is therefore also the number of samples already in the mean: m starts from +0.0 when it is 0 (d_mean's previous
+ * content is then not read) and from d_mean's value otherwise, so a call over [0, a) followed by one over [a, b) equals one over
+ * [0, b) bit for bit.  (The division is the one written at :114, IEEE-rounded; the reference's own `Vec3 / FP` multiplies by 1.0 / rhs,
+ * src/vec3.rs:244-249, which differs in the last bit of some values.)  sample_end <= 0 means camera->samples_per_pixel.  If d_rgba8 is not NULL (4 * w * h bytes, 4-byte aligned), the
+ * display frame of the mean the call arrives at is written with it, in the same pass over the samples: bytes 4p + 0..2 of pixel p are
+ * what rt_resolve_rgb8_device gives at spp = 1 for values 3p + 0..2, byte 4p + 3 is 0xff.  Enqueued on hip_stream, not synchronised;
+ * split into launches, pipelined and sized as rt_render_device is.  rt_render_mean blocks and downloads; when sample_begin > 0 it
+ * uploads `mean` first.  rt_resolve_rgba8_device is the display stage alone, for callers who keep their own mean.
+ * RT_ERR_INVALID_ARGUMENT (the message names the field), before the scene handle or any device work is touched: a null pointer other
+ * than d_rgba8 / rgba8; accumulate != 0 (the mode continues through sample_begin); shard_count > 1; an out_layout other than
+ * RT_OUT_FRAME; sample_begin < 0 or an empty sample range; a d_rgba8 that is not 4-byte aligned. */
+int rt_render_mean_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                          double *d_mean /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *hip_stream);
+int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                   double *mean /* host; read when sample_begin > 0 */, uint8_t *rgba8 /* host, or NULL */);
+int rt_resolve_rgba8_device(int32_t width, int32_t height, const double *d_mean, uint8_t *d_rgba8, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -267,6 +267,9 @@ RT_AMD_SYMBOLS = {
     "rt_resolve_rgb8_spp_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_views_device": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
     "rt_render_views": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p]),
+    "rt_render_mean_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_mean": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
+    "rt_resolve_rgba8_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -757,6 +760,33 @@ class DeviceScene:
         _check(amd_lib().rt_render_views_device(self._handle, arr, len(arr), C.byref(params), C.c_void_p(d_out_ptr),
                                                 C.c_void_p(stream)), "rt_render_views_device")
 
+    def render_mean(self, params: RenderParams, camera: Camera | None = None, mean=None, rgba8: bool = False):
+        """rt_render_mean: the samples of params' range folded into a running mean, m += (c - m) / (s + 1) per sample s (the reference's
+        live_render, src/renderer.rs:114).  `mean`: the (h, w, 3) float64 frame to continue — required when params.sample_begin > 0,
+        which is also the number of samples already in it — written and returned.  With rgba8, returns (mean, (h, w, 4) uint8): the
+        display frame color_to_rgb(mean) with alpha 255."""
+        import numpy as np
+        cam = camera if camera is not None else self.host_scene.camera
+        h, w = cam.image_height, cam.image_width
+        if mean is None:
+            if params.sample_begin > 0:
+                raise RtError("render_mean: params.sample_begin > 0 continues a running mean: pass it as `mean`")
+            mean = np.zeros((h, w, 3), dtype=np.float64)
+        elif mean.shape != (h, w, 3) or mean.dtype != np.float64 or not mean.flags["C_CONTIGUOUS"] or not mean.flags["WRITEABLE"]:
+            raise RtError(f"render_mean: `mean` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        frame = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
+        _check(amd_lib().rt_render_mean(self._handle, C.byref(cam), C.byref(params), C.c_void_p(mean.ctypes.data),
+                                        C.c_void_p(frame.ctypes.data) if rgba8 else None), "rt_render_mean")
+        return (mean, frame) if rgba8 else mean
+
+    def render_mean_device(self, params: RenderParams, d_mean_ptr: int, d_rgba8_ptr: int = 0, stream: int = 0,
+                           camera: Camera | None = None):
+        """rt_render_mean_device: `d_mean_ptr` is a device frame of 3 w h doubles holding the mean of the first params.sample_begin
+        samples (not read when that is 0); `d_rgba8_ptr`, if not 0, 4 w h device bytes for the display frame.  Enqueued on `stream`."""
+        cam = camera if camera is not None else self.host_scene.camera
+        _check(amd_lib().rt_render_mean_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_mean_ptr),
+                                               C.c_void_p(d_rgba8_ptr or None), C.c_void_p(stream)), "rt_render_mean_device")
+
     def render_pixels_device(self, params: RenderParams, d_pixels_ptr: int, n_pixels: int, d_sum_ptr: int,
                              d_sum_sq_ptr: int = 0, stream: int = 0, camera: Camera | None = None):
         """rt_render_pixels_device: the samples of params' range for the n_pixels entries (uint32 pixel indices, device memory) onto
@@ -823,6 +853,12 @@ def resolve_rgb8_values_device(n_values, spp, d_sum_ptr: int, d_rgb8_ptr: int, s
 def resolve_rgb8_spp_device(width, height, d_sum_ptr: int, d_spp_ptr: int, d_rgb8_ptr: int, stream: int = 0):
     _check(amd_lib().rt_resolve_rgb8_spp_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_rgb8_ptr),
                                                 C.c_void_p(stream)), "rt_resolve_rgb8_spp_device")
+
+
+def resolve_rgba8_device(width, height, d_mean_ptr: int, d_rgba8_ptr: int, stream: int = 0):
+    """rt_resolve_rgba8_device: color_to_rgb(mean) with alpha 255 over a device frame of means (4 bytes per pixel)."""
+    _check(amd_lib().rt_resolve_rgba8_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_rgba8_ptr), C.c_void_p(stream)),
+           "rt_resolve_rgba8_device")
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

@@ -206,8 +206,15 @@ struct ViewTable {
     int64_t n;
 };
 
+// Live refinement (rt_render_mean_device): the dense render with `d_out` a frame of running means.  Each launch's samples are folded
+// into it by mean_samples_kernel instead of being added by sum_samples_kernel; the last launch of the call also writes the display
+// frame.  Everything else — chunks, pipelining, scratch, grid — is the dense render's.
+struct MeanOut {
+    uint8_t *d_rgba8; // or null
+};
+
 int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, double *d_out, hipStream_t stream,
-                  rt_counters *out_counters, const PixelList *list = nullptr, const ViewTable *views = nullptr) {
+                  rt_counters *out_counters, const PixelList *list = nullptr, const ViewTable *views = nullptr, const MeanOut *mean = nullptr) {
     int rc = normalise_params(camera, p);
     if (rc != RT_OK) return rc;
     if (list && (p.shard_count != 1 || p.out_layout != RT_OUT_FRAME))
@@ -502,7 +509,10 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         }
         HIP_TRY(hipGetLastError());
         if (pipelined && k > 0) HIP_TRY(hipStreamWaitEvent(s, ws.ev_sum[h ^ 1], 0));
-        if (views) launch_sum_view_samples(K, sum_grid, s);
+        if (mean) {
+            K.mean_rgba8 = sb + ns >= p.sample_end ? mean->d_rgba8 : nullptr; // (the call's last launch: the frame the caller shows)
+            launch_mean_samples(K, sum_grid, s);
+        } else if (views) launch_sum_view_samples(K, sum_grid, s);
         else if (list) launch_sum_listed_samples(K, sum_grid, s);
         else launch_sum_samples(K, sum_grid, s);
         HIP_TRY(hipGetLastError());
@@ -1354,6 +1364,80 @@ int rt_render_adaptive(const rt_scene *scene, const rt_camera *camera, const rt_
     (void)hipFree(buf);
     (void)hipGetLastError();
     return rc;
+}
+
+// ---- live refinement: running-mean frames and their display bytes ----
+namespace {
+// every check of rt_render_mean / rt_render_mean_device: none needs the scene handle or a device.  Fills the normalised parameters.
+static int check_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const void *mean, const char *mean_name,
+               const void *rgba8, const char *rgba8_name, const char *who, rt_render_params &p) {
+    const std::string w(who);
+    if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, w + ": camera is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, w + ": params is null");
+    if (!mean) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + mean_name + " is null");
+    p = *params;
+    if (p.accumulate != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": accumulate must be 0 (a running mean continues through sample_begin)");
+    if (p.shard_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (the live frame is rendered on one device)");
+    if (p.out_layout != RT_OUT_FRAME) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_layout must be RT_OUT_FRAME");
+    if (p.sample_begin < 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sample_begin must not be negative");
+    if ((p.sample_end <= 0 ? camera->samples_per_pixel : p.sample_end) <= p.sample_begin)
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": the range [sample_begin, sample_end) is empty");
+    p.shard_index = 0; p.shard_count = 1;
+    if (int rc = normalise_params(camera, p)) return rc;
+    if (((uintptr_t)rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + rgba8_name + " must be 4-byte aligned");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": scene is null");
+    return RT_OK;
+}
+} // namespace
+
+int rt_render_mean_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *d_mean, uint8_t *d_rgba8,
+                          void *hip_stream) {
+    rt_render_params p;
+    if (int rc = check_mean(scene, camera, params, d_mean, "d_mean", d_rgba8, "d_rgba8", "rt_render_mean_device", p)) return rc;
+    g_last_launch[0] = 0;
+    const MeanOut mean{d_rgba8};
+    return launch_render(const_cast<rt_scene *>(scene), camera, p, d_mean, (hipStream_t)hip_stream, nullptr, nullptr, nullptr, &mean);
+}
+
+int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *mean, uint8_t *rgba8) {
+    const char *who = "rt_render_mean";
+    rt_render_params p;
+    if (int rc = check_mean(scene, camera, params, mean, "mean", nullptr, "rgba8", who, p)) return rc; // (host bytes: any alignment)
+    g_last_launch[0] = 0;
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    std::lock_guard<std::mutex> serial(s->host_render_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height;
+    const size_t mean_bytes = n_pix * 3u * sizeof(double), rgba_bytes = rgba8 ? n_pix * 4u : 0u;
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, mean_bytes + rgba_bytes));
+    double *d_mean = (double *)buf;
+    const MeanOut out{rgba8 ? (uint8_t *)(buf + mean_bytes) : nullptr};
+    int rc = RT_OK;
+    do {
+        if (p.sample_begin > 0 && hipMemcpy(d_mean, mean, mean_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running mean failed");
+            break;
+        }
+        rc = launch_render(s, camera, p, d_mean, nullptr, nullptr, nullptr, nullptr, &out);
+        if (rc != RT_OK) break;
+        hipError_t e = hipMemcpy(mean, d_mean, mean_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rgba8) e = hipMemcpy(rgba8, out.d_rgba8, rgba_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    } while (0);
+    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
+    (void)hipFree(buf);
+    if (rc != RT_OK) (void)hipGetLastError();
+    return rc;
+}
+
+int rt_resolve_rgba8_device(int32_t width, int32_t height, const double *d_mean, uint8_t *d_rgba8, void *hip_stream) {
+    if (!d_mean || !d_rgba8 || width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_resolve_rgba8_device: bad argument");
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_resolve_rgba8_device: d_rgba8 must be 4-byte aligned");
+    if (int rc = select_device_of(d_rgba8, "rt_resolve_rgba8_device")) return rc;
+    launch_resolve_rgba8((int64_t)width * height, d_mean, d_rgba8, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

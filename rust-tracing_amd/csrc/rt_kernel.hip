@@ -1350,6 +1350,45 @@ __global__ void sum_samples_kernel(const KParams P) {
     dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
 }
 
+// ---- live refinement (rt_render_mean_device) --------------------------------------------------------------------------------
+// The display bytes of one pixel's mean: color_to_rgb(avg) with alpha 0xff (src/renderer.rs:124-126) as one little-endian word, byte 0
+// red.  Per value this is resolve_rgb8_kernel's code at inv_spp = 1 (x * 1.0 is x); mean_samples_kernel and resolve_rgba8_kernel both
+// call it, so the fused frame and the stand-alone resolve cannot drift.
+__device__ __forceinline__ uint32_t display_rgba8(double r, double g, double b) {
+    return (uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(r)) | ((uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(g)) << 8) |
+           ((uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(b)) << 16) | 0xff000000u;
+}
+
+// Per-pixel running mean of the sample buffer in sample order (src/renderer.rs:114: `avg += (new - avg) / num_samples`), dense job
+// mode, RT_OUT_FRAME.  sum_samples_kernel's thread-to-pixel mapping and addressing.  Sample s of the render (absolute index: P.sample_begin
+// is the launch's first) has divisor s + 1: a subtraction, a correctly rounded division and an addition per channel, each rounded on its
+// own (no reciprocal, no contraction).  A launch that starts at sample 0 starts from +0.0 and does not read the frame; any other continues
+// the frame's value, so a call cut into several launches gives one launch's bits.  Padding pixels of edge tiles are not written.  With
+// P.mean_rgba8 set (the last launch of a call) the pixel's display bytes are written in the same pass.
+__global__ void mean_samples_kernel(const KParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lt = idx >> 6, p64 = idx & 63u;
+    if (lt >= P.n_local_tiles) return;
+    const int32_t w = P.cam.image_width, h = P.cam.image_height;
+    const int32_t i = (int32_t)(lt % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(lt / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    if (i >= w || j >= h) return;
+    const size_t pixel = (size_t)j * (size_t)w + (size_t)i;
+    double *dst = P.out + pixel * 3u;
+    V3 m = v3(0.0, 0.0, 0.0);
+    if (P.sample_begin != 0) m = v3(dst[0], dst[1], dst[2]);
+    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
+    for (uint32_t s = 0; s < P.n_samples; ++s) {
+        const double n = (double)(P.sample_begin + (int32_t)s + 1);
+        m.x = m.x + (src[0] - m.x) / n;
+        m.y = m.y + (src[1] - m.y) / n;
+        m.z = m.z + (src[2] - m.z) / n;
+        src += 64u * 3u;
+    }
+    dst[0] = m.x; dst[1] = m.y; dst[2] = m.z;
+    if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
+}
+
 // sum_samples_kernel for views mode: local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view, whose frame starts
 // 3 * w * h doubles behind the previous view's.  One thread per (local tile, pixel of the tile); padding pixels of edge tiles are not written.
 __global__ void sum_view_samples_kernel(const KParams P) {
@@ -1517,6 +1556,13 @@ __global__ void resolve_rgb8_kernel(int64_t n_values, double inv_spp, const doub
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n_values) return;
     rgb[idx] = rtm::rt_quantise(rtm::rt_gamma_encode(sum[idx] * inv_spp));
+}
+
+// color_to_rgb(avg) with alpha 0xff over a frame of means, for callers who keep their own mean: one thread and one 4-byte store per pixel
+__global__ void resolve_rgba8_kernel(int64_t n_pixels, const double *__restrict__ mean, uint32_t *__restrict__ rgba) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_pixels) return;
+    rgba[idx] = display_rgba8(mean[idx * 3 + 0], mean[idx * 3 + 1], mean[idx * 3 + 2]);
 }
 
 // test hook: the conservative f32 box test against the exact f64 one on caller-supplied rays and boxes
@@ -1713,6 +1759,9 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
 }
+void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(mean_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
 void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_view_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
 }
@@ -1752,6 +1801,9 @@ void launch_tiles_to_frame_rgb8(int32_t w, int32_t h, int32_t tiles_x, int32_t s
 }
 void launch_resolve_rgb8(int64_t n_values, double inv_spp, const double *sum, uint8_t *rgb, hipStream_t stream) {
     hipLaunchKernelGGL(resolve_rgb8_kernel, dim3((unsigned)((n_values + 255) / 256)), dim3(256), 0, stream, n_values, inv_spp, sum, rgb);
+}
+void launch_resolve_rgba8(int64_t n_pixels, const double *mean, uint8_t *rgba, hipStream_t stream) {
+    hipLaunchKernelGGL(resolve_rgba8_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, stream, n_pixels, mean, (uint32_t *)rgba);
 }
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit) {
     hipLaunchKernelGGL(debug_box_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, n, rays, boxes, tmin, tmax, exact_hit, f32_hit);

@@ -114,6 +114,10 @@ struct KParams {
     const ViewRec *views;
     double inv_tiles_per_view;      // 1 / tiles_per_view (exact decode for lt < 2^27)
     uint32_t tiles_per_view;
+    // live refinement (rt_render_mean_device; mean_samples_kernel): `out` is the frame of running means and `sample_begin` the number of
+    // samples already in it; the display frame (4 bytes per pixel, 4-byte aligned) that the last launch of a call writes, or null.
+    // No other kernel reads this.
+    uint8_t *mean_rgba8;
 };
 
 // What a scene can contain.  A kernel instantiated without a feature has that code compiled out, which matters for
@@ -177,6 +181,7 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream);
 void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream);
 void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream);
+void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream); // live refinement: the running mean instead of the sum
 // adaptive sampling (rt_render_adaptive_device): the list of every pixel in tile order; one convergence step over an active list
 // (spp of the pixels that leave, the survivors compacted in order into list_out, padded to a multiple of 64, their count in *count);
 // the resolve with a per-pixel sample count
@@ -194,6 +199,7 @@ void launch_tiles_to_frame(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_
 void launch_tiles_to_frame_rgb8(int32_t w, int32_t h, int32_t tiles_x, int32_t shard_count, int64_t shard_stride, const uint8_t *gathered,
                                 uint8_t *frame, hipStream_t stream);
 void launch_resolve_rgb8(int64_t n_values, double inv_spp, const double *sum, uint8_t *rgb, hipStream_t stream);
+void launch_resolve_rgba8(int64_t n_pixels, const double *mean, uint8_t *rgba, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

@@ -1,10 +1,13 @@
 // Command-line front end.  reference: src/main.rs:40-54 (Args) and :641-669 (main)
-//   -s/--scene N, -o/--output NAME as in the reference; -l/--live is accepted and refused (no window system
-//   on a GPU node).  Added: --width/--aspect/--spp/--depth (BASELINE.json's configs change these),
+//   -s/--scene N, -o/--output NAME, -l/--live as in the reference.  -l/--live [--live-spp K] refines the frame as the reference's
+//   live_render does (running mean, K samples per pixel between two frames, spp - 1 samples in all: renderer.hpp) and, there being no
+//   window, writes the last frame's RGB bytes to OUTPUT.png; the reference's live mode writes no file, so -o must name one.
+//   Added: --width/--aspect/--spp/--depth (BASELINE.json's configs change these),
 //   --seed/--scene-seed, --gpus, --earth PATH|synthetic:WxH, --bvh reference|sah, --progressive N (rewrite the PNG
-//   every N samples per pixel: what -l/--live shows in a window, written to the file instead), --adaptive REL
+//   every N samples per pixel; continues the sum, not the running mean), --adaptive REL
 //   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
+#include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
 #include <chrono>
@@ -20,6 +23,8 @@ static void usage(const char *argv0) {
             "Usage: %s [-s SCENE] [-o OUTPUT] [--width W] [--aspect A] [--spp N] [--depth D]\n"
             "          [--seed S] [--scene-seed S] [--gpus N] [--progressive SPP_PER_PASS] [--earth PATH|synthetic:WxH] [--bvh reference|sah]\n"
             "          [--adaptive REL [--adaptive-abs A] [--min-spp N] [--batch-spp N]]   (one GPU; --spp is the maximum)\n"
+            "          [-l|--live [--live-spp K] -o OUTPUT]   (one GPU: the reference's live mode without the window — a running mean refined K samples\n"
+            "                         per pixel at a time, default 1, over spp - 1 samples; the last frame goes to OUTPUT.png)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
             "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
@@ -29,7 +34,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false;
+    bool live = false, output_given = false, live_spp_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -44,7 +49,7 @@ int main(int argc, char **argv) {
         };
         if (a == "-l" || a == "--live") live = true;
         else if (a == "-s" || a == "--scene") scene = atoi(need("--scene"));
-        else if (a == "-o" || a == "--output") output = need("--output");
+        else if (a == "-o" || a == "--output") { output = need("--output"); output_given = true; }
         else if (a == "--width") so.image_width = atoll(need("--width"));
         else if (a == "--aspect") so.aspect_ratio = atof(need("--aspect"));
         else if (a == "--spp") so.samples_per_pixel = atoi(need("--spp"));
@@ -53,6 +58,10 @@ int main(int argc, char **argv) {
         else if (a == "--scene-seed") scene_seed = strtoull(need("--scene-seed"), nullptr, 10);
         else if (a == "--gpus") ro.gpus = atoi(need("--gpus"));
         else if (a == "--progressive") ro.progressive_spp = atoi(need("--progressive"));
+        else if (a == "--live-spp") {
+            ro.live_spp = atoi(need("--live-spp")); live_spp_given = true;
+            if (ro.live_spp < 1) { fprintf(stderr, "--live-spp needs a number of samples per frame of at least 1\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--adaptive") { ro.adaptive = true; ro.adaptive_rel = atof(need("--adaptive")); }
         else if (a == "--adaptive-abs") ro.adaptive_abs = atof(need("--adaptive-abs"));
         else if (a == "--min-spp") ro.min_spp = atoi(need("--min-spp"));
@@ -76,8 +85,16 @@ int main(int argc, char **argv) {
         usage(argv[0]);
         return 2;
     }
-    if (live) {
-        fprintf(stderr, "live rendering needs a window system and is not available in this build\n");
+    if (live && (ro.gpus > 1 || ro.progressive_spp > 0 || ro.adaptive || ro.orbit > 0)) {
+        fprintf(stderr, "--live refines one frame on one GPU: it cannot be combined with --gpus > 1, --progressive, --adaptive or --orbit\n");
+        return 2;
+    }
+    if (live_spp_given && !live) {
+        fprintf(stderr, "--live-spp sets the samples per frame of --live: it needs -l/--live\n");
+        return 2;
+    }
+    if (live && !output_given) {
+        fprintf(stderr, "--live has no window to draw in and writes its last frame to a file instead: name it with -o/--output\n");
         return 2;
     }
 
@@ -90,6 +107,18 @@ int main(int argc, char **argv) {
         printf("Building BVH: %.2fms\n",
                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - now).count());
 
+        if (live) {
+            now = std::chrono::steady_clock::now();
+            int frames = 0, samples = 0;
+            const std::vector<uint8_t> rgba = live_render(camera, *bvh, ro, [&](const std::vector<uint8_t> &, int n) { ++frames; samples = n; });
+            printf("Live: %d frames, %d samples per pixel in the last, %.2fs\n", frames, samples,
+                   std::chrono::duration<double>(std::chrono::steady_clock::now() - now).count());
+            std::vector<uint8_t> rgb(rgba.size() / 4u * 3u);
+            for (size_t p = 0; p < rgba.size() / 4u; ++p) { rgb[3 * p] = rgba[4 * p]; rgb[3 * p + 1] = rgba[4 * p + 1]; rgb[3 * p + 2] = rgba[4 * p + 2]; }
+            if (!write_png_rgb8(output + ".png", (int32_t)camera.image_width, (int32_t)camera.image_height, rgb.data()))
+                throw std::runtime_error("Should've encoded the image into a file.");
+            return 0;
+        }
         render(std::make_shared<Camera>(camera), bvh, output, ro);
     } catch (const std::exception &e) {
         fprintf(stderr, "error: %s\n", e.what());

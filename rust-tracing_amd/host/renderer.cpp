@@ -167,6 +167,42 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     return px;
 }
 
+// The running mean and its display frame stay on the device; every pass is one rt_render_mean_device call (the render launches and one
+// reduction that also writes the RGBA8 frame), and only the bytes to show come back.
+std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt,
+                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame) {
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const rt_camera cam = camera.pod();
+    const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
+    std::vector<uint8_t> frame((size_t)n_pix * 4u, 0);
+    for (size_t k = 3; k < frame.size(); k += 4) frame[k] = 0xff; // color_to_rgb(Color::ZERO), alpha 0xff
+    const int last = cam.samples_per_pixel - 1; // `if num_samples < spp` (src/renderer.rs:104): divisors 1 .. spp - 1
+    if (last <= 0) return frame;
+    const int pass = opt.live_spp > 0 ? opt.live_spp : 1;
+    rt_scene *scene = nullptr;
+    void *d_mean = nullptr, *d_rgba8 = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_scene_destroy(scene); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("live_render: " + msg); } };
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
+    check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+    for (int begin = 0; begin < last; begin += pass) {
+        const int end = begin + pass < last ? begin + pass : last;
+        rt_render_params p{};
+        p.seed = opt.seed; p.sample_begin = begin; p.sample_end = end; p.max_depth = cam.max_depth;
+        p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+        check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+        check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
+        if (on_frame) {
+            try { on_frame(frame, end); } catch (...) { cleanup(); throw; }
+        }
+    }
+    cleanup();
+    return frame;
+}
+
 // An orbit on device 0: every view's frame in one rt_render_views call, one PNG per view.
 static void render_orbit(const Camera &camera, const Hittable &world, const std::string &output_file_name, const RenderOptions &opt) {
     using clock = std::chrono::steady_clock;

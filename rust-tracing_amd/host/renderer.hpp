@@ -2,7 +2,8 @@
 // Same contract as the reference's `render(camera, world, output_file_name)`: trace every pixel, then
 // divide by spp, gamma-encode, quantise and write `<output_file_name>.png` — but the pixel loop
 // (src/renderer.rs:26-49) is one call into librt_amd (include/rt_amd.h) instead of a rayon par_iter.
-// live_render (src/renderer.rs:77-137) needs a window system and is not provided.
+// live_render(): the reference's second entry point (src/renderer.rs:77-137) without its window: the running-mean frame it refines
+// one pass at a time, handed to a callback as the RGBA8 bytes the reference blits (include/rt_amd.h "live refinement").
 #pragma once
 #include "camera.hpp"
 #include "hittable.hpp"
@@ -17,10 +18,11 @@ struct RenderOptions {
     uint64_t seed = 1; // render seed (the reference's RNG is unseeded; see include/rt_amd.h "RNG")
     int gpus = 1;      // framebuffer tiles are dealt round-robin to this many devices
     bool quiet = false;
-    // > 0: render in passes of this many samples per pixel and rewrite the PNG after every pass — the batch
-    // counterpart of the reference's live_render (src/renderer.rs:77-137: one more sample per frame, running mean),
-    // without the window.  The final image is bit-identical to a single-pass render (ranges accumulate exactly).
+    // > 0: render in passes of this many samples per pixel and rewrite the PNG after every pass.  It continues the SUM, so the
+    // final image is bit-identical to a single-pass render (ranges accumulate exactly); the reference's running mean is live_render, below.
     int progressive_spp = 0;
+    // live_render: samples per pixel folded into the running mean between two displayed frames (the reference: 1)
+    int live_spp = 1;
     // adaptive sampling (include/rt_amd.h rt_render_adaptive) with these thresholds; the camera's spp is the maximum.  One GPU, single pass.
     bool adaptive = false;
     double adaptive_rel = 0.02;
@@ -40,6 +42,15 @@ std::vector<double> render_sums(const Camera &camera, const Hittable &world, con
 
 // color_to_rgb(c / spp) over the whole frame (src/renderer.rs:55-58)
 std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp);
+
+// The reference's live_render (src/renderer.rs:77-137) without the window, on device 0: passes of opt.live_spp samples per pixel are
+// folded into a running mean, avg += (new - avg) / num_samples (:114), and after every pass on_frame(rgba8, num_samples) gets the
+// frame the reference would show — color_to_rgb(avg) with alpha 0xff, 4 * w * h bytes (:124-126) — and the number of samples in it.
+// It ends as the reference's loop does: that loop starts at num_samples = 1 and draws only `if num_samples < spp` (:104), so its
+// divisors are 1 .. spp - 1 and the frame it settles on holds spp - 1 samples, not spp.  Returns the last frame (all (0, 0, 0, 0xff),
+// the reference's zeroed raw_pixels, when spp <= 1 leaves nothing to draw).  Throws std::runtime_error on a GPU library error.
+std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt = {},
+                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame = nullptr);
 
 void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, const std::string &output_file_name,
             const RenderOptions &opt = {});
