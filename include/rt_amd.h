@@ -450,6 +450,59 @@ int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_rend
                    double *mean /* host; read when sample_begin > 0 */, uint8_t *rgba8 /* host, or NULL */);
 int rt_resolve_rgba8_device(int32_t width, int32_t height, const double *d_mean, uint8_t *d_rgba8, void *hip_stream);
 
+/* ---- denoise: per-pixel moments of a frame and a variance-guided à-trous filter (opt-in; nothing above changes) -----------------------
+ * Adaptive sampling, views and live refinement all produce frames of few samples per pixel; these calls make such a frame showable.
+ *
+ * rt_render_moments_device renders the samples [sample_begin, sample_end) of every pixel and writes two frames of 3 * w * h doubles:
+ * d_sum is, bit for bit, what rt_render_device writes; d_sum_sq holds per channel the in-order sum of each sample's c * c (the product
+ * rounded, then added: rt_render_pixels_device's definition).  params->accumulate continues both.  It is list mode over the list of
+ * every pixel in tile order, with list mode's limits: w * h < 2^27, shard_count 1, out_layout RT_OUT_FRAME — otherwise, and for a null
+ * pointer, RT_ERR_INVALID_ARGUMENT (the message names the field) before the scene handle or any device work is touched.  Enqueued on
+ * hip_stream; the scene keeps the pixel list of a frame size, so only the first call at a size allocates (and waits for the list once).
+ * rt_render_moments blocks and downloads; with accumulate set it uploads both buffers first.
+ *
+ * rt_denoise_device needs no scene: it filters the frame of means S / n that (d_sum, d_sum_sq, sample counts) describe, guided by the
+ * variance of each pixel's mean, and writes the filtered means (and optionally their display bytes).  It is enqueued on hip_stream, does
+ * not synchronise and does not allocate: d_workspace is rt_denoise_workspace_bytes(w, h) bytes of device memory (16-byte aligned) that the
+ * caller owns.  RT_ERR_INVALID_ARGUMENT (the field named) before any device work: width or height < 1 or w * h >= 2^27; a null d_sum,
+ * d_sum_sq, d_mean_out or d_workspace; spp < 2 when d_spp is NULL; a struct_size this library does not know; iterations outside 1..6;
+ * sigma or eps that is not a number > 0; d_mean_out overlapping d_sum or d_sum_sq; a d_rgba8 that is not 4-byte aligned.
+ *
+ * Normative definition.  All arithmetic is f64, every operation rounded on its own ("Arithmetic" below: no FMA, IEEE division and
+ * square root), max(a, b) = (b > a ? b : a).  p is a pixel, n its sample count (spp, or d_spp[p]) as a double.
+ *   Prepare.   m_c = S_c / n.  p is VALID iff n >= 2 and all six of S_c, Q_c are finite.  For a valid pixel
+ *              v_c = (Q_c - S_c * m_c) / (n - 1)          (the adaptive rule's terms)
+ *              V0 = max(max(max(v_r, v_g), v_b), 0) / n;   C0 = m.
+ *              A pixel that is not valid keeps C = m through every iteration, is written to the output unchanged and is never a tap.
+ *   Iteration k = 0 .. K - 1, stride s = 2^k, for every valid p, with L(x) = ((C_r + C_g) + C_b) / 3 of C_k:
+ *              G  = [sum of (g[dy] * g[dx]) * V_k(q)] / [sum of g[dy] * g[dx]], g = (1/4, 1/2, 1/4), over the in-frame valid pixels
+ *                   q = p + (dx, dy), dy = -1..1 outer, dx = -1..1 inner (offsets of one pixel at every stride); both sums start at 0
+ *              sd = sqrt(G);  den = sigma * sd + eps
+ *              sw = sc_c = sv = 0; then for dy = -2..2 outer, dx = -2..2 inner, q = p + s * (dx, dy), skipping q out of frame or not valid,
+ *              with h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *                   x = |L(p) - L(q)| / den;  t = 1 - x * x;  e = (t > 0 ? t * t : 0);  w = (h[dy] * h[dx]) * e
+ *                   sw = sw + w;  sc_c = sc_c + w * C_k(q)_c;  sv = sv + (w * w) * V_k(q)
+ *              C_k+1(p) = sc / sw;  V_k+1(p) = sv / (sw * sw)           (sw >= 9/64: the centre tap has e = 1)
+ *   Output.    d_mean_out = C_K (3 * w * h doubles); d_rgba8, if not NULL, the bytes rt_resolve_rgba8_device gives for C_K, written by
+ *              the last iteration itself. */
+typedef struct rt_denoise_params {
+    uint32_t struct_size;   /* sizeof(rt_denoise_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t iterations;     /* K, 1..6 (default 4): strides 1, 2, 4, ... 2^(K-1) */
+    double sigma;           /* edge-stopping width in standard deviations of the mean (default 4.0), > 0 */
+    double eps;             /* added to the denominator (default 1e-6), > 0 */
+} rt_denoise_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_denoise_params_init_sized(rt_denoise_params *params, uint32_t struct_size);
+/* Bytes of device memory rt_denoise_device needs for a w x h frame (two halves of 4 doubles per pixel); -1 for a size it refuses. */
+int64_t rt_denoise_workspace_bytes(int32_t width, int32_t height);
+int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                      const int32_t *d_spp /* NULL: uniform spp */, const rt_denoise_params *params /* NULL: defaults */,
+                      double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int rt_render_moments_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                             double *d_sum /* 3*w*h */, double *d_sum_sq /* 3*w*h */, void *hip_stream);
+int rt_render_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                      double *sum /* host */, double *sum_sq /* host */);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -216,6 +216,22 @@ def adaptive_params(**kw) -> "AdaptiveParams":
     return a
 
 
+class DenoiseParams(C.Structure):
+    """rt_denoise_params (rt_denoise_device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma", C.c_double), ("eps", C.c_double)]
+
+
+def denoise_params(**kw) -> "DenoiseParams":
+    """rt_denoise_params_init_sized, then the given fields (iterations=, sigma=, eps=)."""
+    d = DenoiseParams()
+    _check(amd_lib().rt_denoise_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(DenoiseParams._fields_):
+            raise TypeError(f"rt_denoise_params has no field {k}")
+        setattr(d, k, v)
+    return d
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -270,6 +286,12 @@ RT_AMD_SYMBOLS = {
     "rt_render_mean_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_mean": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
     "rt_resolve_rgba8_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_denoise_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_denoise_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_moments_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -787,6 +809,29 @@ class DeviceScene:
         _check(amd_lib().rt_render_mean_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_mean_ptr),
                                                C.c_void_p(d_rgba8_ptr or None), C.c_void_p(stream)), "rt_render_mean_device")
 
+    def render_moments(self, params: RenderParams, camera: Camera | None = None, sum=None, sum_sq=None):
+        """rt_render_moments: (sum, sum_sq), two (h, w, 3) float64 frames: the per-pixel sums rt_render gives and the in-order sums of
+        the samples' squares.  With params.accumulate both running frames are required and continued in place."""
+        import numpy as np
+        cam = camera if camera is not None else self.host_scene.camera
+        h, w = cam.image_height, cam.image_width
+        if sum is None and sum_sq is None:
+            if params.accumulate:
+                raise RtError("render_moments: params.accumulate adds to running sums: pass them as `sum` and `sum_sq`")
+            sum, sum_sq = np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 3), dtype=np.float64)
+        for name, a in (("sum", sum), ("sum_sq", sum_sq)):
+            if a is None or a.shape != (h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise RtError(f"render_moments: `{name}` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        _check(amd_lib().rt_render_moments(self._handle, C.byref(cam), C.byref(params), C.c_void_p(sum.ctypes.data),
+                                           C.c_void_p(sum_sq.ctypes.data)), "rt_render_moments")
+        return sum, sum_sq
+
+    def render_moments_device(self, params: RenderParams, d_sum_ptr: int, d_sum_sq_ptr: int, stream: int = 0, camera: Camera | None = None):
+        """rt_render_moments_device: two device frames of 3 w h doubles (sums, sums of squares); enqueued on `stream`."""
+        cam = camera if camera is not None else self.host_scene.camera
+        _check(amd_lib().rt_render_moments_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_sum_ptr),
+                                                  C.c_void_p(d_sum_sq_ptr), C.c_void_p(stream)), "rt_render_moments_device")
+
     def render_pixels_device(self, params: RenderParams, d_pixels_ptr: int, n_pixels: int, d_sum_ptr: int,
                              d_sum_sq_ptr: int = 0, stream: int = 0, camera: Camera | None = None):
         """rt_render_pixels_device: the samples of params' range for the n_pixels entries (uint32 pixel indices, device memory) onto
@@ -859,6 +904,52 @@ def resolve_rgba8_device(width, height, d_mean_ptr: int, d_rgba8_ptr: int, strea
     """rt_resolve_rgba8_device: color_to_rgb(mean) with alpha 255 over a device frame of means (4 bytes per pixel)."""
     _check(amd_lib().rt_resolve_rgba8_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_rgba8_ptr), C.c_void_p(stream)),
            "rt_resolve_rgba8_device")
+
+
+def denoise_workspace_bytes(width, height) -> int:
+    n = int(amd_lib().rt_denoise_workspace_bytes(width, height))
+    if n < 0:
+        raise RtError(f"rt_denoise_workspace_bytes: no workspace for a {width}x{height} frame")
+    return n
+
+
+def denoise_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
+                   d_spp_ptr: int = 0, d_rgba8_ptr: int = 0, params: "DenoiseParams | None" = None, stream: int = 0):
+    """rt_denoise_device: the variance-guided à-trous filter over device frames of sums and sums of squares (3 w h doubles each) with
+    the uniform sample count `spp` or, if d_spp_ptr is not 0, a device map of w h int32.  Writes 3 w h doubles of filtered means and,
+    if d_rgba8_ptr is not 0, 4 w h display bytes; `d_workspace_ptr`: denoise_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
+                                       C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                       C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)), "rt_denoise_device")
+
+
+def denoise(sum, sum_sq, spp, *, spp_map=None, rgba8=False, device=0, **kw):
+    """Uploads (h, w, 3) frames of sums and sums of squares (and an (h, w) int32 spp map, if given), runs rt_denoise_device with
+    denoise_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or (means, (h, w, 4) uint8) with rgba8."""
+    import numpy as np
+    sum = np.ascontiguousarray(sum, dtype=np.float64)
+    sum_sq = np.ascontiguousarray(sum_sq, dtype=np.float64)
+    if sum.ndim != 3 or sum.shape[2] != 3 or sum_sq.shape != sum.shape:
+        raise RtError("denoise: `sum` and `sum_sq` must be (h, w, 3) frames of one shape")
+    h, w = sum.shape[:2]
+    if spp_map is not None:
+        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if spp_map.shape != (h, w):
+            raise RtError(f"denoise: `spp_map` must have shape {(h, w)}")
+    params = denoise_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_sum, d_sq = torch.from_numpy(sum).cuda(), torch.from_numpy(sum_sq).cuda()
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_out = torch.empty_like(d_sum)
+        d_ws = torch.empty(denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        denoise_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
+                       d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0,
+                       params=params, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

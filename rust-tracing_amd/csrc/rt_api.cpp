@@ -138,6 +138,7 @@ void free_scene(rt_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     for (auto &kv : s->workspaces) free_workspace(kv.second->w);
+    for (auto &kv : s->tile_lists) (void)hipFree(kv.second);
     (void)hipFree(s->nodes.ptr); (void)hipFree(s->spheres.ptr); (void)hipFree(s->quads.ptr); (void)hipFree(s->insts.ptr);
     (void)hipFree(s->media.ptr); (void)hipFree(s->mats.ptr); (void)hipFree(s->texs.ptr); (void)hipFree(s->perlins.ptr);
     (void)hipFree(s->images.ptr); (void)hipFree(s->texels.ptr); (void)hipFree(s->lut.ptr); (void)hipFree(s->lds_image.ptr); (void)hipFree(s->oimage.ptr); (void)hipFree(s->oseq.ptr); (void)hipFree(s->aux_image.ptr);
@@ -1437,6 +1438,175 @@ int rt_resolve_rgba8_device(int32_t width, int32_t height, const double *d_mean,
     if (int rc = select_device_of(d_rgba8, "rt_resolve_rgba8_device")) return rc;
     launch_resolve_rgba8((int64_t)width * height, d_mean, d_rgba8, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- denoise: moments of a whole frame, and the à-trous filter (rt_denoise.hip) ----
+namespace {
+constexpr size_t MAX_TILE_LISTS = 8; // frame sizes a scene keeps the all-pixels list of
+
+// every check of rt_render_moments / rt_render_moments_device: none needs the scene handle or a device
+int check_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const void *sum, const char *sum_name,
+                  const void *sum_sq, const char *sum_sq_name, const char *who) {
+    const std::string w(who);
+    if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, w + ": camera is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, w + ": params is null");
+    if (!sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + sum_name + " is null");
+    if (!sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + sum_sq_name + " is null");
+    if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (the moments are rendered on one device)");
+    if (params->out_layout != RT_OUT_FRAME) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_layout must be RT_OUT_FRAME");
+    rt_render_params p = *params;
+    p.shard_index = 0; p.shard_count = 1;
+    if (int rc = normalise_params(camera, p)) return rc;
+    if ((int64_t)camera->image_width * camera->image_height >= ((int64_t)1 << 27))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": image_width x image_height must be below 2^27 pixels");
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": scene is null");
+    return RT_OK;
+}
+
+// The list of every pixel of a w x h frame in tile order (the first list of rt_render_adaptive), kept by the scene per frame size:
+// built once, on `stream`, and waited for there, so that calls on other streams find it complete.  A scene that has seen
+// MAX_TILE_LISTS sizes drops them all (after the device has drained) before it keeps another.
+int tile_list_of(rt_scene *s, int32_t w, int32_t h, hipStream_t stream, const uint32_t **out, uint32_t *n_list) {
+    *n_list = (uint32_t)tiles_total(w, h) * 64u;
+    std::lock_guard<std::mutex> lock(s->mu);
+    const auto key = std::make_pair(w, h);
+    const auto it = s->tile_lists.find(key);
+    if (it != s->tile_lists.end()) {
+        *out = it->second;
+        return RT_OK;
+    }
+    if (s->tile_lists.size() >= MAX_TILE_LISTS) {
+        HIP_TRY(hipDeviceSynchronize());
+        for (auto &kv : s->tile_lists) (void)hipFree(kv.second);
+        s->tile_lists.clear();
+    }
+    uint32_t *list = nullptr;
+    HIP_TRY(hipMalloc((void **)&list, (size_t)*n_list * sizeof(uint32_t)));
+    launch_tile_order_list(w, h, list, stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        (void)hipFree(list);
+        return fail(RT_ERR_HIP, std::string("rt_render_moments: ") + hipGetErrorString(e));
+    }
+    s->tile_lists[key] = list;
+    *out = list;
+    return RT_OK;
+}
+
+int render_moments(rt_scene *s, const rt_camera *camera, const rt_render_params *params, double *d_sum, double *d_sum_sq, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t *list = nullptr;
+    uint32_t n_list = 0;
+    if (int rc = tile_list_of(s, camera->image_width, camera->image_height, stream, &list, &n_list)) return rc;
+    rt_render_params p = *params;
+    p.shard_index = 0; p.shard_count = 1;
+    const PixelList pl{list, (int64_t)n_list, d_sum_sq};
+    return launch_render(s, camera, p, d_sum, stream, nullptr, &pl);
+}
+
+void denoise_defaults(rt_denoise_params &d) {
+    memset(&d, 0, sizeof d);
+    d.struct_size = (uint32_t)sizeof d;
+    d.iterations = 4;
+    d.sigma = 4.0;
+    d.eps = 1e-6;
+}
+bool denoise_size_known(uint32_t size) { return size >= 8 && size <= sizeof(rt_denoise_params) && size % 8 == 0; }
+bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+} // namespace
+
+int rt_render_moments_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *d_sum, double *d_sum_sq,
+                             void *hip_stream) {
+    if (int rc = check_moments(scene, camera, params, d_sum, "d_sum", d_sum_sq, "d_sum_sq", "rt_render_moments_device")) return rc;
+    g_last_launch[0] = 0;
+    return render_moments(const_cast<rt_scene *>(scene), camera, params, d_sum, d_sum_sq, (hipStream_t)hip_stream);
+}
+
+int rt_render_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *sum, double *sum_sq) {
+    const char *who = "rt_render_moments";
+    if (int rc = check_moments(scene, camera, params, sum, "sum", sum_sq, "sum_sq", who)) return rc;
+    g_last_launch[0] = 0;
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    std::lock_guard<std::mutex> serial(s->host_render_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)camera->image_width * (size_t)camera->image_height * 3u * sizeof(double);
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, 2u * bytes));
+    double *d_sum = (double *)buf, *d_sq = (double *)(buf + bytes);
+    int rc = RT_OK;
+    do {
+        if (params->accumulate && (hipMemcpy(d_sum, sum, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                                   hipMemcpy(d_sq, sum_sq, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running sums failed");
+            break;
+        }
+        rc = render_moments(s, camera, params, d_sum, d_sq, nullptr);
+        if (rc != RT_OK) break;
+        hipError_t e = hipMemcpy(sum, d_sum, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(sum_sq, d_sq, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    } while (0);
+    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
+    (void)hipFree(buf);
+    if (rc != RT_OK) (void)hipGetLastError();
+    return rc;
+}
+
+int rt_denoise_params_init_sized(rt_denoise_params *params, uint32_t struct_size) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_params_init_sized: null argument");
+    if (!denoise_size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_params_init_sized: struct_size is not one this library knows");
+    rt_denoise_params full;
+    denoise_defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+
+int64_t rt_denoise_workspace_bytes(int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
+    return (int64_t)width * height * 2 * 4 * (int64_t)sizeof(double);
+}
+
+int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                      const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    const std::string w("rt_denoise_device");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
+    if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
+    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
+    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
+    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
+    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
+    rt_denoise_params d;
+    denoise_defaults(d);
+    if (params) {
+        if (!denoise_size_known(params->struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_params.struct_size is not one this library knows");
+        memcpy(&d, params, params->struct_size); // (an older, shorter struct: the fields it lacks keep their defaults)
+    }
+    if (d.iterations < 1 || d.iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
+    if (!(d.sigma > 0.0) || !std::isfinite(d.sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
+    if (!(d.eps > 0.0) || !std::isfinite(d.eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
+    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
+    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_sum or d_sum_sq");
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (int rc = select_device_of(d_mean_out, "rt_denoise_device")) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    char *half[2] = {(char *)d_workspace, (char *)d_workspace + n_pix * 4u * sizeof(double)};
+    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, half[0], stream);
+    HIP_TRY(hipGetLastError());
+    for (int32_t k = 0; k < d.iterations; ++k) {
+        const bool last = k == d.iterations - 1;
+        launch_denoise_atrous(width, height, (int32_t)1 << k, d.sigma, d.eps, half[k & 1], last ? nullptr : half[(k + 1) & 1],
+                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
+        HIP_TRY(hipGetLastError());
+    }
     return RT_OK;
 }
 

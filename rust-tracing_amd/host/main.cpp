@@ -6,6 +6,8 @@
 //   --seed/--scene-seed, --gpus, --earth PATH|synthetic:WxH, --bvh reference|sah, --progressive N (rewrite the PNG
 //   every N samples per pixel; continues the sum, not the running mean), --adaptive REL
 //   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum),
+//   --denoise [--denoise-iters K] [--denoise-sigma X] (the variance-guided à-trous filter of include/rt_amd.h over the frame before
+//   it is written; with --adaptive it takes the adaptive sums and the spp map),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 #include "image_io.hpp"
 #include "renderer.hpp"
@@ -23,6 +25,8 @@ static void usage(const char *argv0) {
             "Usage: %s [-s SCENE] [-o OUTPUT] [--width W] [--aspect A] [--spp N] [--depth D]\n"
             "          [--seed S] [--scene-seed S] [--gpus N] [--progressive SPP_PER_PASS] [--earth PATH|synthetic:WxH] [--bvh reference|sah]\n"
             "          [--adaptive REL [--adaptive-abs A] [--min-spp N] [--batch-spp N]]   (one GPU; --spp is the maximum)\n"
+            "          [--denoise [--denoise-iters K] [--denoise-sigma X]]   (one GPU, one pass: the PNG is written from the denoised mean; K from 1 to 6,\n"
+            "                         default 4; X > 0, default 4; also with --adaptive)\n"
             "          [-l|--live [--live-spp K] -o OUTPUT]   (one GPU: the reference's live mode without the window — a running mean refined K samples\n"
             "                         per pixel at a time, default 1, over spp - 1 samples; the last frame goes to OUTPUT.png)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
@@ -34,7 +38,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -66,6 +70,15 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive-abs") ro.adaptive_abs = atof(need("--adaptive-abs"));
         else if (a == "--min-spp") ro.min_spp = atoi(need("--min-spp"));
         else if (a == "--batch-spp") ro.batch_spp = atoi(need("--batch-spp"));
+        else if (a == "--denoise") ro.denoise = true;
+        else if (a == "--denoise-iters") {
+            ro.denoise_iters = atoi(need("--denoise-iters")); denoise_knob_given = true;
+            if (ro.denoise_iters < 1 || ro.denoise_iters > 6) { fprintf(stderr, "--denoise-iters needs a number of iterations from 1 to 6\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--denoise-sigma") {
+            ro.denoise_sigma = atof(need("--denoise-sigma")); denoise_knob_given = true;
+            if (!(ro.denoise_sigma > 0.0)) { fprintf(stderr, "--denoise-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--orbit") {
             ro.orbit = atoi(need("--orbit"));
             if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
@@ -87,6 +100,15 @@ int main(int argc, char **argv) {
     }
     if (live && (ro.gpus > 1 || ro.progressive_spp > 0 || ro.adaptive || ro.orbit > 0)) {
         fprintf(stderr, "--live refines one frame on one GPU: it cannot be combined with --gpus > 1, --progressive, --adaptive or --orbit\n");
+        return 2;
+    }
+    if (ro.denoise && (live || ro.gpus > 1 || ro.progressive_spp > 0 || ro.orbit > 0)) {
+        fprintf(stderr, "--denoise filters one frame's sums and sums of squares on one GPU: it cannot be combined with --live (a running mean keeps no "
+                        "second moment), --gpus > 1 (the gather moves sums only), --progressive or --orbit\n");
+        return 2;
+    }
+    if (denoise_knob_given && !ro.denoise) {
+        fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise\n");
         return 2;
     }
     if (live_spp_given && !live) {

@@ -128,6 +128,57 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
     return px;
 }
 
+std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                             const RenderOptions &opt) {
+    const int64_t n_pix = (int64_t)width * height;
+    void *d_mean = nullptr, *d_rgba8 = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_work); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("denoise: " + msg); } };
+    rt_denoise_params dp;
+    check(rt_denoise_params_init_sized(&dp, sizeof dp));
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
+    const int64_t work = rt_denoise_workspace_bytes(width, height);
+    if (work < 0) throw std::runtime_error("denoise: no workspace for a frame of this size");
+    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
+    check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+    check(rt_device_malloc(0, work, &d_work));
+    check(rt_denoise_device(width, height, d_sum, d_sum_sq, spp, d_spp, &dp, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+    std::vector<uint8_t> rgba((size_t)n_pix * 4u);
+    check(rt_device_download(0, rgba.data(), d_rgba8, n_pix * 4, nullptr));
+    cleanup();
+    std::vector<uint8_t> rgb((size_t)n_pix * 3u);
+    for (size_t p = 0; p < (size_t)n_pix; ++p) { rgb[3 * p] = rgba[4 * p]; rgb[3 * p + 1] = rgba[4 * p + 1]; rgb[3 * p + 2] = rgba[4 * p + 2]; }
+    return rgb;
+}
+
+// A plain render on device 0 that ends in the denoiser: the frame's sums and sums of squares (rt_render_moments_device) stay on the
+// device, are filtered there, and only the display bytes come back.
+static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const rt_camera cam = camera.pod();
+    const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
+    rt_scene *scene = nullptr;
+    void *d_sum = nullptr, *d_sq = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_scene_destroy(scene); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
+    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sq));
+    rt_render_params p{};
+    p.seed = opt.seed; p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    check(rt_render_moments_device(scene, &cam, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
+    std::vector<uint8_t> px;
+    try {
+        px = denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), cam.samples_per_pixel,
+                     nullptr, opt);
+    } catch (...) { cleanup(); throw; }
+    cleanup();
+    return px;
+}
+
 // Adaptive sampling on device 0: the frame's sums and per-pixel spp stay on the device, are resolved there with each pixel's own
 // spp, and only the bytes come back.
 static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
@@ -137,8 +188,8 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     const rt_camera cam = camera.pod();
     const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
     rt_scene *scene = nullptr;
-    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr;
-    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_scene_destroy(scene); };
+    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr, *d_sq = nullptr; // (d_sq: only with opt.denoise)
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_device_free(0, d_sq); rt_scene_destroy(scene); };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
@@ -151,12 +202,20 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     check(rt_adaptive_params_init_sized(&a, sizeof a));
     a.min_spp = opt.min_spp; a.batch_spp = opt.batch_spp; a.rel_threshold = opt.adaptive_rel; a.abs_threshold = opt.adaptive_abs;
     rt_adaptive_result res{};
-    check(rt_render_adaptive_device(scene, &cam, &p, &a, static_cast<double *>(d_sum), static_cast<int32_t *>(d_spp), nullptr, nullptr, &res));
-    check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
-                                     static_cast<uint8_t *>(d_rgb8), nullptr));
+    if (opt.denoise) check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sq));
+    check(rt_render_adaptive_device(scene, &cam, &p, &a, static_cast<double *>(d_sum), static_cast<int32_t *>(d_spp), static_cast<double *>(d_sq), nullptr, &res));
     std::vector<uint8_t> px((size_t)n_pix * 3u);
     std::vector<int32_t> spp((size_t)n_pix);
-    check(rt_device_download(0, px.data(), d_rgb8, n_pix * 3, nullptr));
+    if (opt.denoise) { // the frame is written from the denoised mean: every pixel's own spp is its n
+        try {
+            px = denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
+                         static_cast<const int32_t *>(d_spp), opt);
+        } catch (...) { cleanup(); throw; }
+    } else {
+        check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
+                                         static_cast<uint8_t *>(d_rgb8), nullptr));
+        check(rt_device_download(0, px.data(), d_rgb8, n_pix * 3, nullptr));
+    }
     check(rt_device_download(0, spp.data(), d_spp, n_pix * (int64_t)sizeof(int32_t), nullptr));
     cleanup();
     int32_t lo = spp.empty() ? 0 : spp[0], hi = lo;
@@ -254,8 +313,8 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
         render_orbit(*camera, *world, output_file_name, opt);
         return;
     }
-    if (opt.adaptive) {
-        const std::vector<uint8_t> px = render_adaptive_rgb8(*camera, *world, opt);
+    if (opt.adaptive || opt.denoise) {
+        const std::vector<uint8_t> px = opt.adaptive ? render_adaptive_rgb8(*camera, *world, opt) : render_denoised_rgb8(*camera, *world, opt);
         if (!opt.quiet) printf("Render time: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         now = clock::now();
         if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");

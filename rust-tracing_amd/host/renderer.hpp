@@ -32,7 +32,19 @@ struct RenderOptions {
     // axis through look_at along vup by 360 k / orbit degrees (camera.hpp orbit_look_from), with seed + k, and goes to
     // <output_file_name>_<k as three digits>.png.  One GPU, single pass.
     int orbit = 0;
+    // the variance-guided à-trous denoiser (include/rt_amd.h "denoise") over the frame before it is written: a plain render then
+    // goes through rt_render_moments_device, an adaptive one hands over its sums, sums of squares and spp map.  One GPU, single pass.
+    bool denoise = false;
+    int denoise_iters = 4;
+    double denoise_sigma = 4.0;
 };
+
+// rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
+// `spp` or, if d_spp is not null, a device map of w * h int32: allocates the workspace and the outputs, runs the filter with
+// opt.denoise_iters / opt.denoise_sigma and returns the display frame's RGB bytes (3 * w * h).  Throws std::runtime_error on a GPU
+// library error.
+std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                             const RenderOptions &opt = {});
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""MI355X.  What the denoiser costs beside the render it cleans up: milliseconds per rt_denoise_device call (HIP events, after a
+warm-up, the median of --repeats calls) at K = 4 with the display bytes, for the bench scene at 1200 x 800 and at 256 x 256, and
+beside each the milliseconds of the 16-spp rt_render_moments_device of the same frame, measured the same way.
+
+    python tools/denoise_speed.py [--repeats 20] [--iterations 4]
+
+Prints one table row per frame (markdown, for DESIGN.md section 5 "Denoise") and one JSON line."""
+import argparse
+import importlib
+import json
+import statistics
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def timed(fn, repeats, torch):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--iterations", type=int, default=4)
+    ap.add_argument("--spp", type=int, default=16)
+    args = ap.parse_args()
+    import torch
+    rt = importlib.import_module("rust-tracing_amd")
+    rows = []
+    for width, aspect in ((1200, 1.5), (256, 1.0)):
+        hs = rt.HostScene(0, width=width, aspect=aspect, spp=args.spp, depth=50)
+        w, h = hs.width, hs.height
+        ds = rt.DeviceScene(hs)
+        stream = torch.cuda.current_stream().cuda_stream
+        d_s = torch.zeros(3 * w * h, dtype=torch.float64, device="cuda")
+        d_q, d_out = torch.zeros_like(d_s), torch.zeros_like(d_s)
+        d_b = torch.zeros(4 * w * h, dtype=torch.uint8, device="cuda")
+        d_ws = torch.empty(rt.denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        p = rt.render_params(seed=1, sample_end=args.spp)
+        dp = rt.denoise_params(iterations=args.iterations)
+
+        def render():
+            ds.render_moments_device(p, d_s.data_ptr(), d_q.data_ptr(), stream)
+
+        def denoise():
+            rt.denoise_device(w, h, d_s.data_ptr(), d_q.data_ptr(), args.spp, d_out.data_ptr(), d_ws.data_ptr(), d_rgba8_ptr=d_b.data_ptr(),
+                              params=dp, stream=stream)
+
+        render_ms, render_min = timed(render, args.repeats, torch)
+        denoise_ms, denoise_min = timed(denoise, args.repeats, torch)
+        rows.append(dict(width=w, height=h, spp=args.spp, iterations=args.iterations, render_ms=round(render_ms, 4), render_min_ms=round(render_min, 4),
+                         denoise_ms=round(denoise_ms, 4), denoise_min_ms=round(denoise_min, 4), share=round(denoise_ms / (render_ms + denoise_ms), 4)))
+    print(f"| frame | {args.spp}-spp moments render, ms | denoise K = {args.iterations}, ms | denoise share of the preview |")
+    print("|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['width']} x {r['height']} | {r['render_ms']:.3f} | {r['denoise_ms']:.3f} | {100 * r['share']:.1f} % |")
+    print(json.dumps(dict(tool="denoise_speed", device=torch.cuda.get_device_name(0), repeats=args.repeats, rows=rows)))
+
+
+if __name__ == "__main__":
+    main()
