@@ -167,6 +167,13 @@ int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device);
  * out[3] = workgroups. */
 int rt_debug_last_launch(uint32_t out[4]);
 
+/* Which render kernel the calling thread's last render ran (filled where rt_debug_last_launch's figures are, so a refused call
+ * leaves the earlier render's): out[0] = the kernel's feature mask (1 spheres, 2 quads, 4 frames, 8 media, 16 textures; 31: the
+ * every-feature kernel), out[1] = LDS level (3: the scene whole, 1: the records, 0: nothing), out[2] = 1: the library's own trees,
+ * 0: the reference's order, out[3] = 1: four-child records, out[4] = 1: the small tables in the LDS (AUX), out[5] = job mode
+ * (0 dense, 1 pixel list, 2 views), out[6] = ids_ok (0: every attenuation is parked as a colour), out[7] = workgroup threads. */
+int rt_debug_last_kernel(uint32_t out[8]);
+
 /* Test hook: one convergence step of adaptive sampling (rt_render_adaptive) on chosen inputs — the three kernels and the scratch
  * layout of the render's own step, nothing rendered.  Host arrays in and out.  list: n_list entries (a positive multiple of 64),
  * pixel indices below n_pixels (< 2^27) or padding (anything else, by convention 0xffffffff); sum, sum_sq: 3 * n_pixels doubles;

@@ -307,6 +307,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_stage_profile": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_visit_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_last_launch": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "rt_debug_last_kernel": (C.c_int, [C.POINTER(C.c_uint32)]),
     "rt_debug_adaptive_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -481,6 +482,19 @@ def debug_last_launch() -> dict:
     buf = (C.c_uint32 * 4)()
     _check(amd_lib().rt_debug_last_launch(buf), "rt_debug_last_launch")
     return {"launches": int(buf[0]), "lds_level": int(buf[1]), "threads": int(buf[2]), "grid": int(buf[3])}
+
+
+# the render kernels' feature masks (rt_kernels.h) and job modes, as rt_debug_last_kernel reports them
+RT_FEAT_SPHERES_SOLID, RT_FEAT_QUADS_FRAMES, RT_FEAT_QUADS_FRAMES_MEDIA, RT_FEAT_SPHERES_QUADS_TEXTURES, RT_FEAT_ALL = 1, 6, 14, 19, 31
+RT_JOBS_DENSE, RT_JOBS_LIST, RT_JOBS_VIEWS = 0, 1, 2
+
+
+def debug_last_kernel() -> dict:
+    """rt_debug_last_kernel: which render kernel this thread's last render ran (feature mask, LDS level, own trees?, four-child
+    records?, small tables in the LDS?, job mode, ids_ok, workgroup threads)."""
+    buf = (C.c_uint32 * 8)()
+    _check(amd_lib().rt_debug_last_kernel(buf), "rt_debug_last_kernel")
+    return dict(zip(("features", "lds_level", "ordered", "wide", "aux", "jobs", "ids_ok", "threads"), (int(x) for x in buf)))
 
 
 def debug_adaptive_step(pixels, sums, sums_sq, n, rel, abs, *, last=False, spp=None, list_out=None, device=0):

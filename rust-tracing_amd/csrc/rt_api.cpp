@@ -14,6 +14,7 @@ namespace rtapi {
 
 thread_local std::string g_last_error;
 thread_local uint32_t g_last_launch[4] = {0, 0, 0, 0};
+thread_local uint32_t g_last_kernel[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 std::mutex g_stage_profile_mu;
 unsigned long long g_stage_profile[PROF_SLOTS * 3] = {0};
 unsigned long long g_visit_stats[VISIT_STATS] = {0};
@@ -85,6 +86,9 @@ size_t prof_offset(const rt_scene *s, int lds) { return world_offset(s, lds) + (
 size_t dynamic_lds_bytes(const rt_scene *s, int lds, bool counted) {
     return prof_offset(s, lds) + (counted ? prof_bytes(s, lds) : 0);
 }
+// rt_scene::blocks_per_cu's second index: every instantiation a render may launch has its own occupancy figure (only the dense
+// kernel has an instrumented twin)
+int kernel_variant(bool counted, int jobs) { return jobs == JOBS_VIEWS ? 3 : jobs == JOBS_LIST ? 2 : counted ? 1 : 0; }
 
 template <class T> int upload(DeviceArray<T> &dst, const std::vector<T> &src) {
     dst.bytes = src.size() * sizeof(T);
@@ -251,7 +255,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
 
     const int lds = tn.use_lds != 0 ? scene->lds_level : 0;
     const int threads = block_threads(scene, lds);
-    const int bpc = scene->blocks_per_cu[lds][counted ? 1 : 0];
+    const int jobs = views ? JOBS_VIEWS : list ? JOBS_LIST : JOBS_DENSE;
+    const int bpc = scene->blocks_per_cu[lds][kernel_variant(counted, jobs)];
     const size_t dyn_lds = dynamic_lds_bytes(scene, lds, counted);
     // persistent grid: every resident wave pulls jobs until none are left
     int64_t grid = (int64_t)scene->n_cus * bpc;
@@ -505,7 +510,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         {
             void *args[] = {(void *)&K};
             const uint32_t kf = kernel_features_for(scene->features, lds, scene->ordered);
-            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, views ? JOBS_VIEWS : list ? JOBS_LIST : JOBS_DENSE);
+            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, jobs);
             HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, dyn_lds, s));
         }
         HIP_TRY(hipGetLastError());
@@ -523,6 +528,9 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     HIP_TRY(hipEventRecord(ws.ev_done, stream));
     release.completed = true;
     g_last_launch[0] = (uint32_t)k; g_last_launch[1] = (uint32_t)lds; g_last_launch[2] = (uint32_t)threads; g_last_launch[3] = (uint32_t)grid;
+    g_last_kernel[0] = kernel_features_for(scene->features, lds, scene->ordered); g_last_kernel[1] = (uint32_t)lds;
+    g_last_kernel[2] = scene->ordered ? 1u : 0u; g_last_kernel[3] = scene->wide ? 1u : 0u; g_last_kernel[4] = aux_in_lds(scene, lds) ? 1u : 0u;
+    g_last_kernel[5] = (uint32_t)jobs; g_last_kernel[6] = K.ids_ok; g_last_kernel[7] = (uint32_t)threads;
 
     if (counted) {
         unsigned long long host[COUNTER_WORDS];
@@ -1024,16 +1032,20 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
             s->aux_off[3] = (uint32_t)o_media; s->aux_off[4] = (uint32_t)o_perlins;
         }
     }
+    // every kernel a render of this scene may launch — dense, its instrumented twin, the list and the views twin — gets its LDS
+    // attribute set and its own occupancy figure: the twins are code objects of their own, with their own register counts
     for (int lds = 0; lds < 4; ++lds)
-        for (int counted = 0; counted < 2; ++counted) {
-            if (lds && lds != s->lds_level) { s->blocks_per_cu[lds][counted] = 0; continue; }
-            const void *fn = path_kernel_for(lds, counted != 0, kernel_features_for(s->features, lds, s->ordered), s->ordered, aux_in_lds(s, lds), s->wide);
+        for (int variant = 0; variant < 4; ++variant) {
+            if (lds && lds != s->lds_level) { s->blocks_per_cu[lds][variant] = 0; continue; }
+            const bool counted = variant == 1;
+            const int jobs = variant == 3 ? JOBS_VIEWS : variant == 2 ? JOBS_LIST : JOBS_DENSE;
+            const void *fn = path_kernel_for(lds, counted, kernel_features_for(s->features, lds, s->ordered), s->ordered, aux_in_lds(s, lds), s->wide, jobs);
             const int threads = block_threads(s, lds);
-            const size_t dyn = dynamic_lds_bytes(s, lds, counted != 0);
+            const size_t dyn = dynamic_lds_bytes(s, lds, counted);
             if (dyn > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
             int b = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, threads, dyn) != hipSuccess || b < 1) b = 1;
-            s->blocks_per_cu[lds][counted] = b;
+            s->blocks_per_cu[lds][variant] = b;
         }
 
     int rc = RT_OK;

@@ -19,6 +19,7 @@ using namespace rtd;
 using namespace rtk;
 
 extern thread_local uint32_t g_last_launch[4]; // of the calling thread's last render: render-kernel launches, LDS level, workgroup threads, grid
+extern thread_local uint32_t g_last_kernel[8]; // ... and which kernel it ran (rt_debug_last_kernel): features, LDS level, ordered, wide, AUX, job mode, ids_ok, threads
 int fail(int status, const std::string &msg); // sets rt_last_error() of the calling thread, returns `status`
 #define HIP_TRY(expr)                                                                                          \
     do {                                                                                                       \
@@ -145,7 +146,7 @@ using namespace rtapi; // (an internal header of three translation units)
 struct rt_scene {
     int device = 0;
     int n_cus = 0;
-    int blocks_per_cu[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}; // [LDS level][counted?]
+    int blocks_per_cu[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}; // [LDS level][kernel variant: dense, dense counted, list, views]
     rtapi::DeviceArray<uint4> lds_image;               // the LDS-resident copy of nodes / spheres / quads (if they fit)
     uint32_t lds_off_node_b = 0, lds_off_spheres = 0, lds_off_quads = 0, lds_image_bytes = 0;
     uint32_t lds_off_qfilt = 0;                 // the quads' f32 filter records in the LDS image (0: none)

@@ -421,6 +421,12 @@ int rt_debug_last_launch(uint32_t out[4]) {
     return RT_OK;
 }
 
+int rt_debug_last_kernel(uint32_t out[8]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_last_kernel: null argument");
+    for (int k = 0; k < 8; ++k) out[k] = g_last_kernel[k];
+    return RT_OK;
+}
+
 int rt_debug_adaptive_step(int64_t n_list, const uint32_t *list, int64_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
                            int32_t last, double rel_threshold, double abs_threshold, int32_t *spp, uint32_t *list_out, uint32_t *out_count,
                            int device) {

@@ -339,3 +339,21 @@ def many_instances_scene(camera_from, n, seed=3, spheres=True):
         pos = ((gx - side / 2) * 0.9 + rnd.uniform(-0.3, 0.3), rnd.uniform(-1.0, 0.5), (gz - side / 2) * 0.9 + rnd.uniform(-0.3, 0.3))
         world.append(s.translate(s.rotate_y(inner, rnd.uniform(-90, 90)), pos))
     return s.finish(s.list(world))
+
+
+def many_materials_scene(camera_from, n_lambertian, depth=12):
+    """n_lambertian + 2 materials, few of them used but those spread over the whole range: with 65 535 or more, a parked attenuation's
+    16-bit material index no longer names them all and the scene is rendered by the kernels that park colours (rt_api.cpp ids_ok = 0).
+    (The scene of tests/test_gpu_ties.py test_more_materials_than_a_parked_index_can_name.)"""
+    import random
+    rnd = random.Random(3)
+    s = CustomScene(camera_from, spp=4, depth=depth, background=(0.7, 0.8, 1.0))
+    mats = [s.lambertian(rnd.random(), rnd.random(), rnd.random()) for _ in range(n_lambertian)]
+    mats += [s.metal(0.9, 0.8, 0.7, 0.1), s.dielectric(1.5)]
+    n = len(mats)
+    pick = [mats[0], mats[1], mats[65530], mats[65531], mats[n // 2], mats[n - 4], mats[n - 3], mats[n - 2], mats[n - 1]]
+    items = [s.sphere((0.0, -1003.0, 0.0), 1000.0, mats[40000])]
+    for k in range(40):
+        items.append(s.sphere((rnd.uniform(-4, 4), rnd.uniform(-2.5, 1.5), rnd.uniform(-4, 2)), rnd.uniform(0.3, 0.8), pick[k % len(pick)]))
+    items.append(s.quad((-5.0, -3.0, -5.0), (10.0, 0.0, 0.0), (0.0, 6.0, 0.0), mats[n - 5]))
+    return s.finish(s.list(items))
