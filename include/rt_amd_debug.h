@@ -74,6 +74,10 @@ int rt_debug_set_traversal(int32_t ordered, int32_t leaf_max);
 int rt_debug_set_walk_shortcuts(int32_t flat_max, int32_t start_shortcut, int32_t defer_instances, int32_t seq_lookahead,
                                 int32_t slow_min, int32_t slow_age);
 
+/* Test / tuning hook: where the start shortcut's leaf is a single sphere, renders from now on run that sphere's test where a query
+ * starts (1, the default; RT_START_INLINE) or in a round of the sphere stage (0); negative: keep.  Affects speed only, never results. */
+int rt_debug_set_start_inline(int32_t start_inline);
+
 /* Test hook: the ordered layout the scene compiler builds for `desc` (no device needed).  Set the cap_* fields and
  * the pointers (any may be null: only the counts are returned then).
  * nodes: 16 words per record = two boxes as 6 floats (x.lo, x.hi, y.lo, y.hi, z.lo, z.hi), two child references
@@ -173,6 +177,13 @@ int rt_debug_last_launch(uint32_t out[4]);
  * 0: the reference's order, out[3] = 1: four-child records, out[4] = 1: the small tables in the LDS (AUX), out[5] = job mode
  * (0 dense, 1 pixel list, 2 views), out[6] = ids_ok (0: every attenuation is parked as a colour), out[7] = workgroup threads. */
 int rt_debug_last_kernel(uint32_t out[8]);
+
+/* How the queries of the calling thread's last render started (filled where rt_debug_last_kernel's figures are): out[0] = the start
+ * shortcut's stage (1 spheres, 2 quads; 0: none, a query starts at the root), out[1], out[2] = the start leaf's primitives
+ * [first, end), out[3] = 1: the launch asked for the inline start test (one sphere in the leaf, start_inline on).  The test runs
+ * inline only where the kernel has it compiled: feature mask 1 with the library's own trees (out[0], out[2] of rt_debug_last_kernel);
+ * every other kernel ignores the word and tests the leaf in its stage. */
+int rt_debug_last_start(uint32_t out[4]);
 
 /* Test hook: one convergence step of adaptive sampling (rt_render_adaptive) on chosen inputs — the three kernels and the scratch
  * layout of the render's own step, nothing rendered.  Host arrays in and out.  list: n_list entries (a positive multiple of 64),

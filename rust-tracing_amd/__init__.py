@@ -308,6 +308,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_visit_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "rt_debug_last_launch": (C.c_int, [C.POINTER(C.c_uint32)]),
     "rt_debug_last_kernel": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "rt_debug_last_start": (C.c_int, [C.POINTER(C.c_uint32)]),
     "rt_debug_adaptive_step": (C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.c_int]),
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -315,6 +316,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_wide_visits": (C.c_int, [C.c_void_p, C.c_int]),
     "rt_debug_set_traversal": (C.c_int, [C.c_int32, C.c_int32]),
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rt_debug_set_start_inline": (C.c_int, [C.c_int32]),
     "rt_debug_ordered_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_ordered_layout_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tuning": (C.c_int, [C.c_int32] * 6),
@@ -495,6 +497,17 @@ def debug_last_kernel() -> dict:
     buf = (C.c_uint32 * 8)()
     _check(amd_lib().rt_debug_last_kernel(buf), "rt_debug_last_kernel")
     return dict(zip(("features", "lds_level", "ordered", "wide", "aux", "jobs", "ids_ok", "threads"), (int(x) for x in buf)))
+
+
+def debug_last_start() -> dict:
+    """rt_debug_last_start: how the queries of this thread's last render started (the start shortcut's stage, its leaf's primitives
+    [first, end), whether the launch asked for the inline start test) and `ran_inline`: whether the kernel it ran has that test."""
+    buf = (C.c_uint32 * 4)()
+    _check(amd_lib().rt_debug_last_start(buf), "rt_debug_last_start")
+    k = debug_last_kernel()
+    out = dict(zip(("stage", "first", "end", "start_inline"), (int(x) for x in buf)))
+    out["ran_inline"] = int(out["start_inline"] == 1 and k["features"] == RT_FEAT_SPHERES_SOLID and k["ordered"] == 1)
+    return out
 
 
 def debug_adaptive_step(pixels, sums, sums_sq, n, rel, abs, *, last=False, spp=None, list_out=None, device=0):

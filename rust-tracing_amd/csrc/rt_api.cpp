@@ -15,6 +15,7 @@ namespace rtapi {
 thread_local std::string g_last_error;
 thread_local uint32_t g_last_launch[4] = {0, 0, 0, 0};
 thread_local uint32_t g_last_kernel[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+thread_local uint32_t g_last_start[4] = {0, 0, 0, 0};
 std::mutex g_stage_profile_mu;
 unsigned long long g_stage_profile[PROF_SLOTS * 3] = {0};
 unsigned long long g_visit_stats[VISIT_STATS] = {0};
@@ -27,7 +28,7 @@ int fail(int status, const std::string &msg) {
 Tuning::Tuning() {
     auto env = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
     env("RT_TH_PRIM", forced[0]); env("RT_TH_OTHER", forced[1]); env("RT_TH_SHADE", forced[2]); env("RT_TH_BOX", forced[3]); env("RT_TH_NEW", forced[4]);
-    env("RT_USE_LDS", use_lds); env("RT_REFIT", refit); env("RT_ORDERED", ordered); env("RT_JOBS_PER_GRAB", jobs_per_grab); env("RT_GRAB_TAPER", grab_taper); env("RT_DEFER", defer); env("RT_START_SHORTCUT", start_shortcut); env("RT_SEQ_LOOKAHEAD", seq_lookahead); env("RT_SLOW_MIN", slow_min); env("RT_SLOW_AGE", slow_age); env("RT_OVERLAP", overlap);
+    env("RT_USE_LDS", use_lds); env("RT_REFIT", refit); env("RT_ORDERED", ordered); env("RT_JOBS_PER_GRAB", jobs_per_grab); env("RT_GRAB_TAPER", grab_taper); env("RT_DEFER", defer); env("RT_START_SHORTCUT", start_shortcut); env("RT_START_INLINE", start_inline); env("RT_SEQ_LOOKAHEAD", seq_lookahead); env("RT_SLOW_MIN", slow_min); env("RT_SLOW_AGE", slow_age); env("RT_OVERLAP", overlap);
     env("RT_WIDE", wide); env("RT_WIDE_SETASIDE", wide_setaside); env("RT_QUAD_FILTER", quad_filter); env("RT_MEDIUM_FIRST", medium_first);
     if (const char *e = getenv("RT_SAH_LEAF")) ordered_options.leaf_max = (uint32_t)atoi(e);
     if (const char *e = getenv("RT_FLAT_MAX")) ordered_options.flat_max = (uint32_t)atoi(e);
@@ -451,6 +452,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     K.o_start_stage = tn.start_shortcut ? scene->o_start_stage : 0u; K.o_start_prim = scene->o_start_prim; K.o_start_end = scene->o_start_end;
     K.o_start_rest = scene->o_start_rest; K.o_start_slot = scene->o_start_slot;
     K.setaside_direct = tn.wide_setaside != 0 ? 1u : 0u;
+    // the inline start test (path_kernel): the shortcut's leaf is one sphere (OrderedKind SPHERES = Stage ST_SPHERE = 1)
+    K.start_inline = (tn.start_inline != 0 && K.o_start_stage == (uint32_t)OK_SPHERES && K.o_start_end == K.o_start_prim + 1u) ? 1u : 0u;
     if (scene->wide) { // the start shortcut's entry as the kernel pushes it (rt_kernel.hip W_SHIFT: 2-byte entries in the LDS kernels)
         const uint32_t w_shift = lds != 0 ? 12u : 26u, w_full = 0xfu << w_shift;
         if (K.setaside_direct && scene->o_start_direct != 0xffffffffu) K.o_start_rest = scene->o_start_direct | w_full;
@@ -531,6 +534,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     g_last_kernel[0] = kernel_features_for(scene->features, lds, scene->ordered); g_last_kernel[1] = (uint32_t)lds;
     g_last_kernel[2] = scene->ordered ? 1u : 0u; g_last_kernel[3] = scene->wide ? 1u : 0u; g_last_kernel[4] = aux_in_lds(scene, lds) ? 1u : 0u;
     g_last_kernel[5] = (uint32_t)jobs; g_last_kernel[6] = K.ids_ok; g_last_kernel[7] = (uint32_t)threads;
+    g_last_start[0] = scene->ordered ? K.o_start_stage : 0u; g_last_start[1] = K.o_start_prim; g_last_start[2] = K.o_start_end; g_last_start[3] = scene->ordered ? K.start_inline : 0u;
 
     if (counted) {
         unsigned long long host[COUNTER_WORDS];
@@ -1151,7 +1155,8 @@ int rt_render(const rt_scene *scene, const rt_camera *camera, const rt_render_pa
 // the frame-end kernels run on the device that owns the buffers, whichever device the calling thread had selected
 static int select_device_of(const void *device_ptr, const char *who) {
     hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, device_ptr) != hipSuccess) {
+    // (a plain host pointer: an error on some runtimes, success with type "unregistered" and device -1 on others)
+    if (hipPointerGetAttributes(&attr, device_ptr) != hipSuccess || attr.type == hipMemoryTypeUnregistered || attr.device < 0) {
         (void)hipGetLastError();
         return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": not a device pointer");
     }

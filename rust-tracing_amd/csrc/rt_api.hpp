@@ -20,6 +20,7 @@ using namespace rtk;
 
 extern thread_local uint32_t g_last_launch[4]; // of the calling thread's last render: render-kernel launches, LDS level, workgroup threads, grid
 extern thread_local uint32_t g_last_kernel[8]; // ... and which kernel it ran (rt_debug_last_kernel): features, LDS level, ordered, wide, AUX, job mode, ids_ok, threads
+extern thread_local uint32_t g_last_start[4];  // ... and how its queries started (rt_debug_last_start): start stage, the leaf's [prim, end), start_inline as launched
 int fail(int status, const std::string &msg); // sets rt_last_error() of the calling thread, returns `status`
 #define HIP_TRY(expr)                                                                                          \
     do {                                                                                                       \
@@ -94,6 +95,7 @@ struct Tuning {
     int slow_min = 4, slow_age = 32; // KParams::slow_min / slow_age (RT_SLOW_MIN, RT_SLOW_AGE; slow_min 1: nobody waits)
     int seq_lookahead = 1;  // scenes with media: a query looks ahead at the boxes of the sequence's later steps when it starts (RT_SEQ_LOOKAHEAD)
     int start_shortcut = 1; // a root whose one child is a single sphere spanning the scene (random-spheres' ground): queries start with that sphere's test (RT_START_SHORTCUT)
+    int start_inline = 1;   // ... and where that leaf is one sphere, its test runs where the query starts, not in a round of the sphere stage (RT_START_INLINE; rt_debug_set_start_inline)
     int defer = 1;         // ordered walk: the world frame's instances (<= 32) are walked after the world's own tree, one frame change each instead of two (RT_DEFER)
     int grab_taper = 8;    // guided hand-out: a grab takes at most 1 / (waves x this) of the jobs left (RT_GRAB_TAPER; 0: off; tools/sweep_grabs.sh)
     OrderedOptions ordered_options;

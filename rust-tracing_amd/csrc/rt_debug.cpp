@@ -45,6 +45,14 @@ int rt_debug_set_walk_shortcuts(int32_t flat_max, int32_t start_shortcut, int32_
     return RT_OK;
 }
 
+int rt_debug_set_start_inline(int32_t start_inline) {
+    tuning_update([](Tuning &t, const void *arg) {
+        const int32_t v = *static_cast<const int32_t *>(arg);
+        if (v >= 0) t.start_inline = v;
+    }, &start_inline);
+    return RT_OK;
+}
+
 int rt_debug_ordered_layout(const rt_scene_desc *desc, rt_debug_ordered *io) { return rt_debug_ordered_layout_ex(desc, nullptr, io); }
 
 int rt_debug_ordered_layout_ex(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_ordered *io) {
@@ -427,7 +435,13 @@ int rt_debug_last_kernel(uint32_t out[8]) {
     return RT_OK;
 }
 
-int rt_debug_adaptive_step(int64_t n_list, const uint32_t *list, int64_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
+int rt_debug_last_start(uint32_t out[4]) {
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_last_start: null argument");
+    for (int k = 0; k < 4; ++k) out[k] = g_last_start[k];
+    return RT_OK;
+}
+
+int rt_debug_adaptive_step(int64_t n_list,const uint32_t *list, int64_t n_pixels, const double *sum, const double *sum_sq, int32_t n,
                            int32_t last, double rel_threshold, double abs_threshold, int32_t *spp, uint32_t *list_out, uint32_t *out_count,
                            int device) {
     if (!list || !sum || !sum_sq || !spp || !list_out || !out_count) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_adaptive_step: null argument");

@@ -1221,7 +1221,53 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 // (Measured against visiting the root record right here, with its box tests: 5340 vs 5060 Msamples/s on C2.  The blind
                 // test keeps the lanes that start a query together — ONE round of the primitive stage serves them all, then they all walk
                 // —, and a round costs the same for 23 lanes as for 43: the 1.2 tests per sample spent on rays that miss the leaf's box are free.)
-                if (P.o_start_stage != 0u) { // the root's big leaf first, its other child set aside (rt_api.cpp "start shortcut")
+                // Inline start test: where that leaf is ONE sphere (random-spheres' ground) its test runs right here, for the lanes that start
+                // a query — they are together now, which is why the shortcut exists —, not in a round of the sphere stage one pass of the
+                // scheduler later.  Sphere::hit's operations in the stage's order, on a sphere every lane shares (its fields are uniform
+                // reads); what the stage settles per lane is known here: nothing is hit yet, so no tie (inside(root) is 0.001 < root < inf),
+                // and the stack entry the stage's o_next would read back is a kernel argument, so the stack is not touched.
+                // (Compiled for the kernels without textures — the spheres-only ones, 104-109 registers of 128: the textures kernels are at
+                // the limit and spill already; with the test inlined their spills moved, 57 -> 73 registers in the worst of them.)
+                if (HAS_SPHERES && !HAS_TEXTURES && P.start_inline != 0u) { // (wave-uniform; the host sets it only for a start leaf of one sphere)
+                    // TWO COPIES, keep them in step: the test below is the ST_SPHERE block's (its Sphere::hit, with best_prim == PRIM_NONE and
+                    // cur_tmax == INF put in), and what follows it is o_next(false, 0) for sp == 0 with stack[0] = the entry the branch below
+                    // would have stored (the pop, its S_EXIT / leave_frame reading, the StackT truncation).  An edit of either goes here too.
+                    if (COUNT) cn.sphere_tests++;
+                    const uint32_t q = P.o_start_prim;
+                    const Sphere *s = &sphere_tab[q];
+                    V3 center = ld3(s->center);
+                    if ((s->seq_moving & 1u)) center = center + ld3(s->center_vec) * time;
+                    const V3 oc = o - center;
+                    const double half_b = dot(oc, d);
+                    const double c = len2(oc) - s->radius * s->radius;
+                    const double discriminant = half_b * half_b - a * c;
+                    if (!(discriminant < 0.0)) {
+                        const double sqrtd = __builtin_sqrt(discriminant);
+                        double root = (-half_b - sqrtd) / a;
+                        bool ok = 0.001 < root && root < INF;
+                        if (!ok) {
+                            root = (-half_b + sqrtd) / a;
+                            ok = 0.001 < root && root < INF;
+                        }
+                        if (ok) {
+                            cur_tmax = root;
+                            tmax32 = f32_above(root);
+                            best_prim = PRIM_SPHERE | q;
+                            best_inst = cur_inst;
+                        }
+                    }
+                    // on as the stage's o_next(false, 0) would: the root's other child, or nothing left to walk
+                    const uint32_t rest = P.o_start_rest;
+                    stage = ST_SHADE;
+                    if (WIDE ? rest != 0u : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
+                        uint32_t e;
+                        if constexpr (WIDE) e = (StackT)rest;
+                        else e = (StackT)(rest < (1u << OREF_KIND_SHIFT) ? rest : (first_node | (P.o_start_slot ? SKIP_CHILD1 : SKIP_CHILD0)));
+                        const bool leave_frame = HAS_FRAMES && e == S_EXIT; // (o_next's reading of a popped entry; constant false in the spheres-only kernels)
+                        node = leave_frame ? NODE_FRAME_EXIT : e;
+                        stage = leave_frame ? (uint32_t)ST_OTHER : (uint32_t)ST_BOX;
+                    }
+                } else if (P.o_start_stage != 0u) { // the root's big leaf first, its other child set aside (rt_api.cpp "start shortcut")
                     const uint32_t rest = P.o_start_rest;
                     if (WIDE ? rest != 0u : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
                         if constexpr (WIDE) stack[0] = (StackT)rest; // (rest: the entry itself, made on the host in this launch's format)

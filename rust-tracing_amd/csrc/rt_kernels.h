@@ -103,6 +103,12 @@ struct KParams {
     uint32_t lds_stack_off;
     uint32_t lds_seq_off;           // the world frame's sequence, copied in by the ordered kernels (after the stacks)
     uint32_t lds_prof_off;          // COUNT kernels: per-wave profile rows (last)
+    // 1: the start shortcut's leaf is ONE sphere and its test runs where the query starts, for the lanes that start one, not in a round of
+    // the sphere stage (path_kernel "inline start test"; RT_START_INLINE).  (The word sits in what was padding: no other argument moves.)
+    // A kernel may IGNORE it: only the spheres-only ordered kernels (FEAT_SPHERES_SOLID) have the test compiled in; in every other one — a
+    // textured scene with a ground sphere runs the textures kernel — the leaf is tested in the sphere stage as before, the word set or not
+    // (rt_debug_last_start reports the word, rt_debug_last_kernel the kernel).
+    uint32_t start_inline;
     // list mode (rt_render_pixels_device; path_kernel<..., LIST = true>): a "local tile" is a group of 64 entries of this list instead;
     // an entry that is no pixel of the frame (0xffffffff: padding) traces nothing.  The dense instantiations never read these four.
     const uint32_t *pixel_list;
