@@ -21,7 +21,13 @@ typedef enum rt_debug_op {
     RT_DEBUG_SQRT = 6, RT_DEBUG_DIV = 7 /* a / b */, RT_DEBUG_MUL_ADD = 8 /* a * b + a, two roundings */,
     RT_DEBUG_RNG_RANDOM = 9, RT_DEBUG_RNG_RANGE = 10 /* gen_range(-1.0..1.0) */,
     RT_DEBUG_F32_ABOVE = 11, RT_DEBUG_F32_BELOW = 12 /* the ordered walk's outward f32 conversions of an interval end (as doubles) */,
-    RT_DEBUG_RNG_UNNEXT = 13 /* random() number `b` of stream `a` after two draws too many were made and taken back (Rng::unnext) */
+    RT_DEBUG_RNG_UNNEXT = 13 /* random() number `b` of stream `a` after two draws too many were made and taken back (Rng::unnext) */,
+    /* The rejection samplers' accept / reject decision (rt_reject.hpp), on candidates given as RAW 64-bit draws, bit-cast into `a`:
+     * candidate c of the unit sphere is a[3c .. 3c+2], of the unit disk a[2c .. 2c+1]; n counts array elements, b is not read.
+     * VERDICTS: out[Kc] = the f32 classifier's verdict (0 certain reject, 1 certain accept, 2 uncertain), out[Kc + 1] = the exact f64
+     * predicate (1: accepted).  COORDS: out[Kc + k] = the f64 coordinate the kernel builds from draw k. */
+    RT_DEBUG_REJECT_SPHERE_VERDICTS = 14, RT_DEBUG_REJECT_SPHERE_COORDS = 15,
+    RT_DEBUG_REJECT_DISK_VERDICTS = 16, RT_DEBUG_REJECT_DISK_COORDS = 17
 } rt_debug_op;
 int rt_debug_eval(int32_t op, int64_t n, const double *a, const double *b, double *out, int device);
 

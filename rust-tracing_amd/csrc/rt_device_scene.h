@@ -4,6 +4,7 @@
 #include "rt_kernels.h"
 #include "rt_amd_debug.h"
 #include "rt_device_math.h"
+#include "rt_reject.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -60,14 +61,57 @@ RT_DEV void hit_to_world(const Instance *insts, int32_t inst, V3 &p, V3 &n) {
 }
 
 // ---- random vectors (src/vec3.rs:54-88) ------------------------------------------------------------------
-template <bool COUNT> RT_DEV V3 random_in_unit_sphere(Rng &rng, Counts &cn) {
-    for (;;) {
-        const double x = rng.range(-1.0, 1.0);
-        const double y = rng.range(-1.0, 1.0);
-        const double z = rng.range(-1.0, 1.0);
-        if (COUNT) cn.rng_draws += 3;
-        const V3 p = v3(x, y, z);
-        if (len2(p) < 1.0) return p;
+// F32: a pass keeps the raw draws and settles accept / reject in f32 (rt_reject.hpp: conservative, "uncertain" within 2^-19 of the
+// unit sphere — those lanes evaluate the reference's predicate on the spot); the f64 coordinates are built once, from the draws of
+// the pass that accepted, with range's own operations.  The stream and the values are those of the plain loop.
+template <bool COUNT, bool F32 = true> RT_DEV V3 random_in_unit_sphere(Rng &rng, Counts &cn) {
+    if constexpr (F32) {
+        uint64_t wx, wy, wz;
+        for (;;) {
+            wx = rng.next();
+            wy = rng.next();
+            wz = rng.next();
+            if (COUNT) cn.rng_draws += 3;
+            const int verdict = rtm::reject_sphere_f32(wx, wy, wz);
+            bool accept = verdict == rtm::REJECT_YES;
+            // (about 3e-6 of the candidates; the branch around it is the wave's ballot: skipped unless some lane is uncertain)
+            if (__builtin_expect(verdict == rtm::REJECT_UNCERTAIN, 0)) accept = rtm::reject_sphere_exact(wx, wy, wz);
+            if (accept) break;
+        }
+        return v3(rtm::reject_coord(wx), rtm::reject_coord(wy), rtm::reject_coord(wz));
+    } else {
+        for (;;) {
+            const double x = rng.range(-1.0, 1.0);
+            const double y = rng.range(-1.0, 1.0);
+            const double z = rng.range(-1.0, 1.0);
+            if (COUNT) cn.rng_draws += 3;
+            const V3 p = v3(x, y, z);
+            if (len2(p) < 1.0) return p;
+        }
+    }
+}
+// random_in_unit_disk's candidate (src/vec3.rs:77-88), the same way: the raw draws of the pass that accepted
+template <bool COUNT, bool F32 = true> RT_DEV void random_in_unit_disk(Rng &rng, Counts &cn, double &dx, double &dy) {
+    if constexpr (F32) {
+        uint64_t wx, wy;
+        for (;;) {
+            wx = rng.next();
+            wy = rng.next();
+            if (COUNT) cn.rng_draws += 2;
+            const int verdict = rtm::reject_disk_f32(wx, wy);
+            bool accept = verdict == rtm::REJECT_YES;
+            if (__builtin_expect(verdict == rtm::REJECT_UNCERTAIN, 0)) accept = rtm::reject_disk_exact(wx, wy);
+            if (accept) break;
+        }
+        dx = rtm::reject_coord(wx);
+        dy = rtm::reject_coord(wy);
+    } else {
+        for (;;) {
+            dx = rng.range(-1.0, 1.0);
+            dy = rng.range(-1.0, 1.0);
+            if (COUNT) cn.rng_draws += 2;
+            if (dx * dx + dy * dy + 0.0 * 0.0 < 1.0) break;
+        }
     }
 }
 template <bool COUNT> RT_DEV V3 random_unit_vector(Rng &rng, Counts &cn) {

@@ -73,6 +73,11 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     // the quads of a multi-quad leaf go through the conservative f32 filter first (rt_device_scene.h quad_pair_keep): scenes that live
     // in the LDS whole (their filter records with them)
     constexpr bool QFILT = ORDERED && LDS == 3 && HAS_QUADS;
+    // the two rejection samplers (unit sphere: a scattering hit; unit disk: a camera ray with defocus) settle accept / reject in f32
+    // and build the f64 candidate once (rt_reject.hpp).  Not in the media kernels of scenes that live in the LDS whole: at 128 registers
+    // they are the ones the kept draws push further into scratch (+16 bytes a lane in seven of their variants; of the other dense
+    // kernels none gains any — profiles/reject_f32_kernel_usage_{before,after}.txt)
+    constexpr bool REJECT_F32 = !(HAS_MEDIA && LDS == 3);
     // parked attenuations loaded per trip when a path ends: 4 where registers allow (the general kernels at 128 registers
     // already spill; their 256-thread form has 168)
     constexpr uint32_t CHAIN = (HAS_TEXTURES && LDS != 0) ? 1u : 4u;
@@ -966,7 +971,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 V3 tex = v3(1.0, 1.0, 1.0);
                 V3 rs = v3(0.0, 0.0, 0.0);
                 PROF_MARK(6);
-                if (mk != RT_MATERIAL_DIELECTRIC && mk != RT_MATERIAL_DIFFUSE_LIGHT) rs = random_in_unit_sphere<COUNT>(rng, cn);
+                if (mk != RT_MATERIAL_DIELECTRIC && mk != RT_MATERIAL_DIFFUSE_LIGHT) rs = random_in_unit_sphere<COUNT, REJECT_F32>(rng, cn);
                 PROF_MARK(7);
                 if (mk != RT_MATERIAL_DIELECTRIC && mk != RT_MATERIAL_METAL) {
                     if constexpr (HAS_TEXTURES) tex = m->solid ? ld3(m->albedo) : texture_value<COUNT>(P, texs_tab, perlin_tab, m->texture, u, v, p, cn);
@@ -1178,12 +1183,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                                 ro = v3(cam.center.x, cam.center.y, cam.center.z);
                             } else { // random_in_unit_disk (src/vec3.rs:77-88)
                                 double dx, dy;
-                                for (;;) {
-                                    dx = rng.range(-1.0, 1.0);
-                                    dy = rng.range(-1.0, 1.0);
-                                    if (COUNT) cn.rng_draws += 2;
-                                    if (dx * dx + dy * dy + 0.0 * 0.0 < 1.0) break;
-                                }
+                                random_in_unit_disk<COUNT, REJECT_F32>(rng, cn, dx, dy);
                                 ro = v3(cam.center.x, cam.center.y, cam.center.z) + v3(cam.defocus_disk_u.x, cam.defocus_disk_u.y, cam.defocus_disk_u.z) * dx + v3(cam.defocus_disk_v.x, cam.defocus_disk_v.y, cam.defocus_disk_v.z) * dy;
                             }
                             o = ro;
@@ -1722,6 +1722,19 @@ __global__ void debug_eval_kernel(int32_t op, int64_t n, const double *__restric
                                   double *__restrict__ out) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
+    if (op >= RT_DEBUG_REJECT_SPHERE_VERDICTS && op <= RT_DEBUG_REJECT_DISK_COORDS) { // candidates of K raw draws each, a[K c + k]
+        const bool sphere = op <= RT_DEBUG_REJECT_SPHERE_COORDS;
+        const int64_t K = sphere ? 3 : 2, c = idx / K, k = idx - c * K;
+        if (K * c + K > n) { out[idx] = 0.0; return; } // (a ragged tail is no candidate)
+        const uint64_t wx = f2u(a[K * c]), wy = f2u(a[K * c + 1]), wz = sphere ? f2u(a[K * c + 2]) : 0ull;
+        double r;
+        if (op == RT_DEBUG_REJECT_SPHERE_COORDS || op == RT_DEBUG_REJECT_DISK_COORDS) r = rtm::reject_coord(k == 0 ? wx : (k == 1 ? wy : wz));
+        else if (k == 0) r = (double)(sphere ? rtm::reject_sphere_f32(wx, wy, wz) : rtm::reject_disk_f32(wx, wy));
+        else if (k == 1) r = (sphere ? rtm::reject_sphere_exact(wx, wy, wz) : rtm::reject_disk_exact(wx, wy)) ? 1.0 : 0.0;
+        else r = 0.0;
+        out[idx] = r;
+        return;
+    }
     const double x = a[idx], y = b ? b[idx] : 0.0;
     double r = 0.0;
     switch (op) {
