@@ -503,6 +503,84 @@ int rt_render_moments_device(const rt_scene *scene, const rt_camera *camera, con
 int rt_render_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
                       double *sum /* host */, double *sum_sq /* host */);
 
+/* ---- albedo scene and albedo-guided denoise (opt-in; nothing above changes) ------------------------------------------------------------
+ * The filter above stops at edges of the noisy luminance only, so it cannot tell a texture from noise.  A first-hit ALBEDO frame can:
+ * the frame is divided by it, the texture-free irradiance that is left is filtered (stopping at albedo edges as well), and the albedo
+ * is multiplied back in.
+ *
+ * Albedo scene.  The albedo frame needs no new render path: it is an ordinary render of the ALBEDO SCENE of a description, the same
+ * geometry with every material turned into a DIFFUSE_LIGHT that emits the original's albedo texture.  A light does not scatter, so
+ * ray_color returns the first hit's albedo and the path ends there; the RNG is keyed by (seed, pixel, sample) and the camera's and the
+ * media's draws come before a material's, so path (seed, p, s) of the albedo scene meets the first hit of path (seed, p, s) of the
+ * original — defocus, motion blur and the random hit inside a constant medium included.  Normative rule (rt_albedo_materials):
+ *   out_textures[0 .. n_textures) is a copy of desc->textures.  Then, for materials k = 0, 1, ... in order:
+ *     LAMBERTIAN or ISOTROPIC with texture t  ->  {DIFFUSE_LIGHT, texture t}
+ *     METAL                                   ->  {DIFFUSE_LIGHT, texture = a newly appended SOLID of colour `albedo`}
+ *     DIELECTRIC                              ->  {DIFFUSE_LIGHT, texture = a newly appended SOLID of colour (1, 1, 1)}
+ *     DIFFUSE_LIGHT                           ->  copied as it is
+ *   Appended textures come in material order, one per metal or dielectric, behind the copies: {kind SOLID, even = odd = image =
+ *   perlin = -1, _pad 0, color, inv_scale 0, scale 0}.  albedo, fuzz and ir of a rewritten material are zero.
+ *   *out_n_textures = n_textures + (metals + dielectrics).
+ * rt_albedo_materials touches no device.  RT_ERR_INVALID_ARGUMENT (the message names the field), as rt_scene_create gives it: a null
+ * desc, out_materials, out_textures or out_n_textures; abi_version other than RT_ABI_VERSION; a negative n_materials or n_textures,
+ * or a null materials / textures array with a non-zero count; a materials[k].kind that is none of the five; a materials[k].texture
+ * out of range for a kind that reads one.  Nothing is written then.
+ * rt_scene_create_albedo is rt_scene_create_ex on `desc` with those two arrays and n_textures swapped in: geometry, trees and options
+ * are the caller's.  The kernel a scene is rendered by depends on its geometry and on whether any texture is not a SOLID, not on
+ * material kinds, and the appended textures are SOLID: an albedo scene is rendered by the kernel of its original.
+ * The caller's CAMERA decides what a miss contributes: the albedo frame of a pixel whose paths leave the scene is the camera's
+ * background.  The layers above this ABI render the albedo scene with the beauty camera and background = (1, 1, 1), so that a
+ * background pixel's divisor is 1 and it demodulates to the background colour itself. */
+int rt_albedo_materials(const rt_scene_desc *desc, rt_material *out_materials /* desc->n_materials */,
+                        rt_texture *out_textures /* room for desc->n_textures + desc->n_materials */, int32_t *out_n_textures);
+int rt_scene_create_albedo(const rt_scene_desc *desc, int device, const rt_scene_options *options /* NULL: defaults */,
+                           rt_scene **out_scene);
+
+/* rt_denoise_albedo_device is rt_denoise_device with an albedo frame beside the moments: d_albedo_sum holds 3 * w * h doubles, the
+ * per-pixel sums of albedo_spp samples of the albedo scene (what rt_render_device writes for it).  The contract is rt_denoise_device's:
+ * enqueued on hip_stream, not synchronised, nothing allocated; d_workspace is rt_denoise_albedo_workspace_bytes(w, h) bytes of device
+ * memory, 16-byte aligned.  RT_ERR_INVALID_ARGUMENT (the field named) before any device work: everything rt_denoise_device refuses,
+ * and a null d_albedo_sum; albedo_spp < 1; a sigma_albedo or albedo_floor that is not a number > 0; d_mean_out overlapping
+ * d_albedo_sum.
+ *
+ * Normative definition.  All arithmetic is f64, every operation rounded on its own (no FMA, IEEE division and square root),
+ * max(a, b) = (b > a ? b : a).  p is a pixel, n its sample count (spp, or d_spp[p]) and n_a = albedo_spp, as doubles; S, Q, A are p's
+ * entries of d_sum, d_sum_sq, d_albedo_sum.
+ *   Prepare.   m_c = S_c / n;  a_c = A_c / n_a.  p is VALID iff n >= 2 and all nine of S_c, Q_c, A_c are finite.  For a valid pixel
+ *              d_c = max(a_c, albedo_floor)                   (the divisor)
+ *              I_c = m_c / d_c                                 (the irradiance)
+ *              v_c = (Q_c - S_c * m_c) / (n - 1);   u_c = v_c / (d_c * d_c)
+ *              V0 = max(max(max(u_r, u_g), u_b), 0) / n;   C0 = I.
+ *              A pixel that is not valid keeps C = m through every iteration, is written to the output unchanged and is never a tap.
+ *   Iteration k = 0 .. K - 1, stride s = 2^k: exactly the iteration of rt_denoise_device on (C_k, V_k) — G, sd, den, the 25 taps with dy
+ *              outer and dx inner, x, t and e as defined there — with one more factor per tap, from the UN-FLOORED albedo means:
+ *                   da = max(max(|a_r(p) - a_r(q)|, |a_g(p) - a_g(q)|), |a_b(p) - a_b(q)|)
+ *                   y = da / sigma_albedo;  ta = 1 - y * y;  ea = (ta > 0 ? ta * ta : 0)
+ *                   w = (h[dy] * h[dx]) * (e * ea)
+ *              sw, sc, sv, C_k+1 and V_k+1 as there                (sw >= 9/64 still: the centre tap has e = ea = 1)
+ *   Output.    d_mean_out_c = C_K,c * d_c for a valid pixel (m_c for any other); d_rgba8, if not NULL, the bytes rt_resolve_rgba8_device
+ *              gives for d_mean_out, written by the last iteration itself.
+ * With A_c = n_a everywhere (and albedo_floor <= 1), d = 1, I = m, u = v, ea = 1, e * 1 = e and C * 1 = C, each exactly: the result is
+ * rt_denoise_device's bit for bit. */
+typedef struct rt_denoise_albedo_params {
+    uint32_t struct_size;   /* sizeof(rt_denoise_albedo_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t iterations;     /* K, 1..6 (default 4): strides 1, 2, 4, ... 2^(K-1) */
+    double sigma;           /* as rt_denoise_params (default 4.0), > 0 */
+    double eps;             /* as rt_denoise_params (default 1e-6), > 0 */
+    double sigma_albedo;    /* width of the albedo stop: a tap whose albedo differs by this much or more in any channel has weight 0
+                               (default 0.5), > 0 */
+    double albedo_floor;    /* the smallest divisor (default 1e-3), > 0 */
+} rt_denoise_albedo_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_denoise_albedo_params_init_sized(rt_denoise_albedo_params *params, uint32_t struct_size);
+/* Bytes of device memory rt_denoise_albedo_device needs for a w x h frame (the two halves of rt_denoise_device and the guide: three
+ * regions of 4 doubles per pixel); -1 for a size it refuses. */
+int64_t rt_denoise_albedo_workspace_bytes(int32_t width, int32_t height);
+int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                             const int32_t *d_spp /* NULL: uniform spp */, const double *d_albedo_sum /* 3*w*h */,
+                             int32_t albedo_spp /* >= 1 */, const rt_denoise_albedo_params *params /* NULL: defaults */,
+                             double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -232,6 +232,23 @@ def denoise_params(**kw) -> "DenoiseParams":
     return d
 
 
+class DenoiseAlbedoParams(C.Structure):
+    """rt_denoise_albedo_params (rt_denoise_albedo_device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma", C.c_double), ("eps", C.c_double),
+                ("sigma_albedo", C.c_double), ("albedo_floor", C.c_double)]
+
+
+def denoise_albedo_params(**kw) -> "DenoiseAlbedoParams":
+    """rt_denoise_albedo_params_init_sized, then the given fields (iterations=, sigma=, eps=, sigma_albedo=, albedo_floor=)."""
+    d = DenoiseAlbedoParams()
+    _check(amd_lib().rt_denoise_albedo_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_albedo_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(DenoiseAlbedoParams._fields_):
+            raise TypeError(f"rt_denoise_albedo_params has no field {k}")
+        setattr(d, k, v)
+    return d
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -292,6 +309,12 @@ RT_AMD_SYMBOLS = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_moments_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_moments": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
+    "rt_albedo_materials": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rt_scene_create_albedo": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rt_denoise_albedo_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_denoise_albedo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_denoise_albedo_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -742,15 +765,22 @@ def out_size(width, height, out_layout=RT_OUT_FRAME, shard_index=0, shard_count=
 class DeviceScene:
     """rt_scene handle: the compiled scene resident in one GPU's HBM."""
 
-    def __init__(self, host_scene: HostScene, device: int = 0, options: "SceneCreateOptions | None" = None, **option_fields):
+    def __init__(self, host_scene: HostScene, device: int = 0, options: "SceneCreateOptions | None" = None, albedo: bool = False,
+                 **option_fields):
+        """albedo=True: rt_scene_create_albedo, the scene whose render is the first-hit albedo frame (render it with
+        albedo_camera(camera): a miss then contributes (1, 1, 1))."""
         lib = amd_lib()
         self.host_scene = host_scene  # keeps desc memory alive during create
         self.device = device
+        self.albedo = bool(albedo)
         handle = C.c_void_p()
         if option_fields:
             assert options is None
             options = scene_options(**option_fields)
-        if options is None:
+        if albedo:
+            _check(lib.rt_scene_create_albedo(C.byref(host_scene.desc), device, C.byref(options) if options is not None else None,
+                                              C.byref(handle)), "rt_scene_create_albedo")
+        elif options is None:
             _check(lib.rt_scene_create(C.byref(host_scene.desc), device, C.byref(handle)), "rt_scene_create")
         else:
             _check(lib.rt_scene_create_ex(C.byref(host_scene.desc), device, C.byref(options), C.byref(handle)), "rt_scene_create_ex")
@@ -975,6 +1005,73 @@ def denoise(sum, sum_sq, spp, *, spp_map=None, rgba8=False, device=0, **kw):
         denoise_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
                        d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0,
                        params=params, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def albedo_materials(host_scene):
+    """rt_albedo_materials (GPU-free): (materials, textures), ctypes arrays of Material (n_materials entries) and Texture (the
+    description's textures, then one SOLID per metal or dielectric) — the tables of the scene's albedo scene."""
+    desc = host_scene.desc
+    mats = (Material * max(1, desc.n_materials))()
+    texs = (Texture * max(1, desc.n_textures + desc.n_materials))()
+    n = C.c_int32(0)
+    _check(amd_lib().rt_albedo_materials(C.byref(desc), C.addressof(mats), C.addressof(texs), C.byref(n)), "rt_albedo_materials")
+    return (Material * desc.n_materials).from_buffer_copy(mats), (Texture * n.value).from_buffer_copy(texs)
+
+
+def albedo_camera(camera: Camera) -> Camera:
+    """The camera an albedo scene is rendered with: `camera` with background (1, 1, 1), so that a miss demodulates to the background."""
+    cam = Camera.from_buffer_copy(camera)
+    cam.background = Vec3(1.0, 1.0, 1.0)
+    return cam
+
+
+def denoise_albedo_workspace_bytes(width, height) -> int:
+    n = int(amd_lib().rt_denoise_albedo_workspace_bytes(width, height))
+    if n < 0:
+        raise RtError(f"rt_denoise_albedo_workspace_bytes: no workspace for a {width}x{height} frame")
+    return n
+
+
+def denoise_albedo_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int,
+                          d_mean_out_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0, d_rgba8_ptr: int = 0,
+                          params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
+    """rt_denoise_albedo_device: rt_denoise_device with a device frame of albedo sums (3 w h doubles, `albedo_spp` samples of the
+    albedo scene) beside the moments; `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_albedo_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
+                                              C.c_void_p(d_albedo_sum_ptr), albedo_spp, C.byref(params) if params is not None else None,
+                                              C.c_void_p(d_mean_out_ptr), C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr),
+                                              C.c_void_p(stream)), "rt_denoise_albedo_device")
+
+
+def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rgba8=False, device=0, **kw):
+    """Uploads (h, w, 3) frames of sums, sums of squares and albedo sums (and an (h, w) int32 spp map, if given), runs
+    rt_denoise_albedo_device with denoise_albedo_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or
+    (means, (h, w, 4) uint8) with rgba8."""
+    import numpy as np
+    sum = np.ascontiguousarray(sum, dtype=np.float64)
+    sum_sq = np.ascontiguousarray(sum_sq, dtype=np.float64)
+    albedo_sum = np.ascontiguousarray(albedo_sum, dtype=np.float64)
+    if sum.ndim != 3 or sum.shape[2] != 3 or sum_sq.shape != sum.shape or albedo_sum.shape != sum.shape:
+        raise RtError("denoise_albedo: `sum`, `sum_sq` and `albedo_sum` must be (h, w, 3) frames of one shape")
+    h, w = sum.shape[:2]
+    if spp_map is not None:
+        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if spp_map.shape != (h, w):
+            raise RtError(f"denoise_albedo: `spp_map` must have shape {(h, w)}")
+    params = denoise_albedo_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_sum, d_sq, d_alb = torch.from_numpy(sum).cuda(), torch.from_numpy(sum_sq).cuda(), torch.from_numpy(albedo_sum).cuda()
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_out = torch.empty_like(d_sum)
+        d_ws = torch.empty(denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        denoise_albedo_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_alb.data_ptr(), int(albedo_spp), d_out.data_ptr(),
+                              d_ws.data_ptr(), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0,
+                              d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
         return (out, d_rgba.cpu().numpy()) if rgba8 else out

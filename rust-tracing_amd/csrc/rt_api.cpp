@@ -1627,6 +1627,153 @@ int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const 
     return RT_OK;
 }
 
+// ---- albedo scene and the albedo-guided filter (rt_denoise_albedo.hip) ----
+namespace {
+void denoise_albedo_defaults(rt_denoise_albedo_params &d) {
+    memset(&d, 0, sizeof d);
+    d.struct_size = (uint32_t)sizeof d;
+    d.iterations = 4;
+    d.sigma = 4.0;
+    d.eps = 1e-6;
+    d.sigma_albedo = 0.5; // (DESIGN.md section 5 "Albedo-guided denoise": the CPU sweep)
+    d.albedo_floor = 1e-3;
+}
+bool denoise_albedo_size_known(uint32_t size) { return size >= 8 && size <= sizeof(rt_denoise_albedo_params) && size % 8 == 0; }
+} // namespace
+
+int rt_albedo_materials(const rt_scene_desc *desc, rt_material *out_materials, rt_texture *out_textures, int32_t *out_n_textures) {
+    const std::string w("rt_albedo_materials");
+    if (!desc) return fail(RT_ERR_INVALID_ARGUMENT, w + ": desc is null");
+    if (!out_materials) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_materials is null");
+    if (!out_textures) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_textures is null");
+    if (!out_n_textures) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_n_textures is null");
+    if (desc->abi_version != RT_ABI_VERSION) return fail(RT_ERR_INVALID_ARGUMENT, w + ": abi_version mismatch");
+    if (desc->n_materials < 0 || (desc->n_materials > 0 && !desc->materials))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": materials is a null array with a non-zero count, or n_materials is negative");
+    if (desc->n_textures < 0 || (desc->n_textures > 0 && !desc->textures))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": textures is a null array with a non-zero count, or n_textures is negative");
+    // every check before the first write
+    for (int32_t k = 0; k < desc->n_materials; ++k) {
+        const rt_material &m = desc->materials[k];
+        const std::string at = w + ": materials[" + std::to_string(k) + "]";
+        switch (m.kind) {
+        case RT_MATERIAL_LAMBERTIAN:
+        case RT_MATERIAL_DIFFUSE_LIGHT:
+        case RT_MATERIAL_ISOTROPIC:
+            if (m.texture < 0 || m.texture >= desc->n_textures) return fail(RT_ERR_INVALID_ARGUMENT, at + ".texture: texture index out of range");
+            break;
+        case RT_MATERIAL_METAL:
+        case RT_MATERIAL_DIELECTRIC: break;
+        default: return fail(RT_ERR_INVALID_ARGUMENT, at + ".kind: unknown material kind");
+        }
+    }
+    for (int32_t t = 0; t < desc->n_textures; ++t) out_textures[t] = desc->textures[t];
+    int32_t n_tex = desc->n_textures;
+    auto solid = [&](const rt_vec3 &colour) {
+        rt_texture t;
+        memset(&t, 0, sizeof t);
+        t.kind = RT_TEXTURE_SOLID;
+        t.even = t.odd = t.image = t.perlin = -1;
+        t.color = colour;
+        out_textures[n_tex] = t;
+        return n_tex++;
+    };
+    for (int32_t k = 0; k < desc->n_materials; ++k) {
+        const rt_material &m = desc->materials[k];
+        if (m.kind == RT_MATERIAL_DIFFUSE_LIGHT) {
+            out_materials[k] = m;
+            continue;
+        }
+        rt_material o;
+        memset(&o, 0, sizeof o);
+        o.kind = RT_MATERIAL_DIFFUSE_LIGHT;
+        if (m.kind == RT_MATERIAL_METAL) o.texture = solid(m.albedo);
+        else if (m.kind == RT_MATERIAL_DIELECTRIC) o.texture = solid(rt_vec3{1.0, 1.0, 1.0});
+        else o.texture = m.texture;
+        out_materials[k] = o;
+    }
+    *out_n_textures = n_tex;
+    return RT_OK;
+}
+
+int rt_scene_create_albedo(const rt_scene_desc *desc, int device, const rt_scene_options *options, rt_scene **out_scene) {
+    if (!desc || !out_scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_create_albedo: null argument");
+    *out_scene = nullptr;
+    if (desc->n_materials < 0 || desc->n_textures < 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_create_albedo: n_materials or n_textures is negative");
+    std::vector<rt_material> materials((size_t)desc->n_materials + 1u);
+    std::vector<rt_texture> textures((size_t)desc->n_textures + (size_t)desc->n_materials + 1u);
+    int32_t n_textures = 0;
+    if (int rc = rt_albedo_materials(desc, materials.data(), textures.data(), &n_textures)) return rc;
+    rt_scene_desc albedo = *desc;
+    albedo.materials = materials.data();
+    albedo.textures = textures.data();
+    albedo.n_textures = n_textures;
+    return rt_scene_create_ex(&albedo, device, options, out_scene);
+}
+
+int rt_denoise_albedo_params_init_sized(rt_denoise_albedo_params *params, uint32_t struct_size) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_albedo_params_init_sized: null argument");
+    if (!denoise_albedo_size_known(struct_size))
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_albedo_params_init_sized: struct_size is not one this library knows");
+    rt_denoise_albedo_params full;
+    denoise_albedo_defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+
+int64_t rt_denoise_albedo_workspace_bytes(int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
+    return (int64_t)width * height * 3 * 4 * (int64_t)sizeof(double);
+}
+
+int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                             const double *d_albedo_sum, int32_t albedo_spp, const rt_denoise_albedo_params *params, double *d_mean_out,
+                             uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    const std::string w("rt_denoise_albedo_device");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
+    if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
+    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
+    if (!d_albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_albedo_sum is null");
+    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
+    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
+    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
+    if (albedo_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    rt_denoise_albedo_params d;
+    denoise_albedo_defaults(d);
+    if (params) {
+        if (!denoise_albedo_size_known(params->struct_size))
+            return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_albedo_params.struct_size is not one this library knows");
+        memcpy(&d, params, params->struct_size); // (an older, shorter struct: the fields it lacks keep their defaults)
+    }
+    if (d.iterations < 1 || d.iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
+    if (!(d.sigma > 0.0) || !std::isfinite(d.sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
+    if (!(d.eps > 0.0) || !std::isfinite(d.eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
+    if (!(d.sigma_albedo > 0.0) || !std::isfinite(d.sigma_albedo)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
+    if (!(d.albedo_floor > 0.0) || !std::isfinite(d.albedo_floor)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
+    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
+    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes) ||
+        overlaps(d_mean_out, frame_bytes, d_albedo_sum, frame_bytes))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_sum, d_sum_sq or d_albedo_sum");
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (int rc = select_device_of(d_mean_out, "rt_denoise_albedo_device")) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t region = n_pix * 4u * sizeof(double);
+    char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
+    char *guide = (char *)d_workspace + 2u * region;
+    launch_denoise_albedo_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, d.albedo_floor, half[0], guide, stream);
+    HIP_TRY(hipGetLastError());
+    for (int32_t k = 0; k < d.iterations; ++k) {
+        const bool last = k == d.iterations - 1;
+        launch_denoise_albedo_atrous(width, height, (int32_t)1 << k, d.sigma, d.eps, d.sigma_albedo, d.albedo_floor, half[k & 1], guide,
+                                     last ? nullptr : half[(k + 1) & 1], last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return RT_OK;
+}
+
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {
     if (!d_sum || !d_spp || !d_rgb8 || width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_resolve_rgb8_spp_device: bad argument");
     if (int rc = select_device_of(d_rgb8, "rt_resolve_rgb8_spp_device")) return rc;

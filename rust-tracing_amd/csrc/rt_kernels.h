@@ -212,6 +212,13 @@ void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *s
                             hipStream_t stream);
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const void *half_in, void *half_out,
                            double *mean_out, uint8_t *rgba8, hipStream_t stream);
+// the albedo-guided denoiser (rt_denoise_albedo.hip; rt_denoise_albedo_device): the halves as above, and `guide`, a third region of one
+// double4 (a_r, a_g, a_b, 0) per pixel that prepare writes once.  An iteration with half_out null is the last: it multiplies the floored
+// albedo back in and writes mean_out and, if not null, rgba8
+void launch_denoise_albedo_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map,
+                                   const double *albedo_sum, int32_t albedo_spp, double albedo_floor, void *half, void *guide, hipStream_t stream);
+void launch_denoise_albedo_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, double sigma_albedo, double albedo_floor,
+                                  const void *half_in, const void *guide, void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

@@ -8,6 +8,8 @@
 //   [--adaptive-abs A] [--min-spp N] [--batch-spp N] (per-pixel sample counts from a variance bound; --spp is the maximum),
 //   --denoise [--denoise-iters K] [--denoise-sigma X] (the variance-guided à-trous filter of include/rt_amd.h over the frame before
 //   it is written; with --adaptive it takes the adaptive sums and the spp map),
+//   --denoise-albedo [--denoise-albedo-sigma X] (implies --denoise: the albedo-guided filter, with a first-hit albedo frame rendered
+//   from the scene's albedo scene over the same seed and samples),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 #include "image_io.hpp"
 #include "renderer.hpp"
@@ -27,6 +29,8 @@ static void usage(const char *argv0) {
             "          [--adaptive REL [--adaptive-abs A] [--min-spp N] [--batch-spp N]]   (one GPU; --spp is the maximum)\n"
             "          [--denoise [--denoise-iters K] [--denoise-sigma X]]   (one GPU, one pass: the PNG is written from the denoised mean; K from 1 to 6,\n"
             "                         default 4; X > 0, default 4; also with --adaptive)\n"
+            "          [--denoise-albedo [--denoise-albedo-sigma X]]   (implies --denoise: the filter is guided by a first-hit albedo frame as well and works on\n"
+            "                         the frame divided by it; X > 0, default 0.5: the albedo difference at which a tap's weight is 0)\n"
             "          [-l|--live [--live-spp K] -o OUTPUT]   (one GPU: the reference's live mode without the window — a running mean refined K samples\n"
             "                         per pixel at a time, default 1, over spp - 1 samples; the last frame goes to OUTPUT.png)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
@@ -38,7 +42,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -79,6 +83,11 @@ int main(int argc, char **argv) {
             ro.denoise_sigma = atof(need("--denoise-sigma")); denoise_knob_given = true;
             if (!(ro.denoise_sigma > 0.0)) { fprintf(stderr, "--denoise-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--denoise-albedo") ro.denoise = ro.denoise_albedo = true;
+        else if (a == "--denoise-albedo-sigma") {
+            ro.denoise_albedo_sigma = atof(need("--denoise-albedo-sigma")); albedo_knob_given = true;
+            if (!(ro.denoise_albedo_sigma > 0.0)) { fprintf(stderr, "--denoise-albedo-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--orbit") {
             ro.orbit = atoi(need("--orbit"));
             if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
@@ -105,6 +114,10 @@ int main(int argc, char **argv) {
     if (ro.denoise && (live || ro.gpus > 1 || ro.progressive_spp > 0 || ro.orbit > 0)) {
         fprintf(stderr, "--denoise filters one frame's sums and sums of squares on one GPU: it cannot be combined with --live (a running mean keeps no "
                         "second moment), --gpus > 1 (the gather moves sums only), --progressive or --orbit\n");
+        return 2;
+    }
+    if (albedo_knob_given && !ro.denoise_albedo) {
+        fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo\n");
         return 2;
     }
     if (denoise_knob_given && !ro.denoise) {

@@ -128,27 +128,65 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
     return px;
 }
 
-std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
-                             const RenderOptions &opt) {
+// what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
+static std::vector<uint8_t> run_denoise(const char *who, int32_t width, int32_t height, int64_t work,
+                                        const std::function<int(double *, uint8_t *, void *)> &call) {
     const int64_t n_pix = (int64_t)width * height;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_work = nullptr;
     auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_work); };
-    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("denoise: " + msg); } };
-    rt_denoise_params dp;
-    check(rt_denoise_params_init_sized(&dp, sizeof dp));
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
-    const int64_t work = rt_denoise_workspace_bytes(width, height);
-    if (work < 0) throw std::runtime_error("denoise: no workspace for a frame of this size");
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error(std::string(who) + ": " + msg); } };
+    if (work < 0) throw std::runtime_error(std::string(who) + ": no workspace for a frame of this size");
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
     check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
     check(rt_device_malloc(0, work, &d_work));
-    check(rt_denoise_device(width, height, d_sum, d_sum_sq, spp, d_spp, &dp, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+    check(call(static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work));
     std::vector<uint8_t> rgba((size_t)n_pix * 4u);
     check(rt_device_download(0, rgba.data(), d_rgba8, n_pix * 4, nullptr));
     cleanup();
     std::vector<uint8_t> rgb((size_t)n_pix * 3u);
     for (size_t p = 0; p < (size_t)n_pix; ++p) { rgb[3 * p] = rgba[4 * p]; rgb[3 * p + 1] = rgba[4 * p + 1]; rgb[3 * p + 2] = rgba[4 * p + 2]; }
     return rgb;
+}
+
+std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                             const RenderOptions &opt) {
+    rt_denoise_params dp;
+    if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise: ") + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
+    return run_denoise("denoise", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_device(width, height, d_sum, d_sum_sq, spp, d_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
+    });
+}
+
+std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                                    const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt) {
+    rt_denoise_albedo_params dp;
+    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo: ") + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
+    return run_denoise("denoise_albedo", width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_albedo_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
+    });
+}
+
+// The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
+// every pixel with the render's seed under `cam` with a white background, into a new device frame of sums (the caller frees it).
+static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo) {
+    rt_scene *scene = nullptr;
+    int rc = rt_scene_create_albedo(&desc, 0, nullptr, &scene);
+    if (rc == RT_OK) rc = rt_device_malloc(0, (int64_t)cam.image_width * cam.image_height * 3 * (int64_t)sizeof(double), d_albedo);
+    if (rc == RT_OK) {
+        rt_camera white = cam;
+        white.background = rt_vec3{1.0, 1.0, 1.0};
+        rt_render_params p{};
+        p.seed = seed; p.sample_begin = 0; p.sample_end = spp; p.max_depth = cam.max_depth;
+        p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+        rc = rt_render_device(scene, &white, &p, static_cast<double *>(*d_albedo), nullptr);
+        // (the scene is destroyed below while the render may still run: wait for the frame first)
+        double probe = 0.0;
+        if (rc == RT_OK) rc = rt_device_download(0, &probe, *d_albedo, (int64_t)sizeof probe, nullptr);
+    }
+    rt_scene_destroy(scene);
+    return rc;
 }
 
 // A plain render on device 0 that ends in the denoiser: the frame's sums and sums of squares (rt_render_moments_device) stay on the
@@ -160,8 +198,8 @@ static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hit
     const rt_camera cam = camera.pod();
     const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
     rt_scene *scene = nullptr;
-    void *d_sum = nullptr, *d_sq = nullptr;
-    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_scene_destroy(scene); };
+    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_alb: only with opt.denoise_albedo)
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_scene_destroy(scene); };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
@@ -170,10 +208,14 @@ static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hit
     p.seed = opt.seed; p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
     p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
     check(rt_render_moments_device(scene, &cam, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
+    if (opt.denoise_albedo) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_alb));
     std::vector<uint8_t> px;
     try {
-        px = denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), cam.samples_per_pixel,
-                     nullptr, opt);
+        px = opt.denoise_albedo
+                 ? denoise_albedo(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                                  cam.samples_per_pixel, nullptr, static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
+                 : denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                           cam.samples_per_pixel, nullptr, opt);
     } catch (...) { cleanup(); throw; }
     cleanup();
     return px;
@@ -188,8 +230,11 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     const rt_camera cam = camera.pod();
     const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
     rt_scene *scene = nullptr;
-    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr, *d_sq = nullptr; // (d_sq: only with opt.denoise)
-    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_device_free(0, d_sq); rt_scene_destroy(scene); };
+    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_sq: only with opt.denoise; d_alb: with opt.denoise_albedo)
+    auto cleanup = [&]() {
+        rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_device_free(0, d_sq); rt_device_free(0, d_alb);
+        rt_scene_destroy(scene);
+    };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
@@ -206,10 +251,14 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     check(rt_render_adaptive_device(scene, &cam, &p, &a, static_cast<double *>(d_sum), static_cast<int32_t *>(d_spp), static_cast<double *>(d_sq), nullptr, &res));
     std::vector<uint8_t> px((size_t)n_pix * 3u);
     std::vector<int32_t> spp((size_t)n_pix);
-    if (opt.denoise) { // the frame is written from the denoised mean: every pixel's own spp is its n
+    if (opt.denoise) { // the frame is written from the denoised mean: every pixel's own spp is its n (the albedo frame: the maximum's)
+        if (opt.denoise_albedo) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_alb));
         try {
-            px = denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
-                         static_cast<const int32_t *>(d_spp), opt);
+            px = opt.denoise_albedo
+                     ? denoise_albedo(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
+                                      static_cast<const int32_t *>(d_spp), static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
+                     : denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
+                               static_cast<const int32_t *>(d_spp), opt);
         } catch (...) { cleanup(); throw; }
     } else {
         check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),

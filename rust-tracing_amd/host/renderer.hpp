@@ -37,6 +37,11 @@ struct RenderOptions {
     bool denoise = false;
     int denoise_iters = 4;
     double denoise_sigma = 4.0;
+    // with `denoise`: the albedo-guided filter instead (include/rt_amd.h "albedo-guided denoise").  The route creates the albedo scene
+    // from the same description, renders it with rt_render_device over the same seed and sample range (an adaptive render: up to the
+    // camera's spp) under the camera with background (1, 1, 1), and hands that frame to rt_denoise_albedo_device.
+    bool denoise_albedo = false;
+    double denoise_albedo_sigma = 0.5;
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -45,6 +50,11 @@ struct RenderOptions {
 // library error.
 std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                              const RenderOptions &opt = {});
+
+// rt_denoise_albedo_device likewise: d_albedo_sum is a DEVICE frame of 3 * w * h doubles, the sums of albedo_spp samples of the albedo
+// scene; opt.denoise_albedo_sigma is the filter's sigma_albedo.
+std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                                    const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt = {});
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.

@@ -3,9 +3,12 @@
 warm-up, the median of --repeats calls) at K = 4 with the display bytes, for the bench scene at 1200 x 800 and at 256 x 256, and
 beside each the milliseconds of the 16-spp rt_render_moments_device of the same frame, measured the same way.
 
-    python tools/denoise_speed.py [--repeats 20] [--iterations 4]
+    python tools/denoise_speed.py [--repeats 20] [--iterations 4] [--albedo]
 
-Prints one table row per frame (markdown, for DESIGN.md section 5 "Denoise") and one JSON line."""
+Prints one table row per frame (markdown, for DESIGN.md section 5 "Denoise") and one JSON line.  --albedo: the albedo-guided filter's
+table instead (DESIGN.md section 5 "Albedo-guided denoise") — beside the moments render the milliseconds of the albedo pass (the
+albedo scene's rt_render_device over the same samples under the white-background camera), of rt_denoise_albedo_device and of the
+plain rt_denoise_device, all measured the same way in the same run."""
 import argparse
 import importlib
 import json
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--iterations", type=int, default=4)
     ap.add_argument("--spp", type=int, default=16)
+    ap.add_argument("--albedo", action="store_true")
     args = ap.parse_args()
     import torch
     rt = importlib.import_module("rust-tracing_amd")
@@ -64,6 +68,31 @@ def main():
         denoise_ms, denoise_min = timed(denoise, args.repeats, torch)
         rows.append(dict(width=w, height=h, spp=args.spp, iterations=args.iterations, render_ms=round(render_ms, 4), render_min_ms=round(render_min, 4),
                          denoise_ms=round(denoise_ms, 4), denoise_min_ms=round(denoise_min, 4), share=round(denoise_ms / (render_ms + denoise_ms), 4)))
+        if args.albedo:
+            da = rt.DeviceScene(hs, albedo=True)
+            white = rt.albedo_camera(hs.camera)
+            d_a = torch.zeros_like(d_s)
+            d_ws2 = torch.empty(rt.denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+            dap = rt.denoise_albedo_params(iterations=args.iterations)
+
+            def albedo_pass():
+                da.render_device(p, d_a.data_ptr(), stream, camera=white)
+
+            def guided():
+                rt.denoise_albedo_device(w, h, d_s.data_ptr(), d_q.data_ptr(), args.spp, d_a.data_ptr(), args.spp, d_out.data_ptr(), d_ws2.data_ptr(),
+                                         d_rgba8_ptr=d_b.data_ptr(), params=dap, stream=stream)
+
+            albedo_ms, albedo_min = timed(albedo_pass, args.repeats, torch)
+            guided_ms, guided_min = timed(guided, args.repeats, torch)
+            rows[-1].update(albedo_ms=round(albedo_ms, 4), albedo_min_ms=round(albedo_min, 4), guided_ms=round(guided_ms, 4),
+                            guided_min_ms=round(guided_min, 4), albedo_over_render=round(albedo_ms / render_ms, 4))
+    if args.albedo:
+        print(f"| frame | {args.spp}-spp moments render, ms | albedo pass, ms | albedo pass / moments render | guided filter K = {args.iterations}, ms | plain filter, ms |")
+        print("|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['width']} x {r['height']} | {r['render_ms']:.3f} | {r['albedo_ms']:.3f} | {100 * r['albedo_over_render']:.1f} % | {r['guided_ms']:.3f} | {r['denoise_ms']:.3f} |")
+        print(json.dumps(dict(tool="denoise_speed --albedo", device=torch.cuda.get_device_name(0), repeats=args.repeats, rows=rows)))
+        return
     print(f"| frame | {args.spp}-spp moments render, ms | denoise K = {args.iterations}, ms | denoise share of the preview |")
     print("|---|---|---|---|")
     for r in rows:
