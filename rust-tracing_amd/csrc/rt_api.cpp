@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 using namespace rtapi;
 
@@ -1523,17 +1524,91 @@ int render_moments(rt_scene *s, const rt_camera *camera, const rt_render_params 
     return launch_render(s, camera, p, d_sum, stream, nullptr, &pl);
 }
 
-void denoise_defaults(rt_denoise_params &d) {
+// the two params structs of the denoisers (rt_denoise_params, and rt_denoise_albedo_params = its fields and two more): defaults, the
+// struct sizes this library knows, the body of *_params_init_sized.  (Templates: C++ linkage inside this file's extern "C".)
+extern "C++" {
+template <class P> void denoise_defaults(P &d) {
     memset(&d, 0, sizeof d);
     d.struct_size = (uint32_t)sizeof d;
     d.iterations = 4;
     d.sigma = 4.0;
     d.eps = 1e-6;
+    if constexpr (std::is_same_v<P, rt_denoise_albedo_params>) {
+        d.sigma_albedo = 0.5; // (DESIGN.md section 5 "Albedo-guided denoise": the CPU sweep)
+        d.albedo_floor = 1e-3;
+    }
 }
-bool denoise_size_known(uint32_t size) { return size >= 8 && size <= sizeof(rt_denoise_params) && size % 8 == 0; }
+template <class P> bool denoise_size_known(uint32_t size) { return size >= 8 && size <= sizeof(P) && size % 8 == 0; }
+template <class P> int denoise_params_init_sized(P *params, uint32_t struct_size, const char *who) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (!denoise_size_known<P>(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_size is not one this library knows");
+    P full;
+    denoise_defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+// an entry point's params resolved into d: the defaults, and over them the caller's struct as far as it goes (an older, shorter struct:
+// the fields it lacks keep their defaults).  False: its struct_size is not one this library knows
+template <class P> bool denoise_params_resolve(const P *params, P &d) {
+    denoise_defaults(d);
+    if (!params) return true;
+    if (!denoise_size_known<P>(params->struct_size)) return false;
+    memcpy(&d, params, params->struct_size);
+    return true;
+}
+} // extern "C++"
+int64_t denoise_workspace_bytes(int32_t width, int32_t height, int regions) { // regions of 4 doubles per pixel
+    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
+    return (int64_t)width * height * regions * 4 * (int64_t)sizeof(double);
+}
 bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// rt_denoise_device and, with `guide` (what only the guided filter takes; its region is set here), rt_denoise_albedo_device: every check
+// in the header's order, each message under the caller's name `who`, then prepare and the K iterations.  `d` is the caller's resolved
+// params (the fields both structs have), or null where their struct_size was not known: that is refused here, in its place among the checks.
+int run_denoise(const char *who, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    const std::string w(who);
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
+    if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
+    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
+    if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_albedo_sum is null");
+    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
+    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
+    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
+    if (guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    if (!d)
+        return fail(RT_ERR_INVALID_ARGUMENT, w + (guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
+    if (d->iterations < 1 || d->iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
+    if (!(d->sigma > 0.0) || !std::isfinite(d->sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
+    if (!(d->eps > 0.0) || !std::isfinite(d->eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
+    if (guide && (!(guide->sigma_albedo > 0.0) || !std::isfinite(guide->sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
+    if (guide && (!(guide->albedo_floor > 0.0) || !std::isfinite(guide->albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
+    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
+    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes) ||
+        (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + (guide ? "d_sum, d_sum_sq or d_albedo_sum" : "d_sum or d_sum_sq"));
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (int rc = select_device_of(d_mean_out, who)) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t region = n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
+    char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
+    if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
+    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, half[0], stream);
+    HIP_TRY(hipGetLastError());
+    for (int32_t k = 0; k < d->iterations; ++k) {
+        const bool last = k == d->iterations - 1;
+        launch_denoise_atrous(width, height, (int32_t)1 << k, d->sigma, d->eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
+                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return RT_OK;
 }
 } // namespace
 
@@ -1575,72 +1650,20 @@ int rt_render_moments(const rt_scene *scene, const rt_camera *camera, const rt_r
 }
 
 int rt_denoise_params_init_sized(rt_denoise_params *params, uint32_t struct_size) {
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_params_init_sized: null argument");
-    if (!denoise_size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_params_init_sized: struct_size is not one this library knows");
-    rt_denoise_params full;
-    denoise_defaults(full);
-    full.struct_size = struct_size;
-    memcpy(params, &full, struct_size);
-    return RT_OK;
+    return denoise_params_init_sized(params, struct_size, "rt_denoise_params_init_sized");
 }
 
-int64_t rt_denoise_workspace_bytes(int32_t width, int32_t height) {
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
-    return (int64_t)width * height * 2 * 4 * (int64_t)sizeof(double);
-}
+int64_t rt_denoise_workspace_bytes(int32_t width, int32_t height) { return denoise_workspace_bytes(width, height, 2); }
 
 int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                       const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    const std::string w("rt_denoise_device");
-    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
-    if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
-    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
-    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
-    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
-    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
-    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
     rt_denoise_params d;
-    denoise_defaults(d);
-    if (params) {
-        if (!denoise_size_known(params->struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_params.struct_size is not one this library knows");
-        memcpy(&d, params, params->struct_size); // (an older, shorter struct: the fields it lacks keep their defaults)
-    }
-    if (d.iterations < 1 || d.iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
-    if (!(d.sigma > 0.0) || !std::isfinite(d.sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
-    if (!(d.eps > 0.0) || !std::isfinite(d.eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
-    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
-    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes))
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_sum or d_sum_sq");
-    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
-    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
-    if (int rc = select_device_of(d_mean_out, "rt_denoise_device")) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    char *half[2] = {(char *)d_workspace, (char *)d_workspace + n_pix * 4u * sizeof(double)};
-    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, half[0], stream);
-    HIP_TRY(hipGetLastError());
-    for (int32_t k = 0; k < d.iterations; ++k) {
-        const bool last = k == d.iterations - 1;
-        launch_denoise_atrous(width, height, (int32_t)1 << k, d.sigma, d.eps, half[k & 1], last ? nullptr : half[(k + 1) & 1],
-                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return RT_OK;
+    const bool known = denoise_params_resolve(params, d);
+    return run_denoise("rt_denoise_device", width, height, d_sum, d_sum_sq, spp, d_spp, nullptr, known ? &d : nullptr, d_mean_out, d_rgba8,
+                       d_workspace, hip_stream);
 }
 
-// ---- albedo scene and the albedo-guided filter (rt_denoise_albedo.hip) ----
-namespace {
-void denoise_albedo_defaults(rt_denoise_albedo_params &d) {
-    memset(&d, 0, sizeof d);
-    d.struct_size = (uint32_t)sizeof d;
-    d.iterations = 4;
-    d.sigma = 4.0;
-    d.eps = 1e-6;
-    d.sigma_albedo = 0.5; // (DESIGN.md section 5 "Albedo-guided denoise": the CPU sweep)
-    d.albedo_floor = 1e-3;
-}
-bool denoise_albedo_size_known(uint32_t size) { return size >= 8 && size <= sizeof(rt_denoise_albedo_params) && size % 8 == 0; }
-} // namespace
-
+// ---- albedo scene and the albedo-guided filter (rt_denoise.hip, with a guide) ----
 int rt_albedo_materials(const rt_scene_desc *desc, rt_material *out_materials, rt_texture *out_textures, int32_t *out_n_textures) {
     const std::string w("rt_albedo_materials");
     if (!desc) return fail(RT_ERR_INVALID_ARGUMENT, w + ": desc is null");
@@ -1712,66 +1735,20 @@ int rt_scene_create_albedo(const rt_scene_desc *desc, int device, const rt_scene
 }
 
 int rt_denoise_albedo_params_init_sized(rt_denoise_albedo_params *params, uint32_t struct_size) {
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_albedo_params_init_sized: null argument");
-    if (!denoise_albedo_size_known(struct_size))
-        return fail(RT_ERR_INVALID_ARGUMENT, "rt_denoise_albedo_params_init_sized: struct_size is not one this library knows");
-    rt_denoise_albedo_params full;
-    denoise_albedo_defaults(full);
-    full.struct_size = struct_size;
-    memcpy(params, &full, struct_size);
-    return RT_OK;
+    return denoise_params_init_sized(params, struct_size, "rt_denoise_albedo_params_init_sized");
 }
 
-int64_t rt_denoise_albedo_workspace_bytes(int32_t width, int32_t height) {
-    if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
-    return (int64_t)width * height * 3 * 4 * (int64_t)sizeof(double);
-}
+int64_t rt_denoise_albedo_workspace_bytes(int32_t width, int32_t height) { return denoise_workspace_bytes(width, height, 3); }
 
 int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                              const double *d_albedo_sum, int32_t albedo_spp, const rt_denoise_albedo_params *params, double *d_mean_out,
                              uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    const std::string w("rt_denoise_albedo_device");
-    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
-    if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
-    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
-    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
-    if (!d_albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_albedo_sum is null");
-    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
-    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
-    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
-    if (albedo_spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
     rt_denoise_albedo_params d;
-    denoise_albedo_defaults(d);
-    if (params) {
-        if (!denoise_albedo_size_known(params->struct_size))
-            return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_albedo_params.struct_size is not one this library knows");
-        memcpy(&d, params, params->struct_size); // (an older, shorter struct: the fields it lacks keep their defaults)
-    }
-    if (d.iterations < 1 || d.iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
-    if (!(d.sigma > 0.0) || !std::isfinite(d.sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
-    if (!(d.eps > 0.0) || !std::isfinite(d.eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
-    if (!(d.sigma_albedo > 0.0) || !std::isfinite(d.sigma_albedo)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
-    if (!(d.albedo_floor > 0.0) || !std::isfinite(d.albedo_floor)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
-    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
-    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes) ||
-        overlaps(d_mean_out, frame_bytes, d_albedo_sum, frame_bytes))
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_sum, d_sum_sq or d_albedo_sum");
-    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
-    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
-    if (int rc = select_device_of(d_mean_out, "rt_denoise_albedo_device")) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const size_t region = n_pix * 4u * sizeof(double);
-    char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
-    char *guide = (char *)d_workspace + 2u * region;
-    launch_denoise_albedo_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, d.albedo_floor, half[0], guide, stream);
-    HIP_TRY(hipGetLastError());
-    for (int32_t k = 0; k < d.iterations; ++k) {
-        const bool last = k == d.iterations - 1;
-        launch_denoise_albedo_atrous(width, height, (int32_t)1 << k, d.sigma, d.eps, d.sigma_albedo, d.albedo_floor, half[k & 1], guide,
-                                     last ? nullptr : half[(k + 1) & 1], last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return RT_OK;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
+    return run_denoise("rt_denoise_albedo_device", width, height, d_sum, d_sum_sq, spp, d_spp, &guide, known ? &shared : nullptr, d_mean_out,
+                       d_rgba8, d_workspace, hip_stream);
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

@@ -1,26 +1,39 @@
-// rt_denoise.hip — the variance-guided à-trous denoiser of librt_amd (rt_denoise_device, include/rt_amd.h "denoise"): a prepare
-// kernel that turns per-pixel sums and sums of squares into (mean, variance of the mean), and K edge-stopping wavelet iterations
-// at strides 1, 2, 4, ... that ping-pong between the two halves of the caller's workspace.
+// rt_denoise.hip — the à-trous denoisers of librt_amd, one template in two instantiations: the variance-guided filter
+// (rt_denoise_device, include/rt_amd.h "denoise") and, with Guided, the albedo-guided one (rt_denoise_albedo_device, "albedo-guided
+// denoise").  A prepare kernel turns per-pixel sums and sums of squares into (mean, variance of the mean) — Guided: divides the mean
+// by the first-hit albedo (floored) first, which leaves the irradiance — and K edge-stopping wavelet iterations at strides 1, 2, 4, ...
+// ping-pong between the two halves of the caller's workspace.  They stop at luminance edges and, Guided, at edges of the albedo as
+// well: one more factor per tap; the last Guided iteration multiplies the albedo back in.  What only the guided filter does sits
+// behind `if constexpr (Guided)`, so the plain instantiations hold none of it and the two cannot drift apart.
 //
 // Everything is f64 in the header's operation order, each operation rounded on its own (the file is compiled with
 // -ffp-contract=off and without fast-math: no FMA, IEEE division and square root), so a frame equals the numpy restatement in
-// tests/denoise_helpers.py bit for bit.  Nothing here reads a scene; the render kernels (rt_kernel.hip) are not involved.
+// tests/denoise_helpers.py (Guided: tests/albedo_helpers.py) bit for bit, and the guided filter is the plain one where the albedo is 1
+// everywhere.  Nothing here reads a scene; the render kernels (rt_kernel.hip) are not involved.
 //
 // Working set: one double4 (C_r, C_g, C_b, V) per pixel and half.  V = -1 marks a pixel that is not valid (fewer than two samples or
-// a non-finite moment): it keeps its mean through every iteration and is never a tap.
+// a non-finite moment): it keeps its mean through every iteration and is never a tap.  Guided: a third region that prepare writes
+// once, the guide, one double4 (a_r, a_g, a_b, 0) per pixel, the un-floored albedo means.  The divisor max(a, floor) is three
+// compares: the last iteration makes it again from the guide instead of keeping it.
 // Shapes: a workgroup is 256 lanes = a 32 x 8 pixel tile, one pixel per lane, a row of the tile on 32 consecutive lanes (a wave covers
 // two rows: its tap loads are two runs of 32 consecutive pixels, and its ds_read_b64 of 32 consecutive doubles per half-wave are
-// conflict-free).  Strides 1 and 2 stage the tile plus a halo of 2 x stride pixels of (L, C, V) in the LDS, planes apart; out-of-frame
-// halo pixels are staged as not valid, so the tap loop has no bounds test.  Strides >= 4 gather the taps from global memory (the
-// working set stays in L2 / Infinity Cache at the project's frame sizes) and compute a tap's L from its C.
+// conflict-free); the grid is 1-D, tiles row-major.  Strides 1 and 2 stage the tile plus a halo of 2 x stride pixels in the LDS, planes
+// apart: (L, C x 3, V), five planes, and Guided (a x 3) as well, eight (40 x 16 x 8 x 8 B = 40 960 B at stride 2); out-of-frame halo
+// pixels are staged as not valid, so the tap loop has no bounds test.  Strides >= 4 gather the taps from global memory (the working
+// set stays in L2 / Infinity Cache at the project's frame sizes; Guided: two double4 per tap) and compute a tap's L from its C.
 #include "rt_kernels.h"
 #include "rt_shared_math.h"
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 namespace {
 
 constexpr int DN_TW = 32, DN_TH = 8, DN_THREADS = DN_TW * DN_TH;
+
+// what a kernel gets of the guide: the launcher's description, or — the plain instantiations — nothing, so no argument of theirs is live
+struct NoGuide {};
+template <bool Guided> using GuideOf = std::conditional_t<Guided, rtk::DenoiseGuide, NoGuide>;
 
 // rt_kernel.hip's display_rgba8 (color_to_rgb(mean) with alpha 0xff, one little-endian word): the shared host / device code of
 // rt_shared_math.h per value, so the bytes are rt_resolve_rgba8_device's
@@ -31,55 +44,74 @@ __device__ __forceinline__ uint32_t display_rgba8(double r, double g, double b) 
 
 __device__ __forceinline__ bool is_finite(double x) { return ((rtm::f2u(x) >> 52) & 0x7ffu) != 0x7ffu; }
 __device__ __forceinline__ double luminance(double r, double g, double b) { return ((r + g) + b) / 3.0; }
+__device__ __forceinline__ double max_ab(double a, double b) { return b > a ? b : a; } // the header's max(a, b)
 
-// Prepare: m = S / n; a valid pixel's V0 = max(max(max(v_r, v_g), v_b), 0) / n with v_c = (Q_c - S_c * m_c) / (n - 1) and
-// max(a, b) = b > a ? b : a; any other pixel's V = -1.  One thread per pixel.
+// Prepare: m = S / n; a valid pixel's V0 = max(max(max(v_r, v_g), v_b), 0) / n with v_c = (Q_c - S_c * m_c) / (n - 1) and C0 = m; any
+// other pixel's C = m and V = -1.  Guided: a = A / n_a is the guide, a pixel with a non-finite A is not valid either, and a valid
+// pixel's d = max(a, floor), C0 = m / d, V0 from u_c = v_c / (d_c * d_c) in v_c's place.  One thread per pixel.
+template <bool Guided>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_pixels, const double *__restrict__ sum, const double *__restrict__ sum_sq,
-                                                                      int32_t spp, const int32_t *__restrict__ spp_map, double4 *__restrict__ out) {
+                                                                      int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Guided> gd,
+                                                                      double4 *__restrict__ out) {
     const int64_t idx = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
     if (idx >= n_pixels) return;
     const int32_t n = spp_map ? spp_map[idx] : spp;
     const double dn = (double)n;
     const double s[3] = {sum[idx * 3 + 0], sum[idx * 3 + 1], sum[idx * 3 + 2]};
     const double q[3] = {sum_sq[idx * 3 + 0], sum_sq[idx * 3 + 1], sum_sq[idx * 3 + 2]};
-    const double m[3] = {s[0] / dn, s[1] / dn, s[2] / dn};
+    double A[3] = {0.0, 0.0, 0.0}, a[3] = {0.0, 0.0, 0.0};
+    if constexpr (Guided)
+        for (int k = 0; k < 3; ++k) {
+            A[k] = gd.albedo_sum[idx * 3 + k];
+            a[k] = A[k] / gd.albedo_spp;
+        }
+    double c[3] = {s[0] / dn, s[1] / dn, s[2] / dn};
     bool valid = n >= 2;
-    for (int c = 0; c < 3; ++c) valid = valid && is_finite(s[c]) && is_finite(q[c]);
+    for (int k = 0; k < 3; ++k) valid = valid && is_finite(s[k]) && is_finite(q[k]) && is_finite(A[k]);
     double V = -1.0;
     if (valid) {
-        double vmax = (q[0] - s[0] * m[0]) / (dn - 1.0);
-        for (int c = 1; c < 3; ++c) {
-            const double v = (q[c] - s[c] * m[c]) / (dn - 1.0);
-            if (v > vmax) vmax = v;
+        double vmax = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            double v = (q[k] - s[k] * c[k]) / (dn - 1.0);
+            if constexpr (Guided) {
+                const double d = max_ab(a[k], gd.albedo_floor);
+                v = v / (d * d);
+                c[k] = c[k] / d;
+            }
+            vmax = k == 0 ? v : max_ab(vmax, v);
         }
-        if (0.0 > vmax) vmax = 0.0;
+        vmax = max_ab(vmax, 0.0);
         V = vmax / dn;
     }
-    out[idx] = make_double4(m[0], m[1], m[2], V);
+    out[idx] = make_double4(c[0], c[1], c[2], V);
+    if constexpr (Guided) gd.region[idx] = make_double4(a[0], a[1], a[2], 0.0);
 }
 
-struct Tap { double L, r, g, b, V; };
+struct Tap { double L, r, g, b, V, ar, ag, ab; }; // (ar, ag, ab: the tap's albedo means; Guided only, not set otherwise)
 
 // where a lane's taps come from: the workgroup's staged tile (strides 1 and 2) ...
-template <int S> struct LdsSource {
-    static constexpr int HALO = 2 * S, PW = DN_TW + 2 * HALO, PH = DN_TH + 2 * HALO;
-    const double *L, *r, *g, *b, *V;
-    int centre; // the lane's own pixel in the staged planes
+template <int S, bool Guided> struct LdsSource {
+    static constexpr int HALO = 2 * S, PW = DN_TW + 2 * HALO, PH = DN_TH + 2 * HALO, PLANE = PH * PW;
+    enum { P_L, P_R, P_G, P_B, P_V, P_AR, P_AG, P_AB, PLANES = Guided ? 8 : 5 };
+    const double *staged; // PLANES planes of PLANE doubles
+    int centre;           // the lane's own pixel in a plane
+    __device__ __forceinline__ double at(int plane, int k) const { return staged[plane * PLANE + k]; }
     __device__ __forceinline__ bool variance(int dx, int dy, double &v) const {
-        v = V[centre + dy * PW + dx];
+        v = at(P_V, centre + dy * PW + dx);
         return !(v < 0.0);
     }
     __device__ __forceinline__ bool tap(int dx, int dy, Tap &t) const {
         const int k = centre + (dy * PW + dx) * S;
-        t.V = V[k];
+        t.V = at(P_V, k);
         if (t.V < 0.0) return false;
-        t.L = L[k]; t.r = r[k]; t.g = g[k]; t.b = b[k];
+        t.L = at(P_L, k); t.r = at(P_R, k); t.g = at(P_G, k); t.b = at(P_B, k);
+        if constexpr (Guided) { t.ar = at(P_AR, k); t.ag = at(P_AG, k); t.ab = at(P_AB, k); }
         return true;
     }
 };
 // ... or global memory (strides >= 4)
-struct GlobalSource {
-    const double4 *in;
+template <bool Guided> struct GlobalSource {
+    const double4 *in, *guide; // (guide: Guided only)
     int32_t w, h, px, py, stride;
     __device__ __forceinline__ bool variance(int dx, int dy, double &v) const {
         const int32_t x = px + dx, y = py + dy;
@@ -90,16 +122,23 @@ struct GlobalSource {
     __device__ __forceinline__ bool tap(int dx, int dy, Tap &t) const {
         const int32_t x = px + dx * stride, y = py + dy * stride;
         if (x < 0 || x >= w || y < 0 || y >= h) return false;
-        const double4 c = in[(size_t)y * (size_t)w + (size_t)x];
+        const size_t k = (size_t)y * (size_t)w + (size_t)x;
+        const double4 c = in[k];
         if (c.w < 0.0) return false;
         t.L = luminance(c.x, c.y, c.z); t.r = c.x; t.g = c.y; t.b = c.z; t.V = c.w;
+        if constexpr (Guided) {
+            const double4 a = guide[k];
+            t.ar = a.x; t.ag = a.y; t.ab = a.z;
+        }
         return true;
     }
 };
 
-// One iteration for one valid pixel (the header's "Iteration k"): the 3 x 3 prefilter of the variance, then the 25 taps in the order
-// dy outer, dx inner.  Sums start from +0.0 and take one addition per tap used; nothing is reassociated.
-template <class Source> __device__ __forceinline__ double4 filter_pixel(const Source &src, double Lp, double sigma, double eps) {
+// One iteration for one valid pixel p (the header's "Iteration k"), which leaves with its new C and V: the 3 x 3 prefilter of the
+// variance, then the 25 taps in the order dy outer, dx inner, each weighted by the luminance stop e and, Guided, the albedo stop ea.
+// Sums start from +0.0 and take one addition per tap used; nothing is reassociated.
+template <bool Guided, class Source>
+__device__ __forceinline__ void filter_pixel(const Source &src, Tap &p, double sigma, double eps, const GuideOf<Guided> &gd) {
     const double g3[3] = {0.25, 0.5, 0.25};
     double gs = 0.0, ws = 0.0;
 #pragma unroll
@@ -123,9 +162,16 @@ template <class Source> __device__ __forceinline__ double4 filter_pixel(const So
         for (int dx = -2; dx <= 2; ++dx) {
             Tap q;
             if (!src.tap(dx, dy, q)) continue;
-            const double x = __builtin_fabs(Lp - q.L) / den;
+            const double x = __builtin_fabs(p.L - q.L) / den;
             const double t = 1.0 - x * x;
-            const double e = t > 0.0 ? t * t : 0.0;
+            double e = t > 0.0 ? t * t : 0.0;
+            if constexpr (Guided) {
+                const double da = max_ab(max_ab(__builtin_fabs(p.ar - q.ar), __builtin_fabs(p.ag - q.ag)), __builtin_fabs(p.ab - q.ab));
+                const double y = da / gd.sigma_albedo;
+                const double ta = 1.0 - y * y;
+                const double ea = ta > 0.0 ? ta * ta : 0.0;
+                e = e * ea;
+            }
             const double wq = (h5[dy + 2] * h5[dx + 2]) * e;
             sw = sw + wq;
             sr = sr + wq * q.r;
@@ -133,81 +179,120 @@ template <class Source> __device__ __forceinline__ double4 filter_pixel(const So
             sb = sb + wq * q.b;
             sv = sv + (wq * wq) * q.V;
         }
-    return make_double4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
+    p.r = sr / sw; p.g = sg / sw; p.b = sb / sw; p.V = sv / (sw * sw);
 }
 
-// what an iteration writes for its pixel: the other half of the workspace, or — the last one — the caller's frame of means and,
-// in the same pass, its display bytes
+// what an iteration writes for its pixel: the other half of the workspace, or — the last one — the caller's frame of means (Guided: a
+// valid pixel's irradiance times its divisor max(a, floor); any other pixel's mean as it is) and, in the same pass, its display bytes
 struct DenoiseOut {
     double4 *next;      // or null: the last iteration
     double *mean;       // 3 w h
     uint32_t *rgba;     // w h words, or null
 };
-__device__ __forceinline__ void store_pixel(const DenoiseOut &o, size_t pixel, const double4 &c) {
+template <bool Guided>
+__device__ __forceinline__ void store_pixel(const DenoiseOut &o, size_t pixel, Tap p, const GuideOf<Guided> &gd) {
     if (o.next) {
-        o.next[pixel] = c;
+        o.next[pixel] = make_double4(p.r, p.g, p.b, p.V);
         return;
     }
-    o.mean[pixel * 3u + 0u] = c.x; o.mean[pixel * 3u + 1u] = c.y; o.mean[pixel * 3u + 2u] = c.z;
-    if (o.rgba) o.rgba[pixel] = display_rgba8(c.x, c.y, c.z);
+    if constexpr (Guided)
+        if (!(p.V < 0.0)) {
+            p.r = p.r * max_ab(p.ar, gd.albedo_floor);
+            p.g = p.g * max_ab(p.ag, gd.albedo_floor);
+            p.b = p.b * max_ab(p.ab, gd.albedo_floor);
+        }
+    o.mean[pixel * 3u + 0u] = p.r; o.mean[pixel * 3u + 1u] = p.g; o.mean[pixel * 3u + 2u] = p.b;
+    if (o.rgba) o.rgba[pixel] = display_rgba8(p.r, p.g, p.b);
 }
 
-template <int S>
-__global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32_t h, int32_t tiles_x, double sigma, double eps, const double4 *__restrict__ in, DenoiseOut out) {
-    using Src = LdsSource<S>;
-    constexpr int PW = Src::PW, PH = Src::PH, HALO = Src::HALO;
-    __shared__ double sL[PH * PW], sR[PH * PW], sG[PH * PW], sB[PH * PW], sV[PH * PW];
+template <int S, bool Guided>
+__global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32_t h, int32_t tiles_x, double sigma, double eps, GuideOf<Guided> gd,
+                                                                 const double4 *__restrict__ in, DenoiseOut out) {
+    using Src = LdsSource<S, Guided>;
+    constexpr int PW = Src::PW, PLANE = Src::PLANE, HALO = Src::HALO;
+    __shared__ double staged[Src::PLANES * PLANE];
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // a 1-D grid of tiles, row-major
     const int32_t x0 = tile_x * DN_TW - HALO, y0 = tile_y * DN_TH - HALO;
-    for (int k = (int)threadIdx.x; k < PH * PW; k += DN_THREADS) {
+    for (int k = (int)threadIdx.x; k < PLANE; k += DN_THREADS) {
         const int ly = k / PW, lx = k - ly * PW;
         const int32_t gx = x0 + lx, gy = y0 + ly;
-        double4 c = make_double4(0.0, 0.0, 0.0, -1.0);
-        if (gx >= 0 && gx < w && gy >= 0 && gy < h) c = in[(size_t)gy * (size_t)w + (size_t)gx];
-        sR[k] = c.x; sG[k] = c.y; sB[k] = c.z; sV[k] = c.w;
-        sL[k] = luminance(c.x, c.y, c.z);
+        double4 c = make_double4(0.0, 0.0, 0.0, -1.0), a = make_double4(0.0, 0.0, 0.0, 0.0);
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t g = (size_t)gy * (size_t)w + (size_t)gx;
+            c = in[g];
+            if constexpr (Guided) a = gd.region[g];
+        }
+        staged[Src::P_R * PLANE + k] = c.x; staged[Src::P_G * PLANE + k] = c.y; staged[Src::P_B * PLANE + k] = c.z; staged[Src::P_V * PLANE + k] = c.w;
+        staged[Src::P_L * PLANE + k] = luminance(c.x, c.y, c.z);
+        if constexpr (Guided) { staged[Src::P_AR * PLANE + k] = a.x; staged[Src::P_AG * PLANE + k] = a.y; staged[Src::P_AB * PLANE + k] = a.z; }
     }
     __syncthreads();
     const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
     const int32_t px = tile_x * DN_TW + tx, py = tile_y * DN_TH + ty;
     if (px >= w || py >= h) return;
-    const Src src{sL, sR, sG, sB, sV, (HALO + ty) * PW + HALO + tx};
-    double4 c = make_double4(sR[src.centre], sG[src.centre], sB[src.centre], sV[src.centre]);
-    if (!(c.w < 0.0)) c = filter_pixel(src, sL[src.centre], sigma, eps);
-    store_pixel(out, (size_t)py * (size_t)w + (size_t)px, c);
+    const Src src{staged, (HALO + ty) * PW + HALO + tx};
+    const int k = src.centre;
+    Tap p;
+    p.L = src.at(Src::P_L, k); p.r = src.at(Src::P_R, k); p.g = src.at(Src::P_G, k); p.b = src.at(Src::P_B, k); p.V = src.at(Src::P_V, k);
+    if constexpr (Guided) { p.ar = src.at(Src::P_AR, k); p.ag = src.at(Src::P_AG, k); p.ab = src.at(Src::P_AB, k); }
+    if (!(p.V < 0.0)) filter_pixel<Guided>(src, p, sigma, eps, gd);
+    store_pixel<Guided>(out, (size_t)py * (size_t)w + (size_t)px, p, gd);
 }
 
+template <bool Guided>
 __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, int32_t h, int32_t tiles_x, int32_t stride, double sigma, double eps,
-                                                                    const double4 *__restrict__ in, DenoiseOut out) {
+                                                                    GuideOf<Guided> gd, const double4 *__restrict__ in, DenoiseOut out) {
     const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x;
     const int32_t px = tile_x * DN_TW + tx, py = tile_y * DN_TH + ty;
     if (px >= w || py >= h) return;
     const size_t pixel = (size_t)py * (size_t)w + (size_t)px;
-    double4 c = in[pixel];
-    if (!(c.w < 0.0)) c = filter_pixel(GlobalSource{in, w, h, px, py, stride}, luminance(c.x, c.y, c.z), sigma, eps);
-    store_pixel(out, pixel, c);
+    const double4 *guide = nullptr;
+    if constexpr (Guided) guide = gd.region;
+    const double4 c = in[pixel];
+    Tap p;
+    p.L = luminance(c.x, c.y, c.z); p.r = c.x; p.g = c.y; p.b = c.z; p.V = c.w;
+    if constexpr (Guided) {
+        const double4 a = guide[pixel];
+        p.ar = a.x; p.ag = a.y; p.ab = a.z;
+    }
+    if (!(p.V < 0.0)) filter_pixel<Guided>(GlobalSource<Guided>{in, guide, w, h, px, py, stride}, p, sigma, eps, gd);
+    store_pixel<Guided>(out, pixel, p, gd);
+}
+
+template <bool Guided>
+void launch_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Guided> &gd,
+                    void *half, hipStream_t stream) {
+    hipLaunchKernelGGL(denoise_prepare_kernel<Guided>, dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS)), dim3(DN_THREADS), 0, stream,
+                       n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
+}
+
+template <bool Guided>
+void launch_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const GuideOf<Guided> &gd, const void *half_in, const DenoiseOut &out,
+                   hipStream_t stream) {
+    const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
+    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(DN_THREADS); // (w * h < 2^27: fewer than 2^27 tiles)
+    const double4 *in = (const double4 *)half_in;
+    if (stride == 1) hipLaunchKernelGGL((atrous_lds_kernel<1, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
+    else if (stride == 2) hipLaunchKernelGGL((atrous_lds_kernel<2, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
+    else hipLaunchKernelGGL(atrous_global_kernel<Guided>, grid, block, 0, stream, w, h, tiles_x, stride, sigma, eps, gd, in, out);
 }
 
 } // namespace
 
 namespace rtk {
 
-void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, void *half,
-                            hipStream_t stream) {
-    hipLaunchKernelGGL(denoise_prepare_kernel, dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS)), dim3(DN_THREADS), 0, stream,
-                       n_pixels, sum, sum_sq, spp, spp_map, (double4 *)half);
+void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
+                            void *half, hipStream_t stream) {
+    if (guide) launch_prepare<true>(n_pixels, sum, sum_sq, spp, spp_map, *guide, half, stream);
+    else launch_prepare<false>(n_pixels, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
 }
 
-void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const void *half_in, void *half_out,
-                           double *mean_out, uint8_t *rgba8, hipStream_t stream) {
-    const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
-    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(DN_THREADS); // (w * h < 2^27: fewer than 2^27 tiles)
+void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
+                           void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream) {
     const DenoiseOut out{(double4 *)half_out, mean_out, (uint32_t *)rgba8};
-    const double4 *in = (const double4 *)half_in;
-    if (stride == 1) hipLaunchKernelGGL(atrous_lds_kernel<1>, grid, block, 0, stream, w, h, tiles_x, sigma, eps, in, out);
-    else if (stride == 2) hipLaunchKernelGGL(atrous_lds_kernel<2>, grid, block, 0, stream, w, h, tiles_x, sigma, eps, in, out);
-    else hipLaunchKernelGGL(atrous_global_kernel, grid, block, 0, stream, w, h, tiles_x, stride, sigma, eps, in, out);
+    if (guide) launch_atrous<true>(w, h, stride, sigma, eps, *guide, half_in, out, stream);
+    else launch_atrous<false>(w, h, stride, sigma, eps, NoGuide{}, half_in, out, stream);
 }
 
 } // namespace rtk

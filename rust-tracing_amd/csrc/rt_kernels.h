@@ -206,19 +206,21 @@ void launch_tiles_to_frame_rgb8(int32_t w, int32_t h, int32_t tiles_x, int32_t s
                                 uint8_t *frame, hipStream_t stream);
 void launch_resolve_rgb8(int64_t n_values, double inv_spp, const double *sum, uint8_t *rgb, hipStream_t stream);
 void launch_resolve_rgba8(int64_t n_pixels, const double *mean, uint8_t *rgba, hipStream_t stream);
-// the denoiser (rt_denoise.hip; rt_denoise_device): `half` / `half_in` / `half_out` are halves of the caller's workspace, one double4
-// (C_r, C_g, C_b, V) per pixel.  An iteration with half_out null is the last: it writes mean_out (3 w h doubles) and, if not null, rgba8
-void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, void *half,
-                            hipStream_t stream);
-void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const void *half_in, void *half_out,
-                           double *mean_out, uint8_t *rgba8, hipStream_t stream);
-// the albedo-guided denoiser (rt_denoise_albedo.hip; rt_denoise_albedo_device): the halves as above, and `guide`, a third region of one
-// double4 (a_r, a_g, a_b, 0) per pixel that prepare writes once.  An iteration with half_out null is the last: it multiplies the floored
-// albedo back in and writes mean_out and, if not null, rgba8
-void launch_denoise_albedo_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map,
-                                   const double *albedo_sum, int32_t albedo_spp, double albedo_floor, void *half, void *guide, hipStream_t stream);
-void launch_denoise_albedo_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, double sigma_albedo, double albedo_floor,
-                                  const void *half_in, const void *guide, void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream);
+// the denoisers (rt_denoise.hip; rt_denoise_device and, with a guide, rt_denoise_albedo_device): `half` / `half_in` / `half_out` are
+// halves of the caller's workspace, one double4 (C_r, C_g, C_b, V) per pixel.  `guide` null is the plain filter; otherwise the albedo
+// frame and the guided filter's two parameters, and `region`, a third region of the workspace of one double4 (a_r, a_g, a_b, 0) per
+// pixel that prepare writes once and the iterations read.  An iteration with half_out null is the last: it writes mean_out (3 w h
+// doubles; guided: with the floored albedo multiplied back in) and, if not null, rgba8
+struct DenoiseGuide {
+    const double *albedo_sum; // 3 w h doubles: per-pixel sums of albedo_spp samples (prepare reads them)
+    double albedo_spp;        // their count, as the divisor it is
+    double albedo_floor, sigma_albedo;
+    double4 *region;
+};
+void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
+                            void *half, hipStream_t stream);
+void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
+                           void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)
