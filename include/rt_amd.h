@@ -581,6 +581,55 @@ int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum,
                              int32_t albedo_spp /* >= 1 */, const rt_denoise_albedo_params *params /* NULL: defaults */,
                              double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- live denoise: a running second moment beside the running mean, and the filters on (mean, M2) (opt-in; nothing above changes) ----
+ * Live refinement shows the noisiest frames there are — 1, 2, 3 ... samples per pixel — and a running mean keeps no second moment, so
+ * neither filter above can take its frame.  These calls close that gap: a reduction that keeps Welford's M2 beside the mean, and a
+ * means-form input for the two filters.
+ *
+ * rt_render_mean_moments_device is rt_render_mean_device with a second frame of 3 * w * h doubles, d_m2.  Per channel, f64, every
+ * operation rounded on its own (no FMA, IEEE division):
+ *     for s = sample_begin .. sample_end - 1:
+ *         d  = c_s - m
+ *         m' = m + d / (double)(s + 1)            (rt_render_mean_device's recurrence, word for word)
+ *         M2 = M2 + d * (c_s - m')                (the product rounded, then added)
+ *         m  = m'
+ * sample_begin == 0 starts m and M2 from +0.0 and reads neither buffer; any other sample_begin continues both, so [0, a) followed by
+ * [a, b) equals [0, b) bit for bit.  d_mean is, bit for bit, what rt_render_mean_device writes, and d_rgba8 follows its contract (the
+ * call's last launch writes it, in the same pass).  m' lies between m and c_s, so d and c_s - m' have one sign or are zero: every term is
+ * >= 0, M2 never decreases and is never negative, and a pixel whose samples are all equal has M2 = +0.0 exactly — none of which holds
+ * for Q - S * m.  M2 / (n - 1) is the sample variance after n samples.  Limits and refusals are rt_render_mean_device's, and a null
+ * d_m2 / m2: RT_ERR_INVALID_ARGUMENT with the field named, before the scene handle or any device work is touched.
+ * rt_render_mean_moments blocks and downloads; when sample_begin > 0 it uploads `mean` and `m2` first.
+ *
+ * rt_denoise_mean_device and rt_denoise_albedo_mean_device are rt_denoise_device and rt_denoise_albedo_device on such frames: d_mean
+ * and d_m2 (3 * w * h doubles each) after `samples` samples of every pixel — the count is uniform, there is no map — and, guided,
+ * d_albedo_mean, the frame rt_render_mean_device gives for the albedo scene.  Workspaces are rt_denoise_workspace_bytes and
+ * rt_denoise_albedo_workspace_bytes.  Only Prepare differs; with n = (double)samples and m, M2, a the pixel's entries:
+ *   Prepare.   p is VALID iff samples >= 2 and every m_c and M2_c (guided: and a_c) is finite.  For a valid pixel
+ *              v_c = M2_c / (n - 1)
+ *              V0 = max(max(max(v_r, v_g), v_b), 0) / n;   C0 = m
+ *              guided:  d_c = max(a_c, albedo_floor)  (a is not divided);  C0 = m / d;  u_c = v_c / (d_c * d_c) in v_c's place.
+ *              A pixel that is not valid keeps C = m, is written to the output unchanged and is never a tap: with samples < 2 the whole
+ *              output is d_mean, bit for bit.  Any M2 may be passed, a negative one too: the max(.., 0) covers it.
+ *   Iterations and Output: those of rt_denoise_device / rt_denoise_albedo_device, unchanged (guided: the stop reads the un-floored a).
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, as the sums forms give it: width or height < 1 or w * h >= 2^27; a
+ * null d_mean, d_m2, d_albedo_mean, d_mean_out or d_workspace; samples < 1; a struct_size this library does not know; iterations
+ * outside 1..6; sigma, eps, sigma_albedo or albedo_floor that is not a number > 0; d_mean_out overlapping an input; a d_rgba8 that is
+ * not 4-byte aligned. */
+int rt_render_mean_moments_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                                  double *d_mean /* 3*w*h */, double *d_m2 /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */,
+                                  void *hip_stream);
+int rt_render_mean_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
+                           double *mean /* host; read when sample_begin > 0 */, double *m2 /* host; likewise */,
+                           uint8_t *rgba8 /* host, or NULL */);
+int rt_denoise_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                           const rt_denoise_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
+                           uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                  const double *d_albedo_mean /* 3*w*h */, const rt_denoise_albedo_params *params /* NULL: defaults */,
+                                  double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace,
+                                  void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -315,6 +315,13 @@ RT_AMD_SYMBOLS = {
     "rt_denoise_albedo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_denoise_albedo_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_mean_moments_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+    "rt_render_mean_moments": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_mean_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "rt_denoise_albedo_mean_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -867,6 +874,34 @@ class DeviceScene:
         _check(amd_lib().rt_render_mean_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_mean_ptr),
                                                C.c_void_p(d_rgba8_ptr or None), C.c_void_p(stream)), "rt_render_mean_device")
 
+    def render_mean_moments(self, params: RenderParams, camera: Camera | None = None, mean=None, m2=None, rgba8: bool = False):
+        """rt_render_mean_moments: render_mean with Welford's M2 beside the mean, M2 += (c - m) * (c - m') per sample (m the mean before
+        the sample, m' after it).  `mean`, `m2`: the (h, w, 3) float64 frames to continue — both required when params.sample_begin > 0
+        — written and returned: (mean, m2), or (mean, m2, (h, w, 4) uint8) with rgba8."""
+        import numpy as np
+        cam = camera if camera is not None else self.host_scene.camera
+        h, w = cam.image_height, cam.image_width
+        if mean is None and m2 is None:
+            if params.sample_begin > 0:
+                raise RtError("render_mean_moments: params.sample_begin > 0 continues running frames: pass them as `mean` and `m2`")
+            mean, m2 = np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 3), dtype=np.float64)
+        for name, a in (("mean", mean), ("m2", m2)):
+            if a is None or a.shape != (h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise RtError(f"render_mean_moments: `{name}` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        frame = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
+        _check(amd_lib().rt_render_mean_moments(self._handle, C.byref(cam), C.byref(params), C.c_void_p(mean.ctypes.data),
+                                                C.c_void_p(m2.ctypes.data), C.c_void_p(frame.ctypes.data) if rgba8 else None),
+               "rt_render_mean_moments")
+        return (mean, m2, frame) if rgba8 else (mean, m2)
+
+    def render_mean_moments_device(self, params: RenderParams, d_mean_ptr: int, d_m2_ptr: int, d_rgba8_ptr: int = 0, stream: int = 0,
+                                   camera: Camera | None = None):
+        """rt_render_mean_moments_device: render_mean_device with `d_m2_ptr`, a second device frame of 3 w h doubles holding M2 of the
+        first params.sample_begin samples (not read when that is 0).  Enqueued on `stream`."""
+        cam = camera if camera is not None else self.host_scene.camera
+        _check(amd_lib().rt_render_mean_moments_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr),
+                                                       C.c_void_p(d_rgba8_ptr or None), C.c_void_p(stream)), "rt_render_mean_moments_device")
+
     def render_moments(self, params: RenderParams, camera: Camera | None = None, sum=None, sum_sq=None):
         """rt_render_moments: (sum, sum_sq), two (h, w, 3) float64 frames: the per-pixel sums rt_render gives and the in-order sums of
         the samples' squares.  With params.accumulate both running frames are required and continued in place."""
@@ -1075,6 +1110,65 @@ def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rg
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
         return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def denoise_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
+                        d_rgba8_ptr: int = 0, params: "DenoiseParams | None" = None, stream: int = 0):
+    """rt_denoise_mean_device: denoise_device over device frames of running means and of M2 (3 w h doubles each, what
+    render_mean_moments_device keeps) after `samples` samples of every pixel; `d_workspace_ptr`: denoise_workspace_bytes(w, h) device
+    bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples,
+                                            C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                            C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)), "rt_denoise_mean_device")
+
+
+def denoise_albedo_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_mean_out_ptr: int,
+                               d_workspace_ptr: int, *, d_rgba8_ptr: int = 0, params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
+    """rt_denoise_albedo_mean_device: denoise_mean_device with a device frame of albedo means (3 w h doubles: render_mean_device of the
+    albedo scene) beside them; `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_albedo_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples, C.c_void_p(d_albedo_mean_ptr),
+                                                   C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                   C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_albedo_mean_device")
+
+
+def _denoise_means(who, mean, m2, samples, albedo_mean, rgba8, device, kw):
+    """denoise_mean and denoise_albedo_mean: upload, run, download"""
+    import numpy as np
+    frames = [np.array(a, dtype=np.float64, order="C") for a in ((mean, m2) if albedo_mean is None else (mean, m2, albedo_mean))]  # (copies)
+    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
+    h, w = frames[0].shape[:2]
+    params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_in = [torch.from_numpy(a).cuda() for a in frames]
+        d_out = torch.empty_like(d_in[0])
+        d_ws = torch.empty(denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8,
+                           device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+        if albedo_mean is None:
+            denoise_mean_device(w, h, d_in[0].data_ptr(), d_in[1].data_ptr(), int(samples), d_out.data_ptr(), d_ws.data_ptr(), **common)
+        else:
+            denoise_albedo_mean_device(w, h, d_in[0].data_ptr(), d_in[1].data_ptr(), int(samples), d_in[2].data_ptr(), d_out.data_ptr(),
+                                       d_ws.data_ptr(), **common)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def denoise_mean(mean, m2, samples, *, rgba8=False, device=0, **kw):
+    """Uploads (h, w, 3) frames of running means and of M2 after `samples` samples, runs rt_denoise_mean_device with denoise_params(**kw)
+    and downloads: the (h, w, 3) float64 filtered means, or (means, (h, w, 4) uint8) with rgba8."""
+    return _denoise_means("denoise_mean", mean, m2, samples, None, rgba8, device, kw)
+
+
+def denoise_albedo_mean(mean, m2, samples, albedo_mean, *, rgba8=False, device=0, **kw):
+    """denoise_mean with an (h, w, 3) frame of albedo means beside the two: rt_denoise_albedo_mean_device with denoise_albedo_params(**kw)."""
+    if albedo_mean is None:
+        raise RtError("denoise_albedo_mean: `albedo_mean` is required")
+    return _denoise_means("denoise_albedo_mean", mean, m2, samples, albedo_mean, rgba8, device, kw)
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

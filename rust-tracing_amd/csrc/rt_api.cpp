@@ -215,9 +215,11 @@ struct ViewTable {
 
 // Live refinement (rt_render_mean_device): the dense render with `d_out` a frame of running means.  Each launch's samples are folded
 // into it by mean_samples_kernel instead of being added by sum_samples_kernel; the last launch of the call also writes the display
-// frame.  Everything else — chunks, pipelining, scratch, grid — is the dense render's.
+// frame.  Everything else — chunks, pipelining, scratch, grid — is the dense render's.  With `d_m2` (rt_render_mean_moments_device) the
+// reduction is mean_moments_samples_kernel, which keeps Welford's M2 in that frame beside the mean.
 struct MeanOut {
     uint8_t *d_rgba8; // or null
+    double *d_m2;     // or null
 };
 
 int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, double *d_out, hipStream_t stream,
@@ -437,6 +439,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         K.pixel_list = list->pixels; K.n_list = (uint32_t)list->n; K.out_sq = list->d_sum_sq;
         K.inv_width = 1.0 / (double)camera->image_width;
     }
+    if (mean) K.out_sq = mean->d_m2;
     if (views) {
         K.views = ws.views; K.tiles_per_view = (uint32_t)tiles_per_view; K.inv_tiles_per_view = 1.0 / (double)tiles_per_view;
     }
@@ -521,7 +524,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         if (pipelined && k > 0) HIP_TRY(hipStreamWaitEvent(s, ws.ev_sum[h ^ 1], 0));
         if (mean) {
             K.mean_rgba8 = sb + ns >= p.sample_end ? mean->d_rgba8 : nullptr; // (the call's last launch: the frame the caller shows)
-            launch_mean_samples(K, sum_grid, s);
+            if (mean->d_m2) launch_mean_moments_samples(K, sum_grid, s);
+            else launch_mean_samples(K, sum_grid, s);
         } else if (views) launch_sum_view_samples(K, sum_grid, s);
         else if (list) launch_sum_listed_samples(K, sum_grid, s);
         else launch_sum_samples(K, sum_grid, s);
@@ -1387,13 +1391,16 @@ int rt_render_adaptive(const rt_scene *scene, const rt_camera *camera, const rt_
 
 // ---- live refinement: running-mean frames and their display bytes ----
 namespace {
-// every check of rt_render_mean / rt_render_mean_device: none needs the scene handle or a device.  Fills the normalised parameters.
+// every check of rt_render_mean / rt_render_mean_device and, with `m2_name` (the M2 frame's name: it must not be null then), of
+// rt_render_mean_moments / rt_render_mean_moments_device: none needs the scene handle or a device.  Fills the normalised parameters.
 static int check_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, const void *mean, const char *mean_name,
-               const void *rgba8, const char *rgba8_name, const char *who, rt_render_params &p) {
+               const void *rgba8, const char *rgba8_name, const char *who, rt_render_params &p, const void *m2 = nullptr,
+               const char *m2_name = nullptr) {
     const std::string w(who);
     if (!camera) return fail(RT_ERR_INVALID_ARGUMENT, w + ": camera is null");
     if (!params) return fail(RT_ERR_INVALID_ARGUMENT, w + ": params is null");
     if (!mean) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + mean_name + " is null");
+    if (m2_name && !m2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + m2_name + " is null");
     p = *params;
     if (p.accumulate != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": accumulate must be 0 (a running mean continues through sample_begin)");
     if (p.shard_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (the live frame is rendered on one device)");
@@ -1414,33 +1421,42 @@ int rt_render_mean_device(const rt_scene *scene, const rt_camera *camera, const 
     rt_render_params p;
     if (int rc = check_mean(scene, camera, params, d_mean, "d_mean", d_rgba8, "d_rgba8", "rt_render_mean_device", p)) return rc;
     g_last_launch[0] = 0;
-    const MeanOut mean{d_rgba8};
+    const MeanOut mean{d_rgba8, nullptr};
     return launch_render(const_cast<rt_scene *>(scene), camera, p, d_mean, (hipStream_t)hip_stream, nullptr, nullptr, nullptr, &mean);
 }
 
-int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *mean, uint8_t *rgba8) {
-    const char *who = "rt_render_mean";
+int rt_render_mean_moments_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *d_mean, double *d_m2,
+                                  uint8_t *d_rgba8, void *hip_stream) {
     rt_render_params p;
-    if (int rc = check_mean(scene, camera, params, mean, "mean", nullptr, "rgba8", who, p)) return rc; // (host bytes: any alignment)
+    if (int rc = check_mean(scene, camera, params, d_mean, "d_mean", d_rgba8, "d_rgba8", "rt_render_mean_moments_device", p, d_m2, "d_m2")) return rc;
     g_last_launch[0] = 0;
-    rt_scene *s = const_cast<rt_scene *>(scene);
+    const MeanOut mean{d_rgba8, d_m2};
+    return launch_render(const_cast<rt_scene *>(scene), camera, p, d_mean, (hipStream_t)hip_stream, nullptr, nullptr, nullptr, &mean);
+}
+
+namespace {
+// rt_render_mean and, with `m2`, rt_render_mean_moments, past their checks: the frames in one device allocation (mean | M2 | display
+// bytes), the caller's running values uploaded when the call continues them, the render, the downloads
+int render_mean_host(const char *who, rt_scene *s, const rt_camera *camera, const rt_render_params &p, double *mean, double *m2, uint8_t *rgba8) {
     std::lock_guard<std::mutex> serial(s->host_render_mu);
     HIP_TRY(hipSetDevice(s->device));
     const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height;
-    const size_t mean_bytes = n_pix * 3u * sizeof(double), rgba_bytes = rgba8 ? n_pix * 4u : 0u;
+    const size_t mean_bytes = n_pix * 3u * sizeof(double), m2_bytes = m2 ? mean_bytes : 0u, rgba_bytes = rgba8 ? n_pix * 4u : 0u;
     char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, mean_bytes + rgba_bytes));
+    HIP_TRY(hipMalloc((void **)&buf, mean_bytes + m2_bytes + rgba_bytes));
     double *d_mean = (double *)buf;
-    const MeanOut out{rgba8 ? (uint8_t *)(buf + mean_bytes) : nullptr};
+    const MeanOut out{rgba8 ? (uint8_t *)(buf + mean_bytes + m2_bytes) : nullptr, m2 ? (double *)(buf + mean_bytes) : nullptr};
     int rc = RT_OK;
     do {
-        if (p.sample_begin > 0 && hipMemcpy(d_mean, mean, mean_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        if (p.sample_begin > 0 && (hipMemcpy(d_mean, mean, mean_bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                                   (m2 && hipMemcpy(out.d_m2, m2, m2_bytes, hipMemcpyHostToDevice) != hipSuccess))) {
             rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running mean failed");
             break;
         }
         rc = launch_render(s, camera, p, d_mean, nullptr, nullptr, nullptr, nullptr, &out);
         if (rc != RT_OK) break;
         hipError_t e = hipMemcpy(mean, d_mean, mean_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && m2) e = hipMemcpy(m2, out.d_m2, m2_bytes, hipMemcpyDeviceToHost);
         if (e == hipSuccess && rgba8) e = hipMemcpy(rgba8, out.d_rgba8, rgba_bytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     } while (0);
@@ -1448,6 +1464,23 @@ int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_rend
     (void)hipFree(buf);
     if (rc != RT_OK) (void)hipGetLastError();
     return rc;
+}
+} // namespace
+
+int rt_render_mean(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *mean, uint8_t *rgba8) {
+    const char *who = "rt_render_mean";
+    rt_render_params p;
+    if (int rc = check_mean(scene, camera, params, mean, "mean", nullptr, "rgba8", who, p)) return rc; // (host bytes: any alignment)
+    g_last_launch[0] = 0;
+    return render_mean_host(who, const_cast<rt_scene *>(scene), camera, p, mean, nullptr, rgba8);
+}
+
+int rt_render_mean_moments(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *mean, double *m2, uint8_t *rgba8) {
+    const char *who = "rt_render_mean_moments";
+    rt_render_params p;
+    if (int rc = check_mean(scene, camera, params, mean, "mean", nullptr, "rgba8", who, p, m2, "m2")) return rc; // (host bytes: any alignment)
+    g_last_launch[0] = 0;
+    return render_mean_host(who, const_cast<rt_scene *>(scene), camera, p, mean, m2, rgba8);
 }
 
 int rt_resolve_rgba8_device(int32_t width, int32_t height, const double *d_mean, uint8_t *d_rgba8, void *hip_stream) {
@@ -1570,18 +1603,25 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 // rt_denoise_device and, with `guide` (what only the guided filter takes; its region is set here), rt_denoise_albedo_device: every check
 // in the header's order, each message under the caller's name `who`, then prepare and the K iterations.  `d` is the caller's resolved
 // params (the fields both structs have), or null where their struct_size was not known: that is refused here, in its place among the checks.
-int run_denoise(const char *who, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
-                DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+// `form` is the input form: sums and sums of squares with a sample count or map, or (rt_denoise_mean_device, rt_denoise_albedo_mean_device)
+// running means and M2 after `spp` samples of every pixel, the guide's frame a mean as well; the messages name the inputs as the caller does.
+enum class DenoiseInput { Sums, Means };
+int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                const int32_t *d_spp, DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
+                void *hip_stream) {
     const std::string w(who);
+    const bool means = form == DenoiseInput::Means;
+    const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum";
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
-    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum is null");
-    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_sum_sq is null");
-    if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_albedo_sum is null");
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
+    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
+    if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
     if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
     if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
-    if (!d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
-    if (guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
+    if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
+    if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
     if (!d)
         return fail(RT_ERR_INVALID_ARGUMENT, w + (guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
     if (d->iterations < 1 || d->iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
@@ -1592,7 +1632,7 @@ int run_denoise(const char *who, int32_t width, int32_t height, const double *d_
     const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
     if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes) ||
         (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + (guide ? "d_sum, d_sum_sq or d_albedo_sum" : "d_sum or d_sum_sq"));
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
     if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
     if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
     if (int rc = select_device_of(d_mean_out, who)) return rc;
@@ -1600,7 +1640,7 @@ int run_denoise(const char *who, int32_t width, int32_t height, const double *d_
     const size_t region = n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
     char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
     if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
-    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, half[0], stream);
+    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
     HIP_TRY(hipGetLastError());
     for (int32_t k = 0; k < d->iterations; ++k) {
         const bool last = k == d->iterations - 1;
@@ -1659,8 +1699,16 @@ int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const 
                       const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
     rt_denoise_params d;
     const bool known = denoise_params_resolve(params, d);
-    return run_denoise("rt_denoise_device", width, height, d_sum, d_sum_sq, spp, d_spp, nullptr, known ? &d : nullptr, d_mean_out, d_rgba8,
-                       d_workspace, hip_stream);
+    return run_denoise("rt_denoise_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, nullptr, known ? &d : nullptr, d_mean_out,
+                       d_rgba8, d_workspace, hip_stream);
+}
+
+int rt_denoise_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const rt_denoise_params *params,
+                           double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_params d;
+    const bool known = denoise_params_resolve(params, d);
+    return run_denoise("rt_denoise_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, nullptr, known ? &d : nullptr,
+                       d_mean_out, d_rgba8, d_workspace, hip_stream);
 }
 
 // ---- albedo scene and the albedo-guided filter (rt_denoise.hip, with a guide) ----
@@ -1747,8 +1795,18 @@ int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum,
     const bool known = denoise_params_resolve(params, d);
     const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
     DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
-    return run_denoise("rt_denoise_albedo_device", width, height, d_sum, d_sum_sq, spp, d_spp, &guide, known ? &shared : nullptr, d_mean_out,
-                       d_rgba8, d_workspace, hip_stream);
+    return run_denoise("rt_denoise_albedo_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, &guide, known ? &shared : nullptr,
+                       d_mean_out, d_rgba8, d_workspace, hip_stream);
+}
+
+int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const double *d_albedo_mean,
+                                  const rt_denoise_albedo_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_albedo_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr}; // (a frame of means: no count, nothing is divided)
+    return run_denoise("rt_denoise_albedo_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream);
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

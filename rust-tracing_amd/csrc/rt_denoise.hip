@@ -4,7 +4,9 @@
 // by the first-hit albedo (floored) first, which leaves the irradiance — and K edge-stopping wavelet iterations at strides 1, 2, 4, ...
 // ping-pong between the two halves of the caller's workspace.  They stop at luminance edges and, Guided, at edges of the albedo as
 // well: one more factor per tap; the last Guided iteration multiplies the albedo back in.  What only the guided filter does sits
-// behind `if constexpr (Guided)`, so the plain instantiations hold none of it and the two cannot drift apart.
+// behind `if constexpr (Guided)`, so the plain instantiations hold none of it and the two cannot drift apart.  Prepare has a second
+// compile-time parameter, the input form: sums and sums of squares, or (Means: rt_denoise_mean_device, rt_denoise_albedo_mean_device)
+// the live route's running means and Welford's M2; the iterations do not know which it was.
 //
 // Everything is f64 in the header's operation order, each operation rounded on its own (the file is compiled with
 // -ffp-contract=off and without fast-math: no FMA, IEEE division and square root), so a frame equals the numpy restatement in
@@ -49,7 +51,10 @@ __device__ __forceinline__ double max_ab(double a, double b) { return b > a ? b 
 // Prepare: m = S / n; a valid pixel's V0 = max(max(max(v_r, v_g), v_b), 0) / n with v_c = (Q_c - S_c * m_c) / (n - 1) and C0 = m; any
 // other pixel's C = m and V = -1.  Guided: a = A / n_a is the guide, a pixel with a non-finite A is not valid either, and a valid
 // pixel's d = max(a, floor), C0 = m / d, V0 from u_c = v_c / (d_c * d_c) in v_c's place.  One thread per pixel.
-template <bool Guided>
+// Means (rt_denoise_mean_device, rt_denoise_albedo_mean_device: the live route's frames): `sum` holds the running means m and `sum_sq`
+// Welford's M2 after n = spp samples of every pixel (no map), the guide's frame the albedo means a: nothing is divided by a count, and
+// v_c = M2_c / (n - 1).  Everything else is the sums form's, which holds none of this.
+template <bool Guided, bool Means>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_pixels, const double *__restrict__ sum, const double *__restrict__ sum_sq,
                                                                       int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Guided> gd,
                                                                       double4 *__restrict__ out) {
@@ -63,16 +68,21 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
     if constexpr (Guided)
         for (int k = 0; k < 3; ++k) {
             A[k] = gd.albedo_sum[idx * 3 + k];
-            a[k] = A[k] / gd.albedo_spp;
+            if constexpr (Means) a[k] = A[k];
+            else a[k] = A[k] / gd.albedo_spp;
         }
-    double c[3] = {s[0] / dn, s[1] / dn, s[2] / dn};
+    double c[3] = {s[0], s[1], s[2]};
+    if constexpr (!Means)
+        for (int k = 0; k < 3; ++k) c[k] = s[k] / dn;
     bool valid = n >= 2;
     for (int k = 0; k < 3; ++k) valid = valid && is_finite(s[k]) && is_finite(q[k]) && is_finite(A[k]);
     double V = -1.0;
     if (valid) {
         double vmax = 0.0;
         for (int k = 0; k < 3; ++k) {
-            double v = (q[k] - s[k] * c[k]) / (dn - 1.0);
+            double v;
+            if constexpr (Means) v = q[k] / (dn - 1.0);
+            else v = (q[k] - s[k] * c[k]) / (dn - 1.0);
             if constexpr (Guided) {
                 const double d = max_ab(a[k], gd.albedo_floor);
                 v = v / (d * d);
@@ -260,10 +270,10 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, in
     store_pixel<Guided>(out, pixel, p, gd);
 }
 
-template <bool Guided>
+template <bool Guided, bool Means>
 void launch_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Guided> &gd,
                     void *half, hipStream_t stream) {
-    hipLaunchKernelGGL(denoise_prepare_kernel<Guided>, dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS)), dim3(DN_THREADS), 0, stream,
+    hipLaunchKernelGGL((denoise_prepare_kernel<Guided, Means>), dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS)), dim3(DN_THREADS), 0, stream,
                        n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
 }
 
@@ -283,9 +293,12 @@ void launch_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double ep
 namespace rtk {
 
 void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
-                            void *half, hipStream_t stream) {
-    if (guide) launch_prepare<true>(n_pixels, sum, sum_sq, spp, spp_map, *guide, half, stream);
-    else launch_prepare<false>(n_pixels, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
+                            bool means, void *half, hipStream_t stream) {
+    if (means) { // (a uniform count: the means form has no map)
+        if (guide) launch_prepare<true, true>(n_pixels, sum, sum_sq, spp, nullptr, *guide, half, stream);
+        else launch_prepare<false, true>(n_pixels, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
+    } else if (guide) launch_prepare<true, false>(n_pixels, sum, sum_sq, spp, spp_map, *guide, half, stream);
+    else launch_prepare<false, false>(n_pixels, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
 }
 
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,

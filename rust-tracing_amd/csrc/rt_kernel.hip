@@ -1435,6 +1435,43 @@ __global__ void mean_samples_kernel(const KParams P) {
     if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
 }
 
+// mean_samples_kernel with Welford's second moment beside the mean (rt_render_mean_moments_device): its thread-to-pixel mapping and
+// addressing, its recurrence for m word for word — so P.out gets mean_samples_kernel's bits — and per channel M2 = M2 + d * (c - m'),
+// d = c - m the difference before the update and m' the mean after it: the product rounded, then added (no contraction).  d and c - m'
+// have one sign or are zero, so no term is negative.  M2 goes through P.out_sq and starts and continues as the mean does.
+__global__ void mean_moments_samples_kernel(const KParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lt = idx >> 6, p64 = idx & 63u;
+    if (lt >= P.n_local_tiles) return;
+    const int32_t w = P.cam.image_width, h = P.cam.image_height;
+    const int32_t i = (int32_t)(lt % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(lt / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    if (i >= w || j >= h) return;
+    const size_t pixel = (size_t)j * (size_t)w + (size_t)i;
+    double *dst = P.out + pixel * 3u, *dm2 = P.out_sq + pixel * 3u;
+    V3 m = v3(0.0, 0.0, 0.0), q = v3(0.0, 0.0, 0.0);
+    if (P.sample_begin != 0) {
+        m = v3(dst[0], dst[1], dst[2]);
+        q = v3(dm2[0], dm2[1], dm2[2]);
+    }
+    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
+    for (uint32_t s = 0; s < P.n_samples; ++s) {
+        const double n = (double)(P.sample_begin + (int32_t)s + 1);
+        const V3 c = v3(src[0], src[1], src[2]);
+        const V3 d = v3(c.x - m.x, c.y - m.y, c.z - m.z);
+        m.x = m.x + d.x / n;
+        m.y = m.y + d.y / n;
+        m.z = m.z + d.z / n;
+        q.x = q.x + d.x * (c.x - m.x);
+        q.y = q.y + d.y * (c.y - m.y);
+        q.z = q.z + d.z * (c.z - m.z);
+        src += 64u * 3u;
+    }
+    dst[0] = m.x; dst[1] = m.y; dst[2] = m.z;
+    dm2[0] = q.x; dm2[1] = q.y; dm2[2] = q.z;
+    if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
+}
+
 // sum_samples_kernel for views mode: local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view, whose frame starts
 // 3 * w * h doubles behind the previous view's.  One thread per (local tile, pixel of the tile); padding pixels of edge tiles are not written.
 __global__ void sum_view_samples_kernel(const KParams P) {
@@ -1820,6 +1857,9 @@ void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream) {
 }
 void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(mean_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
+void launch_mean_moments_samples(const KParams &K, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(mean_moments_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
 }
 void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_view_samples_kernel, dim3(grid), dim3(256), 0, stream, K);

@@ -10,6 +10,9 @@
 //   it is written; with --adaptive it takes the adaptive sums and the spp map),
 //   --denoise-albedo [--denoise-albedo-sigma X] (implies --denoise: the albedo-guided filter, with a first-hit albedo frame rendered
 //   from the scene's albedo scene over the same seed and samples),
+//   -l --live-denoise [--denoise-iters K] [--denoise-sigma X] (every live frame through the filter, from the running mean and Welford's
+//   M2: include/rt_amd.h "live denoise"), --live-denoise-albedo [--denoise-albedo-sigma X] (implies --live-denoise: the guided filter,
+//   with a running albedo mean folded over the same samples),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 #include "image_io.hpp"
 #include "renderer.hpp"
@@ -33,6 +36,10 @@ static void usage(const char *argv0) {
             "                         the frame divided by it; X > 0, default 0.5: the albedo difference at which a tap's weight is 0)\n"
             "          [-l|--live [--live-spp K] -o OUTPUT]   (one GPU: the reference's live mode without the window — a running mean refined K samples\n"
             "                         per pixel at a time, default 1, over spp - 1 samples; the last frame goes to OUTPUT.png)\n"
+            "          [--live-denoise [--denoise-iters K] [--denoise-sigma X]]   (with -l/--live: every frame shown is the à-trous filter's, from the running\n"
+            "                         mean and a running second moment; the mean itself is not touched)\n"
+            "          [--live-denoise-albedo [--denoise-albedo-sigma X]]   (implies --live-denoise: the albedo-guided filter, with a running first-hit albedo\n"
+            "                         mean over the same samples)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
             "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
@@ -88,6 +95,8 @@ int main(int argc, char **argv) {
             ro.denoise_albedo_sigma = atof(need("--denoise-albedo-sigma")); albedo_knob_given = true;
             if (!(ro.denoise_albedo_sigma > 0.0)) { fprintf(stderr, "--denoise-albedo-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--live-denoise") ro.live_denoise = true;
+        else if (a == "--live-denoise-albedo") ro.live_denoise = ro.live_denoise_albedo = true;
         else if (a == "--orbit") {
             ro.orbit = atoi(need("--orbit"));
             if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
@@ -116,12 +125,16 @@ int main(int argc, char **argv) {
                         "second moment), --gpus > 1 (the gather moves sums only), --progressive or --orbit\n");
         return 2;
     }
-    if (albedo_knob_given && !ro.denoise_albedo) {
-        fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo\n");
+    if (ro.live_denoise && !live) {
+        fprintf(stderr, "--live-denoise and --live-denoise-albedo filter the frames of --live: they need -l/--live\n");
         return 2;
     }
-    if (denoise_knob_given && !ro.denoise) {
-        fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise\n");
+    if (albedo_knob_given && !ro.denoise_albedo && !ro.live_denoise_albedo) {
+        fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo (with --live: --live-denoise-albedo)\n");
+        return 2;
+    }
+    if (denoise_knob_given && !ro.denoise && !ro.live_denoise) {
+        fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise (with --live: --live-denoise)\n");
         return 2;
     }
     if (live_spp_given && !live) {

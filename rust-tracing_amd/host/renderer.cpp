@@ -168,6 +168,32 @@ std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double 
     });
 }
 
+// the params of the two filters from the options (the plain filter's are the guided one's first fields)
+static rt_denoise_albedo_params filter_params(const char *who, const RenderOptions &opt) {
+    rt_denoise_albedo_params dp;
+    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
+    return dp;
+}
+static rt_denoise_params plain_params(const rt_denoise_albedo_params &dp) {
+    return rt_denoise_params{(uint32_t)sizeof(rt_denoise_params), dp.iterations, dp.sigma, dp.eps};
+}
+
+std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const RenderOptions &opt) {
+    const rt_denoise_params dp = plain_params(filter_params("denoise_mean", opt));
+    return run_denoise("denoise_mean", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_mean_device(width, height, d_mean, d_m2, samples, &dp, d_out, d_rgba8, d_work, nullptr);
+    });
+}
+
+std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                         const double *d_albedo_mean, const RenderOptions &opt) {
+    const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean", opt);
+    return run_denoise("denoise_albedo_mean", width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_albedo_mean_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &dp, d_out, d_rgba8, d_work, nullptr);
+    });
+}
+
 // The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
 // every pixel with the render's seed under `cam` with a white background, into a new device frame of sums (the caller frees it).
 static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo) {
@@ -289,19 +315,57 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const int last = cam.samples_per_pixel - 1; // `if num_samples < spp` (src/renderer.rs:104): divisors 1 .. spp - 1
     if (last <= 0) return frame;
     const int pass = opt.live_spp > 0 ? opt.live_spp : 1;
-    rt_scene *scene = nullptr;
-    void *d_mean = nullptr, *d_rgba8 = nullptr;
-    auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_scene_destroy(scene); };
+    // opt.live_denoise: the pass keeps M2 beside the mean, and the frame shown is the filter's, written to d_shown and its bytes to
+    // d_rgba8: the running frames (d_mean, d_m2, and the guided filter's running albedo mean d_alb) are the filter's inputs only
+    const bool denoised = opt.live_denoise || opt.live_denoise_albedo, guided = opt.live_denoise_albedo;
+    const int32_t w = cam.image_width, h = cam.image_height;
+    rt_scene *scene = nullptr, *albedo_scene = nullptr;
+    void *d_mean = nullptr, *d_rgba8 = nullptr, *d_m2 = nullptr, *d_alb = nullptr, *d_shown = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() {
+        rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
+        rt_device_free(0, d_work);
+        rt_scene_destroy(scene); rt_scene_destroy(albedo_scene);
+    };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("live_render: " + msg); } };
+    const int64_t frame_bytes = n_pix * 3 * (int64_t)sizeof(double);
     check(rt_scene_create(&desc, 0, &scene));
-    check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
+    check(rt_device_malloc(0, frame_bytes, &d_mean));
     check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+    rt_denoise_albedo_params dp{};
+    rt_camera white = cam;
+    white.background = rt_vec3{1.0, 1.0, 1.0};
+    if (denoised) {
+        try { dp = filter_params("live_render", opt); } catch (...) { cleanup(); throw; }
+        const int64_t work = guided ? rt_denoise_albedo_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
+        if (work < 0) { cleanup(); throw std::runtime_error("live_render: no denoise workspace for a frame of this size"); }
+        check(rt_device_malloc(0, frame_bytes, &d_m2));
+        check(rt_device_malloc(0, frame_bytes, &d_shown));
+        check(rt_device_malloc(0, work, &d_work));
+        if (guided) {
+            check(rt_scene_create_albedo(&desc, 0, nullptr, &albedo_scene));
+            check(rt_device_malloc(0, frame_bytes, &d_alb));
+        }
+    }
+    const rt_denoise_params plain = plain_params(dp);
     for (int begin = 0; begin < last; begin += pass) {
         const int end = begin + pass < last ? begin + pass : last;
         rt_render_params p{};
         p.seed = opt.seed; p.sample_begin = begin; p.sample_end = end; p.max_depth = cam.max_depth;
         p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
-        check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+        if (!denoised) {
+            check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+        } else {
+            check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
+            if (guided) {
+                check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
+                check(rt_denoise_albedo_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
+                                                    static_cast<const double *>(d_alb), &dp, static_cast<double *>(d_shown),
+                                                    static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+            } else {
+                check(rt_denoise_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &plain,
+                                             static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+            }
+        }
         check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
         if (on_frame) {
             try { on_frame(frame, end); } catch (...) { cleanup(); throw; }

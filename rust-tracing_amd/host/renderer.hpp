@@ -42,6 +42,14 @@ struct RenderOptions {
     // camera's spp) under the camera with background (1, 1, 1), and hands that frame to rt_denoise_albedo_device.
     bool denoise_albedo = false;
     double denoise_albedo_sigma = 0.5;
+    // live_render: every displayed frame goes through the filter (include/rt_amd.h "live denoise").  A pass is then
+    // rt_render_mean_moments_device — the running mean with Welford's M2 beside it — and rt_denoise_mean_device with denoise_iters /
+    // denoise_sigma into a separate display frame: the running mean and M2 are never overwritten by the filter.
+    bool live_denoise = false;
+    // with `live_denoise`: the albedo-guided filter (rt_denoise_albedo_mean_device, denoise_albedo_sigma).  Each pass also folds the
+    // albedo scene's samples of the same range, under the camera with background (1, 1, 1), into a running albedo mean
+    // (rt_render_mean_device).
+    bool live_denoise_albedo = false;
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -55,6 +63,13 @@ std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum,
 // scene; opt.denoise_albedo_sigma is the filter's sigma_albedo.
 std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                                     const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt = {});
+
+// rt_denoise_mean_device and rt_denoise_albedo_mean_device likewise, over DEVICE frames of running means and of M2 after `samples`
+// samples of every pixel (rt_render_mean_moments_device) and, guided, the albedo scene's running mean (rt_render_mean_device).
+std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                  const RenderOptions &opt = {});
+std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                         const double *d_albedo_mean, const RenderOptions &opt = {});
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.
@@ -71,6 +86,7 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp);
 // It ends as the reference's loop does: that loop starts at num_samples = 1 and draws only `if num_samples < spp` (:104), so its
 // divisors are 1 .. spp - 1 and the frame it settles on holds spp - 1 samples, not spp.  Returns the last frame (all (0, 0, 0, 0xff),
 // the reference's zeroed raw_pixels, when spp <= 1 leaves nothing to draw).  Throws std::runtime_error on a GPU library error.
+// With opt.live_denoise the frame handed over is the filtered one (above); the loop still settles on spp - 1 samples.
 std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt = {},
                                  const std::function<void(const std::vector<uint8_t> &, int)> &on_frame = nullptr);
 
