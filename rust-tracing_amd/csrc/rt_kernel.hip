@@ -230,16 +230,21 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     const bool defer = DEFER && P.defer_instances != 0;
     uint32_t deferred = 0;
     constexpr uint32_t SEQ_JUMP = 0x80000000u; // in seq_pc while a tree is walked: see the look-ahead where a query starts
+    // A leaf's reference is NOT decoded here, where every lane of every box round would pay for it: a lane that goes on to a leaf keeps
+    // the packed reference in prim_cur and its primitive stage takes it apart (index, count) when the lane's turn comes.  While a lane
+    // walks boxes, pops an entry or goes to shade, prim_cur holds nothing anyone reads, and while it waits for a primitive stage `node`
+    // does not (what ends the leaf pops the stack, or the tree is done): so neither is selected, both are simply written.
     auto o_next = [&](bool have, uint32_t ref) {
-        uint32_t new_stage, new_node = node, new_cur = prim_cur, new_end = prim_end;
+        uint32_t new_stage, new_node = node;
+        prim_cur = ref;
         if (have) {
             // OrderedKind INNER / SPHERES / QUADS / INSTANCE = 0 / 1 / 2 / 3 = Stage ST_BOX / ST_SPHERE / ST_QUAD / ST_OTHER
-            const uint32_t kind = ref >> OREF_KIND_SHIFT, index = ref & OREF_INDEX_MASK;
-            const bool leaf = kind == OK_SPHERES || kind == OK_QUADS;
+            const uint32_t kind = ref >> OREF_KIND_SHIFT;
             new_stage = kind;
-            new_node = leaf ? node : (kind == OK_INNER ? (index | W_FULL) : index); // (an inner record is come to with all four children to look at)
-            new_cur = leaf ? index : prim_cur;
-            new_end = leaf ? index + ((ref >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u : prim_end;
+            // (an inner record — kind bits 0: the reference is its index — is come to with all four children to look at; an instance's
+            // index goes to ST_OTHER bare; a leaf's lane never reads what lands here)
+            if constexpr (HAS_FRAMES) new_node = kind == OK_INNER ? (ref | W_FULL) : (ref & OREF_INDEX_MASK);
+            else new_node = ref | W_FULL;
         } else if (sp != 0) { // the last child set aside
             sp--;
             const uint32_t e = stack[sp * THREADS];
@@ -284,7 +289,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 }
             }
         }
-        stage = new_stage; node = new_node; prim_cur = new_cur; prim_end = new_end;
+        stage = new_stage; node = new_node;
     };
     // ties (ordered walk): two primitives hit at exactly the same t.  The reference scans in a fixed order and keeps the
     // first unless a later one passes its interval test: Sphere::hit wants t < closest (Interval::surrounds,
@@ -693,7 +698,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             // ---------------- Sphere::hit (src/sphere.rs:58-83), one sphere per round ----------------
             if (stage == ST_SPHERE) {
                 if (COUNT) cn.sphere_tests++;
-                const uint32_t q = prim_cur;
+                // (ordered walk: prim_cur is the leaf's packed reference — o_next —, taken apart here: the sphere's index now, the count below)
+                const uint32_t q = ORDERED ? (prim_cur & OREF_INDEX_MASK) : prim_cur;
                 const Sphere *s = &sphere_tab[q];
                 V3 center = ld3(s->center);
                 if ((s->seq_moving & 1u)) center = center + ld3(s->center_vec) * time;
@@ -724,15 +730,23 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         else mode |= 0x100u;
                     }
                 }
-                prim_cur = q + 1;
-                if (prim_cur >= prim_end) {
-                    if constexpr (ORDERED) o_next(false, 0u);
-                    else stage = node >= n_nodes ? ST_SHADE : ST_BOX;
+                if constexpr (ORDERED) {
+                    // one sphere per round: a leaf of several comes back with its reference stepped in place — index + 1, and one less in
+                    // the count field (which holds the count less one: 0 is the leaf's last sphere).  One register while the lane waits;
+                    // unpacking on first entry would want two and a flag.
+                    if ((prim_cur & (OREF_COUNT_MASK << OREF_COUNT_SHIFT)) == 0u) o_next(false, 0u);
+                    else prim_cur += 1u - (1u << OREF_COUNT_SHIFT);
+                } else {
+                    prim_cur = q + 1;
+                    if (prim_cur >= prim_end) stage = node >= n_nodes ? ST_SHADE : ST_BOX;
                 }
             }
         } else if (HAS_QUADS && run == ST_QUAD) {
             // ---------------- Quad::hit (src/quad.rs:96-127): all quads of the leaf (HittableList order) ----------------
             if (stage == ST_QUAD) {
+                // (ordered walk: prim_cur is the leaf's packed reference — o_next —, taken apart here, once: the whole leaf is this round's)
+                const uint32_t q_cur = ORDERED ? (prim_cur & OREF_INDEX_MASK) : prim_cur;
+                const uint32_t q_end = ORDERED ? q_cur + ((prim_cur >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u : prim_end;
                 auto quad_hit = [&](uint32_t q, bool inside_known) { // inside_known: the filter has shown alpha, beta in [0, 1] for this t
                     if (COUNT) cn.quad_tests++;
                     const Quad *qd = &quad_tab[q];
@@ -764,11 +778,11 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     // times).  A quad the filter drops is one the exact test would reject whatever the interval has shrunk to by then.
                     if (P.lds_off_qfilt != 0xffffffffu) { // (wave-uniform)
                         filtered = true;
-                        const uint32_t count = prim_end - prim_cur;
+                        const uint32_t count = q_end - q_cur;
                         uint32_t keep = 1u; // bits 0-7: survivors; bits 8-15: of them, those whose alpha and beta are known to be inside
                         if (count > 1u) {
                             const QRay32 qr = make_qray32(o, d);
-                            const QFiltPair *rec = reinterpret_cast<const QFiltPair *>(lds_raw + P.lds_off_qfilt) + prim_cur;
+                            const QFiltPair *rec = reinterpret_cast<const QFiltPair *>(lds_raw + P.lds_off_qfilt) + q_cur;
                             keep = 0u;
 #pragma unroll 1
                             for (uint32_t k = 0; k < count; k += 2u) keep |= quad_pair_keep(rec + k, qr, tmin32, tmax32) << k;
@@ -778,15 +792,14 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                             const uint32_t k = (uint32_t)__builtin_ctz(keep);
                             const bool inside_known = (keep >> (8u + k) & 1u) != 0u;
                             keep &= keep - 1u;
-                            quad_hit(prim_cur + k, inside_known);
+                            quad_hit(q_cur + k, inside_known);
                         }
                     }
                 }
                 if (!filtered)
-                    for (uint32_t q = prim_cur; q < prim_end; ++q) quad_hit(q, false);
-                prim_cur = prim_end;
+                    for (uint32_t q = q_cur; q < q_end; ++q) quad_hit(q, false);
                 if constexpr (ORDERED) o_next(false, 0u);
-                else stage = node >= n_nodes ? ST_SHADE : ST_BOX;
+                else { prim_cur = prim_end; stage = node >= n_nodes ? ST_SHADE : ST_BOX; }
             }
         } else if (HAS_OTHER && run == ST_OTHER) {
             // ---------------- frame changes and ConstantMedium steps ----------------
@@ -847,8 +860,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         stage = ST_BOX;
                         if (start != 0u) {
                             stage = start >> OREF_KIND_SHIFT; // (OrderedKind SPHERES / QUADS = Stage ST_SPHERE / ST_QUAD)
-                            prim_cur = start & OREF_INDEX_MASK;
-                            prim_end = prim_cur + ((start >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u;
+                            prim_cur = start; // (the packed reference, as o_next hands it over)
                         }
                     }
                 }
@@ -1274,8 +1286,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         else stack[0] = (StackT)(rest < (1u << OREF_KIND_SHIFT) ? rest : (first_node | (P.o_start_slot ? SKIP_CHILD1 : SKIP_CHILD0)));
                         sp = 1;
                     }
-                    prim_cur = P.o_start_prim;
-                    prim_end = P.o_start_end;
+                    // (the leaf's packed reference, as o_next hands it over, put together from the kernel arguments: scalar work)
+                    prim_cur = (P.o_start_stage << OREF_KIND_SHIFT) | ((P.o_start_end - P.o_start_prim - 1u) << OREF_COUNT_SHIFT) | P.o_start_prim;
                     stage = P.o_start_stage;
                 }
             }
