@@ -630,6 +630,54 @@ int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d
                                   double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace,
                                   void *hip_stream);
 
+/* ---- spatial variance: the means-form filters on frames of too few samples for M2 (opt-in; nothing above changes) ---------------------
+ * The means forms above call a pixel valid only from two samples on, so the first live frame — and every frame of a caller who restarts
+ * the mean on each camera move — leaves them unfiltered.  These calls estimate the variance of such a frame from the spread of the
+ * neighbouring pixels' values instead of from each pixel's own samples (SVGF's fallback for pixels with a short history).
+ *
+ * rt_denoise_mean_spatial_device and rt_denoise_albedo_mean_spatial_device take the means forms' arguments and an
+ * rt_denoise_spatial_params (NULL: defaults).  With samples >= spatial_below the call IS rt_denoise_mean_device /
+ * rt_denoise_albedo_mean_device: the same kernels, bit for bit, and d_m2 is required.  With samples < spatial_below the spatial Prepare
+ * below runs in the means forms' place; d_m2 is not read and may be NULL.  spatial_below = 1 never takes the spatial route.  The contract
+ * is the means forms': enqueued on hip_stream, not synchronised, nothing allocated; the workspaces are rt_denoise_workspace_bytes and
+ * rt_denoise_albedo_workspace_bytes.
+ *
+ * Normative definition.  The arithmetic is that of "denoise": f64 throughout, every operation rounded on its own (no FMA, IEEE
+ * division), max(a, b) = (b > a ? b : a).  m, a are the pixel's entries of d_mean, d_albedo_mean; R = window_radius.
+ *   Prepare.   p is VALID iff every m_c (guided: and every a_c) is finite; d_m2 is not read.
+ *              C0 = m;  guided:  d_c = max(a_c, albedo_floor),  C0_c = m_c / d_c  (the guide written is the un-floored a, as above).
+ *              A pixel that is not valid keeps C = m and V = -1, is written to the output unchanged and is never a tap or a window member.
+ *              For a valid p the window is q = p + (dx, dy), dy = -R..R outer, dx = -R..R inner, over the in-frame valid pixels; p itself
+ *              is a member.  cnt is the number of members, as a double.  Per channel, in that order:
+ *                   s1_c = +0.0;  s1_c = s1_c + C0_c(q)  for every member;          mu_c = s1_c / cnt
+ *                   s2_c = +0.0;  t = C0_c(q) - mu_c;  s2_c = s2_c + t * t          (the product rounded, then added)
+ *                   v_c = s2_c / (cnt - 1)  where cnt >= 2, else +0.0
+ *              V0 = max(max(v_r, v_g), v_b).  Nothing is divided by n: the window's values already are n-sample means, so their spread
+ *              estimates the variance of a mean (plus the signal's own variation).  V0 >= 0 by construction.  On a window whose
+ *              members all equal c it is +0.0 exactly wherever the in-order sums 2c, 3c, .. cnt * c are exact — any c of at most 47
+ *              significant bits, the window having at most 49 members — since then mu = c; for any other c, mu may miss c by rounding
+ *              and V0 is a residue of at most 2 * (cnt * 2^-52 * |c|)^2.
+ *   Iterations and Output: those of rt_denoise_device / rt_denoise_albedo_device, unchanged.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in the means forms' order with the new checks behind `samples`:
+ * everything the means forms refuse (a null d_m2 only as below); an rt_denoise_spatial_params.struct_size this library does not know;
+ * spatial_below < 1; window_radius outside 1..3; a null d_m2 when samples >= spatial_below. */
+typedef struct rt_denoise_spatial_params {
+    uint32_t struct_size;   /* sizeof(rt_denoise_spatial_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t spatial_below;  /* the spatial estimate serves frames of fewer samples than this (default 2: where M2 has nothing), >= 1 */
+    int32_t window_radius;  /* R, 1..3 (default 1): the window is (2R + 1) x (2R + 1) pixels */
+} rt_denoise_spatial_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_denoise_spatial_params_init_sized(rt_denoise_spatial_params *params, uint32_t struct_size);
+int rt_denoise_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2 /* or NULL, see above */,
+                                   int32_t samples, const rt_denoise_spatial_params *spatial /* NULL: defaults */,
+                                   const rt_denoise_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
+                                   uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int rt_denoise_albedo_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2 /* or NULL, see above */,
+                                          int32_t samples, const double *d_albedo_mean /* 3*w*h */,
+                                          const rt_denoise_spatial_params *spatial /* NULL: defaults */,
+                                          const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
+                                          uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

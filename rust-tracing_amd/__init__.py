@@ -249,6 +249,22 @@ def denoise_albedo_params(**kw) -> "DenoiseAlbedoParams":
     return d
 
 
+class DenoiseSpatialParams(C.Structure):
+    """rt_denoise_spatial_params (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("spatial_below", C.c_int32), ("window_radius", C.c_int32)]
+
+
+def denoise_spatial_params(**kw) -> "DenoiseSpatialParams":
+    """rt_denoise_spatial_params_init_sized, then the given fields (spatial_below=, window_radius=)."""
+    d = DenoiseSpatialParams()
+    _check(amd_lib().rt_denoise_spatial_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_spatial_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(DenoiseSpatialParams._fields_):
+            raise TypeError(f"rt_denoise_spatial_params has no field {k}")
+        setattr(d, k, v)
+    return d
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -322,6 +338,11 @@ RT_AMD_SYMBOLS = {
                                          C.c_void_p, C.c_void_p]),
     "rt_denoise_albedo_mean_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_spatial_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_denoise_mean_spatial_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_albedo_mean_spatial_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -1169,6 +1190,71 @@ def denoise_albedo_mean(mean, m2, samples, albedo_mean, *, rgba8=False, device=0
     if albedo_mean is None:
         raise RtError("denoise_albedo_mean: `albedo_mean` is required")
     return _denoise_means("denoise_albedo_mean", mean, m2, samples, albedo_mean, rgba8, device, kw)
+
+
+def denoise_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
+                                d_rgba8_ptr: int = 0, spatial: "DenoiseSpatialParams | None" = None, params: "DenoiseParams | None" = None,
+                                stream: int = 0):
+    """rt_denoise_mean_spatial_device: denoise_mean_device that, for frames of fewer than spatial.spatial_below samples (default 2),
+    takes the variance from the spread of the neighbouring pixels' means; `d_m2_ptr` may then be 0.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
+                                                    C.byref(spatial) if spatial is not None else None,
+                                                    C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                    C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_mean_spatial_device")
+
+
+def denoise_albedo_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_mean_out_ptr: int,
+                                       d_workspace_ptr: int, *, d_rgba8_ptr: int = 0, spatial: "DenoiseSpatialParams | None" = None,
+                                       params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
+    """rt_denoise_albedo_mean_spatial_device: denoise_mean_spatial_device with a device frame of albedo means beside the two;
+    `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_albedo_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
+                                                           C.c_void_p(d_albedo_mean_ptr), C.byref(spatial) if spatial is not None else None,
+                                                           C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                           C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_albedo_mean_spatial_device")
+
+
+def _denoise_means_spatial(who, mean, m2, samples, albedo_mean, rgba8, device, kw):
+    """denoise_mean_spatial and denoise_albedo_mean_spatial: upload, run, download (m2 None: a null d_m2)"""
+    import numpy as np
+    spatial = denoise_spatial_params(**{k: kw.pop(k) for k in ("spatial_below", "window_radius") if k in kw})
+    given = [a for a in (mean, m2, albedo_mean) if a is not None]
+    frames = [np.array(a, dtype=np.float64, order="C") for a in given]  # (copies)
+    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
+    h, w = frames[0].shape[:2]
+    params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_in = [torch.from_numpy(a).cuda() for a in frames]
+        d_mean, d_m2 = d_in[0].data_ptr(), (d_in[1].data_ptr() if m2 is not None else 0)
+        d_out = torch.empty_like(d_in[0])
+        d_ws = torch.empty(denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8,
+                           device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, spatial=spatial, params=params, stream=torch.cuda.current_stream().cuda_stream)
+        if albedo_mean is None:
+            denoise_mean_spatial_device(w, h, d_mean, d_m2, int(samples), d_out.data_ptr(), d_ws.data_ptr(), **common)
+        else:
+            denoise_albedo_mean_spatial_device(w, h, d_mean, d_m2, int(samples), d_in[-1].data_ptr(), d_out.data_ptr(), d_ws.data_ptr(), **common)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def denoise_mean_spatial(mean, m2, samples, *, rgba8=False, device=0, **kw):
+    """denoise_mean through rt_denoise_mean_spatial_device: `m2` may be None where samples < spatial_below; spatial_below= and
+    window_radius= go to denoise_spatial_params, every other keyword to denoise_params."""
+    return _denoise_means_spatial("denoise_mean_spatial", mean, m2, samples, None, rgba8, device, dict(kw))
+
+
+def denoise_albedo_mean_spatial(mean, m2, samples, albedo_mean, *, rgba8=False, device=0, **kw):
+    """denoise_mean_spatial with an (h, w, 3) frame of albedo means beside the two: rt_denoise_albedo_mean_spatial_device."""
+    if albedo_mean is None:
+        raise RtError("denoise_albedo_mean_spatial: `albedo_mean` is required")
+    return _denoise_means_spatial("denoise_albedo_mean_spatial", mean, m2, samples, albedo_mean, rgba8, device, dict(kw))
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

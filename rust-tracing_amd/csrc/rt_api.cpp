@@ -1560,6 +1560,12 @@ int render_moments(rt_scene *s, const rt_camera *camera, const rt_render_params 
 // the two params structs of the denoisers (rt_denoise_params, and rt_denoise_albedo_params = its fields and two more): defaults, the
 // struct sizes this library knows, the body of *_params_init_sized.  (Templates: C++ linkage inside this file's extern "C".)
 extern "C++" {
+inline void denoise_defaults(rt_denoise_spatial_params &d) { // (DESIGN.md section 5 "Spatial variance": the CPU sweep)
+    memset(&d, 0, sizeof d);
+    d.struct_size = (uint32_t)sizeof d;
+    d.spatial_below = 2;
+    d.window_radius = 1;
+}
 template <class P> void denoise_defaults(P &d) {
     memset(&d, 0, sizeof d);
     d.struct_size = (uint32_t)sizeof d;
@@ -1571,7 +1577,10 @@ template <class P> void denoise_defaults(P &d) {
         d.albedo_floor = 1e-3;
     }
 }
-template <class P> bool denoise_size_known(uint32_t size) { return size >= 8 && size <= sizeof(P) && size % 8 == 0; }
+template <class P> bool denoise_size_known(uint32_t size) {
+    if constexpr (std::is_same_v<P, rt_denoise_spatial_params>) return size >= 8 && size <= sizeof(P) && size % 4 == 0; // (its fields are words)
+    else return size >= 8 && size <= sizeof(P) && size % 8 == 0;
+}
 template <class P> int denoise_params_init_sized(P *params, uint32_t struct_size, const char *who) {
     if (!params) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
     if (!denoise_size_known<P>(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_size is not one this library knows");
@@ -1605,23 +1614,40 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 // params (the fields both structs have), or null where their struct_size was not known: that is refused here, in its place among the checks.
 // `form` is the input form: sums and sums of squares with a sample count or map, or (rt_denoise_mean_device, rt_denoise_albedo_mean_device)
 // running means and M2 after `spp` samples of every pixel, the guide's frame a mean as well; the messages name the inputs as the caller does.
+// `spatial` (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device; means form only) is the route choice: with
+// spp < spatial->params.spatial_below the spatial prepare runs in the elementwise one's place and d_sum_sq (d_m2) is not read and may be
+// null; otherwise the call is the means form's, launch for launch.  Its checks sit behind the sample count's and before the filter's params.
 enum class DenoiseInput { Sums, Means };
+struct SpatialRoute {
+    rt_denoise_spatial_params params;
+    bool known; // its struct_size is one this library knows
+};
 int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
                 const int32_t *d_spp, DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
-                void *hip_stream) {
+                void *hip_stream, const SpatialRoute *spatial = nullptr) {
     const std::string w(who);
     const bool means = form == DenoiseInput::Means;
     const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum";
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
     if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
-    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
+    if (!d_sum_sq && !spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
     if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
     if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
     if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
     if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
     if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
     if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    bool spatial_route = false;
+    if (spatial) {
+        const rt_denoise_spatial_params &sp = spatial->params;
+        if (!spatial->known) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_spatial_params.struct_size is not one this library knows");
+        if (sp.spatial_below < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spatial_below must be at least 1");
+        if (sp.window_radius < 1 || sp.window_radius > 3) return fail(RT_ERR_INVALID_ARGUMENT, w + ": window_radius must be 1..3");
+        spatial_route = spp < sp.spatial_below;
+        if (!spatial_route && !d_sum_sq)
+            return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null (it is read when samples >= spatial_below)");
+    }
     if (!d)
         return fail(RT_ERR_INVALID_ARGUMENT, w + (guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
     if (d->iterations < 1 || d->iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
@@ -1630,7 +1656,7 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (guide && (!(guide->sigma_albedo > 0.0) || !std::isfinite(guide->sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
     if (guide && (!(guide->albedo_floor > 0.0) || !std::isfinite(guide->albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
     const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
-    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes) ||
+    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || (d_sum_sq && overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes)) ||
         (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
     if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
@@ -1640,7 +1666,8 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     const size_t region = n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
     char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
     if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
-    launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
+    if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream);
+    else launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
     HIP_TRY(hipGetLastError());
     for (int32_t k = 0; k < d->iterations; ++k) {
         const bool last = k == d->iterations - 1;
@@ -1709,6 +1736,21 @@ int rt_denoise_mean_device(int32_t width, int32_t height, const double *d_mean, 
     const bool known = denoise_params_resolve(params, d);
     return run_denoise("rt_denoise_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, nullptr, known ? &d : nullptr,
                        d_mean_out, d_rgba8, d_workspace, hip_stream);
+}
+
+int rt_denoise_spatial_params_init_sized(rt_denoise_spatial_params *params, uint32_t struct_size) {
+    return denoise_params_init_sized(params, struct_size, "rt_denoise_spatial_params_init_sized");
+}
+
+int rt_denoise_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                   const rt_denoise_spatial_params *spatial, const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8,
+                                   void *d_workspace, void *hip_stream) {
+    rt_denoise_params d;
+    const bool known = denoise_params_resolve(params, d);
+    SpatialRoute route;
+    route.known = denoise_params_resolve(spatial, route.params);
+    return run_denoise("rt_denoise_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, nullptr,
+                       known ? &d : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route);
 }
 
 // ---- albedo scene and the albedo-guided filter (rt_denoise.hip, with a guide) ----
@@ -1807,6 +1849,19 @@ int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d
     DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr}; // (a frame of means: no count, nothing is divided)
     return run_denoise("rt_denoise_albedo_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
                        known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream);
+}
+
+int rt_denoise_albedo_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                          const double *d_albedo_mean, const rt_denoise_spatial_params *spatial, const rt_denoise_albedo_params *params,
+                                          double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_albedo_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr};
+    SpatialRoute route;
+    route.known = denoise_params_resolve(spatial, route.params);
+    return run_denoise("rt_denoise_albedo_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route);
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

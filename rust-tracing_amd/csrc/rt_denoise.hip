@@ -6,7 +6,9 @@
 // well: one more factor per tap; the last Guided iteration multiplies the albedo back in.  What only the guided filter does sits
 // behind `if constexpr (Guided)`, so the plain instantiations hold none of it and the two cannot drift apart.  Prepare has a second
 // compile-time parameter, the input form: sums and sums of squares, or (Means: rt_denoise_mean_device, rt_denoise_albedo_mean_device)
-// the live route's running means and Welford's M2; the iterations do not know which it was.
+// the live route's running means and Welford's M2; the iterations do not know which it was.  A third prepare, a tile kernel, serves
+// frames of so few samples that M2 says nothing (rt_denoise_mean_spatial_device, "spatial variance"): it takes V0 from the spread of the
+// neighbouring pixels' values.
 //
 // Everything is f64 in the header's operation order, each operation rounded on its own (the file is compiled with
 // -ffp-contract=off and without fast-math: no FMA, IEEE division and square root), so a frame equals the numpy restatement in
@@ -95,6 +97,99 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
     }
     out[idx] = make_double4(c[0], c[1], c[2], V);
     if constexpr (Guided) gd.region[idx] = make_double4(a[0], a[1], a[2], 0.0);
+}
+
+// The spatial prepare (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device below their threshold; include/rt_amd.h
+// "spatial variance"): a frame of so few samples that M2 says nothing gets its V0 from the spread of C0 over the valid pixels of the
+// (2R + 1)^2 window around each pixel, C0 = m or, Guided, m / max(a, floor).  It takes the elementwise prepare's place on that route and
+// writes what it writes: (C0, V0) into the first half and, Guided, the guide; d_m2 is not read.  The workgroup stages its tile plus a
+// halo of R pixels, planes apart: (C0 x 3, valid), 38 x 14 x 4 x 8 B = 17 024 B at R = 3; the guided division is done once per staged
+// pixel, and out-of-frame halo pixels are staged as not valid, so the window loops have no bounds test.  A pixel that is not valid is
+// staged with C0 = m, which its own lane writes back.  Each lane then makes the definition's two passes over the staged window, dy
+// outer and dx inner: the sum and the count of the members, then the sum of the squared differences from their mean.  A pixel that
+// is not a member is skipped: nothing is added for it.
+template <int R> struct SpatialTile {
+    static constexpr int PW = DN_TW + 2 * R, PH = DN_TH + 2 * R, PLANE = PH * PW;
+    enum { P_R, P_G, P_B, P_OK, PLANES };
+};
+template <int R, bool Guided>
+__global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int32_t w, int32_t h, int32_t tiles_x, const double *__restrict__ mean,
+                                                                              GuideOf<Guided> gd, double4 *__restrict__ out) {
+    using T = SpatialTile<R>;
+    constexpr int PW = T::PW, PLANE = T::PLANE;
+    __shared__ double staged[T::PLANES * PLANE];
+    const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // a 1-D grid of tiles, row-major
+    const int32_t x0 = tile_x * DN_TW - R, y0 = tile_y * DN_TH - R;
+    for (int k = (int)threadIdx.x; k < PLANE; k += DN_THREADS) {
+        const int ly = k / PW, lx = k - ly * PW;
+        const int32_t gx = x0 + lx, gy = y0 + ly;
+        double c[3] = {0.0, 0.0, 0.0};
+        bool valid = false;
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t g = ((size_t)gy * (size_t)w + (size_t)gx) * 3u;
+            valid = true;
+            for (int ch = 0; ch < 3; ++ch) {
+                c[ch] = mean[g + ch];
+                valid = valid && is_finite(c[ch]);
+            }
+            if constexpr (Guided) {
+                double a[3];
+                for (int ch = 0; ch < 3; ++ch) {
+                    a[ch] = gd.albedo_sum[g + ch];
+                    valid = valid && is_finite(a[ch]);
+                }
+                if (valid)
+                    for (int ch = 0; ch < 3; ++ch) c[ch] = c[ch] / max_ab(a[ch], gd.albedo_floor);
+            }
+        }
+        staged[T::P_R * PLANE + k] = c[0]; staged[T::P_G * PLANE + k] = c[1]; staged[T::P_B * PLANE + k] = c[2];
+        staged[T::P_OK * PLANE + k] = valid ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
+    const int32_t px = tile_x * DN_TW + tx, py = tile_y * DN_TH + ty;
+    if (px >= w || py >= h) return;
+    const int centre = (R + ty) * PW + R + tx;
+    const size_t pixel = (size_t)py * (size_t)w + (size_t)px;
+    double V = -1.0;
+    if (staged[T::P_OK * PLANE + centre] != 0.0) {
+        double cnt = 0.0, s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0}, mu[3];
+#pragma unroll
+        for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) {
+                const int k = centre + dy * PW + dx;
+                if (staged[T::P_OK * PLANE + k] == 0.0) continue;
+                cnt = cnt + 1.0;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) s1[ch] = s1[ch] + staged[ch * PLANE + k];
+            }
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) mu[ch] = s1[ch] / cnt;
+        // (a compiler-only fence: the second pass tests the window's members again.  Without it the first pass's (2R + 1)^2 wave masks
+        // are kept for the second: 106 SGPRs with 10 / 6 of them spilled at R = 3 against 46 / 34 and none with it — DESIGN.md section 5
+        // "Spatial variance" has both tables)
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int dy = -R; dy <= R; ++dy)
+#pragma unroll
+            for (int dx = -R; dx <= R; ++dx) {
+                const int k = centre + dy * PW + dx;
+                if (staged[T::P_OK * PLANE + k] == 0.0) continue;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) {
+                    const double t = staged[ch * PLANE + k] - mu[ch];
+                    s2[ch] = s2[ch] + t * t;
+                }
+            }
+        double v[3] = {0.0, 0.0, 0.0};
+        if (cnt >= 2.0)
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) v[ch] = s2[ch] / (cnt - 1.0);
+        V = max_ab(max_ab(v[0], v[1]), v[2]);
+    }
+    out[pixel] = make_double4(staged[T::P_R * PLANE + centre], staged[T::P_G * PLANE + centre], staged[T::P_B * PLANE + centre], V);
+    if constexpr (Guided) gd.region[pixel] = make_double4(gd.albedo_sum[pixel * 3u + 0u], gd.albedo_sum[pixel * 3u + 1u], gd.albedo_sum[pixel * 3u + 2u], 0.0);
 }
 
 struct Tap { double L, r, g, b, V, ar, ag, ab; }; // (ar, ag, ab: the tap's albedo means; Guided only, not set otherwise)
@@ -277,6 +372,18 @@ void launch_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, i
                        n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
 }
 
+template <int R, bool Guided>
+void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const GuideOf<Guided> &gd, void *half, hipStream_t stream) {
+    const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
+    hipLaunchKernelGGL((denoise_prepare_spatial_kernel<R, Guided>), dim3((unsigned)((int64_t)tiles_x * tiles_y)), dim3(DN_THREADS), 0, stream, w, h,
+                       tiles_x, mean, gd, (double4 *)half);
+}
+template <int R>
+void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const rtk::DenoiseGuide *guide, void *half, hipStream_t stream) {
+    if (guide) launch_prepare_spatial<R, true>(w, h, mean, *guide, half, stream);
+    else launch_prepare_spatial<R, false>(w, h, mean, NoGuide{}, half, stream);
+}
+
 template <bool Guided>
 void launch_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const GuideOf<Guided> &gd, const void *half_in, const DenoiseOut &out,
                    hipStream_t stream) {
@@ -299,6 +406,12 @@ void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *s
         else launch_prepare<false, true>(n_pixels, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
     } else if (guide) launch_prepare<true, false>(n_pixels, sum, sum_sq, spp, spp_map, *guide, half, stream);
     else launch_prepare<false, false>(n_pixels, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
+}
+
+void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream) {
+    if (radius == 1) launch_prepare_spatial<1>(w, h, mean, guide, half, stream);
+    else if (radius == 2) launch_prepare_spatial<2>(w, h, mean, guide, half, stream);
+    else launch_prepare_spatial<3>(w, h, mean, guide, half, stream); // (the caller has checked 1..3)
 }
 
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,

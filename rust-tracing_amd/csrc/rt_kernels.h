@@ -222,6 +222,9 @@ struct DenoiseGuide {
 };
 void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
                             bool means, void *half, hipStream_t stream);
+// the spatial prepare (rt_denoise_mean_spatial_device below its threshold) in launch_denoise_prepare's place: `mean` and, guided,
+// guide->albedo_sum are frames of means; V0 is the spread of C0 over the (2 radius + 1)^2 window, radius 1..3
+void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream);
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
                            void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);

@@ -12,7 +12,9 @@
 //   from the scene's albedo scene over the same seed and samples),
 //   -l --live-denoise [--denoise-iters K] [--denoise-sigma X] (every live frame through the filter, from the running mean and Welford's
 //   M2: include/rt_amd.h "live denoise"), --live-denoise-albedo [--denoise-albedo-sigma X] (implies --live-denoise: the guided filter,
-//   with a running albedo mean folded over the same samples),
+//   with a running albedo mean folded over the same samples), --live-denoise-spatial [N] [--denoise-spatial-radius R] (with
+//   --live-denoise[-albedo]: frames of fewer than N samples, default 2, take their variance from the spread of the neighbouring
+//   pixels over a (2R + 1)^2 window, so the first frame is filtered too: include/rt_amd.h "spatial variance"),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 #include "image_io.hpp"
 #include "renderer.hpp"
@@ -40,6 +42,9 @@ static void usage(const char *argv0) {
             "                         mean and a running second moment; the mean itself is not touched)\n"
             "          [--live-denoise-albedo [--denoise-albedo-sigma X]]   (implies --live-denoise: the albedo-guided filter, with a running first-hit albedo\n"
             "                         mean over the same samples)\n"
+            "          [--live-denoise-spatial [N] [--denoise-spatial-radius R]]   (with --live-denoise or --live-denoise-albedo: frames of fewer than N\n"
+            "                         samples, default 2, take their variance from the neighbouring pixels' spread, so the first frame is filtered too;\n"
+            "                         R from 1 to 3, default 1: the window is (2R + 1) x (2R + 1) pixels)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
             "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
@@ -49,7 +54,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -97,6 +102,15 @@ int main(int argc, char **argv) {
         }
         else if (a == "--live-denoise") ro.live_denoise = true;
         else if (a == "--live-denoise-albedo") ro.live_denoise = ro.live_denoise_albedo = true;
+        else if (a == "--live-denoise-spatial") {
+            ro.live_denoise_spatial = 2; // N is optional: a following word that is a number is N
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') ro.live_denoise_spatial = atoi(argv[++i]);
+            if (ro.live_denoise_spatial < 1) { fprintf(stderr, "--live-denoise-spatial needs a number of samples of at least 1\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--denoise-spatial-radius") {
+            ro.denoise_spatial_radius = atoi(need("--denoise-spatial-radius")); spatial_knob_given = true;
+            if (ro.denoise_spatial_radius < 1 || ro.denoise_spatial_radius > 3) { fprintf(stderr, "--denoise-spatial-radius needs a radius from 1 to 3\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--orbit") {
             ro.orbit = atoi(need("--orbit"));
             if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
@@ -127,6 +141,14 @@ int main(int argc, char **argv) {
     }
     if (ro.live_denoise && !live) {
         fprintf(stderr, "--live-denoise and --live-denoise-albedo filter the frames of --live: they need -l/--live\n");
+        return 2;
+    }
+    if (ro.live_denoise_spatial > 0 && !ro.live_denoise) {
+        fprintf(stderr, "--live-denoise-spatial sets how --live-denoise filters its first frames: it needs --live-denoise or --live-denoise-albedo\n");
+        return 2;
+    }
+    if (spatial_knob_given && ro.live_denoise_spatial == 0) {
+        fprintf(stderr, "--denoise-spatial-radius sets the window of --live-denoise-spatial: it needs --live-denoise-spatial\n");
         return 2;
     }
     if (albedo_knob_given && !ro.denoise_albedo && !ro.live_denoise_albedo) {

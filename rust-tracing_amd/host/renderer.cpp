@@ -194,6 +194,35 @@ std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const do
     });
 }
 
+// the spatial route's params from the options (live_denoise_spatial 0: the library's threshold)
+static rt_denoise_spatial_params spatial_params(const char *who, const RenderOptions &opt) {
+    rt_denoise_spatial_params sp;
+    if (rt_denoise_spatial_params_init_sized(&sp, sizeof sp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
+    if (opt.live_denoise_spatial > 0) sp.spatial_below = opt.live_denoise_spatial;
+    sp.window_radius = opt.denoise_spatial_radius;
+    return sp;
+}
+
+std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                          const RenderOptions &opt) {
+    const rt_denoise_params dp = plain_params(filter_params("denoise_mean_spatial", opt));
+    const rt_denoise_spatial_params sp = spatial_params("denoise_mean_spatial", opt);
+    return run_denoise("denoise_mean_spatial", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_mean_spatial_device(width, height, d_mean, d_m2, samples, &sp, &dp, d_out, d_rgba8, d_work, nullptr);
+    });
+}
+
+std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                                 const double *d_albedo_mean, const RenderOptions &opt) {
+    const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean_spatial", opt);
+    const rt_denoise_spatial_params sp = spatial_params("denoise_albedo_mean_spatial", opt);
+    return run_denoise("denoise_albedo_mean_spatial", width, height, rt_denoise_albedo_workspace_bytes(width, height),
+                       [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+                           return rt_denoise_albedo_mean_spatial_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &sp, &dp, d_out, d_rgba8,
+                                                                        d_work, nullptr);
+                       });
+}
+
 // The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
 // every pixel with the render's seed under `cam` with a white background, into a new device frame of sums (the caller frees it).
 static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo) {
@@ -332,10 +361,15 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     check(rt_device_malloc(0, frame_bytes, &d_mean));
     check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
     rt_denoise_albedo_params dp{};
+    rt_denoise_spatial_params sp{};
+    const bool spatial = opt.live_denoise_spatial > 0; // every pass through the spatial entry points: the first one is filtered too
     rt_camera white = cam;
     white.background = rt_vec3{1.0, 1.0, 1.0};
     if (denoised) {
-        try { dp = filter_params("live_render", opt); } catch (...) { cleanup(); throw; }
+        try {
+            dp = filter_params("live_render", opt);
+            if (spatial) sp = spatial_params("live_render", opt);
+        } catch (...) { cleanup(); throw; }
         const int64_t work = guided ? rt_denoise_albedo_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
         if (work < 0) { cleanup(); throw std::runtime_error("live_render: no denoise workspace for a frame of this size"); }
         check(rt_device_malloc(0, frame_bytes, &d_m2));
@@ -358,12 +392,17 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
             check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
             if (guided) {
                 check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
-                check(rt_denoise_albedo_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
-                                                    static_cast<const double *>(d_alb), &dp, static_cast<double *>(d_shown),
-                                                    static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+                check(spatial ? rt_denoise_albedo_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
+                                                                      static_cast<const double *>(d_alb), &sp, &dp, static_cast<double *>(d_shown),
+                                                                      static_cast<uint8_t *>(d_rgba8), d_work, nullptr)
+                              : rt_denoise_albedo_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
+                                                              static_cast<const double *>(d_alb), &dp, static_cast<double *>(d_shown),
+                                                              static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
             } else {
-                check(rt_denoise_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &plain,
-                                             static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+                check(spatial ? rt_denoise_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &sp,
+                                                               &plain, static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr)
+                              : rt_denoise_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &plain,
+                                                       static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
             }
         }
         check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));

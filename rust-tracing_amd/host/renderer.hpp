@@ -50,6 +50,11 @@ struct RenderOptions {
     // albedo scene's samples of the same range, under the camera with background (1, 1, 1), into a running albedo mean
     // (rt_render_mean_device).
     bool live_denoise_albedo = false;
+    // with `live_denoise`: > 0 sends every pass through rt_denoise_mean_spatial_device / rt_denoise_albedo_mean_spatial_device with
+    // spatial_below = this (include/rt_amd.h "spatial variance"): frames of fewer samples take their variance from the spread of the
+    // neighbouring pixels, so the first pass is shown filtered too.  0: off, the means forms as they are.
+    int live_denoise_spatial = 0;
+    int denoise_spatial_radius = 1; // its window_radius, 1..3
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -71,6 +76,13 @@ std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d
 std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                          const double *d_albedo_mean, const RenderOptions &opt = {});
 
+// rt_denoise_mean_spatial_device and rt_denoise_albedo_mean_spatial_device likewise, with spatial_below = opt.live_denoise_spatial (0:
+// the library's default) and window_radius = opt.denoise_spatial_radius; d_m2 may be null where samples < spatial_below.
+std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                          const RenderOptions &opt = {});
+std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                                 const double *d_albedo_mean, const RenderOptions &opt = {});
+
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.
 // `on_pass(sums, samples_done)`, if given, is called after every progressive pass.
@@ -86,7 +98,8 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp);
 // It ends as the reference's loop does: that loop starts at num_samples = 1 and draws only `if num_samples < spp` (:104), so its
 // divisors are 1 .. spp - 1 and the frame it settles on holds spp - 1 samples, not spp.  Returns the last frame (all (0, 0, 0, 0xff),
 // the reference's zeroed raw_pixels, when spp <= 1 leaves nothing to draw).  Throws std::runtime_error on a GPU library error.
-// With opt.live_denoise the frame handed over is the filtered one (above); the loop still settles on spp - 1 samples.
+// With opt.live_denoise the frame handed over is the filtered one (above); the loop still settles on spp - 1 samples.  With
+// opt.live_denoise_spatial as well, that holds from the first pass on.
 std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt = {},
                                  const std::function<void(const std::vector<uint8_t> &, int)> &on_frame = nullptr);
 
