@@ -678,6 +678,53 @@ int rt_denoise_albedo_mean_spatial_device(int32_t width, int32_t height, const d
                                           const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
                                           uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- views moments: sums and sums of squares per view (opt-in; nothing above changes) ---------------------------------------------------
+ * Views mode renders many small frames of few samples in one launch, and those are the frames that most need the filters above; these
+ * calls give them the second moment the filters read, without giving up the single job space.
+ *
+ * rt_render_views_moments_device is rt_render_views_device with a second buffer: d_sum and d_sum_sq each hold n_views frames of
+ * 3 * w * h doubles, view-major.  Checks, limits and the launch path are rt_render_views_device's.
+ *   d_sum       is, bit for bit, what rt_render_views_device writes.
+ *   d_sum_sq[v] is, bit for bit, what rt_render_moments_device writes as d_sum_sq under (views[v].camera, seed = views[v].seed): per
+ *               channel the in-order sum of each sample's c * c, the product rounded and then added, with no contraction.
+ * params->accumulate continues both buffers; without it neither buffer's previous content is read.  A call that is cut into several
+ * launches gives one launch's bits in both buffers.  Padding pixels of edge tiles are not written, and nothing behind the last view is.
+ * A null d_sum_sq is refused with RT_ERR_INVALID_ARGUMENT (the field named) before any device work: callers who want no squares have
+ * rt_render_views_device.  rt_render_views_moments blocks and downloads; with accumulate set it uploads both buffers first. */
+int rt_render_views_moments_device(const rt_scene *scene, const rt_view *views /* HOST, n_views entries, copied */, int32_t n_views,
+                                   const rt_render_params *params, double *d_sum /* n_views frames of 3*w*h doubles, view-major */,
+                                   double *d_sum_sq /* likewise */, void *hip_stream);
+int rt_render_views_moments(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params,
+                            double *sum /* host */, double *sum_sq /* host */);
+
+/* ---- views denoise: one filter over a stack of frames (opt-in; nothing above changes) ---------------------------------------------------
+ * rt_denoise_device takes one frame per call, K + 1 launches each, and at the sizes views mode serves those launches are what it costs.
+ * rt_denoise_views_device and rt_denoise_albedo_views_device are rt_denoise_device and rt_denoise_albedo_device over n_views frames
+ * in the same K + 1 launches, whatever n_views is.  Every frame pointer is view-major: d_sum, d_sum_sq, d_albedo_sum and d_mean_out
+ * hold n_views frames of 3 * w * h doubles, d_rgba8 n_views frames of 4 * w * h bytes.  spp is uniform (the views share their sample
+ * range: there is no map on this route).  d_workspace is rt_denoise_views_workspace_bytes(w, h, n_views) or
+ * rt_denoise_albedo_views_workspace_bytes(w, h, n_views) bytes, 16-byte aligned: n_views times the single-frame figure, or -1 for what
+ * the call would refuse or what overflows.  Enqueued on hip_stream, not synchronised, nothing allocated.
+ *
+ * Normative.  View v of d_mean_out (and of d_rgba8) is, bit for bit, what the single-frame entry point gives for view v's frames with
+ * the same parameters.  A tap, a halo pixel or a member of the 3 x 3 variance window that lies outside view v's own w x h frame is out
+ * of frame: it is never a pixel of view v - 1 or v + 1, although those lie adjacent in memory.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in the single-frame order with n_views behind the frame size:
+ * everything rt_denoise_device / rt_denoise_albedo_device refuses (spp < 2 always: there is no map); n_views < 1; n_views >
+ * RT_DENOISE_MAX_VIEWS (the view is the second dimension of the launch grid, which carries 65535 at most); d_mean_out overlapping an
+ * input anywhere in the whole n_views extent.  The means forms and the spatial-variance form have no views form: there is no live
+ * views route for them to serve. */
+#define RT_DENOISE_MAX_VIEWS 65535
+int64_t rt_denoise_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views);
+int64_t rt_denoise_albedo_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views);
+int rt_denoise_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                            const rt_denoise_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
+                            uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const double *d_albedo_sum /* n_views x 3*w*h */, int32_t albedo_spp /* >= 1 */,
+                                   const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
+                                   uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -343,6 +343,15 @@ RT_AMD_SYMBOLS = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoise_albedo_mean_spatial_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_render_views_moments_device": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "rt_render_views_moments": (C.c_int, [C.c_void_p, C.POINTER(View), C.c_int32, C.POINTER(RenderParams), C.c_void_p, C.c_void_p]),
+    "rt_denoise_views_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_denoise_albedo_views_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_denoise_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_albedo_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -868,6 +877,32 @@ class DeviceScene:
         _check(amd_lib().rt_render_views_device(self._handle, arr, len(arr), C.byref(params), C.c_void_p(d_out_ptr),
                                                 C.c_void_p(stream)), "rt_render_views_device")
 
+    def render_views_moments(self, params: RenderParams, views, sum=None, sum_sq=None):
+        """rt_render_views_moments: (sum, sum_sq), two (n_views, h, w, 3) float64 arrays from one launch: `sum` is render_views' array,
+        sum_sq[v] what render_moments gives as sum_sq under view v's camera and seed.  With params.accumulate both running arrays are
+        required and continued in place."""
+        import numpy as np
+        arr = _view_array(views)
+        n = len(arr)
+        h, w = (arr[0].camera.image_height, arr[0].camera.image_width) if n else (0, 0)
+        if sum is None and sum_sq is None:
+            if params.accumulate:
+                raise RtError("render_views_moments: params.accumulate adds to running sums: pass them as `sum` and `sum_sq`")
+            sum, sum_sq = np.zeros((n, h, w, 3), dtype=np.float64), np.zeros((n, h, w, 3), dtype=np.float64)
+        for name, a in (("sum", sum), ("sum_sq", sum_sq)):
+            if a is None or a.shape != (n, h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+                raise RtError(f"render_views_moments: `{name}` must be a writable C-contiguous float64 array of shape {(n, h, w, 3)}")
+        _check(amd_lib().rt_render_views_moments(self._handle, arr, n, C.byref(params), C.c_void_p(sum.ctypes.data),
+                                                 C.c_void_p(sum_sq.ctypes.data)), "rt_render_views_moments")
+        return sum, sum_sq
+
+    def render_views_moments_device(self, params: RenderParams, views, d_sum_ptr: int, d_sum_sq_ptr: int, stream: int = 0):
+        """rt_render_views_moments_device: two device buffers of n_views frames of 3 w h doubles, view-major (sums, sums of squares);
+        enqueued on `stream` without synchronising (the view records are copied during the call)."""
+        arr = _view_array(views)
+        _check(amd_lib().rt_render_views_moments_device(self._handle, arr, len(arr), C.byref(params), C.c_void_p(d_sum_ptr),
+                                                        C.c_void_p(d_sum_sq_ptr or None), C.c_void_p(stream)), "rt_render_views_moments_device")
+
     def render_mean(self, params: RenderParams, camera: Camera | None = None, mean=None, rgba8: bool = False):
         """rt_render_mean: the samples of params' range folded into a running mean, m += (c - m) / (s + 1) per sample s (the reference's
         live_render, src/renderer.rs:114).  `mean`: the (h, w, 3) float64 frame to continue — required when params.sample_begin > 0,
@@ -1131,6 +1166,80 @@ def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rg
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
         return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def denoise_views_workspace_bytes(width, height, n_views) -> int:
+    n = int(amd_lib().rt_denoise_views_workspace_bytes(width, height, n_views))
+    if n < 0:
+        raise RtError(f"rt_denoise_views_workspace_bytes: no workspace for {n_views} frames of {width}x{height}")
+    return n
+
+
+def denoise_albedo_views_workspace_bytes(width, height, n_views) -> int:
+    n = int(amd_lib().rt_denoise_albedo_views_workspace_bytes(width, height, n_views))
+    if n < 0:
+        raise RtError(f"rt_denoise_albedo_views_workspace_bytes: no workspace for {n_views} frames of {width}x{height}")
+    return n
+
+
+def denoise_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
+                         d_rgba8_ptr: int = 0, params: "DenoiseParams | None" = None, stream: int = 0):
+    """rt_denoise_views_device: denoise_device over a stack of n_views frames in one set of launches; every buffer is view-major
+    (n_views frames of 3 w h doubles; d_rgba8_ptr, if not 0, n_views frames of 4 w h bytes), `spp` is uniform, `d_workspace_ptr`:
+    denoise_views_workspace_bytes(w, h, n_views) device bytes.  View v equals denoise_device on view v's frames.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
+                                             C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                             C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_views_device")
+
+
+def denoise_albedo_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int,
+                                d_mean_out_ptr: int, d_workspace_ptr: int, *, d_rgba8_ptr: int = 0,
+                                params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
+    """rt_denoise_albedo_views_device: denoise_albedo_device over a stack of n_views frames in one set of launches, the albedo sums
+    view-major as well; `d_workspace_ptr`: denoise_albedo_views_workspace_bytes(w, h, n_views) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_albedo_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
+                                                    C.c_void_p(d_albedo_sum_ptr), albedo_spp, C.byref(params) if params is not None else None,
+                                                    C.c_void_p(d_mean_out_ptr), C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr),
+                                                    C.c_void_p(stream)), "rt_denoise_albedo_views_device")
+
+
+def _denoise_views(who, sum, sum_sq, spp, albedo_sum, albedo_spp, rgba8, device, kw):
+    import numpy as np
+    guided = albedo_sum is not None
+    frames = [np.ascontiguousarray(a, dtype=np.float64) for a in ((sum, sum_sq, albedo_sum) if guided else (sum, sum_sq))]
+    if frames[0].ndim != 4 or frames[0].shape[3] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError(f"{who}: the frames must be (n_views, h, w, 3) arrays of one shape")
+    n, h, w = frames[0].shape[:3]
+    params = denoise_albedo_params(**kw) if guided else denoise_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        dev = [torch.from_numpy(a).cuda() for a in frames]
+        d_out = torch.empty_like(dev[0])
+        ws_bytes = denoise_albedo_views_workspace_bytes(w, h, n) if guided else denoise_views_workspace_bytes(w, h, n)
+        d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((n, h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+        if guided:
+            denoise_albedo_views_device(w, h, n, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), dev[2].data_ptr(), int(albedo_spp),
+                                        d_out.data_ptr(), d_ws.data_ptr(), **common)
+        else:
+            denoise_views_device(w, h, n, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(), **common)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def denoise_views(sum, sum_sq, spp, *, rgba8=False, device=0, **kw):
+    """Uploads (n_views, h, w, 3) stacks of sums and sums of squares (what render_views_moments returns), runs rt_denoise_views_device
+    with denoise_params(**kw) and downloads: the (n_views, h, w, 3) float64 filtered means, or (means, (n_views, h, w, 4) uint8) with rgba8."""
+    return _denoise_views("denoise_views", sum, sum_sq, spp, None, 0, rgba8, device, kw)
+
+
+def denoise_albedo_views(sum, sum_sq, spp, albedo_sum, albedo_spp, *, rgba8=False, device=0, **kw):
+    """denoise_views with an (n_views, h, w, 3) stack of albedo sums (render_views of the albedo scene): rt_denoise_albedo_views_device
+    with denoise_albedo_params(**kw)."""
+    return _denoise_views("denoise_albedo_views", sum, sum_sq, spp, albedo_sum, albedo_spp, rgba8, device, kw)
 
 
 def denoise_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,

@@ -211,6 +211,7 @@ struct PixelList {
 struct ViewTable {
     const ViewRec *recs; // host
     int64_t n;
+    double *d_sum_sq = nullptr; // rt_render_views_moments_device: one frame of sums of squares per view beside the sums, or null
 };
 
 // Live refinement (rt_render_mean_device): the dense render with `d_out` a frame of running means.  Each launch's samples are folded
@@ -442,6 +443,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     if (mean) K.out_sq = mean->d_m2;
     if (views) {
         K.views = ws.views; K.tiles_per_view = (uint32_t)tiles_per_view; K.inv_tiles_per_view = 1.0 / (double)tiles_per_view;
+        K.out_sq = views->d_sum_sq; // (read by sum_view_moments_samples_kernel only)
     }
     K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = lds_image_bytes_for(scene, lds);
     K.lds_off_node_b = scene->lds_off_node_b;
@@ -526,7 +528,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
             K.mean_rgba8 = sb + ns >= p.sample_end ? mean->d_rgba8 : nullptr; // (the call's last launch: the frame the caller shows)
             if (mean->d_m2) launch_mean_moments_samples(K, sum_grid, s);
             else launch_mean_samples(K, sum_grid, s);
-        } else if (views) launch_sum_view_samples(K, sum_grid, s);
+        } else if (views && views->d_sum_sq) launch_sum_view_moments_samples(K, sum_grid, s);
+        else if (views) launch_sum_view_samples(K, sum_grid, s);
         else if (list) launch_sum_listed_samples(K, sum_grid, s);
         else launch_sum_samples(K, sum_grid, s);
         HIP_TRY(hipGetLastError());
@@ -1341,6 +1344,63 @@ int rt_render_views(const rt_scene *scene, const rt_view *views, int32_t n_views
     return rc;
 }
 
+// ---- views moments: rt_render_views_device with the sums of squares beside the sums (sum_view_moments_samples_kernel) ----
+int rt_render_views_moments_device(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *d_sum,
+                                   double *d_sum_sq, void *hip_stream) {
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: scene is null");
+    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: views is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: params is null");
+    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: d_sum is null");
+    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: d_sum_sq is null (rt_render_views_device renders without squares)");
+    g_last_launch[0] = 0;
+    std::vector<ViewRec> recs;
+    if (int rc = check_views(views, n_views, params, "rt_render_views_moments_device", recs)) return rc;
+    rt_render_params p = *params;
+    p.shard_index = 0; p.shard_count = 1;
+    const ViewTable table{recs.data(), n_views, d_sum_sq};
+    return launch_render(const_cast<rt_scene *>(scene), &views[0].camera, p, d_sum, (hipStream_t)hip_stream, nullptr, nullptr, &table);
+}
+
+int rt_render_views_moments(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *sum,
+                            double *sum_sq) {
+    const char *who = "rt_render_views_moments";
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": scene is null");
+    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": views is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": params is null");
+    if (!sum) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": sum is null");
+    if (!sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": sum_sq is null (rt_render_views renders without squares)");
+    g_last_launch[0] = 0;
+    std::vector<ViewRec> recs;
+    if (int rc = check_views(views, n_views, params, who, recs)) return rc;
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    std::lock_guard<std::mutex> serial(s->host_render_mu);
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t bytes = (size_t)n_views * (size_t)views[0].camera.image_width * (size_t)views[0].camera.image_height * 3u * sizeof(double);
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, 2u * bytes));
+    double *d_sum = (double *)buf, *d_sq = (double *)(buf + bytes);
+    int rc = RT_OK;
+    do {
+        if (params->accumulate && (hipMemcpy(d_sum, sum, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                                   hipMemcpy(d_sq, sum_sq, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running sums failed");
+            break;
+        }
+        rt_render_params p = *params;
+        p.shard_index = 0; p.shard_count = 1;
+        const ViewTable table{recs.data(), n_views, d_sq};
+        rc = launch_render(s, &views[0].camera, p, d_sum, nullptr, nullptr, nullptr, &table);
+        if (rc != RT_OK) break;
+        hipError_t e = hipMemcpy(sum, d_sum, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(sum_sq, d_sq, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    } while (0);
+    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
+    (void)hipFree(buf);
+    if (rc != RT_OK) (void)hipGetLastError();
+    return rc;
+}
+
 int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
                               const rt_adaptive_params *adaptive, double *d_sum, int32_t *d_spp, double *d_sum_sq, void *hip_stream,
                               rt_adaptive_result *out_result) {
@@ -1604,6 +1664,15 @@ int64_t denoise_workspace_bytes(int32_t width, int32_t height, int regions) { //
     if (width <= 0 || height <= 0 || (int64_t)width * height >= ((int64_t)1 << 27)) return -1;
     return (int64_t)width * height * regions * 4 * (int64_t)sizeof(double);
 }
+// the views forms': n_views times the single-frame figure; -1 for what the call refuses or (no n_views the call takes gets there) what
+// does not fit an int64
+int64_t denoise_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views, int regions) {
+    const int64_t one = denoise_workspace_bytes(width, height, regions);
+    if (one < 0 || n_views < 1 || n_views > RT_DENOISE_MAX_VIEWS) return -1;
+    int64_t all = 0;
+    if (__builtin_mul_overflow(one, (int64_t)n_views, &all)) return -1;
+    return all;
+}
 bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
@@ -1617,6 +1686,9 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 // `spatial` (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device; means form only) is the route choice: with
 // spp < spatial->params.spatial_below the spatial prepare runs in the elementwise one's place and d_sum_sq (d_m2) is not read and may be
 // null; otherwise the call is the means form's, launch for launch.  Its checks sit behind the sample count's and before the filter's params.
+// `stack` (rt_denoise_views_device, rt_denoise_albedo_views_device; sums form, no map) is a stack of n_views frames, view-major in every
+// buffer and in every region of the workspace, filtered in the same K + 1 launches with the view on the grid's second dimension; its
+// count is checked behind the frame size.  Null is the single frame: a stack of one, launch for launch.
 enum class DenoiseInput { Sums, Means };
 struct SpatialRoute {
     rt_denoise_spatial_params params;
@@ -1624,19 +1696,23 @@ struct SpatialRoute {
 };
 int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
                 const int32_t *d_spp, DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
-                void *hip_stream, const SpatialRoute *spatial = nullptr) {
+                void *hip_stream, const SpatialRoute *spatial = nullptr, const int32_t *stack = nullptr) {
     const std::string w(who);
     const bool means = form == DenoiseInput::Means;
     const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum";
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (stack && *stack < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
+    if (stack && *stack > RT_DENOISE_MAX_VIEWS)
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at most " + std::to_string(RT_DENOISE_MAX_VIEWS) + " (the launch grid's second dimension)");
+    const int32_t n_views = stack ? *stack : 1;
     if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
     if (!d_sum_sq && !spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
     if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
     if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
     if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
     if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
-    if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples) when d_spp is null");
+    if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples)" + (stack ? "" : " when d_spp is null"));
     if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
     bool spatial_route = false;
     if (spatial) {
@@ -1655,7 +1731,7 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (!(d->eps > 0.0) || !std::isfinite(d->eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
     if (guide && (!(guide->sigma_albedo > 0.0) || !std::isfinite(guide->sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
     if (guide && (!(guide->albedo_floor > 0.0) || !std::isfinite(guide->albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
-    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
+    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = (size_t)n_views * n_pix * 3u * sizeof(double); // (the whole stack's)
     if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || (d_sum_sq && overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes)) ||
         (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
@@ -1663,15 +1739,15 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
     if (int rc = select_device_of(d_mean_out, who)) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    const size_t region = n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
+    const size_t region = (size_t)n_views * n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
     char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
     if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
     if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream);
-    else launch_denoise_prepare((int64_t)n_pix, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
+    else launch_denoise_prepare((int64_t)n_pix, n_views, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
     HIP_TRY(hipGetLastError());
     for (int32_t k = 0; k < d->iterations; ++k) {
         const bool last = k == d->iterations - 1;
-        launch_denoise_atrous(width, height, (int32_t)1 << k, d->sigma, d->eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
+        launch_denoise_atrous(width, height, n_views, (int32_t)1 << k, d->sigma, d->eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
                               last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
         HIP_TRY(hipGetLastError());
     }
@@ -1728,6 +1804,18 @@ int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const 
     const bool known = denoise_params_resolve(params, d);
     return run_denoise("rt_denoise_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, nullptr, known ? &d : nullptr, d_mean_out,
                        d_rgba8, d_workspace, hip_stream);
+}
+
+int64_t rt_denoise_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views) {
+    return denoise_views_workspace_bytes(width, height, n_views, 2);
+}
+
+int rt_denoise_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                            const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_params d;
+    const bool known = denoise_params_resolve(params, d);
+    return run_denoise("rt_denoise_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, nullptr, known ? &d : nullptr,
+                       d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views);
 }
 
 int rt_denoise_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const rt_denoise_params *params,
@@ -1839,6 +1927,21 @@ int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum,
     DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
     return run_denoise("rt_denoise_albedo_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, &guide, known ? &shared : nullptr,
                        d_mean_out, d_rgba8, d_workspace, hip_stream);
+}
+
+int64_t rt_denoise_albedo_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views) {
+    return denoise_views_workspace_bytes(width, height, n_views, 3);
+}
+
+int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const double *d_albedo_sum, int32_t albedo_spp, const rt_denoise_albedo_params *params, double *d_mean_out,
+                                   uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_albedo_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
+    return run_denoise("rt_denoise_albedo_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, &guide,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views);
 }
 
 int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const double *d_albedo_mean,

@@ -21,7 +21,11 @@
 // compares: the last iteration makes it again from the guide instead of keeping it.
 // Shapes: a workgroup is 256 lanes = a 32 x 8 pixel tile, one pixel per lane, a row of the tile on 32 consecutive lanes (a wave covers
 // two rows: its tap loads are two runs of 32 consecutive pixels, and its ds_read_b64 of 32 consecutive doubles per half-wave are
-// conflict-free); the grid is 1-D, tiles row-major.  Strides 1 and 2 stage the tile plus a halo of 2 x stride pixels in the LDS, planes
+// conflict-free); the grid's first dimension is the frame's tiles, row-major, its second the view: a launch filters a stack of grid.y
+// frames (rt_denoise_views_device, rt_denoise_albedo_views_device) that lie one behind the other in every buffer, and a workgroup
+// addresses its pixels as `first pixel of its view + pixel of the frame` while every bounds test stays the frame's own, so no tap, halo
+// pixel or window member is ever a neighbouring view's.  The single-frame entry points launch grid.y = 1 and add zero.
+// Strides 1 and 2 stage the tile plus a halo of 2 x stride pixels in the LDS, planes
 // apart: (L, C x 3, V), five planes, and Guided (a x 3) as well, eight (40 x 16 x 8 x 8 B = 40 960 B at stride 2); out-of-frame halo
 // pixels are staged as not valid, so the tap loop has no bounds test.  Strides >= 4 gather the taps from global memory (the working
 // set stays in L2 / Infinity Cache at the project's frame sizes; Guided: two double4 per tap) and compute a tap's L from its C.
@@ -60,8 +64,9 @@ template <bool Guided, bool Means>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_pixels, const double *__restrict__ sum, const double *__restrict__ sum_sq,
                                                                       int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Guided> gd,
                                                                       double4 *__restrict__ out) {
-    const int64_t idx = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
-    if (idx >= n_pixels) return;
+    const int64_t in_frame = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
+    if (in_frame >= n_pixels) return;
+    const size_t idx = (size_t)blockIdx.y * (size_t)n_pixels + (size_t)in_frame; // the pixel in the stack of views (n_pixels: one frame's)
     const int32_t n = spp_map ? spp_map[idx] : spp;
     const double dn = (double)n;
     const double s[3] = {sum[idx * 3 + 0], sum[idx * 3 + 1], sum[idx * 3 + 2]};
@@ -316,14 +321,15 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32
     using Src = LdsSource<S, Guided>;
     constexpr int PW = Src::PW, PLANE = Src::PLANE, HALO = Src::HALO;
     __shared__ double staged[Src::PLANES * PLANE];
-    const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // a 1-D grid of tiles, row-major
+    const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // grid.x: tiles, row-major
+    const size_t view = (size_t)blockIdx.y * ((size_t)w * (size_t)h); // grid.y: the view; its first pixel in every buffer
     const int32_t x0 = tile_x * DN_TW - HALO, y0 = tile_y * DN_TH - HALO;
     for (int k = (int)threadIdx.x; k < PLANE; k += DN_THREADS) {
         const int ly = k / PW, lx = k - ly * PW;
         const int32_t gx = x0 + lx, gy = y0 + ly;
         double4 c = make_double4(0.0, 0.0, 0.0, -1.0), a = make_double4(0.0, 0.0, 0.0, 0.0);
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
-            const size_t g = (size_t)gy * (size_t)w + (size_t)gx;
+            const size_t g = view + (size_t)gy * (size_t)w + (size_t)gx;
             c = in[g];
             if constexpr (Guided) a = gd.region[g];
         }
@@ -341,7 +347,7 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32
     p.L = src.at(Src::P_L, k); p.r = src.at(Src::P_R, k); p.g = src.at(Src::P_G, k); p.b = src.at(Src::P_B, k); p.V = src.at(Src::P_V, k);
     if constexpr (Guided) { p.ar = src.at(Src::P_AR, k); p.ag = src.at(Src::P_AG, k); p.ab = src.at(Src::P_AB, k); }
     if (!(p.V < 0.0)) filter_pixel<Guided>(src, p, sigma, eps, gd);
-    store_pixel<Guided>(out, (size_t)py * (size_t)w + (size_t)px, p, gd);
+    store_pixel<Guided>(out, view + (size_t)py * (size_t)w + (size_t)px, p, gd);
 }
 
 template <bool Guided>
@@ -351,9 +357,10 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, in
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x;
     const int32_t px = tile_x * DN_TW + tx, py = tile_y * DN_TH + ty;
     if (px >= w || py >= h) return;
-    const size_t pixel = (size_t)py * (size_t)w + (size_t)px;
+    const size_t view = (size_t)blockIdx.y * ((size_t)w * (size_t)h), pixel = (size_t)py * (size_t)w + (size_t)px; // (grid.y: the view)
     const double4 *guide = nullptr;
-    if constexpr (Guided) guide = gd.region;
+    if constexpr (Guided) guide = gd.region + view;
+    in += view; // the taps index their own view's frame
     const double4 c = in[pixel];
     Tap p;
     p.L = luminance(c.x, c.y, c.z); p.r = c.x; p.g = c.y; p.b = c.z; p.V = c.w;
@@ -362,14 +369,14 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, in
         p.ar = a.x; p.ag = a.y; p.ab = a.z;
     }
     if (!(p.V < 0.0)) filter_pixel<Guided>(GlobalSource<Guided>{in, guide, w, h, px, py, stride}, p, sigma, eps, gd);
-    store_pixel<Guided>(out, pixel, p, gd);
+    store_pixel<Guided>(out, view + pixel, p, gd);
 }
 
 template <bool Guided, bool Means>
-void launch_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Guided> &gd,
+void launch_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Guided> &gd,
                     void *half, hipStream_t stream) {
-    hipLaunchKernelGGL((denoise_prepare_kernel<Guided, Means>), dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS)), dim3(DN_THREADS), 0, stream,
-                       n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
+    hipLaunchKernelGGL((denoise_prepare_kernel<Guided, Means>), dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS), (unsigned)n_views), dim3(DN_THREADS), 0,
+                       stream, n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
 }
 
 template <int R, bool Guided>
@@ -385,10 +392,10 @@ void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const rtk:
 }
 
 template <bool Guided>
-void launch_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const GuideOf<Guided> &gd, const void *half_in, const DenoiseOut &out,
+void launch_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const GuideOf<Guided> &gd, const void *half_in, const DenoiseOut &out,
                    hipStream_t stream) {
     const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
-    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y)), block(DN_THREADS); // (w * h < 2^27: fewer than 2^27 tiles)
+    const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y), (unsigned)n_views), block(DN_THREADS); // (w * h < 2^27: fewer than 2^27 tiles; n_views <= 65535)
     const double4 *in = (const double4 *)half_in;
     if (stride == 1) hipLaunchKernelGGL((atrous_lds_kernel<1, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
     else if (stride == 2) hipLaunchKernelGGL((atrous_lds_kernel<2, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
@@ -399,13 +406,13 @@ void launch_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double ep
 
 namespace rtk {
 
-void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
+void launch_denoise_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
                             bool means, void *half, hipStream_t stream) {
     if (means) { // (a uniform count: the means form has no map)
-        if (guide) launch_prepare<true, true>(n_pixels, sum, sum_sq, spp, nullptr, *guide, half, stream);
-        else launch_prepare<false, true>(n_pixels, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
-    } else if (guide) launch_prepare<true, false>(n_pixels, sum, sum_sq, spp, spp_map, *guide, half, stream);
-    else launch_prepare<false, false>(n_pixels, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
+        if (guide) launch_prepare<true, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *guide, half, stream);
+        else launch_prepare<false, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
+    } else if (guide) launch_prepare<true, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, *guide, half, stream);
+    else launch_prepare<false, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
 }
 
 void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream) {
@@ -414,11 +421,11 @@ void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const 
     else launch_prepare_spatial<3>(w, h, mean, guide, half, stream); // (the caller has checked 1..3)
 }
 
-void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
+void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
                            void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream) {
     const DenoiseOut out{(double4 *)half_out, mean_out, (uint32_t *)rgba8};
-    if (guide) launch_atrous<true>(w, h, stride, sigma, eps, *guide, half_in, out, stream);
-    else launch_atrous<false>(w, h, stride, sigma, eps, NoGuide{}, half_in, out, stream);
+    if (guide) launch_atrous<true>(w, h, n_views, stride, sigma, eps, *guide, half_in, out, stream);
+    else launch_atrous<false>(w, h, n_views, stride, sigma, eps, NoGuide{}, half_in, out, stream);
 }
 
 } // namespace rtk

@@ -1506,6 +1506,37 @@ __global__ void sum_view_samples_kernel(const KParams P) {
     dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
 }
 
+// sum_view_samples_kernel with the sums of squares beside the sums (rt_render_views_moments_device): its thread-to-pixel mapping and
+// addressing, its additions for the sum word for word — so P.out gets sum_view_samples_kernel's bits — and per channel sq = sq + c * c as
+// sum_listed_samples_kernel keeps it: the product rounded, then added (no contraction).  View v's squares go to P.out_sq at the offset
+// its sums have in P.out; both start from +0.0 or, with P.accumulate, continue.  A kernel of its own: sum_view_samples_kernel stays as it is.
+__global__ void sum_view_moments_samples_kernel(const KParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lt = idx >> 6, p64 = idx & 63u;
+    if (lt >= P.n_local_tiles) return;
+    const int32_t w = P.cam.image_width, h = P.cam.image_height;
+    const uint32_t view = lt / P.tiles_per_view, k = lt - view * P.tiles_per_view;
+    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    if (i >= w || j >= h) return;
+    const size_t at = (size_t)view * ((size_t)w * (size_t)h * 3u) + ((size_t)j * (size_t)w + (size_t)i) * 3u;
+    double *dst = P.out + at, *dsq = P.out_sq + at;
+    V3 acc = v3(0.0, 0.0, 0.0), sq = v3(0.0, 0.0, 0.0);
+    if (P.accumulate) {
+        acc = v3(dst[0], dst[1], dst[2]);
+        sq = v3(dsq[0], dsq[1], dsq[2]);
+    }
+    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
+    for (uint32_t s = 0; s < P.n_samples; ++s) {
+        const V3 c = v3(src[0], src[1], src[2]);
+        acc = acc + c;
+        sq = sq + c * c;
+        src += 64u * 3u;
+    }
+    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
+    dsq[0] = sq.x; dsq[1] = sq.y; dsq[2] = sq.z;
+}
+
 // sum_samples_kernel for list mode: one thread per list entry (group g, entry p of the group); a listed pixel's samples are added in
 // sample order onto out[pixel] and, when out_sq is set, their squares (each product rounded, then added: no contraction) onto
 // out_sq[pixel].  Pixels not in the list, and padding entries, are never written.
@@ -1875,6 +1906,9 @@ void launch_mean_moments_samples(const KParams &K, unsigned grid, hipStream_t st
 }
 void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_view_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+}
+void launch_sum_view_moments_samples(const KParams &K, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_view_moments_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
 }
 void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream) {
     hipLaunchKernelGGL(sum_listed_samples_kernel, dim3(grid), dim3(256), 0, stream, K);

@@ -115,7 +115,8 @@ struct KParams {
     uint32_t n_list;                // entries of pixel_list (the groups beyond it are padding)
     double inv_width;               // 1 / image_width (list mode's pixel -> (i, j) decode; exact for w * h < 2^27)
     double *out_sq;                 // list mode: per-pixel sums of the squared sample colours beside `out`, or null;
-                                    // mean_moments_samples_kernel: the frame of running M2 beside the running means in `out`
+                                    // mean_moments_samples_kernel: the frame of running M2 beside the running means in `out`;
+                                    // sum_view_moments_samples_kernel: one frame of sums of squares per view, laid out as `out` is
     // views mode (rt_render_views_device; path_kernel<..., JOBS_VIEWS>): local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view.
     // `cam` then holds what the views share (frame size); camera and seed of a job come from its view's record.  No other instantiation reads these.
     const ViewRec *views;
@@ -188,6 +189,7 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream);
 void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream);
 void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream);
+void launch_sum_view_moments_samples(const KParams &K, unsigned grid, hipStream_t stream); // ... and each view's sums of squares beside them, in K.out_sq
 void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream); // live refinement: the running mean instead of the sum
 void launch_mean_moments_samples(const KParams &K, unsigned grid, hipStream_t stream); // ... and Welford's M2 beside it, in K.out_sq
 // adaptive sampling (rt_render_adaptive_device): the list of every pixel in tile order; one convergence step over an active list
@@ -213,19 +215,22 @@ void launch_resolve_rgba8(int64_t n_pixels, const double *mean, uint8_t *rgba, h
 // frame and the guided filter's two parameters, and `region`, a third region of the workspace of one double4 (a_r, a_g, a_b, 0) per
 // pixel that prepare writes once and the iterations read.  An iteration with half_out null is the last: it writes mean_out (3 w h
 // doubles; guided: with the floored albedo multiplied back in) and, if not null, rgba8.  `means`: the inputs are a frame of running
-// means and of M2 after `spp` samples of every pixel (rt_denoise_mean_device; no spp map), and the guide's frame holds means as well
+// means and of M2 after `spp` samples of every pixel (rt_denoise_mean_device; no spp map), and the guide's frame holds means as well.
+// `n_views` (1..65535: the grid's second dimension) frames are filtered by one launch: every buffer — the inputs, each half, the guide's
+// frame and its region, mean_out, rgba8 — then holds n_views frames one behind the other, and no tap leaves its own frame.  1 is the
+// single frame.  (The spatial prepare has no views form.)
 struct DenoiseGuide {
     const double *albedo_sum; // 3 w h doubles: per-pixel sums of albedo_spp samples (prepare reads them); means form: their means
     double albedo_spp;        // their count, as the divisor it is (means form: not read)
     double albedo_floor, sigma_albedo;
     double4 *region;
 };
-void launch_denoise_prepare(int64_t n_pixels, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
+void launch_denoise_prepare(int64_t n_pixels /* of one frame */, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
                             bool means, void *half, hipStream_t stream);
 // the spatial prepare (rt_denoise_mean_spatial_device below its threshold) in launch_denoise_prepare's place: `mean` and, guided,
 // guide->albedo_sum are frames of means; V0 is the spread of C0 over the (2 radius + 1)^2 window, radius 1..3
 void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream);
-void launch_denoise_atrous(int32_t w, int32_t h, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
+void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
                            void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);

@@ -16,6 +16,9 @@
 //   --live-denoise[-albedo]: frames of fewer than N samples, default 2, take their variance from the spread of the neighbouring
 //   pixels over a (2R + 1)^2 window, so the first frame is filtered too: include/rt_amd.h "spatial variance"),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
+//   --orbit N --orbit-denoise [--denoise-iters K] [--denoise-sigma X] (the views' sums and sums of squares from one launch, filtered as
+//   one stack: include/rt_amd.h "views denoise"), --orbit-denoise-albedo [--denoise-albedo-sigma X] (the guided filter instead, its albedo
+//   frames from one views launch over the albedo scene).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -47,6 +50,10 @@ static void usage(const char *argv0) {
             "                         R from 1 to 3, default 1: the window is (2R + 1) x (2R + 1) pixels)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
             "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
+            "          [--orbit-denoise [--denoise-iters K] [--denoise-sigma X]]   (with --orbit: every view through the à-trous filter, all views in\n"
+            "                         one set of launches, from sums and sums of squares rendered in one launch)\n"
+            "          [--orbit-denoise-albedo [--denoise-albedo-sigma X]]   (with --orbit, instead of --orbit-denoise: the albedo-guided filter, with\n"
+            "                         first-hit albedo frames of the same views rendered in one launch)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -115,6 +122,8 @@ int main(int argc, char **argv) {
             ro.orbit = atoi(need("--orbit"));
             if (ro.orbit < 1 || ro.orbit > 1000) { fprintf(stderr, "--orbit needs a number of views from 1 to 1000\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--orbit-denoise") ro.orbit_denoise = true;
+        else if (a == "--orbit-denoise-albedo") ro.orbit_denoise_albedo = true;
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -139,6 +148,14 @@ int main(int argc, char **argv) {
                         "second moment), --gpus > 1 (the gather moves sums only), --progressive or --orbit\n");
         return 2;
     }
+    if ((ro.orbit_denoise || ro.orbit_denoise_albedo) && ro.orbit == 0) {
+        fprintf(stderr, "--orbit-denoise and --orbit-denoise-albedo filter the views of --orbit: they need --orbit\n");
+        return 2;
+    }
+    if (ro.orbit_denoise && ro.orbit_denoise_albedo) {
+        fprintf(stderr, "--orbit-denoise and --orbit-denoise-albedo are two filters for the same views: give one of them\n");
+        return 2;
+    }
     if (ro.live_denoise && !live) {
         fprintf(stderr, "--live-denoise and --live-denoise-albedo filter the frames of --live: they need -l/--live\n");
         return 2;
@@ -151,12 +168,14 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--denoise-spatial-radius sets the window of --live-denoise-spatial: it needs --live-denoise-spatial\n");
         return 2;
     }
-    if (albedo_knob_given && !ro.denoise_albedo && !ro.live_denoise_albedo) {
-        fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo (with --live: --live-denoise-albedo)\n");
+    if (albedo_knob_given && !ro.denoise_albedo && !ro.live_denoise_albedo && !ro.orbit_denoise_albedo) {
+        fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo (with --live: --live-denoise-albedo; "
+                        "with --orbit: --orbit-denoise-albedo)\n");
         return 2;
     }
-    if (denoise_knob_given && !ro.denoise && !ro.live_denoise) {
-        fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise (with --live: --live-denoise)\n");
+    if (denoise_knob_given && !ro.denoise && !ro.live_denoise && !ro.orbit_denoise && !ro.orbit_denoise_albedo) {
+        fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise (with --live: --live-denoise; "
+                        "with --orbit: --orbit-denoise)\n");
         return 2;
     }
     if (live_spp_given && !live) {

@@ -129,9 +129,10 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
 }
 
 // what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
+// (n_frames: the views forms' stack of frames, one behind the other in every buffer)
 static std::vector<uint8_t> run_denoise(const char *who, int32_t width, int32_t height, int64_t work,
-                                        const std::function<int(double *, uint8_t *, void *)> &call) {
-    const int64_t n_pix = (int64_t)width * height;
+                                        const std::function<int(double *, uint8_t *, void *)> &call, int32_t n_frames = 1) {
+    const int64_t n_pix = (int64_t)width * height * n_frames;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_work = nullptr;
     auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_work); };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error(std::string(who) + ": " + msg); } };
@@ -166,6 +167,30 @@ std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double 
     return run_denoise("denoise_albedo", width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_albedo_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
     });
+}
+
+std::vector<uint8_t> denoise_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const RenderOptions &opt) {
+    rt_denoise_params dp;
+    if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_views: ") + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
+    if (n_views < 1) throw std::runtime_error("denoise_views: n_views must be at least 1");
+    return run_denoise("denoise_views", width, height, rt_denoise_views_workspace_bytes(width, height, n_views), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+        return rt_denoise_views_device(width, height, n_views, d_sum, d_sum_sq, spp, &dp, d_mean, d_rgba8, d_work, nullptr);
+    }, n_views);
+}
+
+std::vector<uint8_t> denoise_albedo_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                          const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt) {
+    rt_denoise_albedo_params dp;
+    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo_views: ") + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
+    if (n_views < 1) throw std::runtime_error("denoise_albedo_views: n_views must be at least 1");
+    return run_denoise("denoise_albedo_views", width, height, rt_denoise_albedo_views_workspace_bytes(width, height, n_views),
+                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+                           return rt_denoise_albedo_views_device(width, height, n_views, d_sum, d_sum_sq, spp, d_albedo_sum, albedo_spp, &dp, d_mean,
+                                                                 d_rgba8, d_work, nullptr);
+                       }, n_views);
 }
 
 // the params of the two filters from the options (the plain filter's are the guided one's first fields)
@@ -414,6 +439,42 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     return frame;
 }
 
+// An orbit on device 0 that ends in the denoiser (opt.orbit_denoise, opt.orbit_denoise_albedo): every view's sums and sums of squares
+// from one rt_render_views_moments_device call stay on the device and are filtered there as one stack (rt_denoise_views_device); the
+// guided form takes its albedo frames from one rt_render_views_device over the albedo scene, under the views' cameras with a white
+// background and their seeds.  Returns the views' RGB bytes, one frame behind the other.
+static std::vector<uint8_t> render_orbit_denoised_rgb8(const rt_scene_desc &desc, const std::vector<rt_view> &views, const rt_render_params &p,
+                                                       const RenderOptions &opt) {
+    const rt_camera &cam = views[0].camera;
+    const int32_t n = (int32_t)views.size();
+    const int64_t bytes = (int64_t)n * cam.image_width * cam.image_height * 3 * (int64_t)sizeof(double);
+    rt_scene *scene = nullptr, *albedo = nullptr;
+    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_alb: only with opt.orbit_denoise_albedo)
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_scene_destroy(scene); rt_scene_destroy(albedo); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, bytes, &d_sum));
+    check(rt_device_malloc(0, bytes, &d_sq));
+    check(rt_render_views_moments_device(scene, views.data(), n, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
+    if (opt.orbit_denoise_albedo) {
+        std::vector<rt_view> white(views);
+        for (rt_view &v : white) v.camera.background = rt_vec3{1.0, 1.0, 1.0};
+        check(rt_scene_create_albedo(&desc, 0, nullptr, &albedo));
+        check(rt_device_malloc(0, bytes, &d_alb));
+        check(rt_render_views_device(albedo, white.data(), n, &p, static_cast<double *>(d_alb), nullptr));
+    }
+    std::vector<uint8_t> px;
+    try { // (the filter's download waits for everything enqueued before it: the scenes are destroyed after it)
+        px = opt.orbit_denoise_albedo
+                 ? denoise_albedo_views(cam.image_width, cam.image_height, n, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                                        cam.samples_per_pixel, static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
+                 : denoise_views(cam.image_width, cam.image_height, n, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                                 cam.samples_per_pixel, opt);
+    } catch (...) { cleanup(); throw; }
+    cleanup();
+    return px;
+}
+
 // An orbit on device 0: every view's frame in one rt_render_views call, one PNG per view.
 static void render_orbit(const Camera &camera, const Hittable &world, const std::string &output_file_name, const RenderOptions &opt) {
     using clock = std::chrono::steady_clock;
@@ -430,11 +491,24 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
     }
     const rt_camera &cam = views[0].camera;
     const size_t frame = (size_t)cam.image_width * (size_t)cam.image_height * 3u;
-    std::vector<double> sums(frame * views.size(), 0.0);
     rt_scene *scene = nullptr;
     rt_render_params p{};
     p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
     p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    if (opt.orbit_denoise || opt.orbit_denoise_albedo) {
+        const std::vector<uint8_t> px = render_orbit_denoised_rgb8(desc, views, p, opt);
+        if (!opt.quiet) printf("Render time: %.2fs (%d views, denoised)\n", std::chrono::duration<double>(clock::now() - now).count(), opt.orbit);
+        now = clock::now();
+        for (int k = 0; k < opt.orbit; ++k) {
+            char suffix[16];
+            snprintf(suffix, sizeof suffix, "_%03d.png", k);
+            if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, px.data() + frame * (size_t)k))
+                throw std::runtime_error("Should've encoded the image into a file.");
+        }
+        if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+        return;
+    }
+    std::vector<double> sums(frame * views.size(), 0.0);
     int rc = rt_scene_create(&desc, 0, &scene);
     if (rc == RT_OK) rc = rt_render_views(scene, views.data(), opt.orbit, &p, sums.data());
     const std::string msg = rc == RT_OK ? "" : rt_last_error();

@@ -32,6 +32,13 @@ struct RenderOptions {
     // axis through look_at along vup by 360 k / orbit degrees (camera.hpp orbit_look_from), with seed + k, and goes to
     // <output_file_name>_<k as three digits>.png.  One GPU, single pass.
     int orbit = 0;
+    // with `orbit`: the views go through rt_render_views_moments_device and are filtered as one stack by rt_denoise_views_device
+    // (include/rt_amd.h "views denoise") with denoise_iters / denoise_sigma; each PNG is written from its view's filtered mean.
+    bool orbit_denoise = false;
+    // with `orbit`: the albedo-guided filter over the stack instead (rt_denoise_albedo_views_device, denoise_albedo_sigma).  The albedo
+    // frames come from ONE rt_render_views_device over the albedo scene, under the views' cameras with background (1, 1, 1) and their
+    // seeds, over the same sample range.
+    bool orbit_denoise_albedo = false;
     // the variance-guided à-trous denoiser (include/rt_amd.h "denoise") over the frame before it is written: a plain render then
     // goes through rt_render_moments_device, an adaptive one hands over its sums, sums of squares and spp map.  One GPU, single pass.
     bool denoise = false;
@@ -68,6 +75,13 @@ std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum,
 // scene; opt.denoise_albedo_sigma is the filter's sigma_albedo.
 std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                                     const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt = {});
+
+// rt_denoise_views_device and rt_denoise_albedo_views_device likewise, over a stack of n_views frames, view-major in every DEVICE
+// buffer, with the uniform sample count `spp`: the RGB bytes of the n_views display frames, one behind the other (n_views * 3 * w * h).
+std::vector<uint8_t> denoise_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const RenderOptions &opt = {});
+std::vector<uint8_t> denoise_albedo_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                          const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt = {});
 
 // rt_denoise_mean_device and rt_denoise_albedo_mean_device likewise, over DEVICE frames of running means and of M2 after `samples`
 // samples of every pixel (rt_render_mean_moments_device) and, guided, the albedo scene's running mean (rt_render_mean_device).
