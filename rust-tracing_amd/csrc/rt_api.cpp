@@ -461,11 +461,15 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     // the inline start test (path_kernel): the shortcut's leaf is one sphere (OrderedKind SPHERES = Stage ST_SPHERE = 1)
     K.start_inline = (tn.start_inline != 0 && K.o_start_stage == (uint32_t)OK_SPHERES && K.o_start_end == K.o_start_prim + 1u) ? 1u : 0u;
     if (scene->wide) { // the start shortcut's entry as the kernel pushes it (rt_kernel.hip W_SHIFT: 2-byte entries in the LDS kernels)
-        const uint32_t w_shift = lds != 0 ? 12u : 26u, w_full = 0xfu << w_shift;
-        if (K.setaside_direct && scene->o_start_direct != 0xffffffffu) K.o_start_rest = scene->o_start_direct | w_full;
-        else if (scene->o_start_rest != 0u) K.o_start_rest = scene->o_root | (scene->o_start_rest << w_shift);
-        // (no real entry may read as S_EXIT, all ones: a record index of all ones never exists — WIDE_MAX_LDS_RECORDS, OREF_INDEX_MASK)
-        if (K.o_start_rest == (lds != 0 ? 0xffffu : 0xffffffffu)) return fail(RT_ERR_INVALID_ARGUMENT, "start shortcut: entry reads as S_EXIT");
+        // An entry is a record's index and, above it, the mask of its children NOT to be looked at: an inner record set aside as itself is
+        // its bare index.  No entry at all is all ones, which no entry is (one with all four children gone is never made).
+        const uint32_t w_shift = lds != 0 ? 12u : 26u;
+        if (K.setaside_direct && scene->o_start_direct != 0xffffffffu) K.o_start_rest = scene->o_start_direct;
+        else if (scene->o_start_rest != 0u) K.o_start_rest = scene->o_root | ((~scene->o_start_rest & 0xfu) << w_shift);
+        else K.o_start_rest = 0xffffffffu;
+        // (no real entry may read as S_EXIT, all ones in the entry's width)
+        if (K.o_start_rest != 0xffffffffu && (K.o_start_rest & (lds != 0 ? 0xffffu : 0xffffffffu)) == (lds != 0 ? 0xffffu : 0xffffffffu))
+            return fail(RT_ERR_INVALID_ARGUMENT, "start shortcut: entry reads as S_EXIT");
     }
     K.oimage = scene->oimage.ptr; K.o_root = scene->o_root; K.oseq = scene->oseq.ptr; K.n_oseq = scene->n_oseq; K.lds_stack_off = lds_image_bytes_for(scene, lds);
     K.lds_seq_off = (uint32_t)seq_offset(scene, lds);

@@ -432,35 +432,39 @@ RT_DEV void box_quad_f32(const OQuad &b, const RayPair32 &r, float tmin32, float
     }
 }
 // What a visit of a wide record (rt_kernel.hip visit_wide; the test hook debug_wide_kernel) makes of box_quad_f32's distances, in two
-// steps — the kernel takes the world frame's instances out of `hit` and `key` between them.
-// wide_verdict: which of the children in `todo` are entered, and a key per child to choose among them by — in integer arithmetic on
-// the floats' bits (a compare-and-select per child costs two instructions and the wait states between them; these cost one each).  A
-// box is missed iff leave - enter is negative (no NaN can arise here: planes and ray constants are finite, an empty slot gives -inf);
-// the sign, spread over the word, turns the child's key — where the ray enters it — into an all-ones NaN, which the minimum ignores
-// and nothing equals; so does the complement of the entry's mask for a child that is no longer to be looked at.
+// steps — the kernel takes the world frame's instances out of the verdict and `key` between them.
+// wide_verdict: which children are NOT entered (bit k of the result: child k is missed or no longer to be looked at), and a key per
+// child to choose among the others by — in integer arithmetic on the floats' bits (a compare-and-select per child costs two
+// instructions and the wait states between them; these cost one each).  `node` is the walk's entry for the record: its index and, from
+// bit W_SHIFT up, the children that are NOT to be looked at (none for a record come to for the first time: the entry is the bare index).
+// A box is missed iff leave - enter is negative (no NaN can arise here: planes and ray constants are finite, an empty slot gives -inf).
+// The entry, shifted so that the child's bit lands on that sign, makes one word whose sign says "not entered" for either reason (the
+// bits below the sign are never looked at); spread over the word it turns the child's key — where the ray enters it — into an all-ones
+// NaN, which the minimum ignores and nothing equals, and the four signs shifted into one word are the verdict.
 // any_degenerate: wave-uniform, some lane's ray is degenerate (tests/test_gpu_wide_visit.py checks all of this against an f64 reference)
-RT_DEV uint32_t wide_verdict(const float en[4], const float le[4], const uint32_t c[4], uint32_t todo, bool any_degenerate, bool degenerate,
+template <uint32_t W_SHIFT>
+RT_DEV uint32_t wide_verdict(const float en[4], const float le[4], const uint32_t c[4], uint32_t node, bool any_degenerate, bool degenerate,
                              uint32_t key[4]) {
-    uint32_t missed[4];
-    uint32_t miss_bits = 0;
+    uint32_t out = 0;
 #pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-        missed[k] = (uint32_t)((int32_t)__float_as_uint(le[k] - en[k]) >> 31);
-        miss_bits |= missed[k] & (1u << k);
-        key[k] = __float_as_uint(en[k]) | missed[k] | (uint32_t)((int32_t)(~todo << (31u - k)) >> 31);
+    for (uint32_t q = 0; q < 4u; ++q) {
+        const uint32_t k = 3u - q;
+        // (spelled out: left to itself the compiler shifts the entry apart from the difference for two of the four children)
+        uint32_t s;
+        asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(s) : "v"(node), "n"(31u - W_SHIFT - k), "v"(__float_as_uint(le[k] - en[k])));
+        key[k] = __float_as_uint(en[k]) | (uint32_t)((int32_t)s >> 31);
+        out = q == 0u ? s >> 31 : __builtin_amdgcn_alignbit(out, s, 31); // (out << 1 | s >> 31)
     }
-    uint32_t hit = ~miss_bits & todo;
     if (any_degenerate) { // a ray with a zero or infinite direction component: every box that exists is entered
         if (degenerate) {
-            hit = 0;
+            out = (node >> W_SHIFT) & 0xfu;
 #pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) hit |= c[k] < (OK_EMPTY << OREF_KIND_SHIFT) ? (1u << k) : 0u;
-            hit &= todo;
+            for (uint32_t k = 0; k < 4u; ++k) out |= c[k] < (OK_EMPTY << OREF_KIND_SHIFT) ? 0u : (1u << k);
 #pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) key[k] = (hit >> k & 1u) ? 0u : 0xffffffffu; // (in any order)
+            for (uint32_t k = 0; k < 4u; ++k) key[k] = (out >> k & 1u) ? 0xffffffffu : 0u; // (in any order)
         }
     }
-    return hit;
+    return out;
 }
 // wide_nearest: the slot of the nearest of the children that are entered, and its reference (v_min3 / v_min return the operand that
 // is not a NaN); slot 3 where none is — the caller looks at `hit` first

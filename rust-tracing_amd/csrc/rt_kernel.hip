@@ -206,15 +206,18 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     constexpr uint32_t S_EXIT = LDS != 0 ? 0xffffu : 0xffffffffu;
     constexpr uint32_t SKIP_CHILD0 = LDS != 0 ? 0x4000u : 0x40000000u, SKIP_CHILD1 = LDS != 0 ? 0x8000u : 0x80000000u,
                        NODE_INDEX = SKIP_CHILD0 - 1u;
-    // wide records: an entry is a record's index and, above it, the mask of its children still to look at (all four for a record
-    // the walk comes to for the first time, e.g. an inner child set aside as itself)
-    constexpr uint32_t W_SHIFT = LDS != 0 ? 12u : 26u, W_INDEX = (1u << W_SHIFT) - 1u, W_FULL = WIDE ? (0xfu << W_SHIFT) : 0u;
-    static_assert(WIDE_MAX_LDS_RECORDS <= 0xfffu, "a record's own 2-byte entry (index | W_FULL) must never read as S_EXIT");
+    // wide records: an entry is a record's index and, above it, the mask of its children that are NOT to be looked at any more — so a
+    // record the walk comes to for the first time (e.g. an inner child set aside as itself) is its bare index, which is what a reference
+    // to it is, and the visit uses the mask as it stands (wide_verdict).  An entry with all four bits set is never made.
+    constexpr uint32_t W_SHIFT = LDS != 0 ? 12u : 26u, W_INDEX = (1u << W_SHIFT) - 1u;
+    static_assert(WIDE_MAX_LDS_RECORDS <= 0xfffu, "a record's index must fit below the mask of a 2-byte entry");
     constexpr uint32_t NODE_FRAME_EXIT = 0xffffffffu, NODE_SEQ_NEXT = 0xfffffffeu; // ST_OTHER: leave the current frame / take the next step of the world's sequence
     StackT *const stack = reinterpret_cast<StackT *>(lds_raw + P.lds_stack_off) + threadIdx.x;
-    uint32_t sp = 0;
+    // (the stack's position is the ADDRESS of the lane's next free entry: a push stores through it and a pop reads through it with no
+    // index arithmetic in between, and "empty" is a compare against the lane's level-0 entry)
+    StackT *sp = stack;
     uint32_t seq_pc = 0; // (scenes with media) the next step of the world frame's sequence
-    const uint32_t first_node = ORDERED ? (P.o_root == 0xfffffffeu ? P.o_root : (P.o_root | W_FULL)) : 0u;
+    const uint32_t first_node = ORDERED ? P.o_root : 0u;
     // what a lane does next in an ordered walk: go to `ref` if it has one, else take the last child set aside
     // (written as selects of VALUES: when the branches assign different variables the optimiser turns them into one store
     // through a selected address, and the variables end up in scratch memory — in the hottest loop of the kernel)
@@ -241,13 +244,13 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             // OrderedKind INNER / SPHERES / QUADS / INSTANCE = 0 / 1 / 2 / 3 = Stage ST_BOX / ST_SPHERE / ST_QUAD / ST_OTHER
             const uint32_t kind = ref >> OREF_KIND_SHIFT;
             new_stage = kind;
-            // (an inner record — kind bits 0: the reference is its index — is come to with all four children to look at; an instance's
-            // index goes to ST_OTHER bare; a leaf's lane never reads what lands here)
-            if constexpr (HAS_FRAMES) new_node = kind == OK_INNER ? (ref | W_FULL) : (ref & OREF_INDEX_MASK);
-            else new_node = ref | W_FULL;
-        } else if (sp != 0) { // the last child set aside
-            sp--;
-            const uint32_t e = stack[sp * THREADS];
+            // (an inner record — kind bits 0: the reference is its index, which is its entry with all four children to look at; an
+            // instance's index goes to ST_OTHER bare; a leaf's lane never reads what lands here)
+            if constexpr (HAS_FRAMES) new_node = ref & OREF_INDEX_MASK;
+            else new_node = ref;
+        } else if (sp != stack) { // the last child set aside
+            sp -= THREADS;
+            const uint32_t e = *sp;
             const bool leave_frame = HAS_FRAMES && e == S_EXIT;
             new_node = leave_frame ? NODE_FRAME_EXIT : e;
             new_stage = leave_frame ? (uint32_t)ST_OTHER : (uint32_t)ST_BOX;
@@ -281,7 +284,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                             }
                         }
                         if (jump) {
-                            new_node = seq_tab[k].a | W_FULL;
+                            new_node = seq_tab[k].a;
                             new_stage = ST_BOX;
                             seq_pc = k + 1u;
                         }
@@ -468,7 +471,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 if (miss0 && !(pending && first_step)) continue;
                 first_step = false;
                 if (rec->kind == OSEQ_TREE) {
-                    node = rec->a | W_FULL; sp = 0; stage = ST_BOX;
+                    node = rec->a; sp = stack; stage = ST_BOX;
                 } else if (rec->kind == OSEQ_MEDIUM_SPHERE) {
                     medium_sphere_hit(rec->a, ld3(rec->center), ld3(rec->center_vec), rec->moving != 0, rec->radius, rec->neg_inv_density);
                     // (it may have lowered cur_tmax: the following steps are tested against that)
@@ -478,7 +481,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     mode = 1;
                     cur_tmin = -INF;
                     cur_tmax = INF;
-                    node = rec->b | W_FULL; sp = 0; stage = ST_BOX;
+                    node = rec->b; sp = stack; stage = ST_BOX;
                 }
                 break;
             }
@@ -510,8 +513,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             if (h0 && h1) {
                 const uint32_t far_ref = one_first ? nd.c0 : nd.c1;
                 const uint32_t entry = far_ref < (1u << OREF_KIND_SHIFT) ? far_ref : (nid | (one_first ? SKIP_CHILD1 : SKIP_CHILD0));
-                stack[sp * THREADS] = (StackT)entry;
-                sp++;
+                *sp = (StackT)entry;
+                sp += THREADS;
             }
             o_next(h0 || h1, one_first ? nd.c1 : nd.c0);
         }
@@ -523,14 +526,13 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     auto visit_wide = [&](bool any_degenerate) { // (any_degenerate: wave-uniform, some lane's ray is — rays do not change inside the box loop)
         if constexpr (ORDERED && WIDE) {
             const uint32_t nid = node & W_INDEX;
-            const uint32_t todo = (node >> W_SHIFT) & 0xfu;
             const OQuad nd = load_oquad<LDS>(P, lds_raw, nid, r32.offx, r32.offy, r32.offz);
             if (COUNT) cn.node_visits++;
             float en[4], le[4];
             box_quad_f32(nd, r32, tmin32, tmax32, en, le);
-            // which children are entered, and a key per child to choose the nearest by (rt_device_scene.h)
+            // which children are NOT entered, and a key per child to choose the nearest of the others by (rt_device_scene.h)
             uint32_t key[4];
-            uint32_t hit = wide_verdict(en, le, nd.c, todo, any_degenerate, r32.degenerate, key);
+            uint32_t out = wide_verdict<W_SHIFT>(en, le, nd.c, node, any_degenerate, r32.degenerate, key);
             if constexpr (DEFER) {
                 // the world frame's instances are noted, not entered (see `deferred`); rare, so behind a wave-uniform branch
                 const uint32_t c01 = nd.c[0] > nd.c[1] ? nd.c[0] : nd.c[1], c23 = nd.c[2] > nd.c[3] ? nd.c[2] : nd.c[3];
@@ -538,28 +540,30 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     if (cur_inst < 0) {
         #pragma unroll
                         for (uint32_t k = 0; k < 4u; ++k)
-                            if ((hit >> k & 1u) && (nd.c[k] >> OREF_KIND_SHIFT) == OK_INSTANCE) { deferred |= 1u << (nd.c[k] & 31u); hit &= ~(1u << k); key[k] = 0xffffffffu; }
+                            if (!(out >> k & 1u) && (nd.c[k] >> OREF_KIND_SHIFT) == OK_INSTANCE) { deferred |= 1u << (nd.c[k] & 31u); out |= 1u << k; key[k] = 0xffffffffu; }
                     }
                 }
             }
-            // the nearest of the children that are entered
+            // the nearest of the children that are entered; `gone`: what an entry for the others says is not to be looked at
             uint32_t ref;
             const uint32_t t = wide_nearest(key, nd.c, ref);
-            const uint32_t rest = hit & ~(1u << t);
+            const uint32_t gone = out | (1u << t);
             if (COUNT) {
-                const uint32_t nb = (uint32_t)__popc(todo), went = hit == 0u ? 2u : ((ref >> OREF_KIND_SHIFT) == OK_INNER ? 0u : 1u);
+                const uint32_t todo = ~(node >> W_SHIFT) & 0xfu;
+                const uint32_t nb = (uint32_t)__popc(todo), went = out == 0xfu ? 2u : ((ref >> OREF_KIND_SHIFT) == OK_INNER ? 0u : 1u);
                 const uint32_t slot = todo == 0xfu ? 0u : 1u + 3u * (nb - 1u) + went;
         #pragma unroll
                 for (uint32_t k = 0; k < 10u; ++k) vstat[k] += slot == k ? 1u : 0u;
             }
-            if (rest != 0u) {
-                uint32_t entry = nid | (rest << W_SHIFT);
+            if (gone != 0xfu) {
+                uint32_t entry = nid | (gone << W_SHIFT);
                 // One child left, an inner record: set aside as itself (come to later like any record, all four children to look at),
                 // not as this record again with a one-bit mask — that revisit would load and test four boxes only to pick it.  A leaf
                 // left alone keeps the record-and-mask entry: its box is tested again, against the interval as it has shrunk by then,
                 // before its primitives are.  (Same results: the closest hit does not depend on the order; and no visit more — a child
                 // whose slot box the revisit would have culled has all its own boxes inside that box, so its visit culls them all.)
                 if (P.setaside_direct != 0u) {
+                    const uint32_t rest = gone ^ 0xfu;
                     const uint32_t k = (uint32_t)__builtin_ctz(rest); // (the child left, if it is the only one)
                     uint32_t other;
                     if constexpr (LDS != 0) {
@@ -571,13 +575,14 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         const uint32_t lo = (rest & 1u) ? nd.c[0] : nd.c[1], hi = (rest & 4u) ? nd.c[2] : nd.c[3];
                         other = (rest & 3u) ? lo : hi;
                     }
-                    entry = (rest == (1u << k) && other < (1u << OREF_KIND_SHIFT)) ? (other | W_FULL) : entry;
+                    // (an inner record's reference is its entry)
+                    entry = (rest == (1u << k) && other < (1u << OREF_KIND_SHIFT)) ? other : entry;
                 }
-                if (COUNT) { vstat[10] += (entry >> W_SHIFT) == 0xfu ? 0u : 1u; vstat[11] += (entry >> W_SHIFT) == 0xfu ? 1u : 0u; }
-                stack[sp * THREADS] = (StackT)entry;
-                sp++;
+                if (COUNT) { vstat[10] += (entry >> W_SHIFT) == 0u ? 0u : 1u; vstat[11] += (entry >> W_SHIFT) == 0u ? 1u : 0u; }
+                *sp = (StackT)entry;
+                sp += THREADS;
             }
-            o_next(hit != 0u, ref);
+            o_next(out != 0xfu, ref);
         }
     };
     // COUNT only: per stage, rounds run / lanes active in them / shader cycles spent (wave-level, kept by lane 0)
@@ -666,9 +671,10 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             // stays in this loop (one ballot per round) while enough of the wave's live lanes are walking boxes
             uint32_t in_box;
             const bool any_degenerate = ORDERED && WIDE && __ballot(r32.degenerate) != 0ull;
+            bool walking = stage == ST_BOX; // (ordered walk: the compare behind the round's ballot serves the next round's branch too)
             do {
                 if constexpr (ORDERED) {
-                    if (stage == ST_BOX) { if constexpr (WIDE) visit_wide(any_degenerate); else visit_record(); }
+                    if (walking) { if constexpr (WIDE) visit_wide(any_degenerate); else visit_record(); }
                 } else {
                     if (stage == ST_BOX) {
                         const NodeData nd = load_node<LDS>(P, lds_raw, node);
@@ -691,7 +697,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         if (stage == ST_BOX && node >= n_nodes) stage = ST_SHADE;
                     }
                 }
-                in_box = (uint32_t)__popcll(__ballot(stage == ST_BOX));
+                walking = stage == ST_BOX;
+                in_box = (uint32_t)__popcll(__ballot(walking));
                 if (COUNT && in_box * 64u >= th_box * live && in_box > 0) { prof_add(ST_BOX, 0u, 1); prof_add(ST_BOX, 1u, in_box); }
             } while (in_box * 64u >= th_box * live && in_box > 0);
         } else if (HAS_SPHERES && run == ST_SPHERE) {
@@ -810,7 +817,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     if ((mode & 3u) != 0) { // a boundary query of the medium at the previous step
                         const OSeq *rec = &seq_tab[seq_pc - 1u];
                         again = medium_boundary_done(rec->a, rec->neg_inv_density);
-                        if (again) { node = rec->b | W_FULL; sp = 0; stage = ST_BOX; }
+                        if (again) { node = rec->b; sp = stack; stage = ST_BOX; }
                     }
                     if (!again) seq_advance();
                     refresh_interval32();
@@ -830,8 +837,8 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                         apply_instance(inst_tab[node], o, d);
                         cur_inst = (int32_t)node;
                         if (!from_world) {
-                            stack[sp * THREADS] = (StackT)S_EXIT;
-                            sp++;
+                            *sp = (StackT)S_EXIT;
+                            sp += THREADS;
                         }
                     }
                     // (a frame whose tree is one leaf — a box's faces: straight to the leaf's primitives; the frame's box has been tested
@@ -856,7 +863,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     }
                     if (leaving || nothing) o_next(false, 0u);
                     else {
-                        node = inst_tab[cur_inst].root | W_FULL;
+                        node = inst_tab[cur_inst].root;
                         stage = ST_BOX;
                         if (start != 0u) {
                             stage = start >> OREF_KIND_SHIFT; // (OrderedKind SPHERES / QUADS = Stage ST_SPHERE / ST_QUAD)
@@ -1227,7 +1234,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
             best_t = INF; best_prim = PRIM_NONE; best_inst = -1; cur_inst = -1;
             mode = 0;
             node = first_node;
-            sp = 0;
+            sp = stack;
             stage = ST_BOX;
             if constexpr (ORDERED && !HAS_MEDIA) {
                 // (Measured against visiting the root record right here, with its box tests: 5340 vs 5060 Msamples/s on C2.  The blind
@@ -1271,7 +1278,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     // on as the stage's o_next(false, 0) would: the root's other child, or nothing left to walk
                     const uint32_t rest = P.o_start_rest;
                     stage = ST_SHADE;
-                    if (WIDE ? rest != 0u : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
+                    if (WIDE ? rest != 0xffffffffu : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
                         uint32_t e;
                         if constexpr (WIDE) e = (StackT)rest;
                         else e = (StackT)(rest < (1u << OREF_KIND_SHIFT) ? rest : (first_node | (P.o_start_slot ? SKIP_CHILD1 : SKIP_CHILD0)));
@@ -1281,10 +1288,10 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     }
                 } else if (P.o_start_stage != 0u) { // the root's big leaf first, its other child set aside (rt_api.cpp "start shortcut")
                     const uint32_t rest = P.o_start_rest;
-                    if (WIDE ? rest != 0u : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
+                    if (WIDE ? rest != 0xffffffffu : (rest >> OREF_KIND_SHIFT) != OK_EMPTY) {
                         if constexpr (WIDE) stack[0] = (StackT)rest; // (rest: the entry itself, made on the host in this launch's format)
                         else stack[0] = (StackT)(rest < (1u << OREF_KIND_SHIFT) ? rest : (first_node | (P.o_start_slot ? SKIP_CHILD1 : SKIP_CHILD0)));
-                        sp = 1;
+                        sp = stack + THREADS;
                     }
                     // (the leaf's packed reference, as o_next hands it over, put together from the kernel arguments: scalar work)
                     prim_cur = (P.o_start_stage << OREF_KIND_SHIFT) | ((P.o_start_end - P.o_start_prim - 1u) << OREF_COUNT_SHIFT) | P.o_start_prim;
@@ -1786,9 +1793,11 @@ template <int LDS> __global__ __launch_bounds__(DEBUG_WIDE_THREADS) void debug_w
     const OQuad nd = load_oquad<LDS>(P, reinterpret_cast<const unsigned char *>(staged), id, rp.offx, rp.offy, rp.offz);
     float en[4], le[4];
     box_quad_f32(nd, rp, f32_below(tmin), f32_above(tmax), en, le);
-    const uint32_t todo = a.todo[idx] & 0xfu;
+    // (the record's entry as the walk would hold it — the kernels' two formats: 2-byte entries in the LDS, 4-byte ones in global memory)
+    constexpr uint32_t W_SHIFT = LDS != 0 ? 12u : 26u;
+    const uint32_t node = (~a.todo[idx] & 0xfu) << W_SHIFT;
     uint32_t key[4], ref;
-    const uint32_t hit = wide_verdict(en, le, nd.c, todo, any_degenerate, rp.degenerate, key);
+    const uint32_t hit = wide_verdict<W_SHIFT>(en, le, nd.c, node, any_degenerate, rp.degenerate, key) ^ 0xfu;
     const uint32_t t = wide_nearest(key, nd.c, ref);
     for (int k = 0; k < 4; ++k) { a.enter[idx * 4 + k] = en[k]; a.leave[idx * 4 + k] = le[k]; }
     a.hit[idx] = (uint8_t)hit;

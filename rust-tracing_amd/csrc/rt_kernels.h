@@ -92,8 +92,8 @@ struct KParams {
     uint32_t o_root;
     // a query may start with the primitives of a leaf under the root instead of the root record (rt_api.cpp "start shortcut"): the stage of the
     // leaf's kind (ST_SPHERE / ST_QUAD; 0: no shortcut), its primitives [prim, end), the root's other child, which child of the root the leaf is
-    // (wide records: o_start_rest is the stack entry itself, in the launch's format — the root with the mask of its other children, or the
-    // one other child's own entry if that is an inner record (setaside_direct); 0: nothing to set aside)
+    // (wide records: o_start_rest is the stack entry itself, in the launch's format — the root with the mask of its children NOT to look at, or the
+    // one other child's own entry, its index, if that is an inner record (setaside_direct); all ones: nothing to set aside)
     uint32_t o_start_stage, o_start_prim, o_start_end, o_start_rest, o_start_slot;
     uint32_t setaside_direct;       // wide records: 1 = a record with one child left to look at sets that child aside itself if it is an inner record (RT_WIDE_SETASIDE)
     uint32_t inst_shortcut;         // 1: a walk that enters a frame whose tree is one leaf starts with the leaf's primitives (Instance::start_ref)
