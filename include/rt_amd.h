@@ -581,6 +581,86 @@ int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum,
                              int32_t albedo_spp /* >= 1 */, const rt_denoise_albedo_params *params /* NULL: defaults */,
                              double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- surface-ID scene and edge-guided denoise (opt-in; nothing above changes) ------------------------------------------------------------
+ * Neither filter above can stop at a GEOMETRIC edge between two surfaces of one colour: the luminance stop sees only the noisy frame, and
+ * the albedo frame of a white box in front of a white wall is flat.  A per-pixel "which surface did the first hit land on" frame can,
+ * and it needs no new render path either: it is an ordinary render of the SURFACE-ID SCENE of a description.
+ *
+ * Surface-ID scene.  The same geometry with every primitive and every medium given one of RT_SURFACE_ID_COLOURS palette colours, as a
+ * DIFFUSE_LIGHT of a SOLID texture.  As in an albedo scene a light does not scatter, and the camera's and the media's draws come before
+ * a material's: path (seed, p, s) of the ID scene ends at the first hit of path (seed, p, s) of the original and returns that surface's
+ * colour — lens, shutter and the random hit inside a constant medium included — so the frame is anti-aliased by the beauty frame's own
+ * samples.  Normative rule (rt_surface_id_tables):
+ *   Palette entry q, 1 <= q <= 26, is the colour (0.5 * (q % 3), 0.5 * ((q / 3) % 3), 0.5 * (q / 9)) in integer arithmetic: every
+ *   channel is 0, 0.5 or 1, each exactly representable, and black (q = 0) is not in the palette.  Two different entries differ by at
+ *   least 0.5 in some channel.
+ *   out_textures[i], i = 0 .. 25, is {kind SOLID, even = odd = image = perlin = -1, _pad 0, color = palette entry i + 1, inv_scale 0,
+ *   scale 0};  out_materials[i] is {DIFFUSE_LIGHT, texture i, albedo, fuzz and ir zero}.
+ *   Surfaces are numbered k = 0, 1, ... in this order: spheres in array order, then quads, then media.  Surface k uses material k % 26,
+ *   so any 26 consecutive surfaces of a description get distinct colours.
+ *   out_spheres and out_quads are copies of desc->spheres and desc->quads with only `material` rewritten; out_media are copies of
+ *   desc->media with only `phase_material` rewritten.  The description's own materials and textures are not read.
+ * rt_surface_id_tables touches no device.  RT_ERR_INVALID_ARGUMENT (the message names the field), in this order: a null desc,
+ * out_spheres, out_quads, out_media, out_materials or out_textures (each is required even where its count is 0); abi_version other
+ * than RT_ABI_VERSION; a negative n_spheres, n_quads or n_media, or a null spheres / quads / media array with a non-zero count.
+ * Nothing is written then.
+ * rt_scene_create_surface_ids is rt_scene_create_ex on `desc` with those five tables and n_materials = n_textures = 26 swapped in:
+ * everything else — lists, transforms, trees, options — is the caller's.  Every texture of an ID scene is a SOLID, so it is rendered
+ * by the kernel class of its geometry with solid textures, whatever the original's textures were (an image- or noise-textured original
+ * is rendered by another kernel than its ID scene).
+ * The caller's CAMERA decides what a miss contributes.  The layers above this ABI render the ID scene with the beauty camera and
+ * background = (0, 0, 0): black is no palette colour, so the background is a surface of its own to the filter below. */
+#define RT_SURFACE_ID_COLOURS 26
+int rt_surface_id_tables(const rt_scene_desc *desc, rt_sphere *out_spheres /* desc->n_spheres */, rt_quad *out_quads /* desc->n_quads */,
+                         rt_constant_medium *out_media /* desc->n_media */, rt_material *out_materials /* RT_SURFACE_ID_COLOURS */,
+                         rt_texture *out_textures /* RT_SURFACE_ID_COLOURS */);
+int rt_scene_create_surface_ids(const rt_scene_desc *desc, int device, const rt_scene_options *options /* NULL: defaults */,
+                                rt_scene **out_scene);
+
+/* rt_denoise_guided_device is rt_denoise_albedo_device — or, with d_albedo_sum NULL, rt_denoise_device — with an EDGE GUIDE beside
+ * its inputs: d_edge_sum holds 3 * w * h doubles, the per-pixel sums of edge_spp samples of a guide frame (a surface-ID scene's render,
+ * an albedo scene's, or any other frame whose edges the filter should respect).  An edge guide contributes one stop factor per tap and
+ * nothing else: nothing is divided by it and nothing is multiplied back in.  The contract is the other filters': enqueued on
+ * hip_stream, not synchronised, nothing allocated; d_workspace is rt_denoise_guided_workspace_bytes(w, h, d_albedo_sum != NULL) bytes
+ * of device memory, 16-byte aligned.  With d_albedo_sum NULL, albedo_spp, sigma_albedo and albedo_floor are not read.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: width or height < 1 or w * h >= 2^27; a null d_sum,
+ * d_sum_sq, d_edge_sum, d_mean_out or d_workspace; spp < 2 when d_spp is NULL; with an albedo frame, albedo_spp < 1; edge_spp < 1; a
+ * struct_size this library does not know; iterations outside 1..6; sigma or eps that is not a number > 0; with an albedo frame, a
+ * sigma_albedo or albedo_floor that is not a number > 0; a sigma_edge that is not a number > 0; d_mean_out overlapping d_sum, d_sum_sq
+ * or d_albedo_sum; d_mean_out overlapping d_edge_sum; a d_rgba8 that is not 4-byte aligned; a d_workspace that is not 16-byte aligned.
+ *
+ * Normative definition.  Everything is as in rt_denoise_albedo_device (with d_albedo_sum NULL: as in rt_denoise_device), f64 with every
+ * operation rounded on its own, with these additions; E is p's entry of d_edge_sum and n_e = edge_spp as a double:
+ *   Prepare.   g_c = E_c / n_e.  A VALID pixel also needs all three E_c finite.  C0 and V0 are what they are without the edge guide.
+ *   Iteration. One more factor per tap:
+ *                   dg = max(max(|g_r(p) - g_r(q)|, |g_g(p) - g_g(q)|), |g_b(p) - g_b(q)|)
+ *                   z = dg / sigma_edge;  tg = 1 - z * z;  eg = (tg > 0 ? tg * tg : 0)
+ *                   w = (h[dy] * h[dx]) * ((e * ea) * eg)   with an albedo frame,   w = (h[dy] * h[dx]) * (e * eg)   without
+ *              (sw >= 9/64 still: the centre tap has eg = 1)
+ *   Output.    As without the edge guide: it is not multiplied in.
+ * With E_c the same value at every pixel, dg = 0, z = 0, tg = 1, eg = 1 and x * 1 = x, each exactly: the result is
+ * rt_denoise_albedo_device's (rt_denoise_device's) bit for bit.  The means (live), spatial-variance and views forms have no edge guide. */
+typedef struct rt_denoise_guided_params {
+    uint32_t struct_size;   /* sizeof(rt_denoise_guided_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t iterations;     /* K, 1..6 (default 4): strides 1, 2, 4, ... 2^(K-1) */
+    double sigma;           /* as rt_denoise_params (default 4.0), > 0 */
+    double eps;             /* as rt_denoise_params (default 1e-6), > 0 */
+    double sigma_albedo;    /* as rt_denoise_albedo_params (default 0.5), > 0; read only with an albedo frame */
+    double albedo_floor;    /* as rt_denoise_albedo_params (default 1e-3), > 0; read only with an albedo frame */
+    double sigma_edge;      /* width of the edge guide's stop: a tap whose guide differs by this much or more in any channel has weight 0
+                               (default 0.5: two surface-ID colours differ by at least that), > 0 */
+} rt_denoise_guided_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_denoise_guided_params_init_sized(rt_denoise_guided_params *params, uint32_t struct_size);
+/* Bytes of device memory rt_denoise_guided_device needs for a w x h frame: the two halves and the edge guide's region, and with
+ * with_albedo != 0 the albedo guide's as well (three or four regions of 4 doubles per pixel); -1 for a size it refuses. */
+int64_t rt_denoise_guided_workspace_bytes(int32_t width, int32_t height, int32_t with_albedo);
+int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                             const int32_t *d_spp /* NULL: uniform spp */, const double *d_albedo_sum /* 3*w*h, or NULL: no albedo guide */,
+                             int32_t albedo_spp /* >= 1 with an albedo frame */, const double *d_edge_sum /* 3*w*h */,
+                             int32_t edge_spp /* >= 1 */, const rt_denoise_guided_params *params /* NULL: defaults */,
+                             double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
 /* ---- live denoise: a running second moment beside the running mean, and the filters on (mean, M2) (opt-in; nothing above changes) ----
  * Live refinement shows the noisiest frames there are — 1, 2, 3 ... samples per pixel — and a running mean keeps no second moment, so
  * neither filter above can take its frame.  These calls close that gap: a reduction that keeps Welford's M2 beside the mean, and a

@@ -249,6 +249,23 @@ def denoise_albedo_params(**kw) -> "DenoiseAlbedoParams":
     return d
 
 
+class DenoiseGuidedParams(C.Structure):
+    """rt_denoise_guided_params (rt_denoise_guided_device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma", C.c_double), ("eps", C.c_double),
+                ("sigma_albedo", C.c_double), ("albedo_floor", C.c_double), ("sigma_edge", C.c_double)]
+
+
+def denoise_guided_params(**kw) -> "DenoiseGuidedParams":
+    """rt_denoise_guided_params_init_sized, then the given fields (iterations=, sigma=, eps=, sigma_albedo=, albedo_floor=, sigma_edge=)."""
+    d = DenoiseGuidedParams()
+    _check(amd_lib().rt_denoise_guided_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_guided_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(DenoiseGuidedParams._fields_):
+            raise TypeError(f"rt_denoise_guided_params has no field {k}")
+        setattr(d, k, v)
+    return d
+
+
 class DenoiseSpatialParams(C.Structure):
     """rt_denoise_spatial_params (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device)."""
     _fields_ = [("struct_size", C.c_uint32), ("spatial_below", C.c_int32), ("window_radius", C.c_int32)]
@@ -331,6 +348,12 @@ RT_AMD_SYMBOLS = {
     "rt_denoise_albedo_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_denoise_albedo_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_surface_id_tables": (C.c_int, [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_create_surface_ids": (C.c_int, [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rt_denoise_guided_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_denoise_guided_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_denoise_guided_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_render_mean_moments_device": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
     "rt_render_mean_moments": (C.c_int, [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -803,18 +826,25 @@ class DeviceScene:
     """rt_scene handle: the compiled scene resident in one GPU's HBM."""
 
     def __init__(self, host_scene: HostScene, device: int = 0, options: "SceneCreateOptions | None" = None, albedo: bool = False,
-                 **option_fields):
+                 surface_ids: bool = False, **option_fields):
         """albedo=True: rt_scene_create_albedo, the scene whose render is the first-hit albedo frame (render it with
-        albedo_camera(camera): a miss then contributes (1, 1, 1))."""
+        albedo_camera(camera): a miss then contributes (1, 1, 1)).  surface_ids=True: rt_scene_create_surface_ids, the scene whose
+        render is the first-hit surface-ID frame (render it with surface_id_camera(camera): a miss then contributes (0, 0, 0))."""
         lib = amd_lib()
         self.host_scene = host_scene  # keeps desc memory alive during create
         self.device = device
         self.albedo = bool(albedo)
+        self.surface_ids = bool(surface_ids)
+        if albedo and surface_ids:
+            raise RtError("DeviceScene: albedo and surface_ids are two scenes of a description: give one of them")
         handle = C.c_void_p()
         if option_fields:
             assert options is None
             options = scene_options(**option_fields)
-        if albedo:
+        if surface_ids:
+            _check(lib.rt_scene_create_surface_ids(C.byref(host_scene.desc), device, C.byref(options) if options is not None else None,
+                                                   C.byref(handle)), "rt_scene_create_surface_ids")
+        elif albedo:
             _check(lib.rt_scene_create_albedo(C.byref(host_scene.desc), device, C.byref(options) if options is not None else None,
                                               C.byref(handle)), "rt_scene_create_albedo")
         elif options is None:
@@ -1163,6 +1193,83 @@ def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rg
         denoise_albedo_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_alb.data_ptr(), int(albedo_spp), d_out.data_ptr(),
                               d_ws.data_ptr(), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0,
                               d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+RT_SURFACE_ID_COLOURS = 26
+
+
+def surface_id_tables(host_scene):
+    """rt_surface_id_tables (GPU-free): (spheres, quads, media, materials, textures), ctypes arrays — the description's spheres, quads
+    and media with their material rewritten to the surface's palette entry, and the 26 DIFFUSE_LIGHT materials and SOLID textures of
+    the palette: the tables of the scene's surface-ID scene."""
+    desc = host_scene.desc
+    sph = (Sphere * max(1, desc.n_spheres))()
+    qua = (Quad * max(1, desc.n_quads))()
+    med = (ConstantMedium * max(1, desc.n_media))()
+    mats = (Material * RT_SURFACE_ID_COLOURS)()
+    texs = (Texture * RT_SURFACE_ID_COLOURS)()
+    _check(amd_lib().rt_surface_id_tables(C.byref(desc), C.addressof(sph), C.addressof(qua), C.addressof(med), C.addressof(mats),
+                                          C.addressof(texs)), "rt_surface_id_tables")
+    return ((Sphere * desc.n_spheres).from_buffer_copy(sph), (Quad * desc.n_quads).from_buffer_copy(qua),
+            (ConstantMedium * desc.n_media).from_buffer_copy(med), mats, texs)
+
+
+def surface_id_camera(camera: Camera) -> Camera:
+    """The camera a surface-ID scene is rendered with: `camera` with background (0, 0, 0), which is no palette colour."""
+    cam = Camera.from_buffer_copy(camera)
+    cam.background = Vec3(0.0, 0.0, 0.0)
+    return cam
+
+
+def denoise_guided_workspace_bytes(width, height, with_albedo) -> int:
+    n = int(amd_lib().rt_denoise_guided_workspace_bytes(width, height, 1 if with_albedo else 0))
+    if n < 0:
+        raise RtError(f"rt_denoise_guided_workspace_bytes: no workspace for a {width}x{height} frame")
+    return n
+
+
+def denoise_guided_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int, d_edge_sum_ptr: int,
+                          edge_spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0, d_rgba8_ptr: int = 0,
+                          params: "DenoiseGuidedParams | None" = None, stream: int = 0):
+    """rt_denoise_guided_device: rt_denoise_albedo_device (d_albedo_sum_ptr 0: rt_denoise_device) with a device frame of edge-guide sums
+    (3 w h doubles, `edge_spp` samples, e.g. of the surface-ID scene) beside its inputs; `d_workspace_ptr`:
+    denoise_guided_workspace_bytes(w, h, d_albedo_sum_ptr != 0) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_guided_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
+                                              C.c_void_p(d_albedo_sum_ptr or None), albedo_spp, C.c_void_p(d_edge_sum_ptr or None), edge_spp,
+                                              C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                              C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_guided_device")
+
+
+def denoise_guided(sum, sum_sq, spp, edge_sum, edge_spp, *, albedo_sum=None, albedo_spp=0, spp_map=None, rgba8=False, device=0, **kw):
+    """Uploads (h, w, 3) frames of sums, sums of squares and edge-guide sums (and albedo sums and an (h, w) int32 spp map, if given),
+    runs rt_denoise_guided_device with denoise_guided_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or
+    (means, (h, w, 4) uint8) with rgba8."""
+    import numpy as np
+    given = [sum, sum_sq, edge_sum] + ([albedo_sum] if albedo_sum is not None else [])
+    frames = [np.ascontiguousarray(a, dtype=np.float64) for a in given]
+    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError("denoise_guided: `sum`, `sum_sq`, `edge_sum` and `albedo_sum` must be (h, w, 3) frames of one shape")
+    h, w = frames[0].shape[:2]
+    if spp_map is not None:
+        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if spp_map.shape != (h, w):
+            raise RtError(f"denoise_guided: `spp_map` must have shape {(h, w)}")
+    params = denoise_guided_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        dev = [torch.from_numpy(a).cuda() for a in frames]
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_out = torch.empty_like(dev[0])
+        d_ws = torch.empty(denoise_guided_workspace_bytes(w, h, albedo_sum is not None), dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        denoise_guided_device(w, h, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), dev[3].data_ptr() if albedo_sum is not None else 0,
+                              int(albedo_spp), dev[2].data_ptr(), int(edge_spp), d_out.data_ptr(), d_ws.data_ptr(),
+                              d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0,
+                              params=params, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         out = d_out.cpu().numpy()
         return (out, d_rgba.cpu().numpy()) if rgba8 else out

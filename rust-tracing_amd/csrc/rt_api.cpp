@@ -1621,7 +1621,8 @@ int render_moments(rt_scene *s, const rt_camera *camera, const rt_render_params 
     return launch_render(s, camera, p, d_sum, stream, nullptr, &pl);
 }
 
-// the two params structs of the denoisers (rt_denoise_params, and rt_denoise_albedo_params = its fields and two more): defaults, the
+// the params structs of the denoisers (rt_denoise_params, rt_denoise_albedo_params = its fields and two more, and
+// rt_denoise_guided_params = those and sigma_edge): defaults, the
 // struct sizes this library knows, the body of *_params_init_sized.  (Templates: C++ linkage inside this file's extern "C".)
 extern "C++" {
 inline void denoise_defaults(rt_denoise_spatial_params &d) { // (DESIGN.md section 5 "Spatial variance": the CPU sweep)
@@ -1636,10 +1637,11 @@ template <class P> void denoise_defaults(P &d) {
     d.iterations = 4;
     d.sigma = 4.0;
     d.eps = 1e-6;
-    if constexpr (std::is_same_v<P, rt_denoise_albedo_params>) {
+    if constexpr (std::is_same_v<P, rt_denoise_albedo_params> || std::is_same_v<P, rt_denoise_guided_params>) {
         d.sigma_albedo = 0.5; // (DESIGN.md section 5 "Albedo-guided denoise": the CPU sweep)
         d.albedo_floor = 1e-3;
     }
+    if constexpr (std::is_same_v<P, rt_denoise_guided_params>) d.sigma_edge = 0.5; // (DESIGN.md section 5 "Edge-guided denoise")
 }
 template <class P> bool denoise_size_known(uint32_t size) {
     if constexpr (std::is_same_v<P, rt_denoise_spatial_params>) return size >= 8 && size <= sizeof(P) && size % 4 == 0; // (its fields are words)
@@ -1693,6 +1695,8 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 // `stack` (rt_denoise_views_device, rt_denoise_albedo_views_device; sums form, no map) is a stack of n_views frames, view-major in every
 // buffer and in every region of the workspace, filtered in the same K + 1 launches with the view on the grid's second dimension; its
 // count is checked behind the frame size.  Null is the single frame: a stack of one, launch for launch.
+// `edge` (rt_denoise_guided_device; sums form, single frame) is the edge guide, with or without `guide`; its region is set here, the third
+// of the workspace alone and the fourth beside the albedo guide's.  Each of its checks sits behind the albedo guide's of the same kind.
 enum class DenoiseInput { Sums, Means };
 struct SpatialRoute {
     rt_denoise_spatial_params params;
@@ -1700,7 +1704,7 @@ struct SpatialRoute {
 };
 int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
                 const int32_t *d_spp, DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
-                void *hip_stream, const SpatialRoute *spatial = nullptr, const int32_t *stack = nullptr) {
+                void *hip_stream, const SpatialRoute *spatial = nullptr, const int32_t *stack = nullptr, DenoiseEdge *edge = nullptr) {
     const std::string w(who);
     const bool means = form == DenoiseInput::Means;
     const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum";
@@ -1713,11 +1717,13 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
     if (!d_sum_sq && !spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
     if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
+    if (edge && !edge->edge_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_edge_sum is null");
     if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
     if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
     if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
     if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples)" + (stack ? "" : " when d_spp is null"));
     if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    if (edge && edge->edge_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": edge_spp must be at least 1");
     bool spatial_route = false;
     if (spatial) {
         const rt_denoise_spatial_params &sp = spatial->params;
@@ -1729,16 +1735,18 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
             return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null (it is read when samples >= spatial_below)");
     }
     if (!d)
-        return fail(RT_ERR_INVALID_ARGUMENT, w + (guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
+        return fail(RT_ERR_INVALID_ARGUMENT, w + (edge ? ": rt_denoise_guided_params" : guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
     if (d->iterations < 1 || d->iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
     if (!(d->sigma > 0.0) || !std::isfinite(d->sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
     if (!(d->eps > 0.0) || !std::isfinite(d->eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
     if (guide && (!(guide->sigma_albedo > 0.0) || !std::isfinite(guide->sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
     if (guide && (!(guide->albedo_floor > 0.0) || !std::isfinite(guide->albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
+    if (edge && (!(edge->sigma_edge > 0.0) || !std::isfinite(edge->sigma_edge))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_edge must be a number > 0");
     const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = (size_t)n_views * n_pix * 3u * sizeof(double); // (the whole stack's)
     if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || (d_sum_sq && overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes)) ||
         (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
+    if (edge && overlaps(d_mean_out, frame_bytes, edge->edge_sum, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_edge_sum");
     if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
     if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
     if (int rc = select_device_of(d_mean_out, who)) return rc;
@@ -1746,13 +1754,14 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     const size_t region = (size_t)n_views * n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
     char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
     if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
+    if (edge) edge->region = (double4 *)((char *)d_workspace + (guide ? 3u : 2u) * region); // (alone: the albedo guide's place)
     if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream);
-    else launch_denoise_prepare((int64_t)n_pix, n_views, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream);
+    else launch_denoise_prepare((int64_t)n_pix, n_views, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream, edge);
     HIP_TRY(hipGetLastError());
     for (int32_t k = 0; k < d->iterations; ++k) {
         const bool last = k == d->iterations - 1;
         launch_denoise_atrous(width, height, n_views, (int32_t)1 << k, d->sigma, d->eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
-                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream);
+                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream, edge);
         HIP_TRY(hipGetLastError());
     }
     return RT_OK;
@@ -1969,6 +1978,95 @@ int rt_denoise_albedo_mean_spatial_device(int32_t width, int32_t height, const d
     route.known = denoise_params_resolve(spatial, route.params);
     return run_denoise("rt_denoise_albedo_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
                        known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route);
+}
+
+// ---- surface-ID scene and the edge-guided filter (rt_denoise.hip, with an edge guide) ----
+int rt_surface_id_tables(const rt_scene_desc *desc, rt_sphere *out_spheres, rt_quad *out_quads, rt_constant_medium *out_media, rt_material *out_materials,
+                         rt_texture *out_textures) {
+    const std::string w("rt_surface_id_tables");
+    if (!desc) return fail(RT_ERR_INVALID_ARGUMENT, w + ": desc is null");
+    if (!out_spheres) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_spheres is null");
+    if (!out_quads) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_quads is null");
+    if (!out_media) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_media is null");
+    if (!out_materials) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_materials is null");
+    if (!out_textures) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_textures is null");
+    if (desc->abi_version != RT_ABI_VERSION) return fail(RT_ERR_INVALID_ARGUMENT, w + ": abi_version mismatch");
+    if (desc->n_spheres < 0 || (desc->n_spheres > 0 && !desc->spheres))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": spheres is a null array with a non-zero count, or n_spheres is negative");
+    if (desc->n_quads < 0 || (desc->n_quads > 0 && !desc->quads))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": quads is a null array with a non-zero count, or n_quads is negative");
+    if (desc->n_media < 0 || (desc->n_media > 0 && !desc->media))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": media is a null array with a non-zero count, or n_media is negative");
+    // every check before the first write
+    for (int32_t i = 0; i < RT_SURFACE_ID_COLOURS; ++i) {
+        const int32_t q = i + 1; // the palette entry: black, q = 0, is not in it
+        rt_texture t;
+        memset(&t, 0, sizeof t);
+        t.kind = RT_TEXTURE_SOLID;
+        t.even = t.odd = t.image = t.perlin = -1;
+        t.color = rt_vec3{0.5 * (double)(q % 3), 0.5 * (double)((q / 3) % 3), 0.5 * (double)(q / 9)};
+        out_textures[i] = t;
+        rt_material m;
+        memset(&m, 0, sizeof m);
+        m.kind = RT_MATERIAL_DIFFUSE_LIGHT;
+        m.texture = i;
+        out_materials[i] = m;
+    }
+    int64_t k = 0; // the surface's number: spheres, then quads, then media
+    for (int32_t i = 0; i < desc->n_spheres; ++i, ++k) {
+        out_spheres[i] = desc->spheres[i];
+        out_spheres[i].material = (int32_t)(k % RT_SURFACE_ID_COLOURS);
+    }
+    for (int32_t i = 0; i < desc->n_quads; ++i, ++k) {
+        out_quads[i] = desc->quads[i];
+        out_quads[i].material = (int32_t)(k % RT_SURFACE_ID_COLOURS);
+    }
+    for (int32_t i = 0; i < desc->n_media; ++i, ++k) {
+        out_media[i] = desc->media[i];
+        out_media[i].phase_material = (int32_t)(k % RT_SURFACE_ID_COLOURS);
+    }
+    return RT_OK;
+}
+
+int rt_scene_create_surface_ids(const rt_scene_desc *desc, int device, const rt_scene_options *options, rt_scene **out_scene) {
+    if (!desc || !out_scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_create_surface_ids: null argument");
+    *out_scene = nullptr;
+    if (desc->n_spheres < 0 || desc->n_quads < 0 || desc->n_media < 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, "rt_scene_create_surface_ids: n_spheres, n_quads or n_media is negative");
+    std::vector<rt_sphere> spheres((size_t)desc->n_spheres + 1u);
+    std::vector<rt_quad> quads((size_t)desc->n_quads + 1u);
+    std::vector<rt_constant_medium> media((size_t)desc->n_media + 1u);
+    std::vector<rt_material> materials(RT_SURFACE_ID_COLOURS);
+    std::vector<rt_texture> textures(RT_SURFACE_ID_COLOURS);
+    if (int rc = rt_surface_id_tables(desc, spheres.data(), quads.data(), media.data(), materials.data(), textures.data())) return rc;
+    rt_scene_desc ids = *desc;
+    ids.spheres = spheres.data();
+    ids.quads = quads.data();
+    ids.media = media.data();
+    ids.materials = materials.data();
+    ids.textures = textures.data();
+    ids.n_materials = ids.n_textures = RT_SURFACE_ID_COLOURS;
+    return rt_scene_create_ex(&ids, device, options, out_scene);
+}
+
+int rt_denoise_guided_params_init_sized(rt_denoise_guided_params *params, uint32_t struct_size) {
+    return denoise_params_init_sized(params, struct_size, "rt_denoise_guided_params_init_sized");
+}
+
+int64_t rt_denoise_guided_workspace_bytes(int32_t width, int32_t height, int32_t with_albedo) {
+    return denoise_workspace_bytes(width, height, with_albedo ? 4 : 3);
+}
+
+int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                             const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
+                             const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_guided_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr}; // (used only with an albedo frame)
+    DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
+    return run_denoise("rt_denoise_guided_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum ? &guide : nullptr,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

@@ -8,7 +8,12 @@
 // compile-time parameter, the input form: sums and sums of squares, or (Means: rt_denoise_mean_device, rt_denoise_albedo_mean_device)
 // the live route's running means and Welford's M2; the iterations do not know which it was.  A third prepare, a tile kernel, serves
 // frames of so few samples that M2 says nothing (rt_denoise_mean_spatial_device, "spatial variance"): it takes V0 from the spread of the
-// neighbouring pixels' values.
+// neighbouring pixels' values.  The guide is a small compile-time mode (DN_PLAIN, DN_ALBEDO, DN_EDGES, DN_BOTH below): an EDGE guide
+// (rt_denoise_guided_device, "edge-guided denoise") is a guide frame that contributes one more stop factor per tap and nothing else —
+// no division in prepare, nothing multiplied back — alone, where it reuses the albedo mode's guide region, planes and loads, or beside
+// the albedo guide, with a fourth region of the workspace, three more staged planes (eleven: 40 x 16 x 11 x 8 B = 56 320 B at stride
+// 2, two workgroups per CU) and a third double4 per gathered tap.  The plain and albedo instantiations hold none of it: their
+// instruction streams are what they were before the mode existed.
 //
 // Everything is f64 in the header's operation order, each operation rounded on its own (the file is compiled with
 // -ffp-contract=off and without fast-math: no FMA, IEEE division and square root), so a frame equals the numpy restatement in
@@ -39,9 +44,32 @@ namespace {
 
 constexpr int DN_TW = 32, DN_TH = 8, DN_THREADS = DN_TW * DN_TH;
 
-// what a kernel gets of the guide: the launcher's description, or — the plain instantiations — nothing, so no argument of theirs is live
+// the guides of an instantiation, a small mode: none, the demodulating albedo guide, an edge guide (rt_denoise_guided_device: one stop
+// factor per tap and nothing else), or both.  Edges alone reuses what the albedo mode has for its guide — the third region of the
+// workspace, the planes P_AR .. P_AB, a tap's (ar, ag, ab) — for the edge guide's means, without the albedo mode's divisions; beside
+// the albedo guide the edge guide has a region, three planes and three tap fields (er, eg, eb) of its own.
+constexpr int DN_PLAIN = 0, DN_ALBEDO = 1, DN_EDGES = 2, DN_BOTH = 3;
+constexpr bool demodulates(int mode) { return (mode & DN_ALBEDO) != 0; }
+constexpr bool has_edges(int mode) { return (mode & DN_EDGES) != 0; }
+constexpr int guide_mode(bool guided) { return guided ? DN_ALBEDO : DN_PLAIN; } // (the means and spatial forms: no edge guide)
+
+// what a kernel gets of the guides: the launcher's description(s), or — the plain instantiations — nothing, so no argument of theirs is live
 struct NoGuide {};
-template <bool Guided> using GuideOf = std::conditional_t<Guided, rtk::DenoiseGuide, NoGuide>;
+struct BothGuides { rtk::DenoiseGuide albedo; rtk::DenoiseEdge edge; };
+template <int Mode>
+using GuideOf = std::conditional_t<Mode == DN_PLAIN, NoGuide,
+                                   std::conditional_t<Mode == DN_ALBEDO, rtk::DenoiseGuide, std::conditional_t<Mode == DN_EDGES, rtk::DenoiseEdge, BothGuides>>>;
+__device__ __forceinline__ const rtk::DenoiseGuide &albedo_of(const rtk::DenoiseGuide &g) { return g; }
+__device__ __forceinline__ const rtk::DenoiseGuide &albedo_of(const BothGuides &g) { return g.albedo; }
+__device__ __forceinline__ const rtk::DenoiseEdge &edge_of(const rtk::DenoiseEdge &g) { return g; }
+__device__ __forceinline__ const rtk::DenoiseEdge &edge_of(const BothGuides &g) { return g.edge; }
+// the first guide (what the third region, P_AR .. P_AB and (ar, ag, ab) hold): its region and the width of its stop
+__device__ __forceinline__ double4 *first_region(const rtk::DenoiseGuide &g) { return g.region; }
+__device__ __forceinline__ double4 *first_region(const rtk::DenoiseEdge &g) { return g.region; }
+__device__ __forceinline__ double4 *first_region(const BothGuides &g) { return g.albedo.region; }
+__device__ __forceinline__ double first_sigma(const rtk::DenoiseGuide &g) { return g.sigma_albedo; }
+__device__ __forceinline__ double first_sigma(const rtk::DenoiseEdge &g) { return g.sigma_edge; }
+__device__ __forceinline__ double first_sigma(const BothGuides &g) { return g.albedo.sigma_albedo; }
 
 // rt_kernel.hip's display_rgba8 (color_to_rgb(mean) with alpha 0xff, one little-endian word): the shared host / device code of
 // rt_shared_math.h per value, so the bytes are rt_resolve_rgba8_device's
@@ -60,10 +88,14 @@ __device__ __forceinline__ double max_ab(double a, double b) { return b > a ? b 
 // Means (rt_denoise_mean_device, rt_denoise_albedo_mean_device: the live route's frames): `sum` holds the running means m and `sum_sq`
 // Welford's M2 after n = spp samples of every pixel (no map), the guide's frame the albedo means a: nothing is divided by a count, and
 // v_c = M2_c / (n - 1).  Everything else is the sums form's, which holds none of this.
-template <bool Guided, bool Means>
+// An edge guide (Mode with DN_EDGES; sums form): g = E / n_e is written to its region, a pixel with a non-finite E is not valid, and
+// C0 and V0 are not touched by it.
+template <int Mode, bool Means>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_pixels, const double *__restrict__ sum, const double *__restrict__ sum_sq,
-                                                                      int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Guided> gd,
+                                                                      int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Mode> gd,
                                                                       double4 *__restrict__ out) {
+    constexpr bool Guided = demodulates(Mode);
+    static_assert(!(Means && has_edges(Mode)), "the edge guide has no means form");
     const int64_t in_frame = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
     if (in_frame >= n_pixels) return;
     const size_t idx = (size_t)blockIdx.y * (size_t)n_pixels + (size_t)in_frame; // the pixel in the stack of views (n_pixels: one frame's)
@@ -74,15 +106,23 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
     double A[3] = {0.0, 0.0, 0.0}, a[3] = {0.0, 0.0, 0.0};
     if constexpr (Guided)
         for (int k = 0; k < 3; ++k) {
-            A[k] = gd.albedo_sum[idx * 3 + k];
+            A[k] = albedo_of(gd).albedo_sum[idx * 3 + k];
             if constexpr (Means) a[k] = A[k];
-            else a[k] = A[k] / gd.albedo_spp;
+            else a[k] = A[k] / albedo_of(gd).albedo_spp;
+        }
+    double E[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
+    if constexpr (has_edges(Mode))
+        for (int k = 0; k < 3; ++k) {
+            E[k] = edge_of(gd).edge_sum[idx * 3 + k];
+            g[k] = E[k] / edge_of(gd).edge_spp;
         }
     double c[3] = {s[0], s[1], s[2]};
     if constexpr (!Means)
         for (int k = 0; k < 3; ++k) c[k] = s[k] / dn;
     bool valid = n >= 2;
     for (int k = 0; k < 3; ++k) valid = valid && is_finite(s[k]) && is_finite(q[k]) && is_finite(A[k]);
+    if constexpr (has_edges(Mode))
+        for (int k = 0; k < 3; ++k) valid = valid && is_finite(E[k]);
     double V = -1.0;
     if (valid) {
         double vmax = 0.0;
@@ -91,7 +131,7 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
             if constexpr (Means) v = q[k] / (dn - 1.0);
             else v = (q[k] - s[k] * c[k]) / (dn - 1.0);
             if constexpr (Guided) {
-                const double d = max_ab(a[k], gd.albedo_floor);
+                const double d = max_ab(a[k], albedo_of(gd).albedo_floor);
                 v = v / (d * d);
                 c[k] = c[k] / d;
             }
@@ -101,7 +141,8 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
         V = vmax / dn;
     }
     out[idx] = make_double4(c[0], c[1], c[2], V);
-    if constexpr (Guided) gd.region[idx] = make_double4(a[0], a[1], a[2], 0.0);
+    if constexpr (Guided) albedo_of(gd).region[idx] = make_double4(a[0], a[1], a[2], 0.0);
+    if constexpr (has_edges(Mode)) edge_of(gd).region[idx] = make_double4(g[0], g[1], g[2], 0.0);
 }
 
 // The spatial prepare (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device below their threshold; include/rt_amd.h
@@ -119,7 +160,7 @@ template <int R> struct SpatialTile {
 };
 template <int R, bool Guided>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int32_t w, int32_t h, int32_t tiles_x, const double *__restrict__ mean,
-                                                                              GuideOf<Guided> gd, double4 *__restrict__ out) {
+                                                                              GuideOf<guide_mode(Guided)> gd, double4 *__restrict__ out) {
     using T = SpatialTile<R>;
     constexpr int PW = T::PW, PLANE = T::PLANE;
     __shared__ double staged[T::PLANES * PLANE];
@@ -197,12 +238,15 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
     if constexpr (Guided) gd.region[pixel] = make_double4(gd.albedo_sum[pixel * 3u + 0u], gd.albedo_sum[pixel * 3u + 1u], gd.albedo_sum[pixel * 3u + 2u], 0.0);
 }
 
-struct Tap { double L, r, g, b, V, ar, ag, ab; }; // (ar, ag, ab: the tap's albedo means; Guided only, not set otherwise)
+// (ar, ag, ab: the tap's first guide, the albedo means or — edges alone — the edge guide's means; er, eg, eb: the edge guide's means
+// beside an albedo guide; neither is set by an instantiation without it)
+struct Tap { double L, r, g, b, V, ar, ag, ab, er, eg, eb; };
 
 // where a lane's taps come from: the workgroup's staged tile (strides 1 and 2) ...
-template <int S, bool Guided> struct LdsSource {
+template <int S, int Mode> struct LdsSource {
+    static constexpr bool Guided = Mode != DN_PLAIN, Second = Mode == DN_BOTH;
     static constexpr int HALO = 2 * S, PW = DN_TW + 2 * HALO, PH = DN_TH + 2 * HALO, PLANE = PH * PW;
-    enum { P_L, P_R, P_G, P_B, P_V, P_AR, P_AG, P_AB, PLANES = Guided ? 8 : 5 };
+    enum { P_L, P_R, P_G, P_B, P_V, P_AR, P_AG, P_AB, P_ER, P_EG, P_EB, PLANES = Second ? 11 : Guided ? 8 : 5 };
     const double *staged; // PLANES planes of PLANE doubles
     int centre;           // the lane's own pixel in a plane
     __device__ __forceinline__ double at(int plane, int k) const { return staged[plane * PLANE + k]; }
@@ -216,13 +260,17 @@ template <int S, bool Guided> struct LdsSource {
         if (t.V < 0.0) return false;
         t.L = at(P_L, k); t.r = at(P_R, k); t.g = at(P_G, k); t.b = at(P_B, k);
         if constexpr (Guided) { t.ar = at(P_AR, k); t.ag = at(P_AG, k); t.ab = at(P_AB, k); }
+        if constexpr (Second) { t.er = at(P_ER, k); t.eg = at(P_EG, k); t.eb = at(P_EB, k); }
         return true;
     }
 };
 // ... or global memory (strides >= 4)
-template <bool Guided> struct GlobalSource {
-    const double4 *in, *guide; // (guide: Guided only)
+struct NoRegion {};
+template <int Mode> struct GlobalSource {
+    static constexpr bool Guided = Mode != DN_PLAIN, Second = Mode == DN_BOTH;
+    const double4 *in, *guide; // (guide: the first guide's region; Guided only)
     int32_t w, h, px, py, stride;
+    std::conditional_t<Second, const double4 *, NoRegion> edge; // (the edge guide's region beside an albedo guide)
     __device__ __forceinline__ bool variance(int dx, int dy, double &v) const {
         const int32_t x = px + dx, y = py + dy;
         if (x < 0 || x >= w || y < 0 || y >= h) return false;
@@ -240,6 +288,10 @@ template <bool Guided> struct GlobalSource {
             const double4 a = guide[k];
             t.ar = a.x; t.ag = a.y; t.ab = a.z;
         }
+        if constexpr (Second) {
+            const double4 g = edge[k];
+            t.er = g.x; t.eg = g.y; t.eb = g.z;
+        }
         return true;
     }
 };
@@ -247,8 +299,11 @@ template <bool Guided> struct GlobalSource {
 // One iteration for one valid pixel p (the header's "Iteration k"), which leaves with its new C and V: the 3 x 3 prefilter of the
 // variance, then the 25 taps in the order dy outer, dx inner, each weighted by the luminance stop e and, Guided, the albedo stop ea.
 // Sums start from +0.0 and take one addition per tap used; nothing is reassociated.
-template <bool Guided, class Source>
-__device__ __forceinline__ void filter_pixel(const Source &src, Tap &p, double sigma, double eps, const GuideOf<Guided> &gd) {
+// An edge guide's stop eg has ea's form over the edge guide's means and sigma_edge: alone it is the one further factor, e * eg; beside
+// the albedo guide the weight is (e * ea) * eg.
+template <int Mode, class Source>
+__device__ __forceinline__ void filter_pixel(const Source &src, Tap &p, double sigma, double eps, const GuideOf<Mode> &gd) {
+    constexpr bool Guided = Mode != DN_PLAIN;
     const double g3[3] = {0.25, 0.5, 0.25};
     double gs = 0.0, ws = 0.0;
 #pragma unroll
@@ -277,10 +332,17 @@ __device__ __forceinline__ void filter_pixel(const Source &src, Tap &p, double s
             double e = t > 0.0 ? t * t : 0.0;
             if constexpr (Guided) {
                 const double da = max_ab(max_ab(__builtin_fabs(p.ar - q.ar), __builtin_fabs(p.ag - q.ag)), __builtin_fabs(p.ab - q.ab));
-                const double y = da / gd.sigma_albedo;
+                const double y = da / first_sigma(gd);
                 const double ta = 1.0 - y * y;
                 const double ea = ta > 0.0 ? ta * ta : 0.0;
                 e = e * ea;
+            }
+            if constexpr (Mode == DN_BOTH) {
+                const double dg = max_ab(max_ab(__builtin_fabs(p.er - q.er), __builtin_fabs(p.eg - q.eg)), __builtin_fabs(p.eb - q.eb));
+                const double z = dg / gd.edge.sigma_edge;
+                const double tg = 1.0 - z * z;
+                const double eg = tg > 0.0 ? tg * tg : 0.0;
+                e = e * eg;
             }
             const double wq = (h5[dy + 2] * h5[dx + 2]) * e;
             sw = sw + wq;
@@ -299,26 +361,27 @@ struct DenoiseOut {
     double *mean;       // 3 w h
     uint32_t *rgba;     // w h words, or null
 };
-template <bool Guided>
-__device__ __forceinline__ void store_pixel(const DenoiseOut &o, size_t pixel, Tap p, const GuideOf<Guided> &gd) {
+template <int Mode>
+__device__ __forceinline__ void store_pixel(const DenoiseOut &o, size_t pixel, Tap p, const GuideOf<Mode> &gd) {
     if (o.next) {
         o.next[pixel] = make_double4(p.r, p.g, p.b, p.V);
         return;
     }
-    if constexpr (Guided)
+    if constexpr (demodulates(Mode)) // (an edge guide multiplies nothing back in)
         if (!(p.V < 0.0)) {
-            p.r = p.r * max_ab(p.ar, gd.albedo_floor);
-            p.g = p.g * max_ab(p.ag, gd.albedo_floor);
-            p.b = p.b * max_ab(p.ab, gd.albedo_floor);
+            p.r = p.r * max_ab(p.ar, albedo_of(gd).albedo_floor);
+            p.g = p.g * max_ab(p.ag, albedo_of(gd).albedo_floor);
+            p.b = p.b * max_ab(p.ab, albedo_of(gd).albedo_floor);
         }
     o.mean[pixel * 3u + 0u] = p.r; o.mean[pixel * 3u + 1u] = p.g; o.mean[pixel * 3u + 2u] = p.b;
     if (o.rgba) o.rgba[pixel] = display_rgba8(p.r, p.g, p.b);
 }
 
-template <int S, bool Guided>
-__global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32_t h, int32_t tiles_x, double sigma, double eps, GuideOf<Guided> gd,
+template <int S, int Mode>
+__global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32_t h, int32_t tiles_x, double sigma, double eps, GuideOf<Mode> gd,
                                                                  const double4 *__restrict__ in, DenoiseOut out) {
-    using Src = LdsSource<S, Guided>;
+    using Src = LdsSource<S, Mode>;
+    constexpr bool Guided = Src::Guided, Second = Src::Second;
     constexpr int PW = Src::PW, PLANE = Src::PLANE, HALO = Src::HALO;
     __shared__ double staged[Src::PLANES * PLANE];
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // grid.x: tiles, row-major
@@ -331,11 +394,16 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             const size_t g = view + (size_t)gy * (size_t)w + (size_t)gx;
             c = in[g];
-            if constexpr (Guided) a = gd.region[g];
+            if constexpr (Guided) a = first_region(gd)[g];
         }
         staged[Src::P_R * PLANE + k] = c.x; staged[Src::P_G * PLANE + k] = c.y; staged[Src::P_B * PLANE + k] = c.z; staged[Src::P_V * PLANE + k] = c.w;
         staged[Src::P_L * PLANE + k] = luminance(c.x, c.y, c.z);
         if constexpr (Guided) { staged[Src::P_AR * PLANE + k] = a.x; staged[Src::P_AG * PLANE + k] = a.y; staged[Src::P_AB * PLANE + k] = a.z; }
+        if constexpr (Second) {
+            double4 e = make_double4(0.0, 0.0, 0.0, 0.0);
+            if (gx >= 0 && gx < w && gy >= 0 && gy < h) e = gd.edge.region[view + (size_t)gy * (size_t)w + (size_t)gx];
+            staged[Src::P_ER * PLANE + k] = e.x; staged[Src::P_EG * PLANE + k] = e.y; staged[Src::P_EB * PLANE + k] = e.z;
+        }
     }
     __syncthreads();
     const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
@@ -346,20 +414,22 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_lds_kernel(int32_t w, int32
     Tap p;
     p.L = src.at(Src::P_L, k); p.r = src.at(Src::P_R, k); p.g = src.at(Src::P_G, k); p.b = src.at(Src::P_B, k); p.V = src.at(Src::P_V, k);
     if constexpr (Guided) { p.ar = src.at(Src::P_AR, k); p.ag = src.at(Src::P_AG, k); p.ab = src.at(Src::P_AB, k); }
-    if (!(p.V < 0.0)) filter_pixel<Guided>(src, p, sigma, eps, gd);
-    store_pixel<Guided>(out, view + (size_t)py * (size_t)w + (size_t)px, p, gd);
+    if constexpr (Second) { p.er = src.at(Src::P_ER, k); p.eg = src.at(Src::P_EG, k); p.eb = src.at(Src::P_EB, k); }
+    if (!(p.V < 0.0)) filter_pixel<Mode>(src, p, sigma, eps, gd);
+    store_pixel<Mode>(out, view + (size_t)py * (size_t)w + (size_t)px, p, gd);
 }
 
-template <bool Guided>
+template <int Mode>
 __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, int32_t h, int32_t tiles_x, int32_t stride, double sigma, double eps,
-                                                                    GuideOf<Guided> gd, const double4 *__restrict__ in, DenoiseOut out) {
+                                                                    GuideOf<Mode> gd, const double4 *__restrict__ in, DenoiseOut out) {
+    constexpr bool Guided = Mode != DN_PLAIN, Second = Mode == DN_BOTH;
     const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x;
     const int32_t px = tile_x * DN_TW + tx, py = tile_y * DN_TH + ty;
     if (px >= w || py >= h) return;
     const size_t view = (size_t)blockIdx.y * ((size_t)w * (size_t)h), pixel = (size_t)py * (size_t)w + (size_t)px; // (grid.y: the view)
     const double4 *guide = nullptr;
-    if constexpr (Guided) guide = gd.region + view;
+    if constexpr (Guided) guide = first_region(gd) + view;
     in += view; // the taps index their own view's frame
     const double4 c = in[pixel];
     Tap p;
@@ -368,19 +438,24 @@ __global__ __launch_bounds__(DN_THREADS) void atrous_global_kernel(int32_t w, in
         const double4 a = guide[pixel];
         p.ar = a.x; p.ag = a.y; p.ab = a.z;
     }
-    if (!(p.V < 0.0)) filter_pixel<Guided>(GlobalSource<Guided>{in, guide, w, h, px, py, stride}, p, sigma, eps, gd);
-    store_pixel<Guided>(out, view + pixel, p, gd);
+    if constexpr (Second) {
+        const double4 *edge = gd.edge.region + view;
+        const double4 g = edge[pixel];
+        p.er = g.x; p.eg = g.y; p.eb = g.z;
+        if (!(p.V < 0.0)) filter_pixel<Mode>(GlobalSource<Mode>{in, guide, w, h, px, py, stride, edge}, p, sigma, eps, gd);
+    } else if (!(p.V < 0.0)) filter_pixel<Mode>(GlobalSource<Mode>{in, guide, w, h, px, py, stride}, p, sigma, eps, gd);
+    store_pixel<Mode>(out, view + pixel, p, gd);
 }
 
-template <bool Guided, bool Means>
-void launch_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Guided> &gd,
+template <int Mode, bool Means>
+void launch_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const GuideOf<Mode> &gd,
                     void *half, hipStream_t stream) {
-    hipLaunchKernelGGL((denoise_prepare_kernel<Guided, Means>), dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS), (unsigned)n_views), dim3(DN_THREADS), 0,
+    hipLaunchKernelGGL((denoise_prepare_kernel<Mode, Means>), dim3((unsigned)((n_pixels + DN_THREADS - 1) / DN_THREADS), (unsigned)n_views), dim3(DN_THREADS), 0,
                        stream, n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
 }
 
 template <int R, bool Guided>
-void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const GuideOf<Guided> &gd, void *half, hipStream_t stream) {
+void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const GuideOf<guide_mode(Guided)> &gd, void *half, hipStream_t stream) {
     const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
     hipLaunchKernelGGL((denoise_prepare_spatial_kernel<R, Guided>), dim3((unsigned)((int64_t)tiles_x * tiles_y)), dim3(DN_THREADS), 0, stream, w, h,
                        tiles_x, mean, gd, (double4 *)half);
@@ -391,15 +466,15 @@ void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const rtk:
     else launch_prepare_spatial<R, false>(w, h, mean, NoGuide{}, half, stream);
 }
 
-template <bool Guided>
-void launch_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const GuideOf<Guided> &gd, const void *half_in, const DenoiseOut &out,
+template <int Mode>
+void launch_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const GuideOf<Mode> &gd, const void *half_in, const DenoiseOut &out,
                    hipStream_t stream) {
     const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
     const dim3 grid((unsigned)((int64_t)tiles_x * tiles_y), (unsigned)n_views), block(DN_THREADS); // (w * h < 2^27: fewer than 2^27 tiles; n_views <= 65535)
     const double4 *in = (const double4 *)half_in;
-    if (stride == 1) hipLaunchKernelGGL((atrous_lds_kernel<1, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
-    else if (stride == 2) hipLaunchKernelGGL((atrous_lds_kernel<2, Guided>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
-    else hipLaunchKernelGGL(atrous_global_kernel<Guided>, grid, block, 0, stream, w, h, tiles_x, stride, sigma, eps, gd, in, out);
+    if (stride == 1) hipLaunchKernelGGL((atrous_lds_kernel<1, Mode>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
+    else if (stride == 2) hipLaunchKernelGGL((atrous_lds_kernel<2, Mode>), grid, block, 0, stream, w, h, tiles_x, sigma, eps, gd, in, out);
+    else hipLaunchKernelGGL(atrous_global_kernel<Mode>, grid, block, 0, stream, w, h, tiles_x, stride, sigma, eps, gd, in, out);
 }
 
 } // namespace
@@ -407,12 +482,14 @@ void launch_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double
 namespace rtk {
 
 void launch_denoise_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
-                            bool means, void *half, hipStream_t stream) {
-    if (means) { // (a uniform count: the means form has no map)
-        if (guide) launch_prepare<true, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *guide, half, stream);
-        else launch_prepare<false, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
-    } else if (guide) launch_prepare<true, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, *guide, half, stream);
-    else launch_prepare<false, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
+                            bool means, void *half, hipStream_t stream, const DenoiseEdge *edge) {
+    if (means) { // (a uniform count: the means form has no map, and no edge guide)
+        if (guide) launch_prepare<DN_ALBEDO, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *guide, half, stream);
+        else launch_prepare<DN_PLAIN, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
+    } else if (guide && edge) launch_prepare<DN_BOTH, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, BothGuides{*guide, *edge}, half, stream);
+    else if (edge) launch_prepare<DN_EDGES, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, *edge, half, stream);
+    else if (guide) launch_prepare<DN_ALBEDO, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, *guide, half, stream);
+    else launch_prepare<DN_PLAIN, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
 }
 
 void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream) {
@@ -422,10 +499,12 @@ void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const 
 }
 
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
-                           void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream) {
+                           void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream, const DenoiseEdge *edge) {
     const DenoiseOut out{(double4 *)half_out, mean_out, (uint32_t *)rgba8};
-    if (guide) launch_atrous<true>(w, h, n_views, stride, sigma, eps, *guide, half_in, out, stream);
-    else launch_atrous<false>(w, h, n_views, stride, sigma, eps, NoGuide{}, half_in, out, stream);
+    if (guide && edge) launch_atrous<DN_BOTH>(w, h, n_views, stride, sigma, eps, BothGuides{*guide, *edge}, half_in, out, stream);
+    else if (edge) launch_atrous<DN_EDGES>(w, h, n_views, stride, sigma, eps, *edge, half_in, out, stream);
+    else if (guide) launch_atrous<DN_ALBEDO>(w, h, n_views, stride, sigma, eps, *guide, half_in, out, stream);
+    else launch_atrous<DN_PLAIN>(w, h, n_views, stride, sigma, eps, NoGuide{}, half_in, out, stream);
 }
 
 } // namespace rtk

@@ -10,6 +10,8 @@
 //   it is written; with --adaptive it takes the adaptive sums and the spp map),
 //   --denoise-albedo [--denoise-albedo-sigma X] (implies --denoise: the albedo-guided filter, with a first-hit albedo frame rendered
 //   from the scene's albedo scene over the same seed and samples),
+//   --denoise-edges [--denoise-edges-sigma X] (implies --denoise, alone or with --denoise-albedo: the filter also stops at the edges of
+//   a first-hit surface-ID frame rendered from the scene's surface-ID scene over the same seed and samples),
 //   -l --live-denoise [--denoise-iters K] [--denoise-sigma X] (every live frame through the filter, from the running mean and Welford's
 //   M2: include/rt_amd.h "live denoise"), --live-denoise-albedo [--denoise-albedo-sigma X] (implies --live-denoise: the guided filter,
 //   with a running albedo mean folded over the same samples), --live-denoise-spatial [N] [--denoise-spatial-radius R] (with
@@ -39,6 +41,8 @@ static void usage(const char *argv0) {
             "                         default 4; X > 0, default 4; also with --adaptive)\n"
             "          [--denoise-albedo [--denoise-albedo-sigma X]]   (implies --denoise: the filter is guided by a first-hit albedo frame as well and works on\n"
             "                         the frame divided by it; X > 0, default 0.5: the albedo difference at which a tap's weight is 0)\n"
+            "          [--denoise-edges [--denoise-edges-sigma X]]   (implies --denoise, alone or with --denoise-albedo: the filter also stops where a first-hit\n"
+            "                         surface-ID frame changes; X > 0, default 0.5: the difference of that frame at which a tap's weight is 0)\n"
             "          [-l|--live [--live-spp K] -o OUTPUT]   (one GPU: the reference's live mode without the window — a running mean refined K samples\n"
             "                         per pixel at a time, default 1, over spp - 1 samples; the last frame goes to OUTPUT.png)\n"
             "          [--live-denoise [--denoise-iters K] [--denoise-sigma X]]   (with -l/--live: every frame shown is the à-trous filter's, from the running\n"
@@ -61,7 +65,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -106,6 +110,11 @@ int main(int argc, char **argv) {
         else if (a == "--denoise-albedo-sigma") {
             ro.denoise_albedo_sigma = atof(need("--denoise-albedo-sigma")); albedo_knob_given = true;
             if (!(ro.denoise_albedo_sigma > 0.0)) { fprintf(stderr, "--denoise-albedo-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--denoise-edges") ro.denoise = ro.denoise_edges = true;
+        else if (a == "--denoise-edges-sigma") {
+            ro.denoise_edges_sigma = atof(need("--denoise-edges-sigma")); edges_knob_given = true;
+            if (!(ro.denoise_edges_sigma > 0.0)) { fprintf(stderr, "--denoise-edges-sigma needs a width above 0\n"); usage(argv[0]); return 2; }
         }
         else if (a == "--live-denoise") ro.live_denoise = true;
         else if (a == "--live-denoise-albedo") ro.live_denoise = ro.live_denoise_albedo = true;
@@ -171,6 +180,10 @@ int main(int argc, char **argv) {
     if (albedo_knob_given && !ro.denoise_albedo && !ro.live_denoise_albedo && !ro.orbit_denoise_albedo) {
         fprintf(stderr, "--denoise-albedo-sigma sets the filter of --denoise-albedo: it needs --denoise-albedo (with --live: --live-denoise-albedo; "
                         "with --orbit: --orbit-denoise-albedo)\n");
+        return 2;
+    }
+    if (edges_knob_given && !ro.denoise_edges) {
+        fprintf(stderr, "--denoise-edges-sigma sets the filter of --denoise-edges: it needs --denoise-edges\n");
         return 2;
     }
     if (denoise_knob_given && !ro.denoise && !ro.live_denoise && !ro.orbit_denoise && !ro.orbit_denoise_albedo) {

@@ -169,6 +169,18 @@ std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double 
     });
 }
 
+std::vector<uint8_t> denoise_guided(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                                    const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp, const RenderOptions &opt) {
+    rt_denoise_guided_params dp;
+    if (rt_denoise_guided_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_guided: ") + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
+    return run_denoise("denoise_guided", width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_sum != nullptr),
+                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+                           return rt_denoise_guided_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, d_edge_sum, edge_spp, &dp,
+                                                           d_mean, d_rgba8, d_work, nullptr);
+                       });
+}
+
 std::vector<uint8_t> denoise_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                    const RenderOptions &opt) {
     rt_denoise_params dp;
@@ -250,13 +262,14 @@ std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, 
 
 // The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
 // every pixel with the render's seed under `cam` with a white background, into a new device frame of sums (the caller frees it).
-static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo) {
+// `surface_ids` (opt.denoise_edges): the surface-ID scene under `cam` with a black background instead.
+static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo, bool surface_ids = false) {
     rt_scene *scene = nullptr;
-    int rc = rt_scene_create_albedo(&desc, 0, nullptr, &scene);
+    int rc = surface_ids ? rt_scene_create_surface_ids(&desc, 0, nullptr, &scene) : rt_scene_create_albedo(&desc, 0, nullptr, &scene);
     if (rc == RT_OK) rc = rt_device_malloc(0, (int64_t)cam.image_width * cam.image_height * 3 * (int64_t)sizeof(double), d_albedo);
     if (rc == RT_OK) {
         rt_camera white = cam;
-        white.background = rt_vec3{1.0, 1.0, 1.0};
+        white.background = surface_ids ? rt_vec3{0.0, 0.0, 0.0} : rt_vec3{1.0, 1.0, 1.0};
         rt_render_params p{};
         p.seed = seed; p.sample_begin = 0; p.sample_end = spp; p.max_depth = cam.max_depth;
         p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
@@ -278,8 +291,8 @@ static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hit
     const rt_camera cam = camera.pod();
     const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
     rt_scene *scene = nullptr;
-    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_alb: only with opt.denoise_albedo)
-    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_scene_destroy(scene); };
+    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr, *d_ids = nullptr; // (d_alb: only with opt.denoise_albedo; d_ids: with opt.denoise_edges)
+    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_device_free(0, d_ids); rt_scene_destroy(scene); };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_sum));
@@ -289,9 +302,14 @@ static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hit
     p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
     check(rt_render_moments_device(scene, &cam, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
     if (opt.denoise_albedo) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_alb));
+    if (opt.denoise_edges) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_ids, true));
     std::vector<uint8_t> px;
     try {
-        px = opt.denoise_albedo
+        px = opt.denoise_edges
+                 ? denoise_guided(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                                  cam.samples_per_pixel, nullptr, static_cast<const double *>(d_alb), cam.samples_per_pixel,
+                                  static_cast<const double *>(d_ids), cam.samples_per_pixel, opt)
+             : opt.denoise_albedo
                  ? denoise_albedo(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
                                   cam.samples_per_pixel, nullptr, static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
                  : denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
@@ -310,9 +328,9 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     const rt_camera cam = camera.pod();
     const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
     rt_scene *scene = nullptr;
-    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_sq: only with opt.denoise; d_alb: with opt.denoise_albedo)
+    void *d_sum = nullptr, *d_spp = nullptr, *d_rgb8 = nullptr, *d_sq = nullptr, *d_alb = nullptr, *d_ids = nullptr; // (d_sq: only with opt.denoise; d_alb: with opt.denoise_albedo; d_ids: with opt.denoise_edges)
     auto cleanup = [&]() {
-        rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_device_free(0, d_sq); rt_device_free(0, d_alb);
+        rt_device_free(0, d_sum); rt_device_free(0, d_spp); rt_device_free(0, d_rgb8); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_device_free(0, d_ids);
         rt_scene_destroy(scene);
     };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
@@ -333,8 +351,13 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     std::vector<int32_t> spp((size_t)n_pix);
     if (opt.denoise) { // the frame is written from the denoised mean: every pixel's own spp is its n (the albedo frame: the maximum's)
         if (opt.denoise_albedo) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_alb));
+        if (opt.denoise_edges) check(render_albedo_sums(desc, cam, opt.seed, cam.samples_per_pixel, &d_ids, true)); // (the maximum spp, as the albedo frame)
         try {
-            px = opt.denoise_albedo
+            px = opt.denoise_edges
+                     ? denoise_guided(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
+                                      static_cast<const int32_t *>(d_spp), static_cast<const double *>(d_alb), cam.samples_per_pixel,
+                                      static_cast<const double *>(d_ids), cam.samples_per_pixel, opt)
+                 : opt.denoise_albedo
                      ? denoise_albedo(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
                                       static_cast<const int32_t *>(d_spp), static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
                      : denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,

@@ -49,6 +49,12 @@ struct RenderOptions {
     // camera's spp) under the camera with background (1, 1, 1), and hands that frame to rt_denoise_albedo_device.
     bool denoise_albedo = false;
     double denoise_albedo_sigma = 0.5;
+    // with `denoise`: an edge guide for the filter (include/rt_amd.h "edge-guided denoise"), alone or beside `denoise_albedo`.  The
+    // route creates the surface-ID scene from the same description, renders it with rt_render_device over the same seed and sample
+    // range (an adaptive render: up to the camera's spp) under the camera with background (0, 0, 0), and hands that frame to
+    // rt_denoise_guided_device as d_edge_sum; denoise_edges_sigma is the filter's sigma_edge.
+    bool denoise_edges = false;
+    double denoise_edges_sigma = 0.5;
     // live_render: every displayed frame goes through the filter (include/rt_amd.h "live denoise").  A pass is then
     // rt_render_mean_moments_device — the running mean with Welford's M2 beside it — and rt_denoise_mean_device with denoise_iters /
     // denoise_sigma into a separate display frame: the running mean and M2 are never overwritten by the filter.
@@ -75,6 +81,13 @@ std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum,
 // scene; opt.denoise_albedo_sigma is the filter's sigma_albedo.
 std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                                     const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt = {});
+
+// rt_denoise_guided_device likewise: d_edge_sum is a DEVICE frame of 3 * w * h doubles, the sums of edge_spp samples of the edge guide
+// (the surface-ID scene's render); d_albedo_sum may be null (no albedo guide: albedo_spp is not read); opt.denoise_edges_sigma is the
+// filter's sigma_edge.
+std::vector<uint8_t> denoise_guided(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
+                                    const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
+                                    const RenderOptions &opt = {});
 
 // rt_denoise_views_device and rt_denoise_albedo_views_device likewise, over a stack of n_views frames, view-major in every DEVICE
 // buffer, with the uniform sample count `spp`: the RGB bytes of the n_views display frames, one behind the other (n_views * 3 * w * h).
