@@ -805,6 +805,76 @@ int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_view
                                    const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
                                    uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- tone mapping (opt-in; nothing above changes) ----------------------------------------------------------------------------------------
+ * Every route above ends in color_to_rgb: (u8)(256 * clamp(x^(1/2.2), 0, 0.999)).  Radiance above 1 is clipped flat and a dark frame
+ * cannot be lifted.  rt_tonemap_device is that output stage with an exposure and a tone curve in front of the gamma, and optionally an
+ * automatic exposure from the frame's log-average luminance, reduced on the device: the call never synchronises with the host.
+ *
+ * Normative definition.  The arithmetic rules are those of "Arithmetic" below: f64, every operation rounded on its own, no FMA, IEEE
+ * division.
+ *   Input value.  Sums form: m = S * (1.0 / (double)n), the multiplication by the reciprocal that rt_resolve_rgb8_device and
+ *                 rt_resolve_rgb8_spp_device do; n is spp, or d_spp[pixel].  Means form (spp == 1, no map): m = S * 1.0 = S.
+ *   Exposure.     x = m * scale, with scale = exposure when auto_key == 0.  exposure is a linear factor (the layers above this ABI
+ *                 convert stops with exp2).
+ *   Operator.     Per channel, applied only where 0 < x < +inf; any other x (zero, negative, NaN, +-inf) passes through unchanged, so
+ *                 rt_gamma_encode / rt_quantise treat it as they do in the stages above.
+ *                   RT_TONEMAP_CLAMP:     y = x
+ *                   RT_TONEMAP_REINHARD:  w2 = white * white;  r = x / w2;  r = 1 + r;  num = x * r;  den = 1 + x;  y = num / den
+ *                                         (white = +inf is allowed and is the default: r is then exactly 1 and y = x / (1 + x))
+ *                   RT_TONEMAP_ACES:      a = 2.51 * x;  a = a + 0.03;  num = x * a;
+ *                                         b = 2.43 * x;  b = b + 0.59;  den = x * b;  den = den + 0.14;  y = num / den   (Narkowicz's fit)
+ *   Bytes.        rt_quantise(rt_gamma_encode(y)) per value (d_rgb8, 3 * w * h bytes); d_rgba8 packs a pixel's three bytes as
+ *                 rt_resolve_rgba8_device does, with alpha 0xff, in one 32-bit store.
+ *   With RT_TONEMAP_CLAMP, exposure == 1 and auto_key == 0 every step is exact (x * 1.0 == x): the bytes are exactly those of
+ *   rt_resolve_rgb8_device, rt_resolve_rgb8_spp_device and rt_resolve_rgba8_device.
+ *   Auto-exposure (auto_key > 0; Reinhard's log-average).  Per pixel p, in index order j * w + i:
+ *                 L = ((0.2126 * m_r) + (0.7152 * m_g)) + (0.0722 * m_b).  p COUNTS iff all three m_c are finite and L >= 0.  A counting
+ *                 pixel has the term t_p = rt_log(delta + L) (the fixed ln of "Arithmetic"); any other pixel the term +0.0 and count 0.
+ *                 Reduction, in a fixed order: the terms are padded to a multiple of 256 with +0.0 and count 0; each block of 256
+ *                 consecutive entries is reduced by the tree
+ *                     for stride = 128, 64, ..., 1:   e[i] = e[i] + e[i + stride]   for i < stride
+ *                 (counts are integers); the block results, in block order, are the entries of the next level; levels repeat until one
+ *                 entry (T, count) is left — at most four levels below 2^27 pixels.  Then
+ *                     log_mean = T / (double)count;  Lavg = rt_exp(log_mean);  scale = exposure * (auto_key / Lavg)
+ *                 and with count == 0: scale = exposure, log_mean = Lavg = 0.
+ *                 The tree is normative: no floating-point atomics, and no summation order that depends on the launch shape.
+ *
+ * rt_tonemap_device reads d_values (3 * w * h doubles: sums with the uniform count spp or the per-pixel map d_spp, or means with spp = 1)
+ * and writes d_rgb8, d_rgba8 or both; d_values is not written.  With auto_key > 0 it runs the reduction first, in d_workspace
+ * (rt_tonemap_workspace_bytes(w, h) bytes of device memory, 16-byte aligned, the caller's), whose first four doubles are afterwards
+ * log_mean, Lavg, (double)count and scale; the value kernels read scale from there.  rt_log_average_luminance_device is the reduction
+ * alone: it writes log_mean, Lavg, (double)count and 0 to d_out4 (device memory).  Both calls are enqueued on hip_stream, do not
+ * synchronise and allocate nothing.  spp must be >= 1 even where d_spp is given (it is then not read).
+ * With auto_key == 0 the call is elementwise: a stack of n_views frames is a frame of height n_views * h.  Auto-exposure over such a
+ * frame would pool the views into one log-average; callers who want one exposure per view call once per view.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; a null d_values; both
+ * outputs null (rt_log_average_luminance_device: a null d_out4); spp < 1; a struct_size this library does not know; op outside 0..2;
+ * exposure that is not a finite number > 0; delta likewise; auto_key that is not a finite number >= 0; white that is not > 0 (+inf
+ * allowed); with auto_key > 0 (rt_log_average_luminance_device: always) a null d_workspace or one that is not 16-byte aligned; a
+ * d_rgba8 that is not 4-byte aligned; an output overlapping d_values. */
+#define RT_TONEMAP_CLAMP 0
+#define RT_TONEMAP_REINHARD 1
+#define RT_TONEMAP_ACES 2
+typedef struct rt_tonemap_params {
+    uint32_t struct_size;   /* sizeof(rt_tonemap_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t op;             /* RT_TONEMAP_* (default RT_TONEMAP_CLAMP) */
+    double exposure;        /* linear factor (default 1.0), finite, > 0 */
+    double auto_key;        /* 0: off (default); > 0: the key the log-average luminance is mapped to (the layers above: 0.18) */
+    double delta;           /* added to the luminance inside the logarithm (default 1e-4), finite, > 0 */
+    double white;           /* Reinhard: the value that maps to 1 (default +inf), > 0 */
+} rt_tonemap_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_tonemap_params_init_sized(rt_tonemap_params *params, uint32_t struct_size);
+/* Bytes of device memory the reduction needs for a w x h frame (four doubles of results and 16 bytes per block of every level);
+ * -1 for a size the calls refuse. */
+int64_t rt_tonemap_workspace_bytes(int32_t width, int32_t height);
+int rt_tonemap_device(int32_t width, int32_t height, const double *d_values /* 3*w*h */, int32_t spp, const int32_t *d_spp /* NULL: uniform */,
+                      const rt_tonemap_params *params /* NULL: defaults */, uint8_t *d_rgb8 /* 3*w*h, or NULL */,
+                      uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace /* may be NULL when auto_key == 0 */, void *hip_stream);
+int rt_log_average_luminance_device(int32_t width, int32_t height, const double *d_values /* 3*w*h */, int32_t spp,
+                                    const int32_t *d_spp /* NULL: uniform */, double delta, double *d_out4 /* log_mean, Lavg, count, 0 */,
+                                    void *d_workspace, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

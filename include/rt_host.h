@@ -48,6 +48,15 @@ int rth_scene_orbit_look_from(const rth_scene *scene, int32_t k, int32_t n, doub
 
 /* color_to_rgb(sum / spp) over a frame of per-pixel sums (src/renderer.rs:55-58, src/color.rs:12-19). */
 int rth_resolve_rgb8(int32_t width, int32_t height, int32_t spp, const double *rgb_sum, uint8_t *out_rgb8);
+/* The host mirrors of rt_tonemap_device and rt_log_average_luminance_device (rt_amd.h "tone mapping") on host memory: the same shared
+ * per-value functions and the same reduction tree, so the bytes and the four doubles are the device's, bit for bit.  `values` holds
+ * 3 * w * h doubles (sums with spp or the map spp_map, or means with spp = 1); out_rgb8 (3 * w * h bytes) and out_rgba8 (4 * w * h bytes,
+ * alpha 0xff) may each be NULL, not both; out4 receives log_mean, Lavg, (double)count and 0.  They refuse what the device calls refuse
+ * of these arguments, in the same order (-1, the field named in rth_last_error); there is no workspace and no stream. */
+int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
+                const rt_tonemap_params *params /* NULL: defaults */, uint8_t *out_rgb8, uint8_t *out_rgba8);
+int rth_log_average_luminance(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
+                              double delta, double *out4);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* Deterministic procedural RGB8 map used where assets/earth-large.jpg is unavailable. */

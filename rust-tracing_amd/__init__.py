@@ -282,6 +282,32 @@ def denoise_spatial_params(**kw) -> "DenoiseSpatialParams":
     return d
 
 
+RT_TONEMAP_CLAMP, RT_TONEMAP_REINHARD, RT_TONEMAP_ACES = range(3)
+TONEMAP_OPS = {"clamp": RT_TONEMAP_CLAMP, "reinhard": RT_TONEMAP_REINHARD, "aces": RT_TONEMAP_ACES}
+
+
+class TonemapParams(C.Structure):
+    """rt_tonemap_params (rt_tonemap_device, rth_tonemap)."""
+    _fields_ = [("struct_size", C.c_uint32), ("op", C.c_int32), ("exposure", C.c_double), ("auto_key", C.c_double),
+                ("delta", C.c_double), ("white", C.c_double)]
+
+
+def tonemap_params(**kw) -> "TonemapParams":
+    """rt_tonemap_params_init_sized, then the given fields (op= a number or "clamp" / "reinhard" / "aces", exposure=, auto_key=,
+    delta=, white=)."""
+    t = TonemapParams()
+    _check(amd_lib().rt_tonemap_params_init_sized(C.byref(t), C.sizeof(t)), "rt_tonemap_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(TonemapParams._fields_):
+            raise TypeError(f"rt_tonemap_params has no field {k}")
+        if k == "op" and isinstance(v, str):
+            if v not in TONEMAP_OPS:
+                raise RtError(f"tonemap_params: no operator {v!r} (clamp, reinhard, aces)")
+            v = TONEMAP_OPS[v]
+        setattr(t, k, v)
+    return t
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -375,6 +401,12 @@ RT_AMD_SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoise_albedo_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_tonemap_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_tonemap_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_tonemap_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "rt_log_average_luminance_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -666,6 +698,8 @@ RT_HOST_SYMBOLS = {
     "rth_scene_look": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rth_scene_orbit_look_from": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "rth_resolve_rgb8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
+    "rth_tonemap": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rth_log_average_luminance": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_load_image": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -1471,6 +1505,105 @@ def denoise_albedo_mean_spatial(mean, m2, samples, albedo_mean, *, rgba8=False, 
     if albedo_mean is None:
         raise RtError("denoise_albedo_mean_spatial: `albedo_mean` is required")
     return _denoise_means_spatial("denoise_albedo_mean_spatial", mean, m2, samples, albedo_mean, rgba8, device, dict(kw))
+
+
+def tonemap_workspace_bytes(width, height) -> int:
+    n = int(amd_lib().rt_tonemap_workspace_bytes(width, height))
+    if n < 0:
+        raise RtError(f"rt_tonemap_workspace_bytes: no workspace for a {width}x{height} frame")
+    return n
+
+
+def tonemap_device(width, height, d_values_ptr: int, spp: int, *, d_spp_ptr: int = 0, d_rgb8_ptr: int = 0, d_rgba8_ptr: int = 0,
+                   d_workspace_ptr: int = 0, params: "TonemapParams | None" = None, stream: int = 0):
+    """rt_tonemap_device: exposure, tone curve, gamma and quantisation over a device frame of 3 w h doubles — sums with the uniform
+    sample count `spp` or, if d_spp_ptr is not 0, a device map of w h int32; means with spp = 1 — into 3 w h bytes at d_rgb8_ptr, 4 w h
+    bytes at d_rgba8_ptr, or both.  With params.auto_key > 0 the exposure comes from the frame's log-average luminance, reduced in
+    `d_workspace_ptr` (tonemap_workspace_bytes(w, h) device bytes).  Enqueued on `stream`."""
+    _check(amd_lib().rt_tonemap_device(width, height, C.c_void_p(d_values_ptr), spp, C.c_void_p(d_spp_ptr or None),
+                                       C.byref(params) if params is not None else None, C.c_void_p(d_rgb8_ptr or None),
+                                       C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr or None), C.c_void_p(stream)), "rt_tonemap_device")
+
+
+def log_average_luminance_device(width, height, d_values_ptr: int, spp: int, d_out4_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0,
+                                 delta: float = 1e-4, stream: int = 0):
+    """rt_log_average_luminance_device: log_mean, Lavg, count and 0 of a device frame into four device doubles.  Enqueued on `stream`."""
+    _check(amd_lib().rt_log_average_luminance_device(width, height, C.c_void_p(d_values_ptr), spp, C.c_void_p(d_spp_ptr or None), delta,
+                                                     C.c_void_p(d_out4_ptr), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_log_average_luminance_device")
+
+
+def _tonemap_frame(who, values, spp_map):
+    import numpy as np
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    if values.ndim != 3 or values.shape[2] != 3:
+        raise RtError(f"{who}: `values` must be an (h, w, 3) frame")
+    h, w = values.shape[:2]
+    if spp_map is not None:
+        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if spp_map.shape != (h, w):
+            raise RtError(f"{who}: `spp_map` must have shape {(h, w)}")
+    return values, spp_map, w, h
+
+
+def tonemap(values, spp, *, spp_map=None, rgba8=False, device=0, **kw):
+    """Uploads an (h, w, 3) frame of sums (with `spp`, or an (h, w) int32 spp map) or of means (spp = 1), runs rt_tonemap_device with
+    tonemap_params(**kw) and downloads the (h, w, 3) uint8 frame, or (rgb8, (h, w, 4) uint8) with rgba8."""
+    values, spp_map, w, h = _tonemap_frame("tonemap", values, spp_map)
+    params = tonemap_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_values = torch.from_numpy(values).cuda()
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_rgb = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        d_ws = torch.empty(tonemap_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        tonemap_device(w, h, d_values.data_ptr(), int(spp), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgb8_ptr=d_rgb.data_ptr(),
+                       d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, d_workspace_ptr=d_ws.data_ptr(), params=params,
+                       stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        rgb = d_rgb.cpu().numpy()
+        return (rgb, d_rgba.cpu().numpy()) if rgba8 else rgb
+
+
+def log_average_luminance(values, spp, *, spp_map=None, delta=1e-4, device=0):
+    """Uploads a frame as tonemap() takes it, runs rt_log_average_luminance_device and downloads (log_mean, Lavg, count, 0.0)."""
+    values, spp_map, w, h = _tonemap_frame("log_average_luminance", values, spp_map)
+    import torch
+    with torch.cuda.device(device):
+        d_values = torch.from_numpy(values).cuda()
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_out = torch.empty(4, dtype=torch.float64, device="cuda")
+        d_ws = torch.empty(tonemap_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        log_average_luminance_device(w, h, d_values.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
+                                     d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, delta=delta,
+                                     stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return tuple(float(x) for x in d_out.cpu().numpy())
+
+
+def tonemap_host(values, spp, *, spp_map=None, rgba8=False, **kw):
+    """rth_tonemap (librt_host, CPU): the bytes rt_tonemap_device gives, from the same shared functions and the same reduction tree."""
+    import numpy as np
+    values, spp_map, w, h = _tonemap_frame("tonemap_host", values, spp_map)
+    params = tonemap_params(**kw)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
+    if host_lib().rth_tonemap(w, h, values.ctypes.data, int(spp), spp_map.ctypes.data if spp_map is not None else None, C.byref(params),
+                              rgb.ctypes.data, rgba.ctypes.data if rgba8 else None) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return (rgb, rgba) if rgba8 else rgb
+
+
+def log_average_luminance_host(values, spp, *, spp_map=None, delta=1e-4):
+    """rth_log_average_luminance (librt_host, CPU): (log_mean, Lavg, count, 0.0), bit for bit the device's."""
+    import numpy as np
+    values, spp_map, w, h = _tonemap_frame("log_average_luminance_host", values, spp_map)
+    out = np.zeros(4, dtype=np.float64)
+    if host_lib().rth_log_average_luminance(w, h, values.ctypes.data, int(spp), spp_map.ctypes.data if spp_map is not None else None, delta,
+                                            out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return tuple(float(x) for x in out)
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

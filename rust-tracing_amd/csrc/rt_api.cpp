@@ -2,6 +2,7 @@
 // helpers).  Plain C++ over the HIP runtime API; the kernels live in rt_kernel.hip and are reached through rt_kernels.h.
 #include "rt_api.hpp"
 #include "rt_qfilt.hpp"
+#include "rt_tonemap_shared.h"
 
 #include <cmath>
 #include <cstdio>
@@ -2067,6 +2068,80 @@ int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum,
     DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
     return run_denoise("rt_denoise_guided_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum ? &guide : nullptr,
                        known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
+}
+
+// ---- tone mapping (rt_tonemap.hip): exposure and a tone curve in front of the output stage's gamma, auto-exposure from a device reduction ----
+
+int rt_tonemap_params_init_sized(rt_tonemap_params *params, uint32_t struct_size) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tonemap_params_init_sized: null argument");
+    if (!rttm::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tonemap_params_init_sized: struct_size is not one this library knows");
+    rt_tonemap_params full;
+    rttm::defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+
+int64_t rt_tonemap_workspace_bytes(int32_t width, int32_t height) { return rttm::workspace_bytes(width, height); }
+
+int rt_tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const rt_tonemap_params *params,
+                      uint8_t *d_rgb8, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    const std::string w("rt_tonemap_device");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
+    if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (!d_values) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_values is null");
+    if (!d_rgb8 && !d_rgba8) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgb8 and d_rgba8 are both null");
+    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 1");
+    rt_tonemap_params p;
+    if (!rttm::resolve(params, p)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_tonemap_params.struct_size is not one this library knows");
+    if (const char *bad = rttm::bad_field(p)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + bad);
+    const bool automatic = p.auto_key > 0.0;
+    if (automatic && !d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null (auto_key > 0 needs it)");
+    if (automatic && ((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    if ((d_rgb8 && overlaps(d_rgb8, n_pix * 3u, d_values, n_pix * 3u * sizeof(double))) ||
+        (d_rgba8 && overlaps(d_rgba8, n_pix * 4u, d_values, n_pix * 3u * sizeof(double))))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": an output must not overlap d_values");
+    if (int rc = select_device_of(d_rgb8 ? d_rgb8 : d_rgba8, "rt_tonemap_device")) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const double inv_spp = 1.0 / (double)spp, w2 = p.white * p.white;
+    double *out4 = (double *)d_workspace;
+    if (automatic) {
+        launch_log_average((int64_t)n_pix, d_values, inv_spp, d_spp, p.delta, (TonemapPartial *)(out4 + 4), p.exposure, p.auto_key, out4, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    const double *d_scale = automatic ? out4 + 3 : nullptr;
+    if (d_rgb8) {
+        launch_tonemap_rgb8((int64_t)n_pix, d_values, inv_spp, d_spp, p.exposure, d_scale, p.op, w2, d_rgb8, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (d_rgba8) {
+        launch_tonemap_rgba8((int64_t)n_pix, d_values, inv_spp, d_spp, p.exposure, d_scale, p.op, w2, d_rgba8, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return RT_OK;
+}
+
+int rt_log_average_luminance_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double delta,
+                                    double *d_out4, void *d_workspace, void *hip_stream) {
+    const std::string w("rt_log_average_luminance_device");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
+    if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
+    if (!d_values) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_values is null");
+    if (!d_out4) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_out4 is null");
+    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 1");
+    if (!rttm::positive_finite(delta)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": delta must be a finite number > 0");
+    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
+    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    if (overlaps(d_out4, 4u * sizeof(double), d_values, n_pix * 3u * sizeof(double))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_out4 must not overlap d_values");
+    if (int rc = select_device_of(d_out4, "rt_log_average_luminance_device")) return rc;
+    // (the workspace's own four result doubles are not used by this call: the levels' blocks start behind them, as in rt_tonemap_device)
+    launch_log_average((int64_t)n_pix, d_values, 1.0 / (double)spp, d_spp, delta, (TonemapPartial *)((double *)d_workspace + 4), 1.0, 0.0, d_out4,
+                       (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 int rt_resolve_rgb8_spp_device(int32_t width, int32_t height, const double *d_sum, const int32_t *d_spp, uint8_t *d_rgb8, void *hip_stream) {

@@ -241,6 +241,19 @@ void launch_denoise_prepare(int64_t n_pixels /* of one frame */, int32_t n_views
 void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream);
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
                            void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream, const DenoiseEdge *edge = nullptr);
+// the tone-mapping stage (rt_tonemap.hip; rt_tonemap_device, rt_log_average_luminance_device).  launch_log_average runs every level of
+// the log-average tree over a frame of n_pixels pixels (values: 3 per pixel; a pixel's mean is its value times inv_spp or, with a
+// map, times 1 / spp_map[pixel]): `partials` has room for the blocks of every level, level 0's first (rt_tonemap_workspace_bytes), and
+// the last level writes log_mean, Lavg, count and — auto_key > 0 — scale = exposure * (auto_key / Lavg), else 0, to out4.  The value
+// kernels read the scale from d_scale if it is not null (device memory: out4 + 3), else take `scale`; w2 = white * white.
+struct TonemapPartial { double t; uint64_t count; };
+static_assert(sizeof(TonemapPartial) == 16, "TonemapPartial: 16 bytes per block of the workspace");
+void launch_log_average(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double delta, TonemapPartial *partials,
+                        double exposure, double auto_key, double *out4, hipStream_t stream);
+void launch_tonemap_rgb8(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double scale, const double *d_scale, int32_t op,
+                         double w2, uint8_t *rgb, hipStream_t stream);
+void launch_tonemap_rgba8(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double scale, const double *d_scale, int32_t op,
+                          double w2, uint8_t *rgba, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

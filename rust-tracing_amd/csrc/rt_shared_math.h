@@ -5,6 +5,7 @@
 //   rt_exp   exponential (gamma below)
 //   rt_gamma_encode   x^(1/2.2), the output stage's linear_to_gamma (src/color.rs:3-6)
 //   rt_quantise       (256 * clamp(g, 0, 0.999)) as u8 (src/color.rs:12-19)
+//   rt_tonemap, rt_luminance, rt_log_luminance_term, rt_log_average_result   the tone-mapping stage's operator and auto-exposure's terms
 //   rt_adaptive_converged   adaptive sampling's per-pixel stopping rule
 // Coefficients: FreeBSD msun e_log.c / e_exp.c (public constants of the published algorithms).
 #pragma once
@@ -98,6 +99,60 @@ RT_HD uint8_t rt_quantise(double g) {
     if (g != g) return 0;
     const double c = g < 0.0 ? 0.0 : (g > 0.999 ? 0.999 : g);
     return (uint8_t)(256.0 * c);
+}
+
+// The tone-mapping operator of include/rt_amd.h "tone mapping", per channel, on the exposed value x; w2 = white * white (Reinhard only).
+// Applied where 0 < x < +inf; zero, a negative, NaN and +-inf pass through to rt_gamma_encode / rt_quantise unchanged.  Every
+// operation is rounded on its own, in the header's order.  op: RT_TONEMAP_CLAMP 0, RT_TONEMAP_REINHARD 1, RT_TONEMAP_ACES 2.
+RT_HD double rt_tonemap(int32_t op, double x, double w2) {
+    if (!(x > 0.0) || x == __builtin_inf()) return x;
+    if (op == 1) { // Reinhard's extended operator; w2 = +inf: r is exactly 1 and y = x / (1 + x)
+        double r = x / w2;
+        r = 1.0 + r;
+        const double num = x * r;
+        const double den = 1.0 + x;
+        return num / den;
+    }
+    if (op == 2) { // Narkowicz's fit of the ACES filmic curve
+        double a = 2.51 * x;
+        a = a + 0.03;
+        const double num = x * a;
+        double b = 2.43 * x;
+        b = b + 0.59;
+        double den = x * b;
+        den = den + 0.14;
+        return num / den;
+    }
+    return x;
+}
+
+// Rec. 709 luminance of a linear colour, in this order: ((0.2126 r + 0.7152 g) + 0.0722 b)
+RT_HD double rt_luminance(double r, double g, double b) { return ((0.2126 * r) + (0.7152 * g)) + (0.0722 * b); }
+
+// Auto-exposure's per-pixel term (include/rt_amd.h "tone mapping"): the pixel counts iff its three means are finite and its
+// luminance is >= 0; a counting pixel contributes rt_log(delta + L), any other +0.0 and count 0.
+RT_HD double rt_log_luminance_term(double mr, double mg, double mb, double delta, uint32_t *counts) {
+    *counts = 0;
+    if (((f2u(mr) >> 52) & 0x7ff) == 0x7ff || ((f2u(mg) >> 52) & 0x7ff) == 0x7ff || ((f2u(mb) >> 52) & 0x7ff) == 0x7ff) return 0.0;
+    const double L = rt_luminance(mr, mg, mb);
+    if (!(L >= 0.0)) return 0.0;
+    *counts = 1;
+    return rt_log(delta + L);
+}
+
+// What the reduction's last level makes of the total T and the count (include/rt_amd.h "tone mapping", Result): out4 = log_mean, Lavg,
+// (double)count, scale.  auto_key == 0 (rt_log_average_luminance_device) writes 0 in scale's place.
+RT_HD void rt_log_average_result(double T, uint32_t count, double exposure, double auto_key, double out4[4]) {
+    double log_mean = 0.0, lavg = 0.0, scale = exposure;
+    if (count != 0) {
+        log_mean = T / (double)count;
+        lavg = rt_exp(log_mean);
+        scale = exposure * (auto_key / lavg);
+    }
+    out4[0] = log_mean;
+    out4[1] = lavg;
+    out4[2] = (double)count;
+    out4[3] = auto_key > 0.0 ? scale : 0.0;
 }
 
 // Adaptive sampling's convergence rule (include/rt_amd.h rt_render_adaptive), for a pixel with n >= 2 samples, channel sums S

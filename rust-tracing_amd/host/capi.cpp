@@ -4,9 +4,11 @@
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
+#include "../csrc/rt_tonemap_shared.h"
 #include <cstring>
 #include <exception>
 #include <string>
+#include <vector>
 
 using namespace rt;
 
@@ -101,6 +103,87 @@ int rth_resolve_rgb8(int32_t width, int32_t height, int32_t spp, const double *r
     for (size_t i = 0; i < n; ++i) {
         const auto rgb = color_to_rgb(Color(rgb_sum[3 * i] * inv, rgb_sum[3 * i + 1] * inv, rgb_sum[3 * i + 2] * inv));
         out_rgb8[3 * i] = rgb[0]; out_rgb8[3 * i + 1] = rgb[1]; out_rgb8[3 * i + 2] = rgb[2];
+    }
+    return 0;
+}
+
+// ---- tone mapping: the host mirror of rt_tonemap_device (include/rt_amd.h "tone mapping") ----
+
+namespace {
+struct LogPartial { double t; uint32_t count; };
+
+// the normative reduction: 256 entries per block (the last one padded with +0.0, count 0), each block by the tree
+// `for stride = 128 .. 1: e[i] = e[i] + e[i + stride]`, the block results the next level's entries, until one is left
+LogPartial reduce_log_terms(std::vector<LogPartial> entries) {
+    for (;;) {
+        const size_t blocks = (entries.size() + 255u) / 256u;
+        std::vector<LogPartial> next(blocks);
+        for (size_t b = 0; b < blocks; ++b) {
+            LogPartial e[256];
+            for (size_t i = 0; i < 256; ++i) e[i] = b * 256u + i < entries.size() ? entries[b * 256u + i] : LogPartial{0.0, 0u};
+            for (size_t stride = 128; stride >= 1; stride >>= 1)
+                for (size_t i = 0; i < stride; ++i) { e[i].t = e[i].t + e[i + stride].t; e[i].count += e[i + stride].count; }
+            next[b] = e[0];
+        }
+        if (blocks == 1) return next[0];
+        entries.swap(next);
+    }
+}
+
+// out4 = log_mean, Lavg, (double)count, scale (auto_key == 0: 0) of a frame of n pixels
+void log_average(size_t n, const double *values, int32_t spp, const int32_t *spp_map, double delta, double exposure, double auto_key, double out4[4]) {
+    std::vector<LogPartial> terms(n);
+    for (size_t p = 0; p < n; ++p) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[p] : spp);
+        terms[p].t = rtm::rt_log_luminance_term(values[3 * p] * inv, values[3 * p + 1] * inv, values[3 * p + 2] * inv, delta, &terms[p].count);
+    }
+    const LogPartial total = reduce_log_terms(std::move(terms));
+    rtm::rt_log_average_result(total.t, total.count, exposure, auto_key, out4);
+}
+} // namespace
+
+int rth_log_average_luminance(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, double delta,
+                              double *out4) {
+    const std::string w("rth_log_average_luminance");
+    if (width <= 0 || height <= 0) return fail(w + ": width and height must be positive");
+    if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(w + ": width x height must be below 2^27 pixels");
+    if (!values) return fail(w + ": values is null");
+    if (!out4) return fail(w + ": out4 is null");
+    if (spp < 1) return fail(w + ": spp must be at least 1");
+    if (!rttm::positive_finite(delta)) return fail(w + ": delta must be a finite number > 0");
+    log_average((size_t)width * (size_t)height, values, spp, spp_map, delta, 1.0, 0.0, out4);
+    return 0;
+}
+
+int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, const rt_tonemap_params *params,
+                uint8_t *out_rgb8, uint8_t *out_rgba8) {
+    const std::string w("rth_tonemap");
+    if (width <= 0 || height <= 0) return fail(w + ": width and height must be positive");
+    if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(w + ": width x height must be below 2^27 pixels");
+    if (!values) return fail(w + ": values is null");
+    if (!out_rgb8 && !out_rgba8) return fail(w + ": out_rgb8 and out_rgba8 are both null");
+    if (spp < 1) return fail(w + ": spp must be at least 1");
+    rt_tonemap_params p;
+    if (!rttm::resolve(params, p)) return fail(w + ": rt_tonemap_params.struct_size is not one this library knows");
+    if (const char *bad = rttm::bad_field(p)) return fail(w + ": " + bad);
+    const size_t n = (size_t)width * (size_t)height;
+    double scale = p.exposure;
+    if (p.auto_key > 0.0) {
+        double out4[4];
+        log_average(n, values, spp, spp_map, p.delta, p.exposure, p.auto_key, out4);
+        scale = out4[3];
+    }
+    const double w2 = p.white * p.white;
+    for (size_t i = 0; i < n; ++i) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
+        uint8_t rgb[3];
+        for (size_t c = 0; c < 3; ++c) {
+            const double m = values[3 * i + c] * inv;
+            const double x = m * scale;
+            rgb[c] = rtm::rt_quantise(rtm::rt_gamma_encode(rtm::rt_tonemap(p.op, x, w2)));
+        }
+        if (out_rgb8) { out_rgb8[3 * i] = rgb[0]; out_rgb8[3 * i + 1] = rgb[1]; out_rgb8[3 * i + 2] = rgb[2]; }
+        if (out_rgba8) { out_rgba8[4 * i] = rgb[0]; out_rgba8[4 * i + 1] = rgb[1]; out_rgba8[4 * i + 2] = rgb[2]; out_rgba8[4 * i + 3] = 0xff; }
     }
     return 0;
 }

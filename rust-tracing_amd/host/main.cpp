@@ -21,6 +21,9 @@
 //   --orbit N --orbit-denoise [--denoise-iters K] [--denoise-sigma X] (the views' sums and sums of squares from one launch, filtered as
 //   one stack: include/rt_amd.h "views denoise"), --orbit-denoise-albedo [--denoise-albedo-sigma X] (the guided filter instead, its albedo
 //   frames from one views launch over the albedo scene).
+//   --tonemap clamp|reinhard|aces, --exposure EV, --auto-exposure [KEY], --tonemap-white W (the tone-mapping stage of include/rt_amd.h
+//   in the output stage's place, on every single-GPU route: the bytes of the PNG — each PNG of --orbit, each frame of --live — come
+//   from the route's sums or means exposed by 2^EV, or by KEY over the frame's log-average luminance, through the operator).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -58,6 +61,10 @@ static void usage(const char *argv0) {
             "                         one set of launches, from sums and sums of squares rendered in one launch)\n"
             "          [--orbit-denoise-albedo [--denoise-albedo-sigma X]]   (with --orbit, instead of --orbit-denoise: the albedo-guided filter, with\n"
             "                         first-hit albedo frames of the same views rendered in one launch)\n"
+            "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--tonemap-white W]   (one GPU, any route but --progressive:\n"
+            "                         the final bytes go through an exposure and a tone curve before the gamma; EV in stops, |EV| <= 64, default 0;\n"
+            "                         KEY > 0, default 0.18: the exposure maps the frame's log-average luminance to KEY; W > 0: with --tonemap reinhard,\n"
+            "                         the value that maps to white, default none; --orbit exposes each view on its own)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -65,7 +72,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -133,6 +140,29 @@ int main(int argc, char **argv) {
         }
         else if (a == "--orbit-denoise") ro.orbit_denoise = true;
         else if (a == "--orbit-denoise-albedo") ro.orbit_denoise_albedo = true;
+        else if (a == "--tonemap") {
+            const std::string op = need("--tonemap");
+            tonemap_given = true;
+            if (op == "clamp") ro.tonemap = RT_TONEMAP_CLAMP;
+            else if (op == "reinhard") ro.tonemap = RT_TONEMAP_REINHARD;
+            else if (op == "aces") ro.tonemap = RT_TONEMAP_ACES;
+            else { fprintf(stderr, "--tonemap needs an operator: clamp, reinhard or aces\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--exposure") {
+            char *end = nullptr;
+            const char *v = need("--exposure");
+            ro.exposure_ev = strtod(v, &end); tonemap_given = true;
+            if (end == v || *end != 0 || !(ro.exposure_ev >= -64.0 && ro.exposure_ev <= 64.0)) { fprintf(stderr, "--exposure needs a number of stops from -64 to 64\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--auto-exposure") {
+            ro.auto_exposure = 0.18; tonemap_given = true; // KEY is optional: a following word that is a number is KEY
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) ro.auto_exposure = atof(argv[++i]);
+            if (!(ro.auto_exposure > 0.0) || !(ro.auto_exposure < 1e300)) { fprintf(stderr, "--auto-exposure needs a key above 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--tonemap-white") {
+            ro.tonemap_white = atof(need("--tonemap-white")); tonemap_given = white_given = true;
+            if (!(ro.tonemap_white > 0.0)) { fprintf(stderr, "--tonemap-white needs a value above 0\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -191,6 +221,16 @@ int main(int argc, char **argv) {
                         "with --orbit: --orbit-denoise)\n");
         return 2;
     }
+    if (tonemap_given && (ro.gpus > 1 || ro.progressive_spp > 0)) {
+        fprintf(stderr, "--tonemap, --exposure, --auto-exposure and --tonemap-white shape the final bytes of a one-GPU, one-pass route: they cannot be "
+                        "combined with --gpus > 1 or --progressive\n");
+        return 2;
+    }
+    if (white_given && ro.tonemap != RT_TONEMAP_REINHARD) {
+        fprintf(stderr, "--tonemap-white sets the white point of --tonemap reinhard: it needs --tonemap reinhard\n");
+        return 2;
+    }
+    if (tonemap_given && ro.tonemap < 0) ro.tonemap = RT_TONEMAP_CLAMP; // an exposure alone: the stage with the plain clamp
     if (live_spp_given && !live) {
         fprintf(stderr, "--live-spp sets the samples per frame of --live: it needs -l/--live\n");
         return 2;

@@ -2,7 +2,9 @@
 #include "color.hpp"
 #include "image_io.hpp"
 #include "rt_amd.h"
+#include "rt_host.h"
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 #include <thread>
@@ -128,9 +130,45 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
     return px;
 }
 
+// The tone-mapping stage (include/rt_amd.h "tone mapping") is on when any of its options was given: opt.tonemap >= 0.
+static bool tonemapped(const RenderOptions &opt) { return opt.tonemap >= 0; }
+static rt_tonemap_params tonemap_params(const char *who, const RenderOptions &opt) {
+    rt_tonemap_params tp;
+    if (rt_tonemap_params_init_sized(&tp, sizeof tp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
+    tp.op = opt.tonemap; tp.exposure = std::exp2(opt.exposure_ev); tp.auto_key = opt.auto_exposure; tp.white = opt.tonemap_white;
+    return tp;
+}
+
+std::vector<uint8_t> tonemap_rgb8(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
+    const rt_tonemap_params tp = tonemap_params("tonemap", opt);
+    std::vector<uint8_t> px((size_t)width * (size_t)height * 3u);
+    if (values.size() != px.size()) throw std::runtime_error("tonemap: the frame does not hold 3 * width * height values");
+    if (rth_tonemap(width, height, values.data(), spp, nullptr, &tp, px.data(), nullptr) != 0) throw std::runtime_error(rth_last_error());
+    return px;
+}
+
+std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
+                                    const RenderOptions &opt) {
+    const rt_tonemap_params tp = tonemap_params("tonemap", opt);
+    const int64_t n_pix = (int64_t)width * height, bytes = n_pix * (rgba ? 4 : 3), work = rt_tonemap_workspace_bytes(width, height);
+    void *d_out = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_out); rt_device_free(0, d_work); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("tonemap: " + msg); } };
+    if (work < 0) throw std::runtime_error("tonemap: no workspace for a frame of this size");
+    check(rt_device_malloc(0, bytes, &d_out));
+    if (tp.auto_key > 0.0) check(rt_device_malloc(0, work, &d_work));
+    check(rt_tonemap_device(width, height, d_values, spp, d_spp, &tp, rgba ? nullptr : static_cast<uint8_t *>(d_out),
+                            rgba ? static_cast<uint8_t *>(d_out) : nullptr, d_work, nullptr));
+    std::vector<uint8_t> px((size_t)bytes);
+    check(rt_device_download(0, px.data(), d_out, bytes, nullptr)); // (waits for the stage: the buffers are freed behind it)
+    cleanup();
+    return px;
+}
+
 // what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
-// (n_frames: the views forms' stack of frames, one behind the other in every buffer)
-static std::vector<uint8_t> run_denoise(const char *who, int32_t width, int32_t height, int64_t work,
+// (n_frames: the views forms' stack of frames, one behind the other in every buffer).  With the tone-mapping stage on, the filter
+// writes no bytes (a null d_rgba8) and the stage makes them from the filtered means, every frame of a stack as a frame of its own.
+static std::vector<uint8_t> run_denoise(const char *who, const RenderOptions &opt, int32_t width, int32_t height, int64_t work,
                                         const std::function<int(double *, uint8_t *, void *)> &call, int32_t n_frames = 1) {
     const int64_t n_pix = (int64_t)width * height * n_frames;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_work = nullptr;
@@ -138,9 +176,21 @@ static std::vector<uint8_t> run_denoise(const char *who, int32_t width, int32_t 
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error(std::string(who) + ": " + msg); } };
     if (work < 0) throw std::runtime_error(std::string(who) + ": no workspace for a frame of this size");
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
-    check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+    if (!tonemapped(opt)) check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
     check(rt_device_malloc(0, work, &d_work));
     check(call(static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work));
+    if (tonemapped(opt)) {
+        std::vector<uint8_t> rgb;
+        try {
+            for (int32_t k = 0; k < n_frames; ++k) {
+                const std::vector<uint8_t> one = tonemap_device(width, height, static_cast<const double *>(d_mean) + (int64_t)k * width * height * 3, 1,
+                                                                nullptr, false, opt);
+                rgb.insert(rgb.end(), one.begin(), one.end());
+            }
+        } catch (...) { cleanup(); throw; }
+        cleanup();
+        return rgb;
+    }
     std::vector<uint8_t> rgba((size_t)n_pix * 4u);
     check(rt_device_download(0, rgba.data(), d_rgba8, n_pix * 4, nullptr));
     cleanup();
@@ -154,7 +204,7 @@ std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum,
     rt_denoise_params dp;
     if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise: ") + rt_last_error());
     dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
-    return run_denoise("denoise", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_device(width, height, d_sum, d_sum_sq, spp, d_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
     });
 }
@@ -164,7 +214,7 @@ std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double 
     rt_denoise_albedo_params dp;
     if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo: ") + rt_last_error());
     dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
-    return run_denoise("denoise_albedo", width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise_albedo", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_albedo_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
     });
 }
@@ -174,7 +224,7 @@ std::vector<uint8_t> denoise_guided(int32_t width, int32_t height, const double 
     rt_denoise_guided_params dp;
     if (rt_denoise_guided_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_guided: ") + rt_last_error());
     dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
-    return run_denoise("denoise_guided", width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_sum != nullptr),
+    return run_denoise("denoise_guided", opt, width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_sum != nullptr),
                        [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
                            return rt_denoise_guided_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, d_edge_sum, edge_spp, &dp,
                                                            d_mean, d_rgba8, d_work, nullptr);
@@ -187,7 +237,7 @@ std::vector<uint8_t> denoise_views(int32_t width, int32_t height, int32_t n_view
     if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_views: ") + rt_last_error());
     dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
     if (n_views < 1) throw std::runtime_error("denoise_views: n_views must be at least 1");
-    return run_denoise("denoise_views", width, height, rt_denoise_views_workspace_bytes(width, height, n_views), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise_views", opt, width, height, rt_denoise_views_workspace_bytes(width, height, n_views), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_views_device(width, height, n_views, d_sum, d_sum_sq, spp, &dp, d_mean, d_rgba8, d_work, nullptr);
     }, n_views);
 }
@@ -198,7 +248,7 @@ std::vector<uint8_t> denoise_albedo_views(int32_t width, int32_t height, int32_t
     if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo_views: ") + rt_last_error());
     dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
     if (n_views < 1) throw std::runtime_error("denoise_albedo_views: n_views must be at least 1");
-    return run_denoise("denoise_albedo_views", width, height, rt_denoise_albedo_views_workspace_bytes(width, height, n_views),
+    return run_denoise("denoise_albedo_views", opt, width, height, rt_denoise_albedo_views_workspace_bytes(width, height, n_views),
                        [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
                            return rt_denoise_albedo_views_device(width, height, n_views, d_sum, d_sum_sq, spp, d_albedo_sum, albedo_spp, &dp, d_mean,
                                                                  d_rgba8, d_work, nullptr);
@@ -218,7 +268,7 @@ static rt_denoise_params plain_params(const rt_denoise_albedo_params &dp) {
 
 std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const RenderOptions &opt) {
     const rt_denoise_params dp = plain_params(filter_params("denoise_mean", opt));
-    return run_denoise("denoise_mean", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise_mean", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_mean_device(width, height, d_mean, d_m2, samples, &dp, d_out, d_rgba8, d_work, nullptr);
     });
 }
@@ -226,7 +276,7 @@ std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d
 std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                          const double *d_albedo_mean, const RenderOptions &opt) {
     const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean", opt);
-    return run_denoise("denoise_albedo_mean", width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise_albedo_mean", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_albedo_mean_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &dp, d_out, d_rgba8, d_work, nullptr);
     });
 }
@@ -244,7 +294,7 @@ std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const d
                                           const RenderOptions &opt) {
     const rt_denoise_params dp = plain_params(filter_params("denoise_mean_spatial", opt));
     const rt_denoise_spatial_params sp = spatial_params("denoise_mean_spatial", opt);
-    return run_denoise("denoise_mean_spatial", width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+    return run_denoise("denoise_mean_spatial", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
         return rt_denoise_mean_spatial_device(width, height, d_mean, d_m2, samples, &sp, &dp, d_out, d_rgba8, d_work, nullptr);
     });
 }
@@ -253,7 +303,7 @@ std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, 
                                                  const double *d_albedo_mean, const RenderOptions &opt) {
     const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean_spatial", opt);
     const rt_denoise_spatial_params sp = spatial_params("denoise_albedo_mean_spatial", opt);
-    return run_denoise("denoise_albedo_mean_spatial", width, height, rt_denoise_albedo_workspace_bytes(width, height),
+    return run_denoise("denoise_albedo_mean_spatial", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height),
                        [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
                            return rt_denoise_albedo_mean_spatial_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &sp, &dp, d_out, d_rgba8,
                                                                         d_work, nullptr);
@@ -363,6 +413,9 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
                      : denoise(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq), 0,
                                static_cast<const int32_t *>(d_spp), opt);
         } catch (...) { cleanup(); throw; }
+    } else if (tonemapped(opt)) { // each pixel's own spp is its n, through the map
+        try { px = tonemap_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), false, opt); }
+        catch (...) { cleanup(); throw; }
     } else {
         check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
                                          static_cast<uint8_t *>(d_rgb8), nullptr));
@@ -429,31 +482,39 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         }
     }
     const rt_denoise_params plain = plain_params(dp);
+    // with the tone-mapping stage on, the pass and the filters write no bytes (a null d_rgba8): the stage makes the frame shown from
+    // the running mean — or, filtered, from d_shown — and the mean itself is never touched
+    uint8_t *const d_bytes = tonemapped(opt) ? nullptr : static_cast<uint8_t *>(d_rgba8);
     for (int begin = 0; begin < last; begin += pass) {
         const int end = begin + pass < last ? begin + pass : last;
         rt_render_params p{};
         p.seed = opt.seed; p.sample_begin = begin; p.sample_end = end; p.max_depth = cam.max_depth;
         p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
         if (!denoised) {
-            check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+            check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), d_bytes, nullptr));
         } else {
             check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
             if (guided) {
                 check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
                 check(spatial ? rt_denoise_albedo_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
                                                                       static_cast<const double *>(d_alb), &sp, &dp, static_cast<double *>(d_shown),
-                                                                      static_cast<uint8_t *>(d_rgba8), d_work, nullptr)
+                                                                      d_bytes, d_work, nullptr)
                               : rt_denoise_albedo_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
                                                               static_cast<const double *>(d_alb), &dp, static_cast<double *>(d_shown),
-                                                              static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+                                                              d_bytes, d_work, nullptr));
             } else {
                 check(spatial ? rt_denoise_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &sp,
-                                                               &plain, static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr)
+                                                               &plain, static_cast<double *>(d_shown), d_bytes, d_work, nullptr)
                               : rt_denoise_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &plain,
-                                                       static_cast<double *>(d_shown), static_cast<uint8_t *>(d_rgba8), d_work, nullptr));
+                                                       static_cast<double *>(d_shown), d_bytes, d_work, nullptr));
             }
         }
-        check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
+        if (tonemapped(opt)) {
+            try { frame = tonemap_device(w, h, static_cast<const double *>(denoised ? d_shown : d_mean), 1, nullptr, true, opt); }
+            catch (...) { cleanup(); throw; }
+        } else {
+            check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
+        }
         if (on_frame) {
             try { on_frame(frame, end); } catch (...) { cleanup(); throw; }
         }
@@ -547,7 +608,9 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
         const std::vector<double> one(sums.begin() + (ptrdiff_t)(frame * (size_t)k), sums.begin() + (ptrdiff_t)(frame * (size_t)(k + 1)));
         char suffix[16];
         snprintf(suffix, sizeof suffix, "_%03d.png", k);
-        if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, resolve_rgb8(one, cam.samples_per_pixel).data()))
+        const std::vector<uint8_t> px = tonemapped(opt) ? tonemap_rgb8(one, cam.image_width, cam.image_height, cam.samples_per_pixel, opt) // (each view its own frame)
+                                                        : resolve_rgb8(one, cam.samples_per_pixel);
+        if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, px.data()))
             throw std::runtime_error("Should've encoded the image into a file.");
     }
     if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
@@ -585,7 +648,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     }
 
     now = clock::now();
-    const std::vector<uint8_t> px = resolve_rgb8(sums, camera->samples_per_pixel);
+    const std::vector<uint8_t> px = tonemapped(opt) ? tonemap_rgb8(sums, w, h, camera->samples_per_pixel, opt) : resolve_rgb8(sums, camera->samples_per_pixel);
     if (!write_png_rgb8(output_file_name + ".png", (int32_t)camera->image_width, (int32_t)camera->image_height,
                         px.data()))
         throw std::runtime_error("Should've encoded the image into a file."); // src/renderer.rs:72

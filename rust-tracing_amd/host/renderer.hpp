@@ -8,6 +8,7 @@
 #include "camera.hpp"
 #include "hittable.hpp"
 #include <functional>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>
@@ -68,6 +69,14 @@ struct RenderOptions {
     // neighbouring pixels, so the first pass is shown filtered too.  0: off, the means forms as they are.
     int live_denoise_spatial = 0;
     int denoise_spatial_radius = 1; // its window_radius, 1..3
+    // the tone-mapping stage (include/rt_amd.h "tone mapping") in the output stage's place, on every single-GPU route: the final bytes
+    // come from rt_tonemap_device — a plain render's and an unfiltered orbit's from its host mirror rth_tonemap, the same bytes — on the
+    // route's sums (adaptive: with the spp map), the filters' means, or the live route's running mean.  tonemap is the operator
+    // (RT_TONEMAP_*); -1: the stage is off and every route is what it is without it.  Orbit handles each view as a frame of its own.
+    int tonemap = -1;
+    double exposure_ev = 0.0;       // stops: the stage's exposure is exp2(exposure_ev)
+    double auto_exposure = 0.0;     // > 0: the key the frame's log-average luminance is mapped to (auto_key); 0: off
+    double tonemap_white = std::numeric_limits<double>::infinity(); // Reinhard's white
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -109,6 +118,14 @@ std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const d
                                           const RenderOptions &opt = {});
 std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                                  const double *d_albedo_mean, const RenderOptions &opt = {});
+
+// The tone-mapping stage with opt's operator, exposure, key and white.  tonemap_rgb8: on a HOST frame of sums (3 * w * h doubles) with
+// the uniform count spp, through the host mirror; returns 3 * w * h bytes.  tonemap_device: rt_tonemap_device on device 0 over a
+// DEVICE frame (sums with spp or, if d_spp is not null, a device map; means with spp = 1); returns 3 * w * h bytes, or with `rgba`
+// 4 * w * h.  Both throw std::runtime_error on a library error.
+std::vector<uint8_t> tonemap_rgb8(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
+std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
+                                    const RenderOptions &opt);
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.
