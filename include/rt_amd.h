@@ -805,6 +805,56 @@ int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_view
                                    const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
                                    uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- bloom (opt-in; nothing above changes) ------------------------------------------------------------------------------------------------
+ * A tone curve works one pixel at a time: a radiance-15 lamp and a radiance-1.5 wall beside it both end near white.  rt_bloom_device
+ * spreads the light of the pixels above a luminance threshold over their neighbourhood BEFORE the curve: a bright pass, K levels of the
+ * separable five-tap B3-spline blur at strides 1, 2, 4, ... (the a-trous scheme of the denoisers: a glow of radius 2 * (2^K - 1) pixels at
+ * full resolution, ten taps per level, no resampling), the levels' average added back to the frame.  Its output is a frame of MEANS: feed
+ * it to rt_tonemap_device with spp = 1, or to rt_resolve_rgba8_device.
+ *
+ * Normative definition.  The arithmetic rules are those of "Arithmetic" below: f64, every operation rounded on its own, no FMA, IEEE
+ * division.  h = (1/16, 1/4, 3/8, 1/4, 1/16), indexed by d = -2 .. 2; pixel (i, j) has index j * w + i.
+ *   Input value.  m_c = S_c * (1.0 / (double)n), exactly tone mapping's "Input value" (n = spp, or d_spp[pixel]; means form: spp == 1,
+ *                 no map).
+ *   Bright pass.  L = ((0.2126 * m_r) + (0.7152 * m_g)) + (0.0722 * m_b).
+ *                 p is BRIGHT iff all three m_c are finite, L is finite and L > threshold.
+ *                 Bright:  k = (L - threshold) / L;  B0_c = m_c * k.     Any other pixel: B0_c = +0.0.
+ *                 (threshold == 0: k = L / L = 1 exactly, B0 = m.)
+ *   Level k = 0 .. K-1, stride s = 2^k, per channel:
+ *      H_c(i,j)     = acc, where acc = +0.0; for d = -2 .. 2 in order, skipping i + s*d outside [0, w):
+ *                         acc = acc + (h[d] * B_k,c(i + s*d, j))
+ *      B_k+1,c(i,j) = the same along j over H_c (skipping j + s*d outside [0, h))
+ *      A_k+1,c      = A_k,c + B_k+1,c              (A_0 = +0.0)
+ *   Output.       g_c = A_K,c / (double)K;  out_c = m_c + (strength * g_c)     for EVERY pixel, bright or not.
+ * Taps outside the frame are skipped and nothing is renormalised: light that leaves the frame is lost.  A non-finite pixel is never a
+ * source, so NaN and +-inf do not spread; such a pixel keeps its own m through the final addition.
+ * Consequences.  If no pixel is bright, g = +0.0 and out = m (bit for bit on a frame without -0.0): followed by rt_tonemap_device with
+ * the clamp, exposure 1 and no key, the bytes are those of rt_resolve_rgb8_device, rt_resolve_rgb8_spp_device and rt_resolve_rgba8_device.
+ * A single bright pixel of value 1 with threshold 0, far from the border, gives the outer products of h exactly: all weights are dyadic.
+ *
+ * rt_bloom_device reads d_values (3 * w * h doubles: sums with the uniform count spp or the per-pixel map d_spp, or means with spp = 1)
+ * and writes d_mean_out (3 * w * h doubles); d_values is not written.  It works in d_workspace (rt_bloom_workspace_bytes(w, h) bytes of
+ * device memory, 16-byte aligned, the caller's; nothing in it is read before the call writes it).  The call is enqueued on hip_stream,
+ * does not synchronise and allocates nothing.  spp must be >= 1 even where d_spp is given (it is then not read).  There is no views form:
+ * a stack of views is blurred one view per call, because a tap must never leave its own frame.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; a null d_values,
+ * d_mean_out or d_workspace; spp < 1; a struct_size this library does not know; levels outside 1..8; threshold that is not a finite
+ * number >= 0; strength likewise; a d_workspace that is not 16-byte aligned; d_mean_out overlapping d_values. */
+typedef struct rt_bloom_params {
+    uint32_t struct_size;   /* sizeof(rt_bloom_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t levels;         /* K, 1..8 (default 5): strides 1 .. 2^(K-1) */
+    double threshold;       /* luminance above which a pixel is a source: finite, >= 0 (default 1.0) */
+    double strength;        /* factor of the glow added back: finite, >= 0 (default 0.25) */
+} rt_bloom_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_bloom_params_init_sized(rt_bloom_params *params, uint32_t struct_size);
+/* Bytes of device memory the call needs for a w x h frame (three regions — B, H and A — of 24 * w * h bytes, each rounded up to a
+ * multiple of 16); -1 for a size the call refuses. */
+int64_t rt_bloom_workspace_bytes(int32_t width, int32_t height);
+int rt_bloom_device(int32_t width, int32_t height, const double *d_values /* 3*w*h */, int32_t spp, const int32_t *d_spp /* NULL: uniform */,
+                    const rt_bloom_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h MEANS */, void *d_workspace,
+                    void *hip_stream);
+
 /* ---- tone mapping (opt-in; nothing above changes) ----------------------------------------------------------------------------------------
  * Every route above ends in color_to_rgb: (u8)(256 * clamp(x^(1/2.2), 0, 0.999)).  Radiance above 1 is clipped flat and a dark frame
  * cannot be lifted.  rt_tonemap_device is that output stage with an exposure and a tone curve in front of the gamma, and optionally an

@@ -225,6 +225,13 @@ int rt_debug_visit_stats(uint64_t out[12]);
 int rt_debug_set_tuning(int32_t th_prim, int32_t th_other, int32_t th_shade, int32_t th_box, int32_t use_lds,
                         int32_t th_new);
 
+/* Test / tuning hook: the largest stride at which rt_bloom_device calls from now on run a level as ONE launch (the H pass of a tile and
+ * its halo rows into the LDS, a barrier, the V pass from there) instead of two global passes: 0 (never), 1 or 2, whatever the frame;
+ * negative: back to the built-in rule (strides 1 and 2 on frames of at least 512 tiles of 64 x 16 pixels, never on smaller ones).
+ * Returns the value in force before the call (-1: the built-in rule); a max_stride above 2 counts as 2.
+ * Affects speed only, never results.  Process-wide. */
+int rt_debug_set_bloom_fused(int32_t max_stride);
+
 
 #ifdef __cplusplus
 }

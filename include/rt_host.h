@@ -57,6 +57,12 @@ int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp
                 const rt_tonemap_params *params /* NULL: defaults */, uint8_t *out_rgb8, uint8_t *out_rgba8);
 int rth_log_average_luminance(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
                               double delta, double *out4);
+/* The host mirror of rt_bloom_device (rt_amd.h "bloom") on host memory: the same shared per-value functions in the same order, so
+ * out_mean (3 * w * h doubles, a frame of means) holds the device's bits.  `values` as rth_tonemap takes them.  It refuses what the
+ * device call refuses of these arguments, in the same order and with the same words (-1, the field named in rth_last_error); there is
+ * no workspace and no stream. */
+int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
+              const rt_bloom_params *params /* NULL: defaults */, double *out_mean);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* Deterministic procedural RGB8 map used where assets/earth-large.jpg is unavailable. */

@@ -308,6 +308,22 @@ def tonemap_params(**kw) -> "TonemapParams":
     return t
 
 
+class BloomParams(C.Structure):
+    """rt_bloom_params (rt_bloom_device, rth_bloom)."""
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("threshold", C.c_double), ("strength", C.c_double)]
+
+
+def bloom_params(**kw) -> "BloomParams":
+    """rt_bloom_params_init_sized, then the given fields (levels=, threshold=, strength=)."""
+    b = BloomParams()
+    _check(amd_lib().rt_bloom_params_init_sized(C.byref(b), C.sizeof(b)), "rt_bloom_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(BloomParams._fields_):
+            raise TypeError(f"rt_bloom_params has no field {k}")
+        setattr(b, k, v)
+    return b
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -401,6 +417,9 @@ RT_AMD_SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoise_albedo_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_bloom_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_bloom_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_bloom_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_tonemap_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_tonemap_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_tonemap_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -432,6 +451,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_set_traversal": (C.c_int, [C.c_int32, C.c_int32]),
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_debug_set_start_inline": (C.c_int, [C.c_int32]),
+    "rt_debug_set_bloom_fused": (C.c_int, [C.c_int32]),
     "rt_debug_ordered_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_ordered_layout_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tuning": (C.c_int, [C.c_int32] * 6),
@@ -700,6 +720,7 @@ RT_HOST_SYMBOLS = {
     "rth_resolve_rgb8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
     "rth_tonemap": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_log_average_luminance": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]),
+    "rth_bloom": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_load_image": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -1604,6 +1625,52 @@ def log_average_luminance_host(values, spp, *, spp_map=None, delta=1e-4):
                                             out.ctypes.data) != 0:
         raise RtError(host_lib().rth_last_error().decode(errors="replace"))
     return tuple(float(x) for x in out)
+
+
+def bloom_workspace_bytes(width, height) -> int:
+    n = int(amd_lib().rt_bloom_workspace_bytes(width, height))
+    if n < 0:
+        raise RtError(f"rt_bloom_workspace_bytes: no workspace for a {width}x{height} frame")
+    return n
+
+
+def bloom_device(width, height, d_values_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0,
+                 params: "BloomParams | None" = None, stream: int = 0):
+    """rt_bloom_device: the bright pass, the a-trous levels and the glow added back, over a device frame of 3 w h doubles — sums with the
+    uniform sample count `spp` or, if d_spp_ptr is not 0, a device map of w h int32; means with spp = 1 — into the 3 w h doubles of MEANS
+    at d_mean_out_ptr, working in `d_workspace_ptr` (bloom_workspace_bytes(w, h) device bytes).  Enqueued on `stream`."""
+    _check(amd_lib().rt_bloom_device(width, height, C.c_void_p(d_values_ptr or None), spp, C.c_void_p(d_spp_ptr or None),
+                                     C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr or None),
+                                     C.c_void_p(d_workspace_ptr or None), C.c_void_p(stream)), "rt_bloom_device")
+
+
+def bloom(values, spp, *, spp_map=None, device=0, **kw):
+    """Uploads an (h, w, 3) frame of sums (with `spp`, or an (h, w) int32 spp map) or of means (spp = 1), runs rt_bloom_device with
+    bloom_params(**kw) and downloads the (h, w, 3) float64 frame of bloomed means."""
+    values, spp_map, w, h = _tonemap_frame("bloom", values, spp_map)
+    params = bloom_params(**kw)
+    import torch
+    with torch.cuda.device(device):
+        d_values = torch.from_numpy(values).cuda()
+        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
+        d_out = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
+        d_ws = torch.empty(bloom_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+        bloom_device(w, h, d_values.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0,
+                     params=params, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return d_out.cpu().numpy()
+
+
+def bloom_host(values, spp, *, spp_map=None, **kw):
+    """rth_bloom (librt_host, CPU): the frame rt_bloom_device gives, bit for bit, from the same shared functions in the same order."""
+    import numpy as np
+    values, spp_map, w, h = _tonemap_frame("bloom_host", values, spp_map)
+    params = bloom_params(**kw)
+    out = np.zeros((h, w, 3), dtype=np.float64)
+    if host_lib().rth_bloom(w, h, values.ctypes.data, int(spp), spp_map.ctypes.data if spp_map is not None else None, C.byref(params),
+                            out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return out
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

@@ -3,7 +3,9 @@
 #include "rt_api.hpp"
 #include "rt_qfilt.hpp"
 #include "rt_tonemap_shared.h"
+#include "rt_bloom_shared.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2141,6 +2143,67 @@ int rt_log_average_luminance_device(int32_t width, int32_t height, const double 
     launch_log_average((int64_t)n_pix, d_values, 1.0 / (double)spp, d_spp, delta, (TonemapPartial *)((double *)d_workspace + 4), 1.0, 0.0, d_out4,
                        (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- bloom (rt_bloom.hip): a bright pass and K a-trous levels of the B3-spline blur, their average added back to the means ----
+
+// The largest stride whose level runs as the one-launch LDS form; negative: the built-in rule (rt_debug_set_bloom_fused; speed only).
+// The rule is DESIGN.md "Bloom"'s measurement: strides 1 and 2 where the frame has at least two tiles per CU of an MI355X — the form is
+// 5 % ahead on 1200 x 800 (950 tiles) and well behind on 256 x 256 (64 tiles), where its workgroups cannot fill the machine.
+constexpr int64_t BLOOM_FUSED_MIN_TILES = 512;
+static std::atomic<int32_t> g_bloom_fused_max{-1};
+
+int rt_debug_set_bloom_fused(int32_t max_stride) {
+    return g_bloom_fused_max.exchange(max_stride < 0 ? -1 : max_stride > BLOOM_FUSED_MAX_STRIDE ? BLOOM_FUSED_MAX_STRIDE : max_stride);
+}
+
+int rt_bloom_params_init_sized(rt_bloom_params *params, uint32_t struct_size) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_bloom_params_init_sized: null argument");
+    if (!rtbl::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_bloom_params_init_sized: struct_size is not one this library knows");
+    rt_bloom_params full;
+    rtbl::defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+
+int64_t rt_bloom_workspace_bytes(int32_t width, int32_t height) { return rtbl::workspace_bytes(width, height); }
+
+int rt_bloom_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const rt_bloom_params *params,
+                    double *d_mean_out, void *d_workspace, void *hip_stream) {
+    const std::string w("rt_bloom_device");
+    rt_bloom_params p;
+    if (const char *bad = rtbl::bad_argument(true, width, height, d_values, d_mean_out, d_workspace, spp, params, p))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + bad);
+    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = n_pix * 3u * sizeof(double);
+    if (overlaps(d_mean_out, frame_bytes, d_values, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_values");
+    if (int rc = select_device_of(d_mean_out, "rt_bloom_device")) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int64_t region = rtbl::region_bytes(width, height);
+    // the three regions: `cur` holds B_k, `other` takes H (two passes: V writes B_k+1 back into cur) or B_k+1 itself (one launch: they swap)
+    double *cur = (double *)d_workspace, *other = (double *)((char *)d_workspace + region), *a = (double *)((char *)d_workspace + 2 * region);
+    const double inv_spp = 1.0 / (double)spp;
+    launch_bloom_bright((int64_t)n_pix, d_values, inv_spp, d_spp, p.threshold, cur, a, stream);
+    HIP_TRY(hipGetLastError());
+    const BloomOutput out{d_values, inv_spp, d_spp, p.levels, p.strength, d_mean_out};
+    int32_t fused_max = g_bloom_fused_max.load();
+    if (fused_max < 0) fused_max = bloom_fused_tiles(width, height) >= BLOOM_FUSED_MIN_TILES ? BLOOM_FUSED_MAX_STRIDE : 0;
+    for (int32_t k = 0; k < p.levels; ++k) {
+        const int32_t stride = 1 << k;
+        const BloomOutput *last = k == p.levels - 1 ? &out : nullptr;
+        if (stride <= fused_max) {
+            launch_bloom_level_fused(width, height, stride, cur, other, a, last, stream);
+            HIP_TRY(hipGetLastError());
+            std::swap(cur, other);
+        } else {
+            launch_bloom_h(width, height, stride, cur, other, stream);
+            HIP_TRY(hipGetLastError());
+            launch_bloom_v(width, height, stride, other, cur, a, last, stream);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     return RT_OK;
 }
 

@@ -254,6 +254,21 @@ void launch_tonemap_rgb8(int64_t n_pixels, const double *values, double inv_spp,
                          double w2, uint8_t *rgb, hipStream_t stream);
 void launch_tonemap_rgba8(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double scale, const double *d_scale, int32_t op,
                           double w2, uint8_t *rgba, hipStream_t stream);
+// bloom (rt_bloom.hip; rt_bloom_device).  Frames are 3 doubles per pixel, row after row.  launch_bloom_bright writes every pixel's B0
+// to b0 and +0.0 to a.  A level at `stride` reads b_in and leaves B_k+1 in b_out and A += B_k+1 in a; on the last level it writes
+// out = m + strength * (A / levels) instead, from values / inv_spp / spp_map, and neither b_out nor a.  launch_bloom_level_fused is
+// the level as one launch (stride 1 or 2 — BLOOM_FUSED_MAX_STRIDE; b_out must not be b_in), one workgroup per tile of 64 x 16 pixels,
+// bloom_fused_tiles of them; launch_bloom_h and launch_bloom_v are its two global passes at any stride (h: b_in -> h_out; v: h_in ->
+// b_out, which may be the b_in of the h pass).
+constexpr int32_t BLOOM_FUSED_MAX_STRIDE = 2;
+int64_t bloom_fused_tiles(int32_t w, int32_t h);
+struct BloomOutput { const double *values; double inv_spp; const int32_t *spp_map; int32_t levels; double strength; double *out; };
+void launch_bloom_bright(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double threshold, double *b0, double *a,
+                         hipStream_t stream);
+void launch_bloom_level_fused(int32_t w, int32_t h, int32_t stride, const double *b_in, double *b_out, double *a, const BloomOutput *last,
+                              hipStream_t stream);
+void launch_bloom_h(int32_t w, int32_t h, int32_t stride, const double *b_in, double *h_out, hipStream_t stream);
+void launch_bloom_v(int32_t w, int32_t h, int32_t stride, const double *h_in, double *b_out, double *a, const BloomOutput *last, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

@@ -6,6 +6,7 @@
 //   rt_gamma_encode   x^(1/2.2), the output stage's linear_to_gamma (src/color.rs:3-6)
 //   rt_quantise       (256 * clamp(g, 0, 0.999)) as u8 (src/color.rs:12-19)
 //   rt_tonemap, rt_luminance, rt_log_luminance_term, rt_log_average_result   the tone-mapping stage's operator and auto-exposure's terms
+//   rt_bloom_bright, rt_bloom_taps, rt_bloom_output   bloom's bright pass, one five-tap accumulation and its output value
 //   rt_adaptive_converged   adaptive sampling's per-pixel stopping rule
 // Coefficients: FreeBSD msun e_log.c / e_exp.c (public constants of the published algorithms).
 #pragma once
@@ -153,6 +154,40 @@ RT_HD void rt_log_average_result(double T, uint32_t count, double exposure, doub
     out4[1] = lavg;
     out4[2] = (double)count;
     out4[3] = auto_key > 0.0 ? scale : 0.0;
+}
+
+// Bloom (include/rt_amd.h "bloom"), every operation rounded on its own, in the header's order.
+// The bright pass of one pixel with means (mr, mg, mb): it is a source iff the three means and its luminance L are finite and
+// L > threshold; a source's b0 is its means times k = (L - threshold) / L, any other pixel's +0.0.
+RT_HD void rt_bloom_bright(double mr, double mg, double mb, double threshold, double b0[3]) {
+    b0[0] = b0[1] = b0[2] = 0.0;
+    if (((f2u(mr) >> 52) & 0x7ff) == 0x7ff || ((f2u(mg) >> 52) & 0x7ff) == 0x7ff || ((f2u(mb) >> 52) & 0x7ff) == 0x7ff) return;
+    const double L = rt_luminance(mr, mg, mb);
+    if (((f2u(L) >> 52) & 0x7ff) == 0x7ff || !(L > threshold)) return;
+    const double d = L - threshold;
+    const double k = d / L;
+    b0[0] = mr * k;
+    b0[1] = mg * k;
+    b0[2] = mb * k;
+}
+
+// One five-tap accumulation: acc = +0.0; for d = -2 .. 2 in order, acc = acc + (h[d] * v[d + 2]) for the taps whose bit d + 2 of
+// `inside` is set (the others lie outside the frame and are skipped; their v is not read).  h = (1/16, 1/4, 3/8, 1/4, 1/16).
+RT_HD double rt_bloom_taps(const double v[5], uint32_t inside) {
+    double acc = 0.0;
+    if (inside & 1u) acc = acc + (0.0625 * v[0]);
+    if (inside & 2u) acc = acc + (0.25 * v[1]);
+    if (inside & 4u) acc = acc + (0.375 * v[2]);
+    if (inside & 8u) acc = acc + (0.25 * v[3]);
+    if (inside & 16u) acc = acc + (0.0625 * v[4]);
+    return acc;
+}
+
+// The output value: g = A_K / (double)K; out = m + (strength * g)
+RT_HD double rt_bloom_output(double m, double a, int32_t levels, double strength) {
+    const double g = a / (double)levels;
+    const double t = strength * g;
+    return m + t;
 }
 
 // Adaptive sampling's convergence rule (include/rt_amd.h rt_render_adaptive), for a pixel with n >= 2 samples, channel sums S

@@ -5,6 +5,7 @@
 #include "renderer.hpp"
 #include "scenes.hpp"
 #include "../csrc/rt_tonemap_shared.h"
+#include "../csrc/rt_bloom_shared.h"
 #include <cstring>
 #include <exception>
 #include <string>
@@ -184,6 +185,51 @@ int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp
         }
         if (out_rgb8) { out_rgb8[3 * i] = rgb[0]; out_rgb8[3 * i + 1] = rgb[1]; out_rgb8[3 * i + 2] = rgb[2]; }
         if (out_rgba8) { out_rgba8[4 * i] = rgb[0]; out_rgba8[4 * i + 1] = rgb[1]; out_rgba8[4 * i + 2] = rgb[2]; out_rgba8[4 * i + 3] = 0xff; }
+    }
+    return 0;
+}
+
+// ---- bloom: the host mirror of rt_bloom_device (include/rt_amd.h "bloom") ----
+
+int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, const rt_bloom_params *params,
+              double *out_mean) {
+    const std::string who("rth_bloom");
+    rt_bloom_params p;
+    if (const char *bad = rtbl::bad_argument(false, width, height, values, out_mean, nullptr, spp, params, p)) return fail(who + ": " + bad);
+    const size_t w = (size_t)width, h = (size_t)height, n = w * h;
+    {
+        const char *lo = (const char *)values, *out = (const char *)out_mean;
+        if (out < lo + n * 24u && lo < out + n * 24u) return fail(who + ": out_mean must not overlap values");
+    }
+    std::vector<double> b(3 * n), hh(3 * n), a(3 * n, 0.0);
+    for (size_t i = 0; i < n; ++i) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
+        rtm::rt_bloom_bright(values[3 * i] * inv, values[3 * i + 1] * inv, values[3 * i + 2] * inv, p.threshold, &b[3 * i]);
+    }
+    // one five-tap accumulation per value of `dst`, from `src` along pixels (step 1, length w) or along rows (step w, length h)
+    auto pass = [&](const std::vector<double> &src, std::vector<double> &dst, size_t stride, bool along_rows) {
+        for (size_t j = 0; j < h; ++j)
+            for (size_t i = 0; i < w; ++i)
+                for (size_t c = 0; c < 3; ++c) {
+                    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+                    uint32_t inside = 0;
+                    for (int d = 0; d < 5; ++d) {
+                        const int64_t off = (int64_t)stride * (d - 2), ii = (int64_t)i + (along_rows ? 0 : off), jj = (int64_t)j + (along_rows ? off : 0);
+                        if (ii < 0 || ii >= (int64_t)w || jj < 0 || jj >= (int64_t)h) continue;
+                        inside |= 1u << d;
+                        v[d] = src[3 * ((size_t)jj * w + (size_t)ii) + c];
+                    }
+                    dst[3 * (j * w + i) + c] = rtm::rt_bloom_taps(v, inside);
+                }
+    };
+    for (int32_t k = 0; k < p.levels; ++k) {
+        pass(b, hh, (size_t)1 << k, false);
+        pass(hh, b, (size_t)1 << k, true);
+        for (size_t e = 0; e < 3 * n; ++e) a[e] = a[e] + b[e];
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
+        for (size_t c = 0; c < 3; ++c) out_mean[3 * i + c] = rtm::rt_bloom_output(values[3 * i + c] * inv, a[3 * i + c], p.levels, p.strength);
     }
     return 0;
 }

@@ -24,6 +24,9 @@
 //   --tonemap clamp|reinhard|aces, --exposure EV, --auto-exposure [KEY], --tonemap-white W (the tone-mapping stage of include/rt_amd.h
 //   in the output stage's place, on every single-GPU route: the bytes of the PNG — each PNG of --orbit, each frame of --live — come
 //   from the route's sums or means exposed by 2^EV, or by KEY over the frame's log-average luminance, through the operator).
+//   --bloom [STRENGTH] [--bloom-threshold T] [--bloom-levels K] (bloom of include/rt_amd.h in front of that stage, wherever it runs: the
+//   light of the pixels above luminance T is spread over K a-trous levels and added back STRENGTH times; alone it implies the stage with
+//   the clamp).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -65,6 +68,10 @@ static void usage(const char *argv0) {
             "                         the final bytes go through an exposure and a tone curve before the gamma; EV in stops, |EV| <= 64, default 0;\n"
             "                         KEY > 0, default 0.18: the exposure maps the frame's log-average luminance to KEY; W > 0: with --tonemap reinhard,\n"
             "                         the value that maps to white, default none; --orbit exposes each view on its own)\n"
+            "          [--bloom [STRENGTH] [--bloom-threshold T] [--bloom-levels K]]   (one GPU, any route but --progressive: in front of the tone\n"
+            "                         mapping, the light of the pixels whose luminance is above T, default 1, is blurred over K = 1..8 levels,\n"
+            "                         default 5 (a glow of radius 2 * (2^K - 1) pixels), and added back STRENGTH >= 0 times, default 0.25; alone it\n"
+            "                         implies --tonemap clamp; --orbit blooms each view on its own)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -72,7 +79,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -163,6 +170,21 @@ int main(int argc, char **argv) {
             ro.tonemap_white = atof(need("--tonemap-white")); tonemap_given = white_given = true;
             if (!(ro.tonemap_white > 0.0)) { fprintf(stderr, "--tonemap-white needs a value above 0\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--bloom") {
+            ro.bloom = 0.25; // STRENGTH is optional: a following word that is a number is STRENGTH
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) ro.bloom = atof(argv[++i]);
+            if (!(ro.bloom >= 0.0) || !(ro.bloom < 1e300)) { fprintf(stderr, "--bloom needs a strength of at least 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--bloom-threshold") {
+            char *end = nullptr;
+            const char *v = need("--bloom-threshold");
+            ro.bloom_threshold = strtod(v, &end); bloom_knob_given = true;
+            if (end == v || *end != 0 || !(ro.bloom_threshold >= 0.0) || !(ro.bloom_threshold < 1e300)) { fprintf(stderr, "--bloom-threshold needs a luminance of at least 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--bloom-levels") {
+            ro.bloom_levels = atoi(need("--bloom-levels")); bloom_knob_given = true;
+            if (ro.bloom_levels < 1 || ro.bloom_levels > 8) { fprintf(stderr, "--bloom-levels needs a number of levels from 1 to 8\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -226,11 +248,19 @@ int main(int argc, char **argv) {
                         "combined with --gpus > 1 or --progressive\n");
         return 2;
     }
+    if (ro.bloom >= 0.0 && (ro.gpus > 1 || ro.progressive_spp > 0)) {
+        fprintf(stderr, "--bloom runs in front of the tone mapping of a one-GPU, one-pass route: it cannot be combined with --gpus > 1 or --progressive\n");
+        return 2;
+    }
+    if (bloom_knob_given && ro.bloom < 0.0) {
+        fprintf(stderr, "--bloom-threshold and --bloom-levels set the glow of --bloom: they need --bloom\n");
+        return 2;
+    }
     if (white_given && ro.tonemap != RT_TONEMAP_REINHARD) {
         fprintf(stderr, "--tonemap-white sets the white point of --tonemap reinhard: it needs --tonemap reinhard\n");
         return 2;
     }
-    if (tonemap_given && ro.tonemap < 0) ro.tonemap = RT_TONEMAP_CLAMP; // an exposure alone: the stage with the plain clamp
+    if ((tonemap_given || ro.bloom >= 0.0) && ro.tonemap < 0) ro.tonemap = RT_TONEMAP_CLAMP; // an exposure or bloom alone: the stage with the plain clamp
     if (live_spp_given && !live) {
         fprintf(stderr, "--live-spp sets the samples per frame of --live: it needs -l/--live\n");
         return 2;

@@ -130,12 +130,13 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
     return px;
 }
 
-// The tone-mapping stage (include/rt_amd.h "tone mapping") is on when any of its options was given: opt.tonemap >= 0.
-static bool tonemapped(const RenderOptions &opt) { return opt.tonemap >= 0; }
+// The tone-mapping stage (include/rt_amd.h "tone mapping") is on when any of its options was given: opt.tonemap >= 0 — or when bloom
+// is on (opt.bloom >= 0), which runs in front of it: the stage then has the clamp unless an operator was chosen.
+static bool tonemapped(const RenderOptions &opt) { return opt.tonemap >= 0 || opt.bloom >= 0.0; }
 static rt_tonemap_params tonemap_params(const char *who, const RenderOptions &opt) {
     rt_tonemap_params tp;
     if (rt_tonemap_params_init_sized(&tp, sizeof tp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
-    tp.op = opt.tonemap; tp.exposure = std::exp2(opt.exposure_ev); tp.auto_key = opt.auto_exposure; tp.white = opt.tonemap_white;
+    tp.op = opt.tonemap >= 0 ? opt.tonemap : RT_TONEMAP_CLAMP; tp.exposure = std::exp2(opt.exposure_ev); tp.auto_key = opt.auto_exposure; tp.white = opt.tonemap_white;
     return tp;
 }
 
@@ -165,6 +166,57 @@ std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double 
     return px;
 }
 
+// Bloom (include/rt_amd.h "bloom") is on when opt.bloom >= 0; it runs in front of the tone-mapping stage, which then takes means.
+static bool bloomed(const RenderOptions &opt) { return opt.bloom >= 0.0; }
+static rt_bloom_params bloom_params(const RenderOptions &opt) {
+    rt_bloom_params bp;
+    if (rt_bloom_params_init_sized(&bp, sizeof bp) != RT_OK) throw std::runtime_error(std::string("bloom: ") + rt_last_error());
+    bp.levels = opt.bloom_levels; bp.threshold = opt.bloom_threshold; bp.strength = opt.bloom;
+    return bp;
+}
+
+std::vector<double> bloom_means(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
+    const rt_bloom_params bp = bloom_params(opt);
+    std::vector<double> out((size_t)width * (size_t)height * 3u);
+    if (values.size() != out.size()) throw std::runtime_error("bloom: the frame does not hold 3 * width * height values");
+    if (rth_bloom(width, height, values.data(), spp, nullptr, &bp, out.data()) != 0) throw std::runtime_error(rth_last_error());
+    return out;
+}
+
+void bloom_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double *d_mean_out, const RenderOptions &opt) {
+    const rt_bloom_params bp = bloom_params(opt);
+    const int64_t work = rt_bloom_workspace_bytes(width, height);
+    if (work < 0) throw std::runtime_error("bloom: no workspace for a frame of this size");
+    void *d_work = nullptr;
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); rt_device_free(0, d_work); throw std::runtime_error("bloom: " + msg); } };
+    check(rt_device_malloc(0, work, &d_work));
+    check(rt_bloom_device(width, height, d_values, spp, d_spp, &bp, d_mean_out, d_work, nullptr));
+    double first = 0.0; // (a download waits for everything enqueued before it: the workspace is freed behind the call)
+    check(rt_device_download(0, &first, d_mean_out, (int64_t)sizeof first, nullptr));
+    rt_device_free(0, d_work);
+}
+
+// the output stage of a HOST frame of sums when the tone-mapping stage is on: bloom first if it is on, then the stage on its means
+static std::vector<uint8_t> staged_rgb8(const std::vector<double> &sums, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
+    if (!bloomed(opt)) return tonemap_rgb8(sums, width, height, spp, opt);
+    return tonemap_rgb8(bloom_means(sums, width, height, spp, opt), width, height, 1, opt);
+}
+
+// ... and of a DEVICE frame
+static std::vector<uint8_t> staged_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
+                                          const RenderOptions &opt) {
+    if (!bloomed(opt)) return tonemap_device(width, height, d_values, spp, d_spp, rgba, opt);
+    void *d_bloomed = nullptr;
+    if (rt_device_malloc(0, (int64_t)width * height * 3 * (int64_t)sizeof(double), &d_bloomed) != RT_OK) throw std::runtime_error(std::string("bloom: ") + rt_last_error());
+    std::vector<uint8_t> px;
+    try {
+        bloom_device(width, height, d_values, spp, d_spp, static_cast<double *>(d_bloomed), opt);
+        px = tonemap_device(width, height, static_cast<const double *>(d_bloomed), 1, nullptr, rgba, opt);
+    } catch (...) { rt_device_free(0, d_bloomed); throw; }
+    rt_device_free(0, d_bloomed);
+    return px;
+}
+
 // what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
 // (n_frames: the views forms' stack of frames, one behind the other in every buffer).  With the tone-mapping stage on, the filter
 // writes no bytes (a null d_rgba8) and the stage makes them from the filtered means, every frame of a stack as a frame of its own.
@@ -183,8 +235,8 @@ static std::vector<uint8_t> run_denoise(const char *who, const RenderOptions &op
         std::vector<uint8_t> rgb;
         try {
             for (int32_t k = 0; k < n_frames; ++k) {
-                const std::vector<uint8_t> one = tonemap_device(width, height, static_cast<const double *>(d_mean) + (int64_t)k * width * height * 3, 1,
-                                                                nullptr, false, opt);
+                const std::vector<uint8_t> one = staged_device(width, height, static_cast<const double *>(d_mean) + (int64_t)k * width * height * 3, 1,
+                                                               nullptr, false, opt);
                 rgb.insert(rgb.end(), one.begin(), one.end());
             }
         } catch (...) { cleanup(); throw; }
@@ -414,7 +466,7 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
                                static_cast<const int32_t *>(d_spp), opt);
         } catch (...) { cleanup(); throw; }
     } else if (tonemapped(opt)) { // each pixel's own spp is its n, through the map
-        try { px = tonemap_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), false, opt); }
+        try { px = staged_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), false, opt); }
         catch (...) { cleanup(); throw; }
     } else {
         check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
@@ -510,7 +562,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
             }
         }
         if (tonemapped(opt)) {
-            try { frame = tonemap_device(w, h, static_cast<const double *>(denoised ? d_shown : d_mean), 1, nullptr, true, opt); }
+            try { frame = staged_device(w, h, static_cast<const double *>(denoised ? d_shown : d_mean), 1, nullptr, true, opt); }
             catch (...) { cleanup(); throw; }
         } else {
             check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
@@ -608,7 +660,7 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
         const std::vector<double> one(sums.begin() + (ptrdiff_t)(frame * (size_t)k), sums.begin() + (ptrdiff_t)(frame * (size_t)(k + 1)));
         char suffix[16];
         snprintf(suffix, sizeof suffix, "_%03d.png", k);
-        const std::vector<uint8_t> px = tonemapped(opt) ? tonemap_rgb8(one, cam.image_width, cam.image_height, cam.samples_per_pixel, opt) // (each view its own frame)
+        const std::vector<uint8_t> px = tonemapped(opt) ? staged_rgb8(one, cam.image_width, cam.image_height, cam.samples_per_pixel, opt) // (each view its own frame)
                                                         : resolve_rgb8(one, cam.samples_per_pixel);
         if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, px.data()))
             throw std::runtime_error("Should've encoded the image into a file.");
@@ -648,7 +700,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     }
 
     now = clock::now();
-    const std::vector<uint8_t> px = tonemapped(opt) ? tonemap_rgb8(sums, w, h, camera->samples_per_pixel, opt) : resolve_rgb8(sums, camera->samples_per_pixel);
+    const std::vector<uint8_t> px = tonemapped(opt) ? staged_rgb8(sums, w, h, camera->samples_per_pixel, opt) : resolve_rgb8(sums, camera->samples_per_pixel);
     if (!write_png_rgb8(output_file_name + ".png", (int32_t)camera->image_width, (int32_t)camera->image_height,
                         px.data()))
         throw std::runtime_error("Should've encoded the image into a file."); // src/renderer.rs:72

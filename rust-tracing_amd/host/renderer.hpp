@@ -77,6 +77,13 @@ struct RenderOptions {
     double exposure_ev = 0.0;       // stops: the stage's exposure is exp2(exposure_ev)
     double auto_exposure = 0.0;     // > 0: the key the frame's log-average luminance is mapped to (auto_key); 0: off
     double tonemap_white = std::numeric_limits<double>::infinity(); // Reinhard's white
+    // bloom (include/rt_amd.h "bloom") in front of the tone-mapping stage, wherever that stage runs: the route's sums or means go through
+    // rt_bloom_device — a plain render's and an unfiltered orbit's through its host mirror rth_bloom, the same bits — and the stage takes
+    // the bloomed means with spp = 1, auto-exposure included.  bloom is the strength; < 0: off.  With bloom on and tonemap < 0 the
+    // stage runs with the clamp.  Orbit blooms each view on its own.
+    double bloom = -1.0;
+    double bloom_threshold = 1.0;   // luminance above which a pixel glows
+    int bloom_levels = 5;           // K, 1..8: a glow of radius 2 * (2^K - 1) pixels
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -126,6 +133,14 @@ std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, 
 std::vector<uint8_t> tonemap_rgb8(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
 std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
                                     const RenderOptions &opt);
+
+// Bloom with opt's strength, threshold and levels.  bloom_means: on a HOST frame (sums with the uniform count spp; means with spp = 1),
+// through the host mirror; returns the 3 * w * h bloomed means.  bloom_device: rt_bloom_device on device 0 over a DEVICE frame (sums with
+// spp or, if d_spp is not null, a device map; means with spp = 1) into the DEVICE frame d_mean_out (3 * w * h doubles, not d_values):
+// the frame stays on the device; the call's workspace is allocated and freed here, and it returns when the frame is written.  Both throw
+// std::runtime_error on a library error.
+std::vector<double> bloom_means(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
+void bloom_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double *d_mean_out, const RenderOptions &opt);
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.
