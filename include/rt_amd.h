@@ -805,6 +805,81 @@ int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_view
                                    const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
                                    uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- guided upsampling (opt-in; nothing above changes) -------------------------------------------------------------------------------------
+ * A frame's cost is its number of paths.  Where a picture is wanted quickly, trace the beauty frame at 1/F of the width and height —
+ * 1/F^2 of the paths — and bring it to full size with a joint bilateral upsampler that takes its EDGES from a full-size surface-ID
+ * frame and its TEXTURE DETAIL from a full-size albedo frame, both first-hit renders of about one bounce per sample: irradiance is
+ * interpolated between the low pixels, stopped where the guides differ, and the albedo is multiplied back per full-size pixel.
+ *
+ * rt_camera_scaled gives the camera of the small frame.  F = factor, 2, 3 or 4; lw = (w + F - 1) / F and lh = (h + F - 1) / F in integer
+ * arithmetic.  *out is *camera with image_width = lw, image_height = lh, and per component, every operation rounded on its own,
+ *      du' = F * du;   dv' = F * dv                               (du = pixel_delta_u, dv = pixel_delta_v; F as a double)
+ *      pixel00_loc' = (pixel00_loc - (0.5 * (du + dv))) + (0.5 * (du' + dv'))
+ * so that low pixel (I, J) covers exactly the full-size pixels [F I, F I + F) x [F J, F J + F); where F does not divide the size the
+ * last low column or row reaches past the frame.  Lens, background, depth and spp are untouched; out may be camera.  No device is
+ * touched.  RT_ERR_INVALID_ARGUMENT, in this order: a null camera; a null out; a factor outside 2..4.
+ *
+ * Normative definition of rt_upsample_device.  f64, every operation rounded on its own, no FMA, IEEE division;
+ * max(a, b) = (b > a ? b : a).  (x, y) is a full-size pixel, index y * w + x; (I, J) a low pixel, index J * lw + I.  S is a low
+ * pixel's entry of d_low, A and E a full-size pixel's entries of d_albedo_sum and d_edge_sum; n_a = albedo_spp, n_e = edge_spp as doubles.
+ *   Low values.   C_c = S_c * (1.0 / (double)spp).
+ *   Full guides.  a_c(p) = A_c / n_a;  g_c(p) = E_c / n_e                            (each only where that guide is given)
+ *   Low guides.   For each guide given, the mean of the guide's full-size means over the IN-FRAME pixels of the low pixel's F x F block:
+ *                 acc = +0.0; for y = F J .. F J + F - 1 (y < h) outer, x = F I .. F I + F - 1 (x < w) inner: acc_c = acc_c + a_c(x, y);
+ *                 a_low_c = acc_c / (double)count, count the number of pixels added.  g_low likewise.
+ *                 A low pixel is VALID iff its three C_c and, for each guide given, its three low guide values are finite.
+ *                 With an albedo guide  d_c = max(a_low_c, albedo_floor);  R_c = C_c / d_c.   Without one  R = C.
+ *   Footprint.    t = 2 x + 1 - F;  i0 = floor(t / (2 F)) (integer floor division: t is negative in the first columns);
+ *                 rx = t - 2 F i0, in [0, 2 F).  The same in y gives j0 and ry.  Taps: J = j0 - 1 .. j0 + 2 outer, I = i0 - 1 .. i0 + 2
+ *                 inner; a tap outside the low frame or not VALID is skipped.
+ *                 ax = |2 F (I - i0) - rx| (an integer, at most 4 F);  wx = (double)(4 F - ax) / (double)(4 F) >= 0 — a tent of two low pixels'
+ *                 radius about the full-size pixel's centre; exact for F = 2 and 4, one rounded division for F = 3.  For F = 3, t is even and
+ *                 rx can be 0: the tap I = i0 + 2 then has ax = 4 F and weight +0.0, and adds nothing.  wy likewise;  ws = wy * wx.
+ *   Stops.        The denoisers' stops between the FULL guide at p = (x, y) and the LOW guide at the tap q:
+ *                      dg = max(max(|g_r(p) - g_low_r(q)|, |g_g(p) - g_low_g(q)|), |g_b(p) - g_low_b(q)|)
+ *                      z = dg / sigma_edge;  tg = 1 - z * z;  eg = (tg > 0 ? tg * tg : 0)
+ *                 and ea the same from a(p), a_low(q) (both un-floored) and sigma_albedo.
+ *                      w = ws * (ea * eg)  with both guides;  w = ws * ea,  w = ws * eg  with one;  w = ws  with none
+ *                      sw = sw + w;   sc_c = sc_c + (w * R_c(q))                       (both from +0.0)
+ *   Output.       sw > 0:  r_c = sc_c / sw.   Otherwise (every tap outside, invalid or stopped):  r = R of the containing low pixel
+ *                 (x / F, y / F) as it is, valid or not.
+ *                 out_c = r_c * max(a_c(p), albedo_floor) with an albedo guide, out = r without.  d_mean_out holds out; d_rgba8, if not
+ *                 NULL, the bytes rt_resolve_rgba8_device gives for out, written by the same kernel.
+ * A non-finite low pixel is never a tap, so it shows at most in its own block (where every other tap is stopped too) and nowhere else;
+ * a non-finite guide pixel makes its own block's low pixel invalid and stops every tap of its own, and spreads no further.
+ * Consequences.  With no guide and a low frame of one dyadic value, F = 2 or 4: every weight is dyadic and out is that value bit for
+ * bit.  A guide that is the same at every pixel changes nothing against no guide (dg = 0, eg = 1, x * 1 = x, each exactly; an albedo
+ * guide of A = n_a everywhere and albedo_floor <= 1 likewise: d = 1, R = C, ea = 1, r * 1 = r).  A full-size pixel whose in-frame,
+ * valid taps all carry its own guide values takes the plain tent result.
+ *
+ * rt_upsample_device takes the FULL size.  It reads d_low (3 * lw * lh doubles: sums with the count spp, or means with spp = 1) and
+ * the guides given, and writes d_mean_out (3 * w * h doubles) and, if given, d_rgba8 (4 * w * h bytes); no input is written.  It works
+ * in d_workspace (rt_upsample_workspace_bytes(w, h, factor) bytes of device memory, 16-byte aligned, the caller's; nothing in it is read
+ * before the call writes it).  The call is enqueued on hip_stream, does not synchronise and allocates nothing.  Without a guide its spp
+ * and its sigma are not used.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1; w * h >= 2^27; a null d_low, d_mean_out
+ * or d_workspace; spp < 1; an albedo guide with albedo_spp < 1; an edge guide with edge_spp < 1; a struct_size this library does not
+ * know; a factor outside 2..4; sigma_edge, sigma_albedo or albedo_floor that is not a number > 0 (checked whichever guides are given); a
+ * d_rgba8 that is not 4-byte aligned; a d_workspace that is not 16-byte aligned; d_mean_out overlapping d_low, d_albedo_sum or
+ * d_edge_sum. */
+int rt_camera_scaled(const rt_camera *camera, int32_t factor, rt_camera *out);
+typedef struct rt_upsample_params {
+    uint32_t struct_size;   /* sizeof(rt_upsample_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t factor;         /* F, 2..4 (default 2): the low frame is ceil(w / F) x ceil(h / F) */
+    double sigma_edge;      /* width of the edge guide's stop (default 0.5: two surface-ID colours differ by at least that), > 0 */
+    double sigma_albedo;    /* width of the albedo guide's stop (default 0.5), > 0 */
+    double albedo_floor;    /* the smallest divisor and factor (default 1e-3), > 0 */
+} rt_upsample_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_upsample_params_init_sized(rt_upsample_params *params, uint32_t struct_size);
+/* Bytes of device memory the call needs for a FULL size of w x h at this factor (three regions — R with the valid flag, the low albedo
+ * and the low edge guide — of 4 doubles per LOW pixel); -1 for a size or a factor the call refuses. */
+int64_t rt_upsample_workspace_bytes(int32_t width, int32_t height, int32_t factor);
+int rt_upsample_device(int32_t width, int32_t height /* the FULL size */, const double *d_low /* 3*lw*lh */,
+                       int32_t spp /* sums with a count; means: 1 */, const double *d_albedo_sum /* 3*w*h, or NULL */, int32_t albedo_spp,
+                       const double *d_edge_sum /* 3*w*h, or NULL */, int32_t edge_spp, const rt_upsample_params *params /* NULL: defaults */,
+                       double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
 /* ---- bloom (opt-in; nothing above changes) ------------------------------------------------------------------------------------------------
  * A tone curve works one pixel at a time: a radiance-15 lamp and a radiance-1.5 wall beside it both end near white.  rt_bloom_device
  * spreads the light of the pixels above a luminance threshold over their neighbourhood BEFORE the curve: a bright pass, K levels of the

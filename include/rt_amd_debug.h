@@ -232,6 +232,12 @@ int rt_debug_set_tuning(int32_t th_prim, int32_t th_other, int32_t th_shade, int
  * Affects speed only, never results.  Process-wide. */
 int rt_debug_set_bloom_fused(int32_t max_stride);
 
+/* Test / tuning hook: the form of the upsample kernel that rt_upsample_device calls from now on launch, whatever the frame: 0 the direct
+ * form (every tap read from the workspace's regions in global memory), 1 (or more) the LDS form (a tile's low records staged once);
+ * negative: back to the built-in rule (the LDS form, which was the faster one at every size and guide set measured).
+ * Returns the value in force before the call (-1: the built-in rule).  Affects speed only, never results.  Process-wide. */
+int rt_debug_set_upsample_form(int32_t form);
+
 
 #ifdef __cplusplus
 }

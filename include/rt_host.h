@@ -63,6 +63,13 @@ int rth_log_average_luminance(int32_t width, int32_t height, const double *value
  * no workspace and no stream. */
 int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
               const rt_bloom_params *params /* NULL: defaults */, double *out_mean);
+/* The host mirror of rt_upsample_device (rt_amd.h "guided upsampling") on host memory: the same shared per-pixel functions in the same
+ * order, so out_mean (3 * w * h doubles) and out_rgba8 (4 * w * h bytes, or NULL) hold the device's bits.  width and height are the FULL
+ * size; `low` holds 3 * lw * lh doubles.  It refuses what the device call refuses of these arguments, in the same order and with the
+ * same words (-1, the field named in rth_last_error); there is no workspace and no stream. */
+int rth_upsample(int32_t width, int32_t height, const double *low, int32_t spp, const double *albedo_sum /* 3*w*h, or NULL */, int32_t albedo_spp,
+                 const double *edge_sum /* 3*w*h, or NULL */, int32_t edge_spp, const rt_upsample_params *params /* NULL: defaults */,
+                 double *out_mean, uint8_t *out_rgba8 /* or NULL */);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* Deterministic procedural RGB8 map used where assets/earth-large.jpg is unavailable. */

@@ -324,6 +324,23 @@ def bloom_params(**kw) -> "BloomParams":
     return b
 
 
+class UpsampleParams(C.Structure):
+    """rt_upsample_params (rt_upsample_device, rth_upsample)."""
+    _fields_ = [("struct_size", C.c_uint32), ("factor", C.c_int32), ("sigma_edge", C.c_double), ("sigma_albedo", C.c_double),
+                ("albedo_floor", C.c_double)]
+
+
+def upsample_params(**kw) -> "UpsampleParams":
+    """rt_upsample_params_init_sized, then the given fields (factor=, sigma_edge=, sigma_albedo=, albedo_floor=)."""
+    u = UpsampleParams()
+    _check(amd_lib().rt_upsample_params_init_sized(C.byref(u), C.sizeof(u)), "rt_upsample_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(UpsampleParams._fields_):
+            raise TypeError(f"rt_upsample_params has no field {k}")
+        setattr(u, k, v)
+    return u
+
+
 class DebugNode(C.Structure):
     _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3), ("lo32", C.c_float * 3), ("hi32", C.c_float * 3),
                 ("prim_lo", C.c_double * 3), ("prim_hi", C.c_double * 3), ("skip", C.c_uint32), ("kind", C.c_uint32),
@@ -420,6 +437,11 @@ RT_AMD_SYMBOLS = {
     "rt_bloom_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_bloom_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_bloom_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_scaled": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "rt_upsample_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_upsample_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_upsample_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_tonemap_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_tonemap_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_tonemap_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -452,6 +474,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_debug_set_start_inline": (C.c_int, [C.c_int32]),
     "rt_debug_set_bloom_fused": (C.c_int, [C.c_int32]),
+    "rt_debug_set_upsample_form": (C.c_int, [C.c_int32]),
     "rt_debug_ordered_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_ordered_layout_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_tuning": (C.c_int, [C.c_int32] * 6),
@@ -721,6 +744,8 @@ RT_HOST_SYMBOLS = {
     "rth_tonemap": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_log_average_luminance": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]),
     "rth_bloom": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rth_upsample": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_load_image": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -1671,6 +1696,90 @@ def bloom_host(values, spp, *, spp_map=None, **kw):
                             out.ctypes.data) != 0:
         raise RtError(host_lib().rth_last_error().decode(errors="replace"))
     return out
+
+
+def camera_scaled(camera: Camera, factor: int) -> Camera:
+    """rt_camera_scaled (GPU-free): the camera of the small frame — ceil(w / factor) x ceil(h / factor) pixels, each covering a
+    factor x factor block of `camera`'s."""
+    out = Camera()
+    _check(amd_lib().rt_camera_scaled(C.byref(camera), int(factor), C.byref(out)), "rt_camera_scaled")
+    return out
+
+
+def upsample_workspace_bytes(width, height, factor) -> int:
+    n = int(amd_lib().rt_upsample_workspace_bytes(width, height, factor))
+    if n < 0:
+        raise RtError(f"rt_upsample_workspace_bytes: no workspace for a {width}x{height} frame at factor {factor}")
+    return n
+
+
+def upsample_device(width, height, d_low_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_albedo_sum_ptr: int = 0,
+                    albedo_spp: int = 0, d_edge_sum_ptr: int = 0, edge_spp: int = 0, d_rgba8_ptr: int = 0,
+                    params: "UpsampleParams | None" = None, stream: int = 0):
+    """rt_upsample_device: the low device frame at d_low_ptr (3 lw lh doubles, lw = ceil(width / factor): sums with the count `spp`, or
+    means with spp = 1) brought to the FULL size width x height under the full-size guide frames given (3 w h doubles of sums each, with
+    their counts), into the 3 w h doubles at d_mean_out_ptr and, if d_rgba8_ptr is not 0, 4 w h display bytes; `d_workspace_ptr`:
+    upsample_workspace_bytes(w, h, factor) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_upsample_device(width, height, C.c_void_p(d_low_ptr or None), spp, C.c_void_p(d_albedo_sum_ptr or None), albedo_spp,
+                                        C.c_void_p(d_edge_sum_ptr or None), edge_spp, C.byref(params) if params is not None else None,
+                                        C.c_void_p(d_mean_out_ptr or None), C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr or None),
+                                        C.c_void_p(stream)), "rt_upsample_device")
+
+
+def _upsample_frames(who, low, size, factor, albedo_sum, edge_sum):
+    import numpy as np
+    w, h = int(size[0]), int(size[1])
+    low = np.ascontiguousarray(low, dtype=np.float64)
+    if w < 1 or h < 1 or factor < 1:
+        raise RtError(f"{who}: the full size and the factor must be positive")
+    lw, lh = (w + factor - 1) // factor, (h + factor - 1) // factor
+    if low.shape != (lh, lw, 3):
+        raise RtError(f"{who}: `low` must be an ({lh}, {lw}, 3) frame for a {w}x{h} frame at factor {factor}")
+    guides = []
+    for name, g in (("albedo_sum", albedo_sum), ("edge_sum", edge_sum)):
+        if g is not None:
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if g.shape != (h, w, 3):
+                raise RtError(f"{who}: `{name}` must be an ({h}, {w}, 3) frame")
+        guides.append(g)
+    return low, guides[0], guides[1], w, h
+
+
+def upsample(low, spp, size, *, albedo_sum=None, albedo_spp=0, edge_sum=None, edge_spp=0, rgba8=False, device=0, **kw):
+    """Uploads the low (lh, lw, 3) frame (sums with `spp`, or means with spp = 1) and the full-size (h, w, 3) guide frames of sums given,
+    runs rt_upsample_device with upsample_params(**kw) for the full size `size` = (w, h) and downloads: the (h, w, 3) float64 frame, or
+    (frame, (h, w, 4) uint8) with rgba8."""
+    params = upsample_params(**kw)
+    low, albedo_sum, edge_sum, w, h = _upsample_frames("upsample", low, size, params.factor, albedo_sum, edge_sum)
+    import torch
+    with torch.cuda.device(device):
+        d_low = torch.from_numpy(low).cuda()
+        d_alb = torch.from_numpy(albedo_sum).cuda() if albedo_sum is not None else None
+        d_edge = torch.from_numpy(edge_sum).cuda() if edge_sum is not None else None
+        d_out = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
+        d_ws = torch.empty(upsample_workspace_bytes(w, h, params.factor), dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
+        upsample_device(w, h, d_low.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
+                        d_albedo_sum_ptr=d_alb.data_ptr() if d_alb is not None else 0, albedo_spp=int(albedo_spp),
+                        d_edge_sum_ptr=d_edge.data_ptr() if d_edge is not None else 0, edge_spp=int(edge_spp),
+                        d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+
+
+def upsample_host(low, spp, size, *, albedo_sum=None, albedo_spp=0, edge_sum=None, edge_spp=0, rgba8=False, **kw):
+    """rth_upsample (librt_host, CPU): what rt_upsample_device gives, bit for bit, from the same shared functions in the same order."""
+    import numpy as np
+    params = upsample_params(**kw)
+    low, albedo_sum, edge_sum, w, h = _upsample_frames("upsample_host", low, size, params.factor, albedo_sum, edge_sum)
+    out = np.zeros((h, w, 3), dtype=np.float64)
+    rgba = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
+    if host_lib().rth_upsample(w, h, low.ctypes.data, int(spp), albedo_sum.ctypes.data if albedo_sum is not None else None, int(albedo_spp),
+                               edge_sum.ctypes.data if edge_sum is not None else None, int(edge_spp), C.byref(params), out.ctypes.data,
+                               rgba.ctypes.data if rgba8 else None) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return (out, rgba) if rgba8 else out
 
 
 def tiles_to_frame_rgb8_device(width, height, shard_count, d_gathered_ptr: int, d_frame_ptr: int, stream: int = 0):

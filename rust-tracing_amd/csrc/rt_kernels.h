@@ -269,6 +269,21 @@ void launch_bloom_level_fused(int32_t w, int32_t h, int32_t stride, const double
                               hipStream_t stream);
 void launch_bloom_h(int32_t w, int32_t h, int32_t stride, const double *b_in, double *h_out, hipStream_t stream);
 void launch_bloom_v(int32_t w, int32_t h, int32_t stride, const double *h_in, double *b_out, double *a, const BloomOutput *last, hipStream_t stream);
+// guided upsampling (rt_upsample.hip; rt_upsample_device).  w x h is the FULL size, lw x lh the low one; rec_r, rec_a and rec_g are the
+// workspace's regions of 4 doubles per low pixel (rt_upsample_shared.h).  launch_upsample_prepare writes rec_r and, per guide given
+// (albedo_sum / edge_sum not null), rec_a / rec_g; launch_upsample reads them and writes out (3 w h doubles) and, if not null, rgba (w h
+// words): lds = true stages a tile's records in the LDS, false reads every tap from the regions; the bits are the same.
+struct UpsampleArgs {
+    int32_t w, h, lw, lh, factor;
+    const double *low; double inv_spp;
+    const double *albedo_sum; double n_a;
+    const double *edge_sum; double n_e;
+    double sigma_albedo, sigma_edge, albedo_floor;
+    double *rec_r, *rec_a, *rec_g;
+    double *out; uint32_t *rgba;
+};
+void launch_upsample_prepare(const UpsampleArgs &u, hipStream_t stream);
+void launch_upsample(const UpsampleArgs &u, bool lds, hipStream_t stream);
 void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

@@ -6,6 +6,7 @@
 #include "scenes.hpp"
 #include "../csrc/rt_tonemap_shared.h"
 #include "../csrc/rt_bloom_shared.h"
+#include "../csrc/rt_upsample_shared.h"
 #include <cstring>
 #include <exception>
 #include <string>
@@ -231,6 +232,46 @@ int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, 
         const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
         for (size_t c = 0; c < 3; ++c) out_mean[3 * i + c] = rtm::rt_bloom_output(values[3 * i + c] * inv, a[3 * i + c], p.levels, p.strength);
     }
+    return 0;
+}
+
+// ---- guided upsampling: the host mirror of rt_upsample_device (include/rt_amd.h "guided upsampling") ----
+
+int rth_upsample(int32_t width, int32_t height, const double *low, int32_t spp, const double *albedo_sum, int32_t albedo_spp, const double *edge_sum,
+                 int32_t edge_spp, const rt_upsample_params *params, double *out_mean, uint8_t *out_rgba8) {
+    const std::string who("rth_upsample");
+    rt_upsample_params p;
+    if (const char *bad = rtup::bad_argument(false, width, height, low, out_mean, nullptr, spp, albedo_sum, albedo_spp, edge_sum, edge_spp, params, p))
+        return fail(who + ": " + bad);
+    if (const char *bad = rtup::bad_overlap(false, width, height, p.factor, out_mean, low, albedo_sum, edge_sum)) return fail(who + ": " + bad);
+    const int32_t F = p.factor, lw = rtm::rt_up_low_size(width, F), lh = rtm::rt_up_low_size(height, F);
+    const size_t n_low = (size_t)lw * (size_t)lh;
+    std::vector<double> rec_r(4 * n_low), rec_a(albedo_sum ? 4 * n_low : 0), rec_g(edge_sum ? 4 * n_low : 0);
+    const double inv_spp = 1.0 / (double)spp, n_a = (double)albedo_spp, n_e = (double)edge_spp;
+    for (int32_t J = 0; J < lh; ++J)
+        for (int32_t I = 0; I < lw; ++I) {
+            const size_t q = ((size_t)J * (size_t)lw + (size_t)I) * 4u;
+            rtm::rt_upsample_prepare(I, J, width, height, F, low, inv_spp, albedo_sum, n_a, edge_sum, n_e, p.albedo_floor, &rec_r[q],
+                                     albedo_sum ? &rec_a[q] : nullptr, edge_sum ? &rec_g[q] : nullptr);
+        }
+    const rtm::UpsampleRegions regions{rec_r.data(), rec_a.data(), rec_g.data(), lw};
+    for (int32_t y = 0; y < height; ++y)
+        for (int32_t x = 0; x < width; ++x) {
+            const size_t px = (size_t)y * (size_t)width + (size_t)x;
+            double ap[3] = {0.0, 0.0, 0.0}, gp[3] = {0.0, 0.0, 0.0}, *out = out_mean + 3 * px;
+            for (int k = 0; k < 3; ++k) {
+                if (albedo_sum) ap[k] = albedo_sum[3 * px + k] / n_a;
+                if (edge_sum) gp[k] = edge_sum[3 * px + k] / n_e;
+            }
+            if (albedo_sum && edge_sum) rtm::rt_upsample_pixel<true, true>(x, y, F, lw, lh, ap, gp, p.sigma_albedo, p.sigma_edge, p.albedo_floor, regions, regions, out);
+            else if (albedo_sum) rtm::rt_upsample_pixel<true, false>(x, y, F, lw, lh, ap, gp, p.sigma_albedo, p.sigma_edge, p.albedo_floor, regions, regions, out);
+            else if (edge_sum) rtm::rt_upsample_pixel<false, true>(x, y, F, lw, lh, ap, gp, p.sigma_albedo, p.sigma_edge, p.albedo_floor, regions, regions, out);
+            else rtm::rt_upsample_pixel<false, false>(x, y, F, lw, lh, ap, gp, p.sigma_albedo, p.sigma_edge, p.albedo_floor, regions, regions, out);
+            if (out_rgba8) {
+                const uint32_t word = rtm::rt_upsample_rgba8(out);
+                for (int k = 0; k < 4; ++k) out_rgba8[4 * px + (size_t)k] = (uint8_t)(word >> (8 * k));
+            }
+        }
     return 0;
 }
 

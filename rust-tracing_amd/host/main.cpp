@@ -27,6 +27,10 @@
 //   --bloom [STRENGTH] [--bloom-threshold T] [--bloom-levels K] (bloom of include/rt_amd.h in front of that stage, wherever it runs: the
 //   light of the pixels above luminance T is spread over K a-trous levels and added back STRENGTH times; alone it implies the stage with
 //   the clamp).
+//   --upsample F [--upsample-albedo] [--upsample-edges] (guided upsampling of include/rt_amd.h: the beauty frame is traced at 1/F of the
+//   width and height, F = 2..4, and brought to full size under the full-size albedo and surface-ID frames asked for; the --denoise
+//   and --live-denoise families then filter the small frame, and bloom and the tone mapping run on the full-size one; --live renders the
+//   guide frames once per session).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -72,6 +76,12 @@ static void usage(const char *argv0) {
             "                         mapping, the light of the pixels whose luminance is above T, default 1, is blurred over K = 1..8 levels,\n"
             "                         default 5 (a glow of radius 2 * (2^K - 1) pixels), and added back STRENGTH >= 0 times, default 0.25; alone it\n"
             "                         implies --tonemap clamp; --orbit blooms each view on its own)\n"
+            "          [--upsample F [--upsample-albedo] [--upsample-edges]]   (one GPU; a plain render, the --denoise family or --live: the frame is\n"
+            "                         traced at 1/F of the width and height, F = 2, 3 or 4 — 1/F^2 of the paths — and brought to full size by a\n"
+            "                         joint bilateral upsampler; --upsample-albedo multiplies the full-size first-hit albedo frame back in,\n"
+            "                         --upsample-edges stops the interpolation at the edges of the full-size surface-ID frame; --denoise* and\n"
+            "                         --live-denoise* then filter the small frame, and --live renders the guides once, at up to 16 spp; not with\n"
+            "                         --orbit, --adaptive, --gpus > 1 or --progressive)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -185,6 +195,15 @@ int main(int argc, char **argv) {
             ro.bloom_levels = atoi(need("--bloom-levels")); bloom_knob_given = true;
             if (ro.bloom_levels < 1 || ro.bloom_levels > 8) { fprintf(stderr, "--bloom-levels needs a number of levels from 1 to 8\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--upsample") {
+            char *end = nullptr;
+            const char *v = need("--upsample");
+            const long f = strtol(v, &end, 10);
+            if (end == v || *end != 0 || f < 2 || f > 4) { fprintf(stderr, "--upsample needs a factor of 2, 3 or 4\n"); usage(argv[0]); return 2; }
+            ro.upsample = (int)f;
+        }
+        else if (a == "--upsample-albedo") ro.upsample_albedo = true;
+        else if (a == "--upsample-edges") ro.upsample_edges = true;
         else if (a == "--earth") so.earth_image = need("--earth");
         else if (a == "--bvh") bvh_policy() = std::string(need("--bvh")) == "sah" ? BvhPolicy::Sah : BvhPolicy::Reference;
         else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
@@ -254,6 +273,15 @@ int main(int argc, char **argv) {
     }
     if (bloom_knob_given && ro.bloom < 0.0) {
         fprintf(stderr, "--bloom-threshold and --bloom-levels set the glow of --bloom: they need --bloom\n");
+        return 2;
+    }
+    if ((ro.upsample_albedo || ro.upsample_edges) && ro.upsample == 0) {
+        fprintf(stderr, "--upsample-albedo and --upsample-edges are the guides of --upsample: they need --upsample\n");
+        return 2;
+    }
+    if (ro.upsample > 0 && (ro.orbit > 0 || ro.adaptive || ro.gpus > 1 || ro.progressive_spp > 0)) {
+        fprintf(stderr, "--upsample traces a smaller frame on a one-GPU route — a plain render, the --denoise family or -l/--live: it cannot be "
+                        "combined with --orbit, --adaptive, --gpus > 1 or --progressive\n");
         return 2;
     }
     if (white_given && ro.tonemap != RT_TONEMAP_REINHARD) {

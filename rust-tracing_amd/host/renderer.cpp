@@ -217,6 +217,43 @@ static std::vector<uint8_t> staged_device(int32_t width, int32_t height, const d
     return px;
 }
 
+// Guided upsampling (include/rt_amd.h "guided upsampling") is on when opt.upsample is a factor, 2..4.
+static rt_upsample_params upsample_params(const RenderOptions &opt) {
+    rt_upsample_params up;
+    if (rt_upsample_params_init_sized(&up, sizeof up) != RT_OK) throw std::runtime_error(std::string("upsample: ") + rt_last_error());
+    up.factor = opt.upsample;
+    return up;
+}
+
+std::vector<double> upsample_means(const std::vector<double> &low, int32_t width, int32_t height, int32_t spp, const std::vector<double> &albedo_sum,
+                                   int32_t albedo_spp, const std::vector<double> &edge_sum, int32_t edge_spp, const RenderOptions &opt) {
+    const rt_upsample_params up = upsample_params(opt);
+    const size_t full = width > 0 && height > 0 ? (size_t)width * (size_t)height * 3u : 0u;
+    const int32_t F = up.factor >= 2 && up.factor <= 4 ? up.factor : 2; // (a factor out of range is refused below, by the library)
+    const size_t small = full ? (size_t)((width + F - 1) / F) * (size_t)((height + F - 1) / F) * 3u : 0u;
+    if (low.size() != small || (!albedo_sum.empty() && albedo_sum.size() != full) || (!edge_sum.empty() && edge_sum.size() != full))
+        throw std::runtime_error("upsample: a frame does not hold the values of its size");
+    std::vector<double> out(full);
+    if (rth_upsample(width, height, low.data(), spp, albedo_sum.empty() ? nullptr : albedo_sum.data(), albedo_spp,
+                     edge_sum.empty() ? nullptr : edge_sum.data(), edge_spp, &up, out.data(), nullptr) != 0)
+        throw std::runtime_error(rth_last_error());
+    return out;
+}
+
+void upsample_device(int32_t width, int32_t height, const double *d_low, int32_t spp, const double *d_albedo_sum, int32_t albedo_spp,
+                     const double *d_edge_sum, int32_t edge_spp, double *d_mean_out, const RenderOptions &opt) {
+    const rt_upsample_params up = upsample_params(opt);
+    const int64_t work = rt_upsample_workspace_bytes(width, height, up.factor);
+    if (work < 0) throw std::runtime_error("upsample: no workspace for a frame of this size at this factor");
+    void *d_work = nullptr;
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); rt_device_free(0, d_work); throw std::runtime_error("upsample: " + msg); } };
+    check(rt_device_malloc(0, work, &d_work));
+    check(rt_upsample_device(width, height, d_low, spp, d_albedo_sum, albedo_spp, d_edge_sum, edge_spp, &up, d_mean_out, nullptr, d_work, nullptr));
+    double first = 0.0; // (a download waits for everything enqueued before it: the workspace is freed behind the call)
+    check(rt_device_download(0, &first, d_mean_out, (int64_t)sizeof first, nullptr));
+    rt_device_free(0, d_work);
+}
+
 // what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
 // (n_frames: the views forms' stack of frames, one behind the other in every buffer).  With the tone-mapping stage on, the filter
 // writes no bytes (a null d_rgba8) and the stage makes them from the filtered means, every frame of a stack as a frame of its own.
@@ -384,6 +421,82 @@ static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, u
     return rc;
 }
 
+// A render on device 0 that is traced small and shown large (opt.upsample): the beauty frame under rt_camera_scaled — its sums, or with
+// opt.denoise its moments, filtered at the low size under low-size guides — the full-size guide frames asked for, the upsampler, and
+// then bloom and the tone-mapping stage if they are on, or the plain output stage on the full-size means.  Everything stays on the
+// device until the display bytes, or the means they are made from, come back.
+static std::vector<uint8_t> render_upsampled_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const rt_camera cam = camera.pod();
+    rt_camera low;
+    if (rt_camera_scaled(&cam, opt.upsample, &low) != RT_OK) throw std::runtime_error(std::string("render: ") + rt_last_error());
+    const int32_t w = cam.image_width, h = cam.image_height, lw = low.image_width, lh = low.image_height, spp = cam.samples_per_pixel;
+    const int64_t frame = (int64_t)w * h * 3 * (int64_t)sizeof(double), low_frame = (int64_t)lw * lh * 3 * (int64_t)sizeof(double);
+    rt_scene *scene = nullptr;
+    void *d_sum = nullptr, *d_sq = nullptr, *d_low_alb = nullptr, *d_low_ids = nullptr, *d_low_mean = nullptr, *d_work = nullptr, *d_alb = nullptr,
+         *d_ids = nullptr, *d_out = nullptr;
+    auto cleanup = [&]() {
+        for (void *p : {d_sum, d_sq, d_low_alb, d_low_ids, d_low_mean, d_work, d_alb, d_ids, d_out}) rt_device_free(0, p);
+        rt_scene_destroy(scene);
+    };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, low_frame, &d_sum));
+    check(rt_device_malloc(0, frame, &d_out));
+    rt_render_params p{};
+    p.seed = opt.seed; p.sample_begin = 0; p.sample_end = spp; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    const double *d_low = static_cast<const double *>(d_sum);
+    int32_t low_spp = spp;
+    if (opt.denoise) { // the low frame's own filter, with its guides rendered under the scaled camera
+        check(rt_device_malloc(0, low_frame, &d_sq));
+        check(rt_device_malloc(0, low_frame, &d_low_mean));
+        check(rt_render_moments_device(scene, &low, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
+        if (opt.denoise_albedo) check(render_albedo_sums(desc, low, opt.seed, spp, &d_low_alb));
+        if (opt.denoise_edges) check(render_albedo_sums(desc, low, opt.seed, spp, &d_low_ids, true));
+        rt_denoise_guided_params dp;
+        check(rt_denoise_guided_params_init_sized(&dp, sizeof dp));
+        dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
+        const int64_t work = opt.denoise_edges ? rt_denoise_guided_workspace_bytes(lw, lh, opt.denoise_albedo)
+                             : opt.denoise_albedo ? rt_denoise_albedo_workspace_bytes(lw, lh) : rt_denoise_workspace_bytes(lw, lh);
+        if (work < 0) { cleanup(); throw std::runtime_error("render: no denoise workspace for a frame of this size"); }
+        check(rt_device_malloc(0, work, &d_work));
+        const double *S = static_cast<const double *>(d_sum), *Q = static_cast<const double *>(d_sq);
+        double *out = static_cast<double *>(d_low_mean);
+        if (opt.denoise_edges) {
+            check(rt_denoise_guided_device(lw, lh, S, Q, spp, nullptr, static_cast<const double *>(d_low_alb), spp, static_cast<const double *>(d_low_ids), spp,
+                                           &dp, out, nullptr, d_work, nullptr));
+        } else if (opt.denoise_albedo) {
+            const rt_denoise_albedo_params ap{(uint32_t)sizeof(rt_denoise_albedo_params), dp.iterations, dp.sigma, dp.eps, dp.sigma_albedo, dp.albedo_floor};
+            check(rt_denoise_albedo_device(lw, lh, S, Q, spp, nullptr, static_cast<const double *>(d_low_alb), spp, &ap, out, nullptr, d_work, nullptr));
+        } else {
+            const rt_denoise_params pp{(uint32_t)sizeof(rt_denoise_params), dp.iterations, dp.sigma, dp.eps};
+            check(rt_denoise_device(lw, lh, S, Q, spp, nullptr, &pp, out, nullptr, d_work, nullptr));
+        }
+        d_low = out;
+        low_spp = 1; // the filter writes means
+    } else {
+        check(rt_render_device(scene, &low, &p, static_cast<double *>(d_sum), nullptr));
+    }
+    if (opt.upsample_albedo) check(render_albedo_sums(desc, cam, opt.seed, spp, &d_alb));
+    if (opt.upsample_edges) check(render_albedo_sums(desc, cam, opt.seed, spp, &d_ids, true));
+    std::vector<uint8_t> px;
+    try {
+        upsample_device(w, h, d_low, low_spp, static_cast<const double *>(d_alb), spp, static_cast<const double *>(d_ids), spp, static_cast<double *>(d_out), opt);
+        if (tonemapped(opt)) {
+            px = staged_device(w, h, static_cast<const double *>(d_out), 1, nullptr, false, opt);
+        } else {
+            std::vector<double> means((size_t)w * (size_t)h * 3u);
+            if (rt_device_download(0, means.data(), d_out, frame, nullptr) != RT_OK) throw std::runtime_error(std::string("render: ") + rt_last_error());
+            px = resolve_rgb8(means, 1);
+        }
+    } catch (...) { cleanup(); throw; }
+    cleanup();
+    return px;
+}
+
 // A plain render on device 0 that ends in the denoiser: the frame's sums and sums of squares (rt_render_moments_device) stay on the
 // device, are filtered there, and only the display bytes come back.
 static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
@@ -483,6 +596,10 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
     return px;
 }
 
+// the samples per pixel of the full-size guide frames a live session with opt.upsample renders once, before its first pass (fewer if
+// the session itself settles on fewer): first-hit frames, whose only noise is the anti-aliasing of their edges
+constexpr int32_t LIVE_UPSAMPLE_GUIDE_SPP = 16;
+
 // The running mean and its display frame stay on the device; every pass is one rt_render_mean_device call (the render launches and one
 // reduction that also writes the RGBA8 frame), and only the bytes to show come back.
 std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt,
@@ -490,9 +607,16 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     SceneDescriber sd;
     const rt_ref root = world.describe(sd);
     const rt_scene_desc desc = sd.desc(root);
-    const rt_camera cam = camera.pod();
-    const int64_t n_pix = (int64_t)cam.image_width * cam.image_height;
-    std::vector<uint8_t> frame((size_t)n_pix * 4u, 0);
+    const rt_camera full = camera.pod();
+    // opt.upsample: every pass traces and filters the frame of the scaled camera `cam`; the frame shown is rt_upsample_device's, at the
+    // full size, under full-size guide frames rendered ONCE, before the first pass (d_up_alb, d_up_ids); they, the full-size frame d_full
+    // and the upsampler's workspace are kept across the passes
+    const bool upsampled = opt.upsample > 0;
+    rt_camera cam = full;
+    if (upsampled && rt_camera_scaled(&full, opt.upsample, &cam) != RT_OK) throw std::runtime_error(std::string("live_render: ") + rt_last_error());
+    const int32_t fw = full.image_width, fh = full.image_height;
+    const int64_t n_pix = (int64_t)cam.image_width * cam.image_height, n_shown = (int64_t)fw * fh; // traced and shown pixels
+    std::vector<uint8_t> frame((size_t)n_shown * 4u, 0);
     for (size_t k = 3; k < frame.size(); k += 4) frame[k] = 0xff; // color_to_rgb(Color::ZERO), alpha 0xff
     const int last = cam.samples_per_pixel - 1; // `if num_samples < spp` (src/renderer.rs:104): divisors 1 .. spp - 1
     if (last <= 0) return frame;
@@ -503,16 +627,28 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const int32_t w = cam.image_width, h = cam.image_height;
     rt_scene *scene = nullptr, *albedo_scene = nullptr;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_m2 = nullptr, *d_alb = nullptr, *d_shown = nullptr, *d_work = nullptr;
+    void *d_up_alb = nullptr, *d_up_ids = nullptr, *d_full = nullptr, *d_up_work = nullptr;
     auto cleanup = [&]() {
         rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
-        rt_device_free(0, d_work);
+        rt_device_free(0, d_work); rt_device_free(0, d_up_alb); rt_device_free(0, d_up_ids); rt_device_free(0, d_full); rt_device_free(0, d_up_work);
         rt_scene_destroy(scene); rt_scene_destroy(albedo_scene);
     };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("live_render: " + msg); } };
     const int64_t frame_bytes = n_pix * 3 * (int64_t)sizeof(double);
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, frame_bytes, &d_mean));
-    check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+    check(rt_device_malloc(0, n_shown * 4, &d_rgba8));
+    rt_upsample_params up{};
+    const int32_t guide_spp = last < LIVE_UPSAMPLE_GUIDE_SPP ? last : LIVE_UPSAMPLE_GUIDE_SPP;
+    if (upsampled) {
+        try { up = upsample_params(opt); } catch (...) { cleanup(); throw; }
+        const int64_t up_work = rt_upsample_workspace_bytes(fw, fh, up.factor);
+        if (up_work < 0) { cleanup(); throw std::runtime_error("live_render: no upsample workspace for a frame of this size at this factor"); }
+        check(rt_device_malloc(0, n_shown * 3 * (int64_t)sizeof(double), &d_full));
+        check(rt_device_malloc(0, up_work, &d_up_work));
+        if (opt.upsample_albedo) check(render_albedo_sums(desc, full, opt.seed, guide_spp, &d_up_alb));
+        if (opt.upsample_edges) check(render_albedo_sums(desc, full, opt.seed, guide_spp, &d_up_ids, true));
+    }
     rt_denoise_albedo_params dp{};
     rt_denoise_spatial_params sp{};
     const bool spatial = opt.live_denoise_spatial > 0; // every pass through the spatial entry points: the first one is filtered too
@@ -536,7 +672,8 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const rt_denoise_params plain = plain_params(dp);
     // with the tone-mapping stage on, the pass and the filters write no bytes (a null d_rgba8): the stage makes the frame shown from
     // the running mean — or, filtered, from d_shown — and the mean itself is never touched
-    uint8_t *const d_bytes = tonemapped(opt) ? nullptr : static_cast<uint8_t *>(d_rgba8);
+    // ... and with the upsampler on it is the upsampler that writes the bytes, at the full size
+    uint8_t *const d_bytes = tonemapped(opt) || upsampled ? nullptr : static_cast<uint8_t *>(d_rgba8);
     for (int begin = 0; begin < last; begin += pass) {
         const int end = begin + pass < last ? begin + pass : last;
         rt_render_params p{};
@@ -561,11 +698,17 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
                                                        static_cast<double *>(d_shown), d_bytes, d_work, nullptr));
             }
         }
+        const double *d_means = static_cast<const double *>(denoised ? d_shown : d_mean); // the pass's frame of means, at the traced size
+        if (upsampled) {
+            check(rt_upsample_device(fw, fh, d_means, 1, static_cast<const double *>(d_up_alb), guide_spp, static_cast<const double *>(d_up_ids), guide_spp,
+                                     &up, static_cast<double *>(d_full), tonemapped(opt) ? nullptr : static_cast<uint8_t *>(d_rgba8), d_up_work, nullptr));
+            d_means = static_cast<const double *>(d_full);
+        }
         if (tonemapped(opt)) {
-            try { frame = staged_device(w, h, static_cast<const double *>(denoised ? d_shown : d_mean), 1, nullptr, true, opt); }
+            try { frame = staged_device(fw, fh, d_means, 1, nullptr, true, opt); }
             catch (...) { cleanup(); throw; }
         } else {
-            check(rt_device_download(0, frame.data(), d_rgba8, n_pix * 4, nullptr));
+            check(rt_device_download(0, frame.data(), d_rgba8, n_shown * 4, nullptr));
         }
         if (on_frame) {
             try { on_frame(frame, end); } catch (...) { cleanup(); throw; }
@@ -673,12 +816,18 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     using clock = std::chrono::steady_clock;
     auto now = clock::now();
     const int32_t w = (int32_t)camera->image_width, h = (int32_t)camera->image_height;
+    if (opt.upsample != 0 && (opt.upsample < 2 || opt.upsample > 4)) throw std::runtime_error("render: upsample must be 0 (off), 2, 3 or 4");
+    if (opt.upsample > 0 && (opt.orbit > 0 || opt.adaptive || opt.gpus > 1 || opt.progressive_spp > 0))
+        throw std::runtime_error("render: upsample is a one-GPU, one-pass route: it cannot be combined with orbit, adaptive, gpus > 1 or progressive_spp");
+    if ((opt.upsample_albedo || opt.upsample_edges) && opt.upsample == 0) throw std::runtime_error("render: upsample_albedo and upsample_edges need upsample");
     if (opt.orbit > 0) {
         render_orbit(*camera, *world, output_file_name, opt);
         return;
     }
-    if (opt.adaptive || opt.denoise) {
-        const std::vector<uint8_t> px = opt.adaptive ? render_adaptive_rgb8(*camera, *world, opt) : render_denoised_rgb8(*camera, *world, opt);
+    if (opt.adaptive || opt.denoise || opt.upsample > 0) {
+        const std::vector<uint8_t> px = opt.upsample > 0 ? render_upsampled_rgb8(*camera, *world, opt)
+                                        : opt.adaptive   ? render_adaptive_rgb8(*camera, *world, opt)
+                                                         : render_denoised_rgb8(*camera, *world, opt);
         if (!opt.quiet) printf("Render time: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         now = clock::now();
         if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");

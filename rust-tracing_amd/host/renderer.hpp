@@ -84,6 +84,17 @@ struct RenderOptions {
     double bloom = -1.0;
     double bloom_threshold = 1.0;   // luminance above which a pixel glows
     int bloom_levels = 5;           // K, 1..8: a glow of radius 2 * (2^K - 1) pixels
+    // guided upsampling (include/rt_amd.h "guided upsampling"): upsample = F in 2..4 traces the beauty frame under rt_camera_scaled —
+    // 1 / F^2 of the paths — and brings it to the camera's size with rt_upsample_device; 0: off.  upsample_albedo / upsample_edges
+    // render the full-size albedo / surface-ID frame (the denoise routes' guide scenes and cameras, the render's seed and spp) as the
+    // upsampler's guides.  With `denoise` on, the filter — and its own guides — run at the low size, in front of the upsampler;
+    // bloom and the tone-mapping stage run behind it on the full-size means.  One GPU, one pass; not on the adaptive, orbit or
+    // progressive routes (render() throws).  live_render: every pass traces — and with live_denoise* filters — the small frame and
+    // shows the upsampled one; the full-size guide frames are rendered once, before the first pass, at min(spp - 1, 16) samples per
+    // pixel, and they, the full-size frame and the upsampler's workspace are kept across the passes.
+    int upsample = 0;
+    bool upsample_albedo = false;
+    bool upsample_edges = false;
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -141,6 +152,17 @@ std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double 
 // std::runtime_error on a library error.
 std::vector<double> bloom_means(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
 void bloom_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double *d_mean_out, const RenderOptions &opt);
+
+// Guided upsampling with opt's factor and the library's default stops; width x height is the FULL size, the low frame holds
+// 3 * ceil(w / F) * ceil(h / F) values (sums with the count spp; means with spp = 1), each guide 3 * w * h sums with its count, or null /
+// empty.  upsample_means: on HOST frames, through the host mirror rth_upsample; returns the 3 * w * h full-size means.
+// upsample_device: rt_upsample_device on device 0 over DEVICE frames into the DEVICE frame d_mean_out: the frame stays on the device;
+// the call's workspace is allocated and freed here, and it returns when the frame is written.  Both throw std::runtime_error on a
+// library error.
+std::vector<double> upsample_means(const std::vector<double> &low, int32_t width, int32_t height, int32_t spp, const std::vector<double> &albedo_sum,
+                                   int32_t albedo_spp, const std::vector<double> &edge_sum, int32_t edge_spp, const RenderOptions &opt);
+void upsample_device(int32_t width, int32_t height, const double *d_low, int32_t spp, const double *d_albedo_sum, int32_t albedo_spp,
+                     const double *d_edge_sum, int32_t edge_spp, double *d_mean_out, const RenderOptions &opt);
 
 // Returns the per-pixel sums (w*h*3 doubles, row-major) exactly like the reference's `raw_pixels`
 // (src/renderer.rs:26-49).  Throws std::runtime_error if the GPU library reports an error.
