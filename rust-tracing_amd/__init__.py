@@ -902,6 +902,13 @@ def out_size(width, height, out_layout=RT_OUT_FRAME, shard_index=0, shard_count=
     return n
 
 
+def _frame_arg(who, name, a, shape):
+    """a caller's array that a host-buffer render writes in place: float64, C-contiguous, writable and of this shape"""
+    import numpy as np
+    if a is None or a.shape != shape or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+        raise RtError(f"{who}: `{name}` must be a writable C-contiguous float64 array of shape {shape}")
+
+
 class DeviceScene:
     """rt_scene handle: the compiled scene resident in one GPU's HBM."""
 
@@ -938,12 +945,17 @@ class DeviceScene:
         _check(amd_lib().rt_scene_get_stats(self._handle, C.byref(st)), "rt_scene_get_stats")
         return st.as_dict()
 
-    def render(self, params: RenderParams, camera: Camera | None = None):
-        """rt_render: host buffer out (numpy float64)."""
+    def render(self, params: RenderParams, camera: Camera | None = None, out=None):
+        """rt_render: host buffer out (numpy float64, flat: out_size(...) values).  `out`: the array to write (with params.accumulate:
+        the running sums this call adds to, so it is required then); returned."""
         import numpy as np
         cam = camera if camera is not None else self.host_scene.camera
         n = out_size(cam.image_width, cam.image_height, params.out_layout, params.shard_index, params.shard_count)
-        out = np.zeros(n, dtype=np.float64)
+        if out is None:
+            if params.accumulate:
+                raise RtError("render: params.accumulate adds to running sums: pass them as `out`")
+            out = np.zeros(n, dtype=np.float64)
+        _frame_arg("render", "out", out, (n,))
         _check(amd_lib().rt_render(self._handle, C.byref(cam), C.byref(params),
                                    out.ctypes.data_as(C.POINTER(C.c_double))), "rt_render")
         return out
@@ -975,8 +987,7 @@ class DeviceScene:
             if params.accumulate:
                 raise RtError("render_views: params.accumulate adds to running sums: pass them as `out`")
             out = np.zeros((n, h, w, 3), dtype=np.float64)
-        elif out.shape != (n, h, w, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
-            raise RtError(f"render_views: `out` must be a writable C-contiguous float64 array of shape {(n, h, w, 3)}")
+        _frame_arg("render_views", "out", out, (n, h, w, 3))
         _check(amd_lib().rt_render_views(self._handle, arr, n, C.byref(params), C.c_void_p(out.ctypes.data)), "rt_render_views")
         return out
 
@@ -999,9 +1010,8 @@ class DeviceScene:
             if params.accumulate:
                 raise RtError("render_views_moments: params.accumulate adds to running sums: pass them as `sum` and `sum_sq`")
             sum, sum_sq = np.zeros((n, h, w, 3), dtype=np.float64), np.zeros((n, h, w, 3), dtype=np.float64)
-        for name, a in (("sum", sum), ("sum_sq", sum_sq)):
-            if a is None or a.shape != (n, h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
-                raise RtError(f"render_views_moments: `{name}` must be a writable C-contiguous float64 array of shape {(n, h, w, 3)}")
+        _frame_arg("render_views_moments", "sum", sum, (n, h, w, 3))
+        _frame_arg("render_views_moments", "sum_sq", sum_sq, (n, h, w, 3))
         _check(amd_lib().rt_render_views_moments(self._handle, arr, n, C.byref(params), C.c_void_p(sum.ctypes.data),
                                                  C.c_void_p(sum_sq.ctypes.data)), "rt_render_views_moments")
         return sum, sum_sq
@@ -1025,8 +1035,7 @@ class DeviceScene:
             if params.sample_begin > 0:
                 raise RtError("render_mean: params.sample_begin > 0 continues a running mean: pass it as `mean`")
             mean = np.zeros((h, w, 3), dtype=np.float64)
-        elif mean.shape != (h, w, 3) or mean.dtype != np.float64 or not mean.flags["C_CONTIGUOUS"] or not mean.flags["WRITEABLE"]:
-            raise RtError(f"render_mean: `mean` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        _frame_arg("render_mean", "mean", mean, (h, w, 3))
         frame = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
         _check(amd_lib().rt_render_mean(self._handle, C.byref(cam), C.byref(params), C.c_void_p(mean.ctypes.data),
                                         C.c_void_p(frame.ctypes.data) if rgba8 else None), "rt_render_mean")
@@ -1051,9 +1060,8 @@ class DeviceScene:
             if params.sample_begin > 0:
                 raise RtError("render_mean_moments: params.sample_begin > 0 continues running frames: pass them as `mean` and `m2`")
             mean, m2 = np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 3), dtype=np.float64)
-        for name, a in (("mean", mean), ("m2", m2)):
-            if a is None or a.shape != (h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
-                raise RtError(f"render_mean_moments: `{name}` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        _frame_arg("render_mean_moments", "mean", mean, (h, w, 3))
+        _frame_arg("render_mean_moments", "m2", m2, (h, w, 3))
         frame = np.zeros((h, w, 4), dtype=np.uint8) if rgba8 else None
         _check(amd_lib().rt_render_mean_moments(self._handle, C.byref(cam), C.byref(params), C.c_void_p(mean.ctypes.data),
                                                 C.c_void_p(m2.ctypes.data), C.c_void_p(frame.ctypes.data) if rgba8 else None),
@@ -1078,9 +1086,8 @@ class DeviceScene:
             if params.accumulate:
                 raise RtError("render_moments: params.accumulate adds to running sums: pass them as `sum` and `sum_sq`")
             sum, sum_sq = np.zeros((h, w, 3), dtype=np.float64), np.zeros((h, w, 3), dtype=np.float64)
-        for name, a in (("sum", sum), ("sum_sq", sum_sq)):
-            if a is None or a.shape != (h, w, 3) or a.dtype != np.float64 or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
-                raise RtError(f"render_moments: `{name}` must be a writable C-contiguous float64 array of shape {(h, w, 3)}")
+        _frame_arg("render_moments", "sum", sum, (h, w, 3))
+        _frame_arg("render_moments", "sum_sq", sum_sq, (h, w, 3))
         _check(amd_lib().rt_render_moments(self._handle, C.byref(cam), C.byref(params), C.c_void_p(sum.ctypes.data),
                                            C.c_void_p(sum_sq.ctypes.data)), "rt_render_moments")
         return sum, sum_sq
@@ -1165,11 +1172,33 @@ def resolve_rgba8_device(width, height, d_mean_ptr: int, d_rgba8_ptr: int, strea
            "rt_resolve_rgba8_device")
 
 
-def denoise_workspace_bytes(width, height) -> int:
-    n = int(amd_lib().rt_denoise_workspace_bytes(width, height))
+def _workspace_bytes(symbol, what, *args) -> int:
+    n = int(getattr(amd_lib(), symbol)(*args))
     if n < 0:
-        raise RtError(f"rt_denoise_workspace_bytes: no workspace for a {width}x{height} frame")
+        raise RtError(f"{symbol}: no workspace for {what}")
     return n
+
+
+def _frame_end(device, inputs, out_shape, rgba8_shape, ws_bytes, call, out_dtype="float64"):
+    """The device work of the blocking frame-end wrappers, on `device`: uploads `inputs` (numpy arrays; None stays None), allocates the
+    output, `ws_bytes` of workspace and, with rgba8_shape, the display frame, makes the *_device call on the current stream —
+    call(the inputs' device pointers (0 for None), output, workspace, display frame or 0, stream) —, synchronises and downloads:
+    the output, or (output, display frame) with rgba8_shape."""
+    import torch
+    with torch.cuda.device(device):
+        d_in = [torch.from_numpy(a).cuda() if a is not None else None for a in inputs]
+        d_out = torch.empty(out_shape, dtype=getattr(torch, out_dtype), device="cuda")
+        d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+        d_rgba = torch.empty(rgba8_shape, dtype=torch.uint8, device="cuda") if rgba8_shape else None
+        call([t.data_ptr() if t is not None else 0 for t in d_in], d_out.data_ptr(), d_ws.data_ptr(), d_rgba.data_ptr() if rgba8_shape else 0,
+             torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        return (out, d_rgba.cpu().numpy()) if rgba8_shape else out
+
+
+def denoise_workspace_bytes(width, height) -> int:
+    return _workspace_bytes("rt_denoise_workspace_bytes", f"a {width}x{height} frame", width, height)
 
 
 def denoise_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
@@ -1196,19 +1225,9 @@ def denoise(sum, sum_sq, spp, *, spp_map=None, rgba8=False, device=0, **kw):
         if spp_map.shape != (h, w):
             raise RtError(f"denoise: `spp_map` must have shape {(h, w)}")
     params = denoise_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_sum, d_sq = torch.from_numpy(sum).cuda(), torch.from_numpy(sum_sq).cuda()
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_out = torch.empty_like(d_sum)
-        d_ws = torch.empty(denoise_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        denoise_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
-                       d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0,
-                       params=params, stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+    return _frame_end(device, [sum, sum_sq, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_workspace_bytes(w, h),
+                      lambda d, out, ws, rgba, stream: denoise_device(w, h, d[0], d[1], int(spp), out, ws, d_spp_ptr=d[2], d_rgba8_ptr=rgba,
+                                                                      params=params, stream=stream))
 
 
 def albedo_materials(host_scene):
@@ -1230,10 +1249,7 @@ def albedo_camera(camera: Camera) -> Camera:
 
 
 def denoise_albedo_workspace_bytes(width, height) -> int:
-    n = int(amd_lib().rt_denoise_albedo_workspace_bytes(width, height))
-    if n < 0:
-        raise RtError(f"rt_denoise_albedo_workspace_bytes: no workspace for a {width}x{height} frame")
-    return n
+    return _workspace_bytes("rt_denoise_albedo_workspace_bytes", f"a {width}x{height} frame", width, height)
 
 
 def denoise_albedo_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int,
@@ -1263,19 +1279,9 @@ def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rg
         if spp_map.shape != (h, w):
             raise RtError(f"denoise_albedo: `spp_map` must have shape {(h, w)}")
     params = denoise_albedo_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_sum, d_sq, d_alb = torch.from_numpy(sum).cuda(), torch.from_numpy(sum_sq).cuda(), torch.from_numpy(albedo_sum).cuda()
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_out = torch.empty_like(d_sum)
-        d_ws = torch.empty(denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        denoise_albedo_device(w, h, d_sum.data_ptr(), d_sq.data_ptr(), int(spp), d_alb.data_ptr(), int(albedo_spp), d_out.data_ptr(),
-                              d_ws.data_ptr(), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0,
-                              d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+    return _frame_end(device, [sum, sum_sq, albedo_sum, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_albedo_workspace_bytes(w, h),
+                      lambda d, out, ws, rgba, stream: denoise_albedo_device(w, h, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws, d_spp_ptr=d[3],
+                                                                             d_rgba8_ptr=rgba, params=params, stream=stream))
 
 
 RT_SURFACE_ID_COLOURS = 26
@@ -1305,10 +1311,7 @@ def surface_id_camera(camera: Camera) -> Camera:
 
 
 def denoise_guided_workspace_bytes(width, height, with_albedo) -> int:
-    n = int(amd_lib().rt_denoise_guided_workspace_bytes(width, height, 1 if with_albedo else 0))
-    if n < 0:
-        raise RtError(f"rt_denoise_guided_workspace_bytes: no workspace for a {width}x{height} frame")
-    return n
+    return _workspace_bytes("rt_denoise_guided_workspace_bytes", f"a {width}x{height} frame", width, height, 1 if with_albedo else 0)
 
 
 def denoise_guided_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int, d_edge_sum_ptr: int,
@@ -1339,34 +1342,18 @@ def denoise_guided(sum, sum_sq, spp, edge_sum, edge_spp, *, albedo_sum=None, alb
         if spp_map.shape != (h, w):
             raise RtError(f"denoise_guided: `spp_map` must have shape {(h, w)}")
     params = denoise_guided_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        dev = [torch.from_numpy(a).cuda() for a in frames]
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_out = torch.empty_like(dev[0])
-        d_ws = torch.empty(denoise_guided_workspace_bytes(w, h, albedo_sum is not None), dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        denoise_guided_device(w, h, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), dev[3].data_ptr() if albedo_sum is not None else 0,
-                              int(albedo_spp), dev[2].data_ptr(), int(edge_spp), d_out.data_ptr(), d_ws.data_ptr(),
-                              d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0,
-                              params=params, stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+    albedo = frames[3] if albedo_sum is not None else None
+    return _frame_end(device, frames[:3] + [albedo, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_guided_workspace_bytes(w, h, albedo is not None),
+                      lambda d, out, ws, rgba, stream: denoise_guided_device(w, h, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2], int(edge_spp), out, ws,
+                                                                             d_spp_ptr=d[4], d_rgba8_ptr=rgba, params=params, stream=stream))
 
 
 def denoise_views_workspace_bytes(width, height, n_views) -> int:
-    n = int(amd_lib().rt_denoise_views_workspace_bytes(width, height, n_views))
-    if n < 0:
-        raise RtError(f"rt_denoise_views_workspace_bytes: no workspace for {n_views} frames of {width}x{height}")
-    return n
+    return _workspace_bytes("rt_denoise_views_workspace_bytes", f"{n_views} frames of {width}x{height}", width, height, n_views)
 
 
 def denoise_albedo_views_workspace_bytes(width, height, n_views) -> int:
-    n = int(amd_lib().rt_denoise_albedo_views_workspace_bytes(width, height, n_views))
-    if n < 0:
-        raise RtError(f"rt_denoise_albedo_views_workspace_bytes: no workspace for {n_views} frames of {width}x{height}")
-    return n
+    return _workspace_bytes("rt_denoise_albedo_views_workspace_bytes", f"{n_views} frames of {width}x{height}", width, height, n_views)
 
 
 def denoise_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
@@ -1399,22 +1386,14 @@ def _denoise_views(who, sum, sum_sq, spp, albedo_sum, albedo_spp, rgba8, device,
         raise RtError(f"{who}: the frames must be (n_views, h, w, 3) arrays of one shape")
     n, h, w = frames[0].shape[:3]
     params = denoise_albedo_params(**kw) if guided else denoise_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        dev = [torch.from_numpy(a).cuda() for a in frames]
-        d_out = torch.empty_like(dev[0])
-        ws_bytes = denoise_albedo_views_workspace_bytes(w, h, n) if guided else denoise_views_workspace_bytes(w, h, n)
-        d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((n, h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+
+    def call(d, out, ws, rgba, stream):
         if guided:
-            denoise_albedo_views_device(w, h, n, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), dev[2].data_ptr(), int(albedo_spp),
-                                        d_out.data_ptr(), d_ws.data_ptr(), **common)
+            denoise_albedo_views_device(w, h, n, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
         else:
-            denoise_views_device(w, h, n, dev[0].data_ptr(), dev[1].data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(), **common)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+            denoise_views_device(w, h, n, d[0], d[1], int(spp), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
+    ws_bytes = denoise_albedo_views_workspace_bytes(w, h, n) if guided else denoise_views_workspace_bytes(w, h, n)
+    return _frame_end(device, frames, (n, h, w, 3), rgba8 and (n, h, w, 4), ws_bytes, call)
 
 
 def denoise_views(sum, sum_sq, spp, *, rgba8=False, device=0, **kw):
@@ -1457,22 +1436,14 @@ def _denoise_means(who, mean, m2, samples, albedo_mean, rgba8, device, kw):
         raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
     h, w = frames[0].shape[:2]
     params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_in = [torch.from_numpy(a).cuda() for a in frames]
-        d_out = torch.empty_like(d_in[0])
-        d_ws = torch.empty(denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8,
-                           device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
+
+    def call(d, out, ws, rgba, stream):
         if albedo_mean is None:
-            denoise_mean_device(w, h, d_in[0].data_ptr(), d_in[1].data_ptr(), int(samples), d_out.data_ptr(), d_ws.data_ptr(), **common)
+            denoise_mean_device(w, h, d[0], d[1], int(samples), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
         else:
-            denoise_albedo_mean_device(w, h, d_in[0].data_ptr(), d_in[1].data_ptr(), int(samples), d_in[2].data_ptr(), d_out.data_ptr(),
-                                       d_ws.data_ptr(), **common)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+            denoise_albedo_mean_device(w, h, d[0], d[1], int(samples), d[2], out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
+    ws_bytes = denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h)
+    return _frame_end(device, frames, (h, w, 3), rgba8 and (h, w, 4), ws_bytes, call)
 
 
 def denoise_mean(mean, m2, samples, *, rgba8=False, device=0, **kw):
@@ -1522,22 +1493,16 @@ def _denoise_means_spatial(who, mean, m2, samples, albedo_mean, rgba8, device, k
         raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
     h, w = frames[0].shape[:2]
     params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_in = [torch.from_numpy(a).cuda() for a in frames]
-        d_mean, d_m2 = d_in[0].data_ptr(), (d_in[1].data_ptr() if m2 is not None else 0)
-        d_out = torch.empty_like(d_in[0])
-        d_ws = torch.empty(denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h), dtype=torch.uint8,
-                           device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        common = dict(d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, spatial=spatial, params=params, stream=torch.cuda.current_stream().cuda_stream)
+    inputs = [frames[0], frames[1] if m2 is not None else None, frames[-1] if albedo_mean is not None else None]
+
+    def call(d, out, ws, rgba, stream):
         if albedo_mean is None:
-            denoise_mean_spatial_device(w, h, d_mean, d_m2, int(samples), d_out.data_ptr(), d_ws.data_ptr(), **common)
+            denoise_mean_spatial_device(w, h, d[0], d[1], int(samples), out, ws, d_rgba8_ptr=rgba, spatial=spatial, params=params, stream=stream)
         else:
-            denoise_albedo_mean_spatial_device(w, h, d_mean, d_m2, int(samples), d_in[-1].data_ptr(), d_out.data_ptr(), d_ws.data_ptr(), **common)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+            denoise_albedo_mean_spatial_device(w, h, d[0], d[1], int(samples), d[2], out, ws, d_rgba8_ptr=rgba, spatial=spatial, params=params,
+                                               stream=stream)
+    ws_bytes = denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h)
+    return _frame_end(device, inputs, (h, w, 3), rgba8 and (h, w, 4), ws_bytes, call)
 
 
 def denoise_mean_spatial(mean, m2, samples, *, rgba8=False, device=0, **kw):
@@ -1554,10 +1519,7 @@ def denoise_albedo_mean_spatial(mean, m2, samples, albedo_mean, *, rgba8=False, 
 
 
 def tonemap_workspace_bytes(width, height) -> int:
-    n = int(amd_lib().rt_tonemap_workspace_bytes(width, height))
-    if n < 0:
-        raise RtError(f"rt_tonemap_workspace_bytes: no workspace for a {width}x{height} frame")
-    return n
+    return _workspace_bytes("rt_tonemap_workspace_bytes", f"a {width}x{height} frame", width, height)
 
 
 def tonemap_device(width, height, d_values_ptr: int, spp: int, *, d_spp_ptr: int = 0, d_rgb8_ptr: int = 0, d_rgba8_ptr: int = 0,
@@ -1597,35 +1559,18 @@ def tonemap(values, spp, *, spp_map=None, rgba8=False, device=0, **kw):
     tonemap_params(**kw) and downloads the (h, w, 3) uint8 frame, or (rgb8, (h, w, 4) uint8) with rgba8."""
     values, spp_map, w, h = _tonemap_frame("tonemap", values, spp_map)
     params = tonemap_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_values = torch.from_numpy(values).cuda()
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_rgb = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        d_ws = torch.empty(tonemap_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
-        tonemap_device(w, h, d_values.data_ptr(), int(spp), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, d_rgb8_ptr=d_rgb.data_ptr(),
-                       d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, d_workspace_ptr=d_ws.data_ptr(), params=params,
-                       stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        rgb = d_rgb.cpu().numpy()
-        return (rgb, d_rgba.cpu().numpy()) if rgba8 else rgb
+    return _frame_end(device, [values, spp_map], (h, w, 3), rgba8 and (h, w, 4), tonemap_workspace_bytes(w, h),
+                      lambda d, rgb, ws, rgba, stream: tonemap_device(w, h, d[0], int(spp), d_spp_ptr=d[1], d_rgb8_ptr=rgb, d_rgba8_ptr=rgba,
+                                                                      d_workspace_ptr=ws, params=params, stream=stream), out_dtype="uint8")
 
 
 def log_average_luminance(values, spp, *, spp_map=None, delta=1e-4, device=0):
     """Uploads a frame as tonemap() takes it, runs rt_log_average_luminance_device and downloads (log_mean, Lavg, count, 0.0)."""
     values, spp_map, w, h = _tonemap_frame("log_average_luminance", values, spp_map)
-    import torch
-    with torch.cuda.device(device):
-        d_values = torch.from_numpy(values).cuda()
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_out = torch.empty(4, dtype=torch.float64, device="cuda")
-        d_ws = torch.empty(tonemap_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
-        log_average_luminance_device(w, h, d_values.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
-                                     d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0, delta=delta,
-                                     stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return tuple(float(x) for x in d_out.cpu().numpy())
+    out4 = _frame_end(device, [values, spp_map], (4,), None, tonemap_workspace_bytes(w, h),
+                      lambda d, out, ws, rgba, stream: log_average_luminance_device(w, h, d[0], int(spp), out, ws, d_spp_ptr=d[1], delta=delta,
+                                                                                    stream=stream))
+    return tuple(float(x) for x in out4)
 
 
 def tonemap_host(values, spp, *, spp_map=None, rgba8=False, **kw):
@@ -1653,10 +1598,7 @@ def log_average_luminance_host(values, spp, *, spp_map=None, delta=1e-4):
 
 
 def bloom_workspace_bytes(width, height) -> int:
-    n = int(amd_lib().rt_bloom_workspace_bytes(width, height))
-    if n < 0:
-        raise RtError(f"rt_bloom_workspace_bytes: no workspace for a {width}x{height} frame")
-    return n
+    return _workspace_bytes("rt_bloom_workspace_bytes", f"a {width}x{height} frame", width, height)
 
 
 def bloom_device(width, height, d_values_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0,
@@ -1674,16 +1616,8 @@ def bloom(values, spp, *, spp_map=None, device=0, **kw):
     bloom_params(**kw) and downloads the (h, w, 3) float64 frame of bloomed means."""
     values, spp_map, w, h = _tonemap_frame("bloom", values, spp_map)
     params = bloom_params(**kw)
-    import torch
-    with torch.cuda.device(device):
-        d_values = torch.from_numpy(values).cuda()
-        d_spp = torch.from_numpy(spp_map).cuda() if spp_map is not None else None
-        d_out = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
-        d_ws = torch.empty(bloom_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
-        bloom_device(w, h, d_values.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(), d_spp_ptr=d_spp.data_ptr() if d_spp is not None else 0,
-                     params=params, stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return d_out.cpu().numpy()
+    return _frame_end(device, [values, spp_map], (h, w, 3), None, bloom_workspace_bytes(w, h),
+                      lambda d, out, ws, rgba, stream: bloom_device(w, h, d[0], int(spp), out, ws, d_spp_ptr=d[1], params=params, stream=stream))
 
 
 def bloom_host(values, spp, *, spp_map=None, **kw):
@@ -1707,10 +1641,7 @@ def camera_scaled(camera: Camera, factor: int) -> Camera:
 
 
 def upsample_workspace_bytes(width, height, factor) -> int:
-    n = int(amd_lib().rt_upsample_workspace_bytes(width, height, factor))
-    if n < 0:
-        raise RtError(f"rt_upsample_workspace_bytes: no workspace for a {width}x{height} frame at factor {factor}")
-    return n
+    return _workspace_bytes("rt_upsample_workspace_bytes", f"a {width}x{height} frame at factor {factor}", width, height, factor)
 
 
 def upsample_device(width, height, d_low_ptr: int, spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_albedo_sum_ptr: int = 0,
@@ -1751,21 +1682,10 @@ def upsample(low, spp, size, *, albedo_sum=None, albedo_spp=0, edge_sum=None, ed
     (frame, (h, w, 4) uint8) with rgba8."""
     params = upsample_params(**kw)
     low, albedo_sum, edge_sum, w, h = _upsample_frames("upsample", low, size, params.factor, albedo_sum, edge_sum)
-    import torch
-    with torch.cuda.device(device):
-        d_low = torch.from_numpy(low).cuda()
-        d_alb = torch.from_numpy(albedo_sum).cuda() if albedo_sum is not None else None
-        d_edge = torch.from_numpy(edge_sum).cuda() if edge_sum is not None else None
-        d_out = torch.empty((h, w, 3), dtype=torch.float64, device="cuda")
-        d_ws = torch.empty(upsample_workspace_bytes(w, h, params.factor), dtype=torch.uint8, device="cuda")
-        d_rgba = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda") if rgba8 else None
-        upsample_device(w, h, d_low.data_ptr(), int(spp), d_out.data_ptr(), d_ws.data_ptr(),
-                        d_albedo_sum_ptr=d_alb.data_ptr() if d_alb is not None else 0, albedo_spp=int(albedo_spp),
-                        d_edge_sum_ptr=d_edge.data_ptr() if d_edge is not None else 0, edge_spp=int(edge_spp),
-                        d_rgba8_ptr=d_rgba.data_ptr() if rgba8 else 0, params=params, stream=torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        out = d_out.cpu().numpy()
-        return (out, d_rgba.cpu().numpy()) if rgba8 else out
+    return _frame_end(device, [low, albedo_sum, edge_sum], (h, w, 3), rgba8 and (h, w, 4), upsample_workspace_bytes(w, h, params.factor),
+                      lambda d, out, ws, rgba, stream: upsample_device(w, h, d[0], int(spp), out, ws, d_albedo_sum_ptr=d[1], albedo_spp=int(albedo_spp),
+                                                                       d_edge_sum_ptr=d[2], edge_spp=int(edge_spp), d_rgba8_ptr=rgba, params=params,
+                                                                       stream=stream))
 
 
 def upsample_host(low, spp, size, *, albedo_sum=None, albedo_spp=0, edge_sum=None, edge_spp=0, rgba8=False, **kw):

@@ -6,6 +6,7 @@
 #include "rt_bloom_shared.h"
 #include "rt_upsample_shared.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -160,6 +161,60 @@ int64_t tiles_total(int32_t w, int32_t h) {
 }
 int64_t tiles_local(int32_t w, int32_t h, int32_t shard_index, int32_t shard_count) {
     return (tiles_total(w, h) - shard_index + shard_count - 1) / shard_count;
+}
+// every pixel of the shard's tiles that lies inside the frame: fn(where its three values start in the shard's tile buffer, where in the frame)
+template <class Fn> void for_each_shard_pixel(int32_t w, int32_t h, int32_t shard_index, int32_t shard_count, Fn &&fn) {
+    const int32_t tiles_x = (w + RT_TILE_W - 1) / RT_TILE_W;
+    const int64_t n_local = tiles_local(w, h, shard_index, shard_count);
+    for (int64_t lt = 0; lt < n_local; ++lt) {
+        const int64_t k = lt * shard_count + shard_index;
+        const int32_t x0 = (int32_t)(k % tiles_x) * RT_TILE_W, y0 = (int32_t)(k / tiles_x) * RT_TILE_H;
+        for (int32_t ty = 0; ty < RT_TILE_H; ++ty)
+            for (int32_t tx = 0; tx < RT_TILE_W; ++tx) {
+                const int32_t i = x0 + tx, j = y0 + ty;
+                if (i >= w || j >= h) continue;
+                fn((size_t)((lt * RT_TILE_H + ty) * RT_TILE_W + tx) * 3u, ((size_t)j * w + i) * 3u);
+            }
+    }
+}
+
+// One buffer of a host-memory render entry point.  `host` null with bytes > 0: device-only scratch.  bytes 0: no such buffer.
+struct HostPart {
+    void *host;
+    size_t bytes;
+    bool upload; // the call continues the caller's running values: copy them to the device before the render
+};
+
+// The staging of every host-memory render entry point, past its checks: the scene's device, one allocation for all parts (each starts
+// 16-byte aligned; an empty part's device pointer is null), the uploads, `render(d)` with the parts' device pointers on the null stream,
+// the downloads of the parts that have a host pointer, in list order.  `serial`: calls on one scene run one at a time (host_render_mu).
+// A call that fails behind the allocation may still have launches in flight on the null stream — launch_render's own guard waits for
+// its internal streams only — so the device is drained before the buffer is freed, and the sticky error cleared after it.  (rt_render
+// and rt_render_views used to free at once.)
+template <size_t N, class Render> int render_staged(const char *who, rt_scene *s, bool serial, const HostPart (&parts)[N], Render &&render) {
+    std::unique_lock<std::mutex> lock(s->host_render_mu, std::defer_lock);
+    if (serial) lock.lock();
+    HIP_TRY(hipSetDevice(s->device));
+    size_t total = 0;
+    for (const HostPart &p : parts) total += align16(p.bytes);
+    char *buf = nullptr;
+    HIP_TRY(hipMalloc((void **)&buf, total));
+    void *d[N];
+    for (size_t i = 0, off = 0; i < N; off += align16(parts[i].bytes), ++i) d[i] = parts[i].bytes ? buf + off : nullptr;
+    int rc = RT_OK;
+    for (size_t i = 0; i < N && rc == RT_OK; ++i)
+        if (parts[i].upload && parts[i].host && parts[i].bytes && hipMemcpy(d[i], parts[i].host, parts[i].bytes, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running values failed");
+    if (rc == RT_OK) rc = render(d);
+    for (size_t i = 0; i < N && rc == RT_OK; ++i) {
+        if (!parts[i].host || !parts[i].bytes) continue;
+        const hipError_t e = hipMemcpy(parts[i].host, d[i], parts[i].bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    if (rc != RT_OK) (void)hipDeviceSynchronize();
+    (void)hipFree(buf);
+    if (rc != RT_OK) (void)hipGetLastError();
+    return rc;
 }
 
 int normalise_params(const rt_camera *cam, rt_render_params &p) {
@@ -1119,53 +1174,23 @@ int rt_render(const rt_scene *scene, const rt_camera *camera, const rt_render_pa
     rt_render_params p = *params;
     int rc = normalise_params(camera, p);
     if (rc != RT_OK) return rc;
-    rt_scene *s = const_cast<rt_scene *>(scene);
-    std::lock_guard<std::mutex> serial(s->host_render_mu);
-    HIP_TRY(hipSetDevice(s->device));
     const int32_t w = camera->image_width, h = camera->image_height;
-    // on the device the shard always renders into its compact tile buffer; the requested layout is produced on the host
+    const int64_t n_vals = rt_out_size(w, h, RT_OUT_TILES, p.shard_index, p.shard_count);
+    if (n_vals <= 0) return RT_OK;
+    // on the device the shard always renders into its compact tile buffer; the frame layout is produced on the host, around a staged
+    // copy of the tiles (only the pixels of this shard's tiles are read or written in the caller's frame)
     rt_render_params dp = p;
     dp.out_layout = RT_OUT_TILES;
-    const int64_t n_tiles_vals = rt_out_size(w, h, RT_OUT_TILES, p.shard_index, p.shard_count);
-    if (n_tiles_vals <= 0) return RT_OK;
-    const int32_t tiles_x = (w + RT_TILE_W - 1) / RT_TILE_W;
-    const int64_t n_local = n_tiles_vals / (RT_TILE_W * RT_TILE_H * 3);
-    std::vector<double> tiles((size_t)n_tiles_vals);
-    auto for_each_pixel = [&](auto &&fn) {
-        for (int64_t lt = 0; lt < n_local; ++lt) {
-            const int64_t k = lt * p.shard_count + p.shard_index;
-            const int32_t x0 = (int32_t)(k % tiles_x) * RT_TILE_W, y0 = (int32_t)(k / tiles_x) * RT_TILE_H;
-            for (int32_t ty = 0; ty < RT_TILE_H; ++ty)
-                for (int32_t tx = 0; tx < RT_TILE_W; ++tx) {
-                    const int32_t i = x0 + tx, j = y0 + ty;
-                    if (i >= w || j >= h) continue;
-                    fn(&tiles[(size_t)((lt * RT_TILE_H + ty) * RT_TILE_W + tx) * 3u], ((size_t)j * w + i) * 3u);
-                }
-        }
-    };
-    if (p.accumulate) { // seed the device buffer with the caller's running sums
-        if (p.out_layout == RT_OUT_TILES) std::copy(out_rgb_sum, out_rgb_sum + n_tiles_vals, tiles.begin());
-        else for_each_pixel([&](double *t, size_t f) { t[0] = out_rgb_sum[f]; t[1] = out_rgb_sum[f + 1]; t[2] = out_rgb_sum[f + 2]; });
-    }
-    double *d_tiles = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_tiles, (size_t)n_tiles_vals * sizeof(double)));
-    hipStream_t stream = nullptr;
-    rc = RT_OK;
-    do {
-        if (p.accumulate && hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            rc = fail(RT_ERR_HIP, "rt_render: upload of running sums failed");
-            break;
-        }
-        rc = launch_render(s, camera, dp, d_tiles, stream, nullptr);
-        if (rc != RT_OK) break;
-        hipError_t e = hipMemcpy(tiles.data(), d_tiles, tiles.size() * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = fail(RT_ERR_HIP, std::string("rt_render: ") + hipGetErrorString(e)); break; }
-    } while (0);
-    (void)hipFree(d_tiles);
-    if (rc != RT_OK) return rc;
-    if (p.out_layout == RT_OUT_TILES) std::copy(tiles.begin(), tiles.end(), out_rgb_sum);
-    else for_each_pixel([&](double *t, size_t f) { out_rgb_sum[f] = t[0]; out_rgb_sum[f + 1] = t[1]; out_rgb_sum[f + 2] = t[2]; });
-    return RT_OK;
+    const bool frame = p.out_layout == RT_OUT_FRAME;
+    std::vector<double> tiles(frame ? (size_t)n_vals : 0u);
+    if (frame && p.accumulate) // seed the tiles with the caller's running sums
+        for_each_shard_pixel(w, h, p.shard_index, p.shard_count, [&](size_t t, size_t f) { std::copy_n(out_rgb_sum + f, 3, &tiles[t]); });
+    rt_scene *s = const_cast<rt_scene *>(scene);
+    const HostPart parts[] = {{frame ? tiles.data() : out_rgb_sum, (size_t)n_vals * sizeof(double), p.accumulate != 0}};
+    rc = render_staged("rt_render", s, true, parts, [&](void *const *d) { return launch_render(s, camera, dp, (double *)d[0], nullptr, nullptr); });
+    if (rc == RT_OK && frame)
+        for_each_shard_pixel(w, h, p.shard_index, p.shard_count, [&](size_t t, size_t f) { std::copy_n(&tiles[t], 3, out_rgb_sum + f); });
+    return rc;
 }
 
 // the frame-end kernels run on the device that owns the buffers, whichever device the calling thread had selected
@@ -1273,9 +1298,17 @@ constexpr int64_t VIEWS_MAX_ROWS = (int64_t)1 << 27, VIEWS_MAX_JOBS = MAX_JOBS_P
 constexpr int64_t VIEWS_MAX_TILES = (VIEWS_MAX_ROWS < VIEWS_MAX_JOBS / 64 ? VIEWS_MAX_ROWS : VIEWS_MAX_JOBS / 64) - 1; // n_views x tiles per frame at most
 static_assert(VIEWS_MAX_TILES + 1 == RT_VIEWS_MAX_TILES, "rt_amd.h states the bound");
 
-// every check of rt_render_views / rt_render_views_device that needs no device; fills the records
-int check_views(const rt_view *views, int32_t n_views, const rt_render_params *params, const char *who, std::vector<ViewRec> &recs) {
+// every check of the four views entry points, none of which needs a device: the null arguments first (`sq_name`: the squares' buffer, which
+// a moments form must be given; `plain`: the entry point that renders without them).  Fills the records.
+int check_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, const void *out, const char *out_name,
+                const char *who, std::vector<ViewRec> &recs, const void *sq = nullptr, const char *sq_name = nullptr, const char *plain = nullptr) {
     const std::string w(who);
+    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, w + ": scene is null");
+    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, w + ": views is null");
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, w + ": params is null");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + out_name + " is null");
+    if (sq_name && !sq) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + sq_name + " is null (" + plain + " renders without squares)");
+    g_last_launch[0] = 0; // (rt_debug_last_launch: a call that is refused from here on has launched nothing)
     if (n_views < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
     if (params->shard_count > 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": shard_count must be 1 (views are not sharded)");
     if (params->out_layout != RT_OUT_FRAME) return fail(RT_ERR_INVALID_ARGUMENT, w + ": out_layout must be RT_OUT_FRAME");
@@ -1303,110 +1336,54 @@ int check_views(const rt_view *views, int32_t n_views, const rt_render_params *p
     }
     return RT_OK;
 }
+
+// the views' launch: one frame of sums per view at d_out and, with d_sum_sq, one of sums of squares beside it
+int launch_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, const std::vector<ViewRec> &recs,
+                 double *d_out, double *d_sum_sq, hipStream_t stream) {
+    rt_render_params p = *params;
+    p.shard_index = 0; p.shard_count = 1;
+    const ViewTable table{recs.data(), n_views, d_sum_sq};
+    return launch_render(const_cast<rt_scene *>(scene), &views[0].camera, p, d_out, stream, nullptr, nullptr, &table);
+}
+size_t views_bytes(const rt_view *views, int32_t n_views) {
+    return (size_t)n_views * (size_t)views[0].camera.image_width * (size_t)views[0].camera.image_height * 3u * sizeof(double);
+}
 } // namespace
 
 int rt_render_views_device(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *d_out,
                            void *hip_stream) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: scene is null");
-    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: views is null");
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: params is null");
-    if (!d_out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_device: d_out is null");
-    g_last_launch[0] = 0; // (rt_debug_last_launch: a call that is refused has launched nothing)
     std::vector<ViewRec> recs;
-    if (int rc = check_views(views, n_views, params, "rt_render_views_device", recs)) return rc;
-    rt_render_params p = *params;
-    p.shard_index = 0; p.shard_count = 1;
-    const ViewTable table{recs.data(), n_views};
-    return launch_render(const_cast<rt_scene *>(scene), &views[0].camera, p, d_out, (hipStream_t)hip_stream, nullptr, nullptr, &table);
+    if (int rc = check_views(scene, views, n_views, params, d_out, "d_out", "rt_render_views_device", recs)) return rc;
+    return launch_views(scene, views, n_views, params, recs, d_out, nullptr, (hipStream_t)hip_stream);
 }
 
 int rt_render_views(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *out) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: scene is null");
-    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: views is null");
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: params is null");
-    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views: out is null");
-    g_last_launch[0] = 0;
     std::vector<ViewRec> recs;
-    if (int rc = check_views(views, n_views, params, "rt_render_views", recs)) return rc;
-    rt_scene *s = const_cast<rt_scene *>(scene);
-    std::lock_guard<std::mutex> serial(s->host_render_mu);
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)n_views * (size_t)views[0].camera.image_width * (size_t)views[0].camera.image_height * 3u * sizeof(double);
-    double *d_out = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_out, bytes));
-    int rc = RT_OK;
-    do {
-        if (params->accumulate && hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            rc = fail(RT_ERR_HIP, "rt_render_views: upload of running sums failed");
-            break;
-        }
-        rt_render_params p = *params;
-        p.shard_index = 0; p.shard_count = 1;
-        const ViewTable table{recs.data(), n_views};
-        rc = launch_render(s, &views[0].camera, p, d_out, nullptr, nullptr, nullptr, &table);
-        if (rc != RT_OK) break;
-        const hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string("rt_render_views: ") + hipGetErrorString(e));
-    } while (0);
-    (void)hipFree(d_out);
-    return rc;
+    if (int rc = check_views(scene, views, n_views, params, out, "out", "rt_render_views", recs)) return rc;
+    const HostPart parts[] = {{out, views_bytes(views, n_views), params->accumulate != 0}};
+    return render_staged("rt_render_views", const_cast<rt_scene *>(scene), true, parts, [&](void *const *d) {
+        return launch_views(scene, views, n_views, params, recs, (double *)d[0], nullptr, nullptr);
+    });
 }
 
 // ---- views moments: rt_render_views_device with the sums of squares beside the sums (sum_view_moments_samples_kernel) ----
 int rt_render_views_moments_device(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *d_sum,
                                    double *d_sum_sq, void *hip_stream) {
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: scene is null");
-    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: views is null");
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: params is null");
-    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: d_sum is null");
-    if (!d_sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_views_moments_device: d_sum_sq is null (rt_render_views_device renders without squares)");
-    g_last_launch[0] = 0;
     std::vector<ViewRec> recs;
-    if (int rc = check_views(views, n_views, params, "rt_render_views_moments_device", recs)) return rc;
-    rt_render_params p = *params;
-    p.shard_index = 0; p.shard_count = 1;
-    const ViewTable table{recs.data(), n_views, d_sum_sq};
-    return launch_render(const_cast<rt_scene *>(scene), &views[0].camera, p, d_sum, (hipStream_t)hip_stream, nullptr, nullptr, &table);
+    if (int rc = check_views(scene, views, n_views, params, d_sum, "d_sum", "rt_render_views_moments_device", recs, d_sum_sq, "d_sum_sq", "rt_render_views_device"))
+        return rc;
+    return launch_views(scene, views, n_views, params, recs, d_sum, d_sum_sq, (hipStream_t)hip_stream);
 }
 
 int rt_render_views_moments(const rt_scene *scene, const rt_view *views, int32_t n_views, const rt_render_params *params, double *sum,
                             double *sum_sq) {
-    const char *who = "rt_render_views_moments";
-    if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": scene is null");
-    if (!views) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": views is null");
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": params is null");
-    if (!sum) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": sum is null");
-    if (!sum_sq) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": sum_sq is null (rt_render_views renders without squares)");
-    g_last_launch[0] = 0;
     std::vector<ViewRec> recs;
-    if (int rc = check_views(views, n_views, params, who, recs)) return rc;
-    rt_scene *s = const_cast<rt_scene *>(scene);
-    std::lock_guard<std::mutex> serial(s->host_render_mu);
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t bytes = (size_t)n_views * (size_t)views[0].camera.image_width * (size_t)views[0].camera.image_height * 3u * sizeof(double);
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, 2u * bytes));
-    double *d_sum = (double *)buf, *d_sq = (double *)(buf + bytes);
-    int rc = RT_OK;
-    do {
-        if (params->accumulate && (hipMemcpy(d_sum, sum, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                                   hipMemcpy(d_sq, sum_sq, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running sums failed");
-            break;
-        }
-        rt_render_params p = *params;
-        p.shard_index = 0; p.shard_count = 1;
-        const ViewTable table{recs.data(), n_views, d_sq};
-        rc = launch_render(s, &views[0].camera, p, d_sum, nullptr, nullptr, nullptr, &table);
-        if (rc != RT_OK) break;
-        hipError_t e = hipMemcpy(sum, d_sum, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(sum_sq, d_sq, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    } while (0);
-    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
-    (void)hipFree(buf);
-    if (rc != RT_OK) (void)hipGetLastError();
-    return rc;
+    if (int rc = check_views(scene, views, n_views, params, sum, "sum", "rt_render_views_moments", recs, sum_sq, "sum_sq", "rt_render_views")) return rc;
+    const bool running = params->accumulate != 0;
+    const HostPart parts[] = {{sum, views_bytes(views, n_views), running}, {sum_sq, views_bytes(views, n_views), running}};
+    return render_staged("rt_render_views_moments", const_cast<rt_scene *>(scene), true, parts, [&](void *const *d) {
+        return launch_views(scene, views, n_views, params, recs, (double *)d[0], (double *)d[1], nullptr);
+    });
 }
 
 int rt_render_adaptive_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params,
@@ -1436,25 +1413,12 @@ int rt_render_adaptive(const rt_scene *scene, const rt_camera *camera, const rt_
     if (!out_result) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": out_result is null");
     if (!scene) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": scene is null");
     rt_scene *s = const_cast<rt_scene *>(scene);
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height;
-    const size_t sum_bytes = n_pix * 3u * sizeof(double), spp_bytes = n_pix * sizeof(int32_t);
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, 2u * sum_bytes + spp_bytes));
-    double *d_sum = (double *)buf, *d_sq = (double *)(buf + sum_bytes);
-    int32_t *d_spp = (int32_t *)(buf + 2u * sum_bytes);
-    int rc = render_adaptive(s, camera, p, a, max_spp, d_sum, d_spp, d_sq, nullptr, out_result);
-    if (rc == RT_OK) {
-        hipError_t e = hipMemcpy(out_rgb_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(out_spp, d_spp, spp_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && out_rgb_sum_sq) e = hipMemcpy(out_rgb_sum_sq, d_sq, sum_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    } else {
-        (void)hipDeviceSynchronize(); // (a failed batch may still be in flight on the null stream)
-    }
-    (void)hipFree(buf);
-    (void)hipGetLastError();
-    return rc;
+    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height, sum_bytes = n_pix * 3u * sizeof(double);
+    const HostPart parts[] = {{out_rgb_sum, sum_bytes, false}, {out_rgb_sum_sq, sum_bytes, false}, {out_spp, n_pix * sizeof(int32_t), false}};
+    // (not serialised: render_adaptive owns its scratch, and concurrent adaptive calls on one scene have always run side by side)
+    return render_staged(who, s, false, parts, [&](void *const *d) {
+        return render_adaptive(s, camera, p, a, max_spp, (double *)d[0], (int32_t *)d[2], (double *)d[1], nullptr, out_result);
+    });
 }
 
 // ---- live refinement: running-mean frames and their display bytes ----
@@ -1503,35 +1467,16 @@ int rt_render_mean_moments_device(const rt_scene *scene, const rt_camera *camera
 }
 
 namespace {
-// rt_render_mean and, with `m2`, rt_render_mean_moments, past their checks: the frames in one device allocation (mean | M2 | display
-// bytes), the caller's running values uploaded when the call continues them, the render, the downloads
+// rt_render_mean and, with `m2`, rt_render_mean_moments, past their checks: the frames staged as mean | M2 | display bytes, the first two
+// uploaded when the call continues them
 int render_mean_host(const char *who, rt_scene *s, const rt_camera *camera, const rt_render_params &p, double *mean, double *m2, uint8_t *rgba8) {
-    std::lock_guard<std::mutex> serial(s->host_render_mu);
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height;
-    const size_t mean_bytes = n_pix * 3u * sizeof(double), m2_bytes = m2 ? mean_bytes : 0u, rgba_bytes = rgba8 ? n_pix * 4u : 0u;
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, mean_bytes + m2_bytes + rgba_bytes));
-    double *d_mean = (double *)buf;
-    const MeanOut out{rgba8 ? (uint8_t *)(buf + mean_bytes + m2_bytes) : nullptr, m2 ? (double *)(buf + mean_bytes) : nullptr};
-    int rc = RT_OK;
-    do {
-        if (p.sample_begin > 0 && (hipMemcpy(d_mean, mean, mean_bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                                   (m2 && hipMemcpy(out.d_m2, m2, m2_bytes, hipMemcpyHostToDevice) != hipSuccess))) {
-            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running mean failed");
-            break;
-        }
-        rc = launch_render(s, camera, p, d_mean, nullptr, nullptr, nullptr, nullptr, &out);
-        if (rc != RT_OK) break;
-        hipError_t e = hipMemcpy(mean, d_mean, mean_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && m2) e = hipMemcpy(m2, out.d_m2, m2_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rgba8) e = hipMemcpy(rgba8, out.d_rgba8, rgba_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    } while (0);
-    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
-    (void)hipFree(buf);
-    if (rc != RT_OK) (void)hipGetLastError();
-    return rc;
+    const size_t n_pix = (size_t)camera->image_width * (size_t)camera->image_height, mean_bytes = n_pix * 3u * sizeof(double);
+    const bool running = p.sample_begin > 0;
+    const HostPart parts[] = {{mean, mean_bytes, running}, {m2, m2 ? mean_bytes : 0u, running}, {rgba8, rgba8 ? n_pix * 4u : 0u, false}};
+    return render_staged(who, s, true, parts, [&](void *const *d) {
+        const MeanOut out{(uint8_t *)d[2], (double *)d[1]};
+        return launch_render(s, camera, p, (double *)d[0], nullptr, nullptr, nullptr, nullptr, &out);
+    });
 }
 } // namespace
 
@@ -1651,14 +1596,18 @@ template <class P> bool denoise_size_known(uint32_t size) {
     if constexpr (std::is_same_v<P, rt_denoise_spatial_params>) return size >= 8 && size <= sizeof(P) && size % 4 == 0; // (its fields are words)
     else return size >= 8 && size <= sizeof(P) && size % 8 == 0;
 }
-template <class P> int denoise_params_init_sized(P *params, uint32_t struct_size, const char *who) {
+// the body of every *_params_init_sized of the frame-end stages, over a stage's own size_known and defaults
+template <class P> int params_init_sized(P *params, uint32_t struct_size, const char *who, bool (*size_known)(uint32_t), void (*defaults)(P &)) {
     if (!params) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": null argument");
-    if (!denoise_size_known<P>(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_size is not one this library knows");
+    if (!size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_size is not one this library knows");
     P full;
-    denoise_defaults(full);
+    defaults(full);
     full.struct_size = struct_size;
     memcpy(params, &full, struct_size);
     return RT_OK;
+}
+template <class P> int denoise_params_init_sized(P *params, uint32_t struct_size, const char *who) {
+    return params_init_sized<P>(params, struct_size, who, denoise_size_known<P>, denoise_defaults);
 }
 // an entry point's params resolved into d: the defaults, and over them the caller's struct as far as it goes (an older, shorter struct:
 // the fields it lacks keep their defaults).  False: its struct_size is not one this library knows
@@ -1784,29 +1733,10 @@ int rt_render_moments(const rt_scene *scene, const rt_camera *camera, const rt_r
     if (int rc = check_moments(scene, camera, params, sum, "sum", sum_sq, "sum_sq", who)) return rc;
     g_last_launch[0] = 0;
     rt_scene *s = const_cast<rt_scene *>(scene);
-    std::lock_guard<std::mutex> serial(s->host_render_mu);
-    HIP_TRY(hipSetDevice(s->device));
     const size_t bytes = (size_t)camera->image_width * (size_t)camera->image_height * 3u * sizeof(double);
-    char *buf = nullptr;
-    HIP_TRY(hipMalloc((void **)&buf, 2u * bytes));
-    double *d_sum = (double *)buf, *d_sq = (double *)(buf + bytes);
-    int rc = RT_OK;
-    do {
-        if (params->accumulate && (hipMemcpy(d_sum, sum, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                                   hipMemcpy(d_sq, sum_sq, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-            rc = fail(RT_ERR_HIP, std::string(who) + ": upload of the running sums failed");
-            break;
-        }
-        rc = render_moments(s, camera, params, d_sum, d_sq, nullptr);
-        if (rc != RT_OK) break;
-        hipError_t e = hipMemcpy(sum, d_sum, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(sum_sq, d_sq, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(RT_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    } while (0);
-    if (rc != RT_OK) (void)hipDeviceSynchronize(); // (a failed call may still have launches in flight on the null stream)
-    (void)hipFree(buf);
-    if (rc != RT_OK) (void)hipGetLastError();
-    return rc;
+    const bool running = params->accumulate != 0;
+    const HostPart parts[] = {{sum, bytes, running}, {sum_sq, bytes, running}};
+    return render_staged(who, s, true, parts, [&](void *const *d) { return render_moments(s, camera, params, (double *)d[0], (double *)d[1], nullptr); });
 }
 
 int rt_denoise_params_init_sized(rt_denoise_params *params, uint32_t struct_size) {
@@ -2076,13 +2006,7 @@ int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum,
 // ---- tone mapping (rt_tonemap.hip): exposure and a tone curve in front of the output stage's gamma, auto-exposure from a device reduction ----
 
 int rt_tonemap_params_init_sized(rt_tonemap_params *params, uint32_t struct_size) {
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tonemap_params_init_sized: null argument");
-    if (!rttm::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_tonemap_params_init_sized: struct_size is not one this library knows");
-    rt_tonemap_params full;
-    rttm::defaults(full);
-    full.struct_size = struct_size;
-    memcpy(params, &full, struct_size);
-    return RT_OK;
+    return params_init_sized(params, struct_size, "rt_tonemap_params_init_sized", rttm::size_known, rttm::defaults);
 }
 
 int64_t rt_tonemap_workspace_bytes(int32_t width, int32_t height) { return rttm::workspace_bytes(width, height); }
@@ -2160,13 +2084,7 @@ int rt_debug_set_bloom_fused(int32_t max_stride) {
 }
 
 int rt_bloom_params_init_sized(rt_bloom_params *params, uint32_t struct_size) {
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_bloom_params_init_sized: null argument");
-    if (!rtbl::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_bloom_params_init_sized: struct_size is not one this library knows");
-    rt_bloom_params full;
-    rtbl::defaults(full);
-    full.struct_size = struct_size;
-    memcpy(params, &full, struct_size);
-    return RT_OK;
+    return params_init_sized(params, struct_size, "rt_bloom_params_init_sized", rtbl::size_known, rtbl::defaults);
 }
 
 int64_t rt_bloom_workspace_bytes(int32_t width, int32_t height) { return rtbl::workspace_bytes(width, height); }
@@ -2241,13 +2159,7 @@ static std::atomic<int32_t> g_upsample_form{-1};
 int rt_debug_set_upsample_form(int32_t form) { return g_upsample_form.exchange(form < 0 ? -1 : form > 0 ? 1 : 0); }
 
 int rt_upsample_params_init_sized(rt_upsample_params *params, uint32_t struct_size) {
-    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_upsample_params_init_sized: null argument");
-    if (!rtup::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_upsample_params_init_sized: struct_size is not one this library knows");
-    rt_upsample_params full;
-    rtup::defaults(full);
-    full.struct_size = struct_size;
-    memcpy(params, &full, struct_size);
-    return RT_OK;
+    return params_init_sized(params, struct_size, "rt_upsample_params_init_sized", rtup::size_known, rtup::defaults);
 }
 
 int64_t rt_upsample_workspace_bytes(int32_t width, int32_t height, int32_t factor) { return rtup::workspace_bytes(width, height, factor); }

@@ -184,7 +184,7 @@ struct rt_scene {
     std::mutex mu;
     std::map<hipStream_t, std::unique_ptr<rtapi::WorkspaceSlot>> workspaces; // one per stream: launches on a stream are ordered
     rt_scene_options options;                    // the caller's per-scene options (rt_scene_create_ex); unset fields: process defaults
-    std::mutex host_render_mu;                   // rt_render (host-buffer form) calls on one scene run one at a time
+    std::mutex host_render_mu;                   // the host-memory render entry points (rt_api.cpp render_staged) on one scene run one at a time
     std::map<std::pair<int32_t, int32_t>, uint32_t *> tile_lists; // rt_render_moments_device: (w, h) -> every pixel in tile order, device memory (under mu)
 };
 
