@@ -639,7 +639,8 @@ int rt_scene_create_surface_ids(const rt_scene_desc *desc, int device, const rt_
  *              (sw >= 9/64 still: the centre tap has eg = 1)
  *   Output.    As without the edge guide: it is not multiplied in.
  * With E_c the same value at every pixel, dg = 0, z = 0, tg = 1, eg = 1 and x * 1 = x, each exactly: the result is
- * rt_denoise_albedo_device's (rt_denoise_device's) bit for bit.  The means (live), spatial-variance and views forms have no edge guide. */
+ * rt_denoise_albedo_device's (rt_denoise_device's) bit for bit.  The means (live), spatial-variance and views forms of this call are rt_denoise_guided_mean_device,
+ * rt_denoise_guided_mean_spatial_device and rt_denoise_guided_views_device: "edge guide on every route" below. */
 typedef struct rt_denoise_guided_params {
     uint32_t struct_size;   /* sizeof(rt_denoise_guided_params) as the CALLER was compiled (grows like rt_scene_options) */
     int32_t iterations;     /* K, 1..6 (default 4): strides 1, 2, 4, ... 2^(K-1) */
@@ -804,6 +805,72 @@ int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_view
                                    const double *d_albedo_sum /* n_views x 3*w*h */, int32_t albedo_spp /* >= 1 */,
                                    const rt_denoise_albedo_params *params /* NULL: defaults */, double *d_mean_out /* n_views x 3*w*h */,
                                    uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+
+/* ---- edge guide on every route: the means, spatial-variance and views forms of rt_denoise_guided_device (opt-in; nothing above changes) ----
+ * The edge guide of rt_denoise_guided_device on the three other routes of the filter.  All three take rt_denoise_guided_params (NULL:
+ * defaults; struct_size as everywhere) and an optional albedo frame: with it NULL, albedo_spp, sigma_albedo and albedo_floor are not
+ * read and the call is the plain form's with an edge guide.  Each is enqueued on hip_stream, not synchronised, and allocates nothing;
+ * d_workspace is 16-byte aligned.
+ *
+ * rt_denoise_guided_mean_device is rt_denoise_albedo_mean_device (d_albedo_mean NULL: rt_denoise_mean_device) with an edge guide.
+ * d_edge_mean holds 3 * w * h doubles, a frame of MEANS — what rt_render_mean_device gives for the surface-ID scene — so there is no
+ * count.  d_workspace is rt_denoise_guided_workspace_bytes(w, h, d_albedo_mean != NULL) bytes.  Normative, as "live denoise" with:
+ *   Prepare.   g_c = E_c, nothing divided (as a is not).  A VALID pixel also needs all three E_c finite.  C0 and V0 are untouched.
+ *   Iterations and Output: rt_denoise_guided_device's.
+ * With samples < 2 the output is d_mean bit for bit.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: width or height < 1 or w * h >= 2^27; a null d_mean,
+ * d_m2, d_edge_mean, d_mean_out or d_workspace; samples < 1; a struct_size this library does not know; iterations outside 1..6; sigma
+ * or eps that is not a number > 0; with an albedo frame, a sigma_albedo or albedo_floor that is not a number > 0; a sigma_edge that is
+ * not a number > 0; d_mean_out overlapping d_mean, d_m2 or d_albedo_mean; d_mean_out overlapping d_edge_mean; a d_rgba8 that is not
+ * 4-byte aligned; a d_workspace that is not 16-byte aligned.
+ *
+ * rt_denoise_guided_mean_spatial_device is rt_denoise_albedo_mean_spatial_device (rt_denoise_mean_spatial_device) with an edge guide.
+ * With samples >= spatial_below the call IS rt_denoise_guided_mean_device: the same kernels, d_m2 required.  Below it an EDGE-AWARE
+ * spatial Prepare runs and d_m2 is not read and may be NULL.  The workspace is rt_denoise_guided_mean_device's.  Normative, as "spatial
+ * variance" (f64, every operation rounded on its own, max(a, b) = (b > a ? b : a)) with g = E, the pixel's entry of d_edge_mean:
+ *   Prepare.   p is VALID iff every m_c is finite, with an albedo frame every a_c is finite, and every E_c is finite.
+ *              For a valid p and an in-frame valid q of the (2R + 1)^2 window, dy outer and dx inner:
+ *                   dg = max(max(|g_r(p) - g_r(q)|, |g_g(p) - g_g(q)|), |g_b(p) - g_b(q)|)
+ *                   z = dg / sigma_edge;  tg = 1 - z * z;  q is a MEMBER iff tg > 0
+ *              (the iterations' edge stop is non-zero exactly there).  p is a member of its own window: dg = 0.  cnt, s1, mu, s2, v_c
+ *              and V0 are "spatial variance"'s over the members, and nothing else changes.  The albedo stop does not decide
+ *              membership: demodulation already took the albedo out of C0.  The guide of an out-of-frame or invalid pixel is never
+ *              read.  The edge region is written (g = E), and with an albedo frame the albedo region as there.
+ *   Iterations and Output: rt_denoise_guided_device's.
+ * With E the same at every pixel every valid window pixel is a member, and the result is the unguided spatial form's bit for bit.
+ * With samples < 2 and no spatial route (spatial_below = 1) the output is d_mean bit for bit.
+ * RT_ERR_INVALID_ARGUMENT, in rt_denoise_guided_mean_device's order with the spatial checks behind `samples`: width or height < 1 or
+ * w * h >= 2^27; a null d_mean, d_edge_mean, d_mean_out or d_workspace; samples < 1; an rt_denoise_spatial_params.struct_size this
+ * library does not know; spatial_below < 1; window_radius outside 1..3; a null d_m2 when samples >= spatial_below; then everything
+ * from "a struct_size this library does not know" on as above.
+ *
+ * rt_denoise_guided_views_device is rt_denoise_albedo_views_device (d_albedo_sum NULL: rt_denoise_views_device) with an edge guide,
+ * view-major everywhere: d_sum, d_sum_sq, d_albedo_sum, d_edge_sum and d_mean_out hold n_views frames of 3 * w * h doubles, d_rgba8
+ * n_views frames of 4 * w * h bytes.  View v of d_mean_out (and of d_rgba8) is, bit for bit, rt_denoise_guided_device on view v's
+ * frames; no tap, halo pixel or window member is another view's.  d_workspace is rt_denoise_guided_views_workspace_bytes(w, h, n_views,
+ * d_albedo_sum != NULL) bytes: n_views times rt_denoise_guided_workspace_bytes, or -1 for what the call refuses or what overflows.
+ * RT_ERR_INVALID_ARGUMENT, in this order: width or height < 1 or w * h >= 2^27; n_views < 1; n_views > RT_DENOISE_MAX_VIEWS; a null
+ * d_sum, d_sum_sq, d_edge_sum, d_mean_out or d_workspace; spp < 2; with an albedo frame, albedo_spp < 1; edge_spp < 1; a struct_size
+ * this library does not know; iterations outside 1..6; sigma or eps that is not a number > 0; with an albedo frame, a sigma_albedo or
+ * albedo_floor that is not a number > 0; a sigma_edge that is not a number > 0; d_mean_out overlapping d_sum, d_sum_sq or d_albedo_sum
+ * anywhere in the whole n_views extent; d_mean_out overlapping d_edge_sum likewise; a d_rgba8 that is not 4-byte aligned; a
+ * d_workspace that is not 16-byte aligned. */
+int rt_denoise_guided_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                  const double *d_albedo_mean /* 3*w*h, or NULL: no albedo guide */, const double *d_edge_mean /* 3*w*h */,
+                                  const rt_denoise_guided_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
+                                  uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int rt_denoise_guided_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2 /* or NULL, see above */,
+                                          int32_t samples, const double *d_albedo_mean /* 3*w*h, or NULL: no albedo guide */,
+                                          const double *d_edge_mean /* 3*w*h */, const rt_denoise_spatial_params *spatial /* NULL: defaults */,
+                                          const rt_denoise_guided_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h */,
+                                          uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
+int64_t rt_denoise_guided_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views, int32_t with_albedo);
+int rt_denoise_guided_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const double *d_albedo_sum /* n_views x 3*w*h, or NULL: no albedo guide */,
+                                   int32_t albedo_spp /* >= 1 with an albedo frame */, const double *d_edge_sum /* n_views x 3*w*h */,
+                                   int32_t edge_spp /* >= 1 */, const rt_denoise_guided_params *params /* NULL: defaults */,
+                                   double *d_mean_out /* n_views x 3*w*h */, uint8_t *d_rgba8 /* n_views x 4*w*h, or NULL */,
+                                   void *d_workspace, void *hip_stream);
 
 /* ---- guided upsampling (opt-in; nothing above changes) -------------------------------------------------------------------------------------
  * A frame's cost is its number of paths.  Where a picture is wanted quickly, trace the beauty frame at 1/F of the width and height —

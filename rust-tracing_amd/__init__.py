@@ -250,7 +250,7 @@ def denoise_albedo_params(**kw) -> "DenoiseAlbedoParams":
 
 
 class DenoiseGuidedParams(C.Structure):
-    """rt_denoise_guided_params (rt_denoise_guided_device)."""
+    """rt_denoise_guided_params (rt_denoise_guided_device and its _mean, _mean_spatial and _views forms)."""
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma", C.c_double), ("eps", C.c_double),
                 ("sigma_albedo", C.c_double), ("albedo_floor", C.c_double), ("sigma_edge", C.c_double)]
 
@@ -434,6 +434,13 @@ RT_AMD_SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_denoise_albedo_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_guided_mean_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_guided_mean_spatial_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_denoise_guided_views_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rt_denoise_guided_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                 C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_bloom_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_bloom_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_bloom_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -1516,6 +1523,107 @@ def denoise_albedo_mean_spatial(mean, m2, samples, albedo_mean, *, rgba8=False, 
     if albedo_mean is None:
         raise RtError("denoise_albedo_mean_spatial: `albedo_mean` is required")
     return _denoise_means_spatial("denoise_albedo_mean_spatial", mean, m2, samples, albedo_mean, rgba8, device, dict(kw))
+
+
+def denoise_guided_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_edge_mean_ptr: int,
+                               d_mean_out_ptr: int, d_workspace_ptr: int, *, d_rgba8_ptr: int = 0, params: "DenoiseGuidedParams | None" = None,
+                               stream: int = 0):
+    """rt_denoise_guided_mean_device: denoise_albedo_mean_device (d_albedo_mean_ptr 0: denoise_mean_device) with a device frame of
+    edge-guide means (3 w h doubles: render_mean_device of the surface-ID scene) beside its inputs; `d_workspace_ptr`:
+    denoise_guided_workspace_bytes(w, h, d_albedo_mean_ptr != 0) device bytes.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_guided_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples,
+                                                   C.c_void_p(d_albedo_mean_ptr or None), C.c_void_p(d_edge_mean_ptr or None),
+                                                   C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                   C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_guided_mean_device")
+
+
+def denoise_guided_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_edge_mean_ptr: int,
+                                       d_mean_out_ptr: int, d_workspace_ptr: int, *, d_rgba8_ptr: int = 0,
+                                       spatial: "DenoiseSpatialParams | None" = None, params: "DenoiseGuidedParams | None" = None, stream: int = 0):
+    """rt_denoise_guided_mean_spatial_device: denoise_guided_mean_device that, for frames of fewer than spatial.spatial_below samples,
+    takes the variance from the spread of the neighbouring pixels of the same surface; `d_m2_ptr` may then be 0.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_guided_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
+                                                           C.c_void_p(d_albedo_mean_ptr or None), C.c_void_p(d_edge_mean_ptr or None),
+                                                           C.byref(spatial) if spatial is not None else None,
+                                                           C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                           C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_guided_mean_spatial_device")
+
+
+def denoise_guided_views_workspace_bytes(width, height, n_views, with_albedo) -> int:
+    return _workspace_bytes("rt_denoise_guided_views_workspace_bytes", f"{n_views} frames of {width}x{height}", width, height, n_views,
+                            1 if with_albedo else 0)
+
+
+def denoise_guided_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int,
+                                d_edge_sum_ptr: int, edge_spp: int, d_mean_out_ptr: int, d_workspace_ptr: int, *, d_rgba8_ptr: int = 0,
+                                params: "DenoiseGuidedParams | None" = None, stream: int = 0):
+    """rt_denoise_guided_views_device: denoise_guided_device over a stack of n_views frames in one set of launches, every buffer
+    view-major; `d_workspace_ptr`: denoise_guided_views_workspace_bytes(w, h, n_views, d_albedo_sum_ptr != 0) device bytes.  View v
+    equals denoise_guided_device on view v's frames.  Enqueued on `stream`."""
+    _check(amd_lib().rt_denoise_guided_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
+                                                    C.c_void_p(d_albedo_sum_ptr or None), albedo_spp, C.c_void_p(d_edge_sum_ptr or None), edge_spp,
+                                                    C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
+                                                    C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
+           "rt_denoise_guided_views_device")
+
+
+def _denoise_guided_means(who, mean, m2, samples, edge_mean, albedo_mean, spatial, rgba8, device, kw):
+    """denoise_guided_mean and (`spatial`: the route's params) denoise_guided_mean_spatial: upload, run, download (m2 None: a null d_m2)"""
+    import numpy as np
+    if edge_mean is None:
+        raise RtError(f"{who}: `edge_mean` is required")
+    inputs = [None if a is None else np.array(a, dtype=np.float64, order="C") for a in (mean, m2, edge_mean, albedo_mean)]  # (copies)
+    frames = [a for a in inputs if a is not None]
+    if inputs[0] is None or frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
+    h, w = frames[0].shape[:2]
+    params = denoise_guided_params(**kw)
+
+    def call(d, out, ws, rgba, stream):
+        if spatial is None:
+            denoise_guided_mean_device(w, h, d[0], d[1], int(samples), d[3], d[2], out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
+        else:
+            denoise_guided_mean_spatial_device(w, h, d[0], d[1], int(samples), d[3], d[2], out, ws, d_rgba8_ptr=rgba, spatial=spatial,
+                                               params=params, stream=stream)
+    return _frame_end(device, inputs, (h, w, 3), rgba8 and (h, w, 4), denoise_guided_workspace_bytes(w, h, albedo_mean is not None), call)
+
+
+def denoise_guided_mean(mean, m2, samples, edge_mean, *, albedo_mean=None, rgba8=False, device=0, **kw):
+    """Uploads (h, w, 3) frames of running means, of M2 after `samples` samples and of edge-guide means (and of albedo means, if given),
+    runs rt_denoise_guided_mean_device with denoise_guided_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or
+    (means, (h, w, 4) uint8) with rgba8."""
+    if m2 is None:
+        raise RtError("denoise_guided_mean: `m2` is required")
+    return _denoise_guided_means("denoise_guided_mean", mean, m2, samples, edge_mean, albedo_mean, None, rgba8, device, dict(kw))
+
+
+def denoise_guided_mean_spatial(mean, m2, samples, edge_mean, *, albedo_mean=None, rgba8=False, device=0, **kw):
+    """denoise_guided_mean through rt_denoise_guided_mean_spatial_device: `m2` may be None where samples < spatial_below; spatial_below=
+    and window_radius= go to denoise_spatial_params, every other keyword to denoise_guided_params."""
+    kw = dict(kw)
+    spatial = denoise_spatial_params(**{k: kw.pop(k) for k in ("spatial_below", "window_radius") if k in kw})
+    return _denoise_guided_means("denoise_guided_mean_spatial", mean, m2, samples, edge_mean, albedo_mean, spatial, rgba8, device, kw)
+
+
+def denoise_guided_views(sum, sum_sq, spp, edge_sum, edge_spp, *, albedo_sum=None, albedo_spp=0, rgba8=False, device=0, **kw):
+    """Uploads (n_views, h, w, 3) stacks of sums, sums of squares and edge-guide sums (render_views of the surface-ID scene; and of
+    albedo sums, if given), runs rt_denoise_guided_views_device with denoise_guided_params(**kw) and downloads: the (n_views, h, w, 3)
+    float64 filtered means, or (means, (n_views, h, w, 4) uint8) with rgba8."""
+    import numpy as np
+    if edge_sum is None:
+        raise RtError("denoise_guided_views: `edge_sum` is required")
+    inputs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (sum, sum_sq, edge_sum, albedo_sum)]
+    frames = [a for a in inputs if a is not None]
+    if inputs[0] is None or inputs[1] is None or frames[0].ndim != 4 or frames[0].shape[3] != 3 or any(a.shape != frames[0].shape for a in frames):
+        raise RtError("denoise_guided_views: the frames must be (n_views, h, w, 3) arrays of one shape")
+    n, h, w = frames[0].shape[:3]
+    params = denoise_guided_params(**kw)
+    return _frame_end(device, inputs, (n, h, w, 3), rgba8 and (n, h, w, 4), denoise_guided_views_workspace_bytes(w, h, n, albedo_sum is not None),
+                      lambda d, out, ws, rgba, stream: denoise_guided_views_device(w, h, n, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2],
+                                                                                   int(edge_spp), out, ws, d_rgba8_ptr=rgba, params=params,
+                                                                                   stream=stream))
 
 
 def tonemap_workspace_bytes(width, height) -> int:

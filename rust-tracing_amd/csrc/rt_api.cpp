@@ -1648,8 +1648,9 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
 // `stack` (rt_denoise_views_device, rt_denoise_albedo_views_device; sums form, no map) is a stack of n_views frames, view-major in every
 // buffer and in every region of the workspace, filtered in the same K + 1 launches with the view on the grid's second dimension; its
 // count is checked behind the frame size.  Null is the single frame: a stack of one, launch for launch.
-// `edge` (rt_denoise_guided_device; sums form, single frame) is the edge guide, with or without `guide`; its region is set here, the third
-// of the workspace alone and the fourth beside the albedo guide's.  Each of its checks sits behind the albedo guide's of the same kind.
+// `edge` (rt_denoise_guided_device and its _mean, _mean_spatial and _views forms) is the edge guide, with or without `guide`; its region is
+// set here, the third of the workspace alone and the fourth beside the albedo guide's.  Each of its checks sits behind the albedo guide's
+// of the same kind.  In the means forms its frame holds means, as the albedo guide's does, and its count is neither read nor checked.
 enum class DenoiseInput { Sums, Means };
 struct SpatialRoute {
     rt_denoise_spatial_params params;
@@ -1660,7 +1661,8 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
                 void *hip_stream, const SpatialRoute *spatial = nullptr, const int32_t *stack = nullptr, DenoiseEdge *edge = nullptr) {
     const std::string w(who);
     const bool means = form == DenoiseInput::Means;
-    const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum";
+    const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum",
+               *fourth = means ? "d_edge_mean" : "d_edge_sum";
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
     if (stack && *stack < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
@@ -1670,13 +1672,13 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
     if (!d_sum_sq && !spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
     if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
-    if (edge && !edge->edge_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_edge_sum is null");
+    if (edge && !edge->edge_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + fourth + " is null");
     if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
     if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
     if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
     if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples)" + (stack ? "" : " when d_spp is null"));
     if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
-    if (edge && edge->edge_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": edge_spp must be at least 1");
+    if (!means && edge && edge->edge_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": edge_spp must be at least 1");
     bool spatial_route = false;
     if (spatial) {
         const rt_denoise_spatial_params &sp = spatial->params;
@@ -1699,7 +1701,7 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || (d_sum_sq && overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes)) ||
         (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
-    if (edge && overlaps(d_mean_out, frame_bytes, edge->edge_sum, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap d_edge_sum");
+    if (edge && overlaps(d_mean_out, frame_bytes, edge->edge_sum, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + fourth);
     if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
     if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
     if (int rc = select_device_of(d_mean_out, who)) return rc;
@@ -1708,7 +1710,7 @@ int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t heigh
     char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
     if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
     if (edge) edge->region = (double4 *)((char *)d_workspace + (guide ? 3u : 2u) * region); // (alone: the albedo guide's place)
-    if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream);
+    if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream, edge);
     else launch_denoise_prepare((int64_t)n_pix, n_views, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream, edge);
     HIP_TRY(hipGetLastError());
     for (int32_t k = 0; k < d->iterations; ++k) {
@@ -2001,6 +2003,50 @@ int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum,
     DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
     return run_denoise("rt_denoise_guided_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum ? &guide : nullptr,
                        known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
+}
+
+// the edge guide on the other routes (include/rt_amd.h "edge guide on every route"): the means, spatial-variance and views forms
+int rt_denoise_guided_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const double *d_albedo_mean,
+                                  const double *d_edge_mean, const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8,
+                                  void *d_workspace, void *hip_stream) {
+    rt_denoise_guided_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr}; // (used only with an albedo frame)
+    DenoiseEdge edge{d_edge_mean, 1.0, d.sigma_edge, nullptr};
+    return run_denoise("rt_denoise_guided_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, d_albedo_mean ? &guide : nullptr,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
+}
+
+int rt_denoise_guided_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                          const double *d_albedo_mean, const double *d_edge_mean, const rt_denoise_spatial_params *spatial,
+                                          const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
+                                          void *hip_stream) {
+    rt_denoise_guided_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr};
+    DenoiseEdge edge{d_edge_mean, 1.0, d.sigma_edge, nullptr};
+    SpatialRoute route;
+    route.known = denoise_params_resolve(spatial, route.params);
+    return run_denoise("rt_denoise_guided_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr,
+                       d_albedo_mean ? &guide : nullptr, known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route, nullptr, &edge);
+}
+
+int64_t rt_denoise_guided_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views, int32_t with_albedo) {
+    return denoise_views_workspace_bytes(width, height, n_views, with_albedo ? 4 : 3);
+}
+
+int rt_denoise_guided_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                   const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
+                                   const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    rt_denoise_guided_params d;
+    const bool known = denoise_params_resolve(params, d);
+    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
+    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
+    DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
+    return run_denoise("rt_denoise_guided_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, d_albedo_sum ? &guide : nullptr,
+                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views, &edge);
 }
 
 // ---- tone mapping (rt_tonemap.hip): exposure and a tone curve in front of the output stage's gamma, auto-exposure from a device reduction ----

@@ -8,7 +8,7 @@
 // compile-time parameter, the input form: sums and sums of squares, or (Means: rt_denoise_mean_device, rt_denoise_albedo_mean_device)
 // the live route's running means and Welford's M2; the iterations do not know which it was.  A third prepare, a tile kernel, serves
 // frames of so few samples that M2 says nothing (rt_denoise_mean_spatial_device, "spatial variance"): it takes V0 from the spread of the
-// neighbouring pixels' values.  The guide is a small compile-time mode (DN_PLAIN, DN_ALBEDO, DN_EDGES, DN_BOTH below): an EDGE guide
+// neighbouring pixels' values — and, with an edge guide, of those of its own surface only.  The guide is a small compile-time mode (DN_PLAIN, DN_ALBEDO, DN_EDGES, DN_BOTH below): an EDGE guide
 // (rt_denoise_guided_device, "edge-guided denoise") is a guide frame that contributes one more stop factor per tap and nothing else —
 // no division in prepare, nothing multiplied back — alone, where it reuses the albedo mode's guide region, planes and loads, or beside
 // the albedo guide, with a fourth region of the workspace, three more staged planes (eleven: 40 x 16 x 11 x 8 B = 56 320 B at stride
@@ -51,7 +51,6 @@ constexpr int DN_TW = 32, DN_TH = 8, DN_THREADS = DN_TW * DN_TH;
 constexpr int DN_PLAIN = 0, DN_ALBEDO = 1, DN_EDGES = 2, DN_BOTH = 3;
 constexpr bool demodulates(int mode) { return (mode & DN_ALBEDO) != 0; }
 constexpr bool has_edges(int mode) { return (mode & DN_EDGES) != 0; }
-constexpr int guide_mode(bool guided) { return guided ? DN_ALBEDO : DN_PLAIN; } // (the means and spatial forms: no edge guide)
 
 // what a kernel gets of the guides: the launcher's description(s), or — the plain instantiations — nothing, so no argument of theirs is live
 struct NoGuide {};
@@ -88,14 +87,13 @@ __device__ __forceinline__ double max_ab(double a, double b) { return b > a ? b 
 // Means (rt_denoise_mean_device, rt_denoise_albedo_mean_device: the live route's frames): `sum` holds the running means m and `sum_sq`
 // Welford's M2 after n = spp samples of every pixel (no map), the guide's frame the albedo means a: nothing is divided by a count, and
 // v_c = M2_c / (n - 1).  Everything else is the sums form's, which holds none of this.
-// An edge guide (Mode with DN_EDGES; sums form): g = E / n_e is written to its region, a pixel with a non-finite E is not valid, and
-// C0 and V0 are not touched by it.
+// An edge guide (Mode with DN_EDGES): g = E / n_e is written to its region, a pixel with a non-finite E is not valid, and C0 and V0
+// are not touched by it.  Means (rt_denoise_guided_mean_device): the guide's frame holds means, g = E with nothing divided, as a is.
 template <int Mode, bool Means>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_pixels, const double *__restrict__ sum, const double *__restrict__ sum_sq,
                                                                       int32_t spp, const int32_t *__restrict__ spp_map, GuideOf<Mode> gd,
                                                                       double4 *__restrict__ out) {
     constexpr bool Guided = demodulates(Mode);
-    static_assert(!(Means && has_edges(Mode)), "the edge guide has no means form");
     const int64_t in_frame = (int64_t)blockIdx.x * DN_THREADS + threadIdx.x;
     if (in_frame >= n_pixels) return;
     const size_t idx = (size_t)blockIdx.y * (size_t)n_pixels + (size_t)in_frame; // the pixel in the stack of views (n_pixels: one frame's)
@@ -114,7 +112,8 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
     if constexpr (has_edges(Mode))
         for (int k = 0; k < 3; ++k) {
             E[k] = edge_of(gd).edge_sum[idx * 3 + k];
-            g[k] = E[k] / edge_of(gd).edge_spp;
+            if constexpr (Means) g[k] = E[k];
+            else g[k] = E[k] / edge_of(gd).edge_spp;
         }
     double c[3] = {s[0], s[1], s[2]};
     if constexpr (!Means)
@@ -154,14 +153,29 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_kernel(int64_t n_p
 // staged with C0 = m, which its own lane writes back.  Each lane then makes the definition's two passes over the staged window, dy
 // outer and dx inner: the sum and the count of the members, then the sum of the squared differences from their mean.  A pixel that
 // is not a member is skipped: nothing is added for it.
-template <int R> struct SpatialTile {
+// An edge guide (Mode with DN_EDGES; rt_denoise_guided_mean_spatial_device, "edge guide on every route") restricts the window to the
+// centre pixel's own surface: three more planes hold the guide's means g (seven: 38 x 14 x 7 x 8 B = 29 792 B at R = 3), a pixel with
+// a non-finite g is not valid, and a valid window pixel is a member only where the iterations' edge stop would let it through,
+// tg = 1 - (dg / sigma_edge)^2 > 0 with dg the largest channel difference from the centre's g.  P_OK is tested first, so the staged
+// guide of an out-of-frame or invalid pixel is never read.  Both passes make the test: nothing of the first is kept for the second.
+// The plain and albedo instantiations hold none of it.
+template <int R, int Mode> struct SpatialTile {
     static constexpr int PW = DN_TW + 2 * R, PH = DN_TH + 2 * R, PLANE = PH * PW;
-    enum { P_R, P_G, P_B, P_OK, PLANES };
+    enum { P_R, P_G, P_B, P_OK, P_ER, P_EG, P_EB, PLANES = has_edges(Mode) ? 7 : 4 };
+    // q, a valid pixel at k of the staged planes, is of the centre's surface (the centre's guide is e)
+    static __device__ __forceinline__ bool member(const double *staged, int k, const double (&e)[3], double sigma_edge) {
+        const double dg = max_ab(max_ab(__builtin_fabs(e[0] - staged[P_ER * PLANE + k]), __builtin_fabs(e[1] - staged[P_EG * PLANE + k])),
+                                 __builtin_fabs(e[2] - staged[P_EB * PLANE + k]));
+        const double z = dg / sigma_edge;
+        const double tg = 1.0 - z * z;
+        return tg > 0.0;
+    }
 };
-template <int R, bool Guided>
+template <int R, int Mode>
 __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int32_t w, int32_t h, int32_t tiles_x, const double *__restrict__ mean,
-                                                                              GuideOf<guide_mode(Guided)> gd, double4 *__restrict__ out) {
-    using T = SpatialTile<R>;
+                                                                              GuideOf<Mode> gd, double4 *__restrict__ out) {
+    constexpr bool Guided = demodulates(Mode), Edges = has_edges(Mode);
+    using T = SpatialTile<R, Mode>;
     constexpr int PW = T::PW, PLANE = T::PLANE;
     __shared__ double staged[T::PLANES * PLANE];
     const int32_t tile_y = (int32_t)(blockIdx.x / (uint32_t)tiles_x), tile_x = (int32_t)blockIdx.x - tile_y * tiles_x; // a 1-D grid of tiles, row-major
@@ -170,6 +184,7 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
         const int ly = k / PW, lx = k - ly * PW;
         const int32_t gx = x0 + lx, gy = y0 + ly;
         double c[3] = {0.0, 0.0, 0.0};
+        [[maybe_unused]] double e[3] = {0.0, 0.0, 0.0};
         bool valid = false;
         if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
             const size_t g = ((size_t)gy * (size_t)w + (size_t)gx) * 3u;
@@ -178,18 +193,24 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
                 c[ch] = mean[g + ch];
                 valid = valid && is_finite(c[ch]);
             }
+            if constexpr (Edges)
+                for (int ch = 0; ch < 3; ++ch) {
+                    e[ch] = edge_of(gd).edge_sum[g + ch];
+                    valid = valid && is_finite(e[ch]);
+                }
             if constexpr (Guided) {
                 double a[3];
                 for (int ch = 0; ch < 3; ++ch) {
-                    a[ch] = gd.albedo_sum[g + ch];
+                    a[ch] = albedo_of(gd).albedo_sum[g + ch];
                     valid = valid && is_finite(a[ch]);
                 }
                 if (valid)
-                    for (int ch = 0; ch < 3; ++ch) c[ch] = c[ch] / max_ab(a[ch], gd.albedo_floor);
+                    for (int ch = 0; ch < 3; ++ch) c[ch] = c[ch] / max_ab(a[ch], albedo_of(gd).albedo_floor);
             }
         }
         staged[T::P_R * PLANE + k] = c[0]; staged[T::P_G * PLANE + k] = c[1]; staged[T::P_B * PLANE + k] = c[2];
         staged[T::P_OK * PLANE + k] = valid ? 1.0 : 0.0;
+        if constexpr (Edges) { staged[T::P_ER * PLANE + k] = e[0]; staged[T::P_EG * PLANE + k] = e[1]; staged[T::P_EB * PLANE + k] = e[2]; }
     }
     __syncthreads();
     const int tx = (int)threadIdx.x & (DN_TW - 1), ty = (int)threadIdx.x / DN_TW;
@@ -200,12 +221,16 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
     double V = -1.0;
     if (staged[T::P_OK * PLANE + centre] != 0.0) {
         double cnt = 0.0, s1[3] = {0.0, 0.0, 0.0}, s2[3] = {0.0, 0.0, 0.0}, mu[3];
+        [[maybe_unused]] double e[3] = {0.0, 0.0, 0.0}; // the centre's guide
+        if constexpr (Edges) { e[0] = staged[T::P_ER * PLANE + centre]; e[1] = staged[T::P_EG * PLANE + centre]; e[2] = staged[T::P_EB * PLANE + centre]; }
 #pragma unroll
         for (int dy = -R; dy <= R; ++dy)
 #pragma unroll
             for (int dx = -R; dx <= R; ++dx) {
                 const int k = centre + dy * PW + dx;
                 if (staged[T::P_OK * PLANE + k] == 0.0) continue;
+                if constexpr (Edges)
+                    if (!T::member(staged, k, e, edge_of(gd).sigma_edge)) continue;
                 cnt = cnt + 1.0;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) s1[ch] = s1[ch] + staged[ch * PLANE + k];
@@ -222,6 +247,8 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
             for (int dx = -R; dx <= R; ++dx) {
                 const int k = centre + dy * PW + dx;
                 if (staged[T::P_OK * PLANE + k] == 0.0) continue;
+                if constexpr (Edges)
+                    if (!T::member(staged, k, e, edge_of(gd).sigma_edge)) continue;
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) {
                     const double t = staged[ch * PLANE + k] - mu[ch];
@@ -235,7 +262,12 @@ __global__ __launch_bounds__(DN_THREADS) void denoise_prepare_spatial_kernel(int
         V = max_ab(max_ab(v[0], v[1]), v[2]);
     }
     out[pixel] = make_double4(staged[T::P_R * PLANE + centre], staged[T::P_G * PLANE + centre], staged[T::P_B * PLANE + centre], V);
-    if constexpr (Guided) gd.region[pixel] = make_double4(gd.albedo_sum[pixel * 3u + 0u], gd.albedo_sum[pixel * 3u + 1u], gd.albedo_sum[pixel * 3u + 2u], 0.0);
+    if constexpr (Guided) {
+        const rtk::DenoiseGuide &ag = albedo_of(gd);
+        ag.region[pixel] = make_double4(ag.albedo_sum[pixel * 3u + 0u], ag.albedo_sum[pixel * 3u + 1u], ag.albedo_sum[pixel * 3u + 2u], 0.0);
+    }
+    if constexpr (Edges) // (the staged guide is the frame's entry itself, valid or not)
+        edge_of(gd).region[pixel] = make_double4(staged[T::P_ER * PLANE + centre], staged[T::P_EG * PLANE + centre], staged[T::P_EB * PLANE + centre], 0.0);
 }
 
 // (ar, ag, ab: the tap's first guide, the albedo means or — edges alone — the edge guide's means; er, eg, eb: the edge guide's means
@@ -454,16 +486,18 @@ void launch_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const 
                        stream, n_pixels, sum, sum_sq, spp, spp_map, gd, (double4 *)half);
 }
 
-template <int R, bool Guided>
-void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const GuideOf<guide_mode(Guided)> &gd, void *half, hipStream_t stream) {
+template <int R, int Mode>
+void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const GuideOf<Mode> &gd, void *half, hipStream_t stream) {
     const int32_t tiles_x = (w + DN_TW - 1) / DN_TW, tiles_y = (h + DN_TH - 1) / DN_TH;
-    hipLaunchKernelGGL((denoise_prepare_spatial_kernel<R, Guided>), dim3((unsigned)((int64_t)tiles_x * tiles_y)), dim3(DN_THREADS), 0, stream, w, h,
+    hipLaunchKernelGGL((denoise_prepare_spatial_kernel<R, Mode>), dim3((unsigned)((int64_t)tiles_x * tiles_y)), dim3(DN_THREADS), 0, stream, w, h,
                        tiles_x, mean, gd, (double4 *)half);
 }
 template <int R>
-void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const rtk::DenoiseGuide *guide, void *half, hipStream_t stream) {
-    if (guide) launch_prepare_spatial<R, true>(w, h, mean, *guide, half, stream);
-    else launch_prepare_spatial<R, false>(w, h, mean, NoGuide{}, half, stream);
+void launch_prepare_spatial(int32_t w, int32_t h, const double *mean, const rtk::DenoiseGuide *guide, const rtk::DenoiseEdge *edge, void *half, hipStream_t stream) {
+    if (guide && edge) launch_prepare_spatial<R, DN_BOTH>(w, h, mean, BothGuides{*guide, *edge}, half, stream);
+    else if (edge) launch_prepare_spatial<R, DN_EDGES>(w, h, mean, *edge, half, stream);
+    else if (guide) launch_prepare_spatial<R, DN_ALBEDO>(w, h, mean, *guide, half, stream);
+    else launch_prepare_spatial<R, DN_PLAIN>(w, h, mean, NoGuide{}, half, stream);
 }
 
 template <int Mode>
@@ -483,8 +517,10 @@ namespace rtk {
 
 void launch_denoise_prepare(int64_t n_pixels, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
                             bool means, void *half, hipStream_t stream, const DenoiseEdge *edge) {
-    if (means) { // (a uniform count: the means form has no map, and no edge guide)
-        if (guide) launch_prepare<DN_ALBEDO, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *guide, half, stream);
+    if (means) { // (a uniform count: the means form has no map)
+        if (guide && edge) launch_prepare<DN_BOTH, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, BothGuides{*guide, *edge}, half, stream);
+        else if (edge) launch_prepare<DN_EDGES, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *edge, half, stream);
+        else if (guide) launch_prepare<DN_ALBEDO, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, *guide, half, stream);
         else launch_prepare<DN_PLAIN, true>(n_pixels, n_views, sum, sum_sq, spp, nullptr, NoGuide{}, half, stream);
     } else if (guide && edge) launch_prepare<DN_BOTH, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, BothGuides{*guide, *edge}, half, stream);
     else if (edge) launch_prepare<DN_EDGES, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, *edge, half, stream);
@@ -492,10 +528,11 @@ void launch_denoise_prepare(int64_t n_pixels, int32_t n_views, const double *sum
     else launch_prepare<DN_PLAIN, false>(n_pixels, n_views, sum, sum_sq, spp, spp_map, NoGuide{}, half, stream);
 }
 
-void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream) {
-    if (radius == 1) launch_prepare_spatial<1>(w, h, mean, guide, half, stream);
-    else if (radius == 2) launch_prepare_spatial<2>(w, h, mean, guide, half, stream);
-    else launch_prepare_spatial<3>(w, h, mean, guide, half, stream); // (the caller has checked 1..3)
+void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream,
+                                    const DenoiseEdge *edge) {
+    if (radius == 1) launch_prepare_spatial<1>(w, h, mean, guide, edge, half, stream);
+    else if (radius == 2) launch_prepare_spatial<2>(w, h, mean, guide, edge, half, stream);
+    else launch_prepare_spatial<3>(w, h, mean, guide, edge, half, stream); // (the caller has checked 1..3)
 }
 
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,

@@ -225,20 +225,22 @@ struct DenoiseGuide {
     double albedo_floor, sigma_albedo;
     double4 *region;
 };
-// the edge guide (rt_denoise_guided_device; sums form, single frame): a frame that contributes one stop factor per tap and nothing
+// the edge guide (rt_denoise_guided_device and its means, spatial and views forms): a frame that contributes one stop factor per tap and nothing
 // else.  `edge` null: none.  Alone it takes the albedo guide's place in the workspace (the third region) and in the staged planes;
 // beside an albedo guide its region of one double4 (g_r, g_g, g_b, 0) per pixel is a fourth.
 struct DenoiseEdge {
-    const double *edge_sum; // 3 w h doubles: per-pixel sums of edge_spp samples of the guide frame (prepare reads them)
-    double edge_spp;        // their count, as the divisor it is
+    const double *edge_sum; // 3 w h doubles: per-pixel sums of edge_spp samples of the guide frame (prepare reads them); means form: their means
+    double edge_spp;        // their count, as the divisor it is (means form: not read)
     double sigma_edge;
     double4 *region;
 };
 void launch_denoise_prepare(int64_t n_pixels /* of one frame */, int32_t n_views, const double *sum, const double *sum_sq, int32_t spp, const int32_t *spp_map, const DenoiseGuide *guide,
-                            bool means, void *half, hipStream_t stream, const DenoiseEdge *edge = nullptr /* sums form only */);
+                            bool means, void *half, hipStream_t stream, const DenoiseEdge *edge = nullptr);
 // the spatial prepare (rt_denoise_mean_spatial_device below its threshold) in launch_denoise_prepare's place: `mean` and, guided,
-// guide->albedo_sum are frames of means; V0 is the spread of C0 over the (2 radius + 1)^2 window, radius 1..3
-void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream);
+// guide->albedo_sum are frames of means; V0 is the spread of C0 over the (2 radius + 1)^2 window, radius 1..3.  With `edge`
+// (edge->edge_sum: a frame of means as well) the window holds only the pixels the edge stop lets through from its centre
+void launch_denoise_prepare_spatial(int32_t w, int32_t h, int32_t radius, const double *mean, const DenoiseGuide *guide, void *half, hipStream_t stream,
+                                    const DenoiseEdge *edge = nullptr);
 void launch_denoise_atrous(int32_t w, int32_t h, int32_t n_views, int32_t stride, double sigma, double eps, const DenoiseGuide *guide, const void *half_in,
                            void *half_out, double *mean_out, uint8_t *rgba8, hipStream_t stream, const DenoiseEdge *edge = nullptr);
 // the tone-mapping stage (rt_tonemap.hip; rt_tonemap_device, rt_log_average_luminance_device).  launch_log_average runs every level of

@@ -17,10 +17,14 @@
 //   with a running albedo mean folded over the same samples), --live-denoise-spatial [N] [--denoise-spatial-radius R] (with
 //   --live-denoise[-albedo]: frames of fewer than N samples, default 2, take their variance from the spread of the neighbouring
 //   pixels over a (2R + 1)^2 window, so the first frame is filtered too: include/rt_amd.h "spatial variance"),
+//   --live-denoise-edges [--denoise-edges-sigma X] (implies --live-denoise, alone or with --live-denoise-albedo and
+//   --live-denoise-spatial: every frame's filter also stops at the edges of a surface-ID frame rendered once per session, and the
+//   spatial window keeps to its centre's surface: include/rt_amd.h "edge guide on every route"; not with --upsample),
 //   --orbit N (N views around the scene's look_at in one launch: OUTPUT_000.png .. OUTPUT_<N-1>.png, view k with seed + k).
 //   --orbit N --orbit-denoise [--denoise-iters K] [--denoise-sigma X] (the views' sums and sums of squares from one launch, filtered as
 //   one stack: include/rt_amd.h "views denoise"), --orbit-denoise-albedo [--denoise-albedo-sigma X] (the guided filter instead, its albedo
-//   frames from one views launch over the albedo scene).
+//   frames from one views launch over the albedo scene), --orbit-denoise-edges [--denoise-edges-sigma X] (alone, or beside either of
+//   the two: the stack's filter also stops at the edges of the views' surface-ID frames, rendered in one views launch).
 //   --tonemap clamp|reinhard|aces, --exposure EV, --auto-exposure [KEY], --tonemap-white W (the tone-mapping stage of include/rt_amd.h
 //   in the output stage's place, on every single-GPU route: the bytes of the PNG — each PNG of --orbit, each frame of --live — come
 //   from the route's sums or means exposed by 2^EV, or by KEY over the frame's log-average luminance, through the operator).
@@ -62,12 +66,17 @@ static void usage(const char *argv0) {
             "          [--live-denoise-spatial [N] [--denoise-spatial-radius R]]   (with --live-denoise or --live-denoise-albedo: frames of fewer than N\n"
             "                         samples, default 2, take their variance from the neighbouring pixels' spread, so the first frame is filtered too;\n"
             "                         R from 1 to 3, default 1: the window is (2R + 1) x (2R + 1) pixels)\n"
+            "          [--live-denoise-edges [--denoise-edges-sigma X]]   (implies --live-denoise, alone or with --live-denoise-albedo and\n"
+            "                         --live-denoise-spatial: the filter also stops where a first-hit surface-ID frame, rendered once per session,\n"
+            "                         changes, and the spatial window keeps to its centre's surface; not with --upsample)\n"
             "          [--orbit N]   (N from 1 to 1000, the file names' three digits; one GPU, one launch: N views, look_from turned about the axis through look_at along vup by\n"
             "                         360 k / N degrees, view k with seed + k, written to OUTPUT_000.png .. OUTPUT_<N-1>.png)\n"
             "          [--orbit-denoise [--denoise-iters K] [--denoise-sigma X]]   (with --orbit: every view through the à-trous filter, all views in\n"
             "                         one set of launches, from sums and sums of squares rendered in one launch)\n"
             "          [--orbit-denoise-albedo [--denoise-albedo-sigma X]]   (with --orbit, instead of --orbit-denoise: the albedo-guided filter, with\n"
             "                         first-hit albedo frames of the same views rendered in one launch)\n"
+            "          [--orbit-denoise-edges [--denoise-edges-sigma X]]   (with --orbit, alone or beside --orbit-denoise or --orbit-denoise-albedo:\n"
+            "                         the views' filter also stops where their first-hit surface-ID frames, rendered in one launch, change)\n"
             "          [--tonemap clamp|reinhard|aces] [--exposure EV] [--auto-exposure [KEY]] [--tonemap-white W]   (one GPU, any route but --progressive:\n"
             "                         the final bytes go through an exposure and a tone curve before the gamma; EV in stops, |EV| <= 64, default 0;\n"
             "                         KEY > 0, default 0.18: the exposure maps the frame's log-average luminance to KEY; W > 0: with --tonemap reinhard,\n"
@@ -142,6 +151,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--live-denoise") ro.live_denoise = true;
         else if (a == "--live-denoise-albedo") ro.live_denoise = ro.live_denoise_albedo = true;
+        else if (a == "--live-denoise-edges") ro.live_denoise = ro.live_denoise_edges = true;
         else if (a == "--live-denoise-spatial") {
             ro.live_denoise_spatial = 2; // N is optional: a following word that is a number is N
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') ro.live_denoise_spatial = atoi(argv[++i]);
@@ -157,6 +167,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--orbit-denoise") ro.orbit_denoise = true;
         else if (a == "--orbit-denoise-albedo") ro.orbit_denoise_albedo = true;
+        else if (a == "--orbit-denoise-edges") ro.orbit_denoise_edges = true;
         else if (a == "--tonemap") {
             const std::string op = need("--tonemap");
             tonemap_given = true;
@@ -232,6 +243,15 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--orbit-denoise and --orbit-denoise-albedo filter the views of --orbit: they need --orbit\n");
         return 2;
     }
+    if (ro.orbit_denoise_edges && ro.orbit == 0) {
+        fprintf(stderr, "--orbit-denoise-edges guides the filter of the views of --orbit: it needs --orbit\n");
+        return 2;
+    }
+    if (ro.live_denoise_edges && ro.upsample > 0) {
+        fprintf(stderr, "--live-denoise-edges takes its surface-ID frame at the size it filters: it cannot be combined with --upsample (the guide "
+                        "would have to be made at the low size)\n");
+        return 2;
+    }
     if (ro.orbit_denoise && ro.orbit_denoise_albedo) {
         fprintf(stderr, "--orbit-denoise and --orbit-denoise-albedo are two filters for the same views: give one of them\n");
         return 2;
@@ -253,11 +273,12 @@ int main(int argc, char **argv) {
                         "with --orbit: --orbit-denoise-albedo)\n");
         return 2;
     }
-    if (edges_knob_given && !ro.denoise_edges) {
-        fprintf(stderr, "--denoise-edges-sigma sets the filter of --denoise-edges: it needs --denoise-edges\n");
+    if (edges_knob_given && !ro.denoise_edges && !ro.live_denoise_edges && !ro.orbit_denoise_edges) {
+        fprintf(stderr, "--denoise-edges-sigma sets the filter of --denoise-edges: it needs --denoise-edges (with --live: --live-denoise-edges; "
+                        "with --orbit: --orbit-denoise-edges)\n");
         return 2;
     }
-    if (denoise_knob_given && !ro.denoise && !ro.live_denoise && !ro.orbit_denoise && !ro.orbit_denoise_albedo) {
+    if (denoise_knob_given && !ro.denoise && !ro.live_denoise && !ro.orbit_denoise && !ro.orbit_denoise_albedo && !ro.orbit_denoise_edges) {
         fprintf(stderr, "--denoise-iters and --denoise-sigma set the filter of --denoise: they need --denoise (with --live: --live-denoise; "
                         "with --orbit: --orbit-denoise)\n");
         return 2;

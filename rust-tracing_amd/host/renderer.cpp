@@ -399,10 +399,47 @@ std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, 
                        });
 }
 
+// the edge-guided filter's params from the options
+static rt_denoise_guided_params guided_params(const char *who, const RenderOptions &opt) {
+    rt_denoise_guided_params dp;
+    if (rt_denoise_guided_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
+    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
+    return dp;
+}
+
+std::vector<uint8_t> denoise_guided_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                         const double *d_albedo_mean, const double *d_edge_mean, const RenderOptions &opt) {
+    const rt_denoise_guided_params dp = guided_params("denoise_guided_mean", opt);
+    const bool spatial = opt.live_denoise_spatial > 0;
+    rt_denoise_spatial_params sp{};
+    if (spatial) sp = spatial_params("denoise_guided_mean", opt);
+    return run_denoise("denoise_guided_mean", opt, width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_mean != nullptr),
+                       [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
+                           return spatial ? rt_denoise_guided_mean_spatial_device(width, height, d_mean, d_m2, samples, d_albedo_mean, d_edge_mean, &sp, &dp,
+                                                                                  d_out, d_rgba8, d_work, nullptr)
+                                          : rt_denoise_guided_mean_device(width, height, d_mean, d_m2, samples, d_albedo_mean, d_edge_mean, &dp, d_out,
+                                                                          d_rgba8, d_work, nullptr);
+                       });
+}
+
+std::vector<uint8_t> denoise_guided_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                          const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
+                                          const RenderOptions &opt) {
+    const rt_denoise_guided_params dp = guided_params("denoise_guided_views", opt);
+    if (n_views < 1) throw std::runtime_error("denoise_guided_views: n_views must be at least 1");
+    return run_denoise("denoise_guided_views", opt, width, height, rt_denoise_guided_views_workspace_bytes(width, height, n_views, d_albedo_sum != nullptr),
+                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
+                           return rt_denoise_guided_views_device(width, height, n_views, d_sum, d_sum_sq, spp, d_albedo_sum, albedo_spp, d_edge_sum,
+                                                                 edge_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
+                       }, n_views);
+}
+
 // The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
 // every pixel with the render's seed under `cam` with a white background, into a new device frame of sums (the caller frees it).
-// `surface_ids` (opt.denoise_edges): the surface-ID scene under `cam` with a black background instead.
-static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo, bool surface_ids = false) {
+// `surface_ids` (opt.denoise_edges): the surface-ID scene under `cam` with a black background instead.  `means` (the live route's edge
+// guide): the frame of running means rt_render_mean_device gives over those samples, not their sums.
+static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, uint64_t seed, int32_t spp, void **d_albedo, bool surface_ids = false,
+                              bool means = false) {
     rt_scene *scene = nullptr;
     int rc = surface_ids ? rt_scene_create_surface_ids(&desc, 0, nullptr, &scene) : rt_scene_create_albedo(&desc, 0, nullptr, &scene);
     if (rc == RT_OK) rc = rt_device_malloc(0, (int64_t)cam.image_width * cam.image_height * 3 * (int64_t)sizeof(double), d_albedo);
@@ -412,7 +449,8 @@ static int render_albedo_sums(const rt_scene_desc &desc, const rt_camera &cam, u
         rt_render_params p{};
         p.seed = seed; p.sample_begin = 0; p.sample_end = spp; p.max_depth = cam.max_depth;
         p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
-        rc = rt_render_device(scene, &white, &p, static_cast<double *>(*d_albedo), nullptr);
+        rc = means ? rt_render_mean_device(scene, &white, &p, static_cast<double *>(*d_albedo), nullptr, nullptr)
+                   : rt_render_device(scene, &white, &p, static_cast<double *>(*d_albedo), nullptr);
         // (the scene is destroyed below while the render may still run: wait for the frame first)
         double probe = 0.0;
         if (rc == RT_OK) rc = rt_device_download(0, &probe, *d_albedo, (int64_t)sizeof probe, nullptr);
@@ -623,13 +661,16 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const int pass = opt.live_spp > 0 ? opt.live_spp : 1;
     // opt.live_denoise: the pass keeps M2 beside the mean, and the frame shown is the filter's, written to d_shown and its bytes to
     // d_rgba8: the running frames (d_mean, d_m2, and the guided filter's running albedo mean d_alb) are the filter's inputs only
-    const bool denoised = opt.live_denoise || opt.live_denoise_albedo, guided = opt.live_denoise_albedo;
+    // opt.live_denoise_edges: the surface-ID scene's frame of means d_ids, rendered ONCE, before the first pass, is every pass's edge guide
+    const bool edges = opt.live_denoise_edges;
+    const bool denoised = opt.live_denoise || opt.live_denoise_albedo || edges, guided = opt.live_denoise_albedo;
+    if (edges && opt.upsample > 0) throw std::runtime_error("live_render: live_denoise_edges cannot be combined with upsample (the guide would have to be made at the low size)");
     const int32_t w = cam.image_width, h = cam.image_height;
     rt_scene *scene = nullptr, *albedo_scene = nullptr;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_m2 = nullptr, *d_alb = nullptr, *d_shown = nullptr, *d_work = nullptr;
-    void *d_up_alb = nullptr, *d_up_ids = nullptr, *d_full = nullptr, *d_up_work = nullptr;
+    void *d_up_alb = nullptr, *d_up_ids = nullptr, *d_full = nullptr, *d_up_work = nullptr, *d_ids = nullptr;
     auto cleanup = [&]() {
-        rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
+        rt_device_free(0, d_ids); rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
         rt_device_free(0, d_work); rt_device_free(0, d_up_alb); rt_device_free(0, d_up_ids); rt_device_free(0, d_full); rt_device_free(0, d_up_work);
         rt_scene_destroy(scene); rt_scene_destroy(albedo_scene);
     };
@@ -650,6 +691,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         if (opt.upsample_edges) check(render_albedo_sums(desc, full, opt.seed, guide_spp, &d_up_ids, true));
     }
     rt_denoise_albedo_params dp{};
+    rt_denoise_guided_params gp{};
     rt_denoise_spatial_params sp{};
     const bool spatial = opt.live_denoise_spatial > 0; // every pass through the spatial entry points: the first one is filtered too
     rt_camera white = cam;
@@ -658,8 +700,9 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         try {
             dp = filter_params("live_render", opt);
             if (spatial) sp = spatial_params("live_render", opt);
+            if (edges) gp = guided_params("live_render", opt);
         } catch (...) { cleanup(); throw; }
-        const int64_t work = guided ? rt_denoise_albedo_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
+        const int64_t work = edges ? rt_denoise_guided_workspace_bytes(w, h, guided) : guided ? rt_denoise_albedo_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
         if (work < 0) { cleanup(); throw std::runtime_error("live_render: no denoise workspace for a frame of this size"); }
         check(rt_device_malloc(0, frame_bytes, &d_m2));
         check(rt_device_malloc(0, frame_bytes, &d_shown));
@@ -668,6 +711,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
             check(rt_scene_create_albedo(&desc, 0, nullptr, &albedo_scene));
             check(rt_device_malloc(0, frame_bytes, &d_alb));
         }
+        if (edges) check(render_albedo_sums(desc, cam, opt.seed, guide_spp, &d_ids, true, true));
     }
     const rt_denoise_params plain = plain_params(dp);
     // with the tone-mapping stage on, the pass and the filters write no bytes (a null d_rgba8): the stage makes the frame shown from
@@ -683,8 +727,15 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
             check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), d_bytes, nullptr));
         } else {
             check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
-            if (guided) {
-                check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
+            if (guided) check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
+            if (edges) { // (d_alb is null without the albedo guide: the plain filter with the edge guide)
+                check(spatial ? rt_denoise_guided_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
+                                                                      static_cast<const double *>(d_alb), static_cast<const double *>(d_ids), &sp, &gp,
+                                                                      static_cast<double *>(d_shown), d_bytes, d_work, nullptr)
+                              : rt_denoise_guided_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
+                                                              static_cast<const double *>(d_alb), static_cast<const double *>(d_ids), &gp,
+                                                              static_cast<double *>(d_shown), d_bytes, d_work, nullptr));
+            } else if (guided) {
                 check(spatial ? rt_denoise_albedo_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
                                                                       static_cast<const double *>(d_alb), &sp, &dp, static_cast<double *>(d_shown),
                                                                       d_bytes, d_work, nullptr)
@@ -718,7 +769,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     return frame;
 }
 
-// An orbit on device 0 that ends in the denoiser (opt.orbit_denoise, opt.orbit_denoise_albedo): every view's sums and sums of squares
+// An orbit on device 0 that ends in the denoiser (opt.orbit_denoise, opt.orbit_denoise_albedo, opt.orbit_denoise_edges): every view's sums and sums of squares
 // from one rt_render_views_moments_device call stay on the device and are filtered there as one stack (rt_denoise_views_device); the
 // guided form takes its albedo frames from one rt_render_views_device over the albedo scene, under the views' cameras with a white
 // background and their seeds.  Returns the views' RGB bytes, one frame behind the other.
@@ -727,9 +778,12 @@ static std::vector<uint8_t> render_orbit_denoised_rgb8(const rt_scene_desc &desc
     const rt_camera &cam = views[0].camera;
     const int32_t n = (int32_t)views.size();
     const int64_t bytes = (int64_t)n * cam.image_width * cam.image_height * 3 * (int64_t)sizeof(double);
-    rt_scene *scene = nullptr, *albedo = nullptr;
-    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr; // (d_alb: only with opt.orbit_denoise_albedo)
-    auto cleanup = [&]() { rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_scene_destroy(scene); rt_scene_destroy(albedo); };
+    rt_scene *scene = nullptr, *albedo = nullptr, *ids = nullptr;
+    void *d_sum = nullptr, *d_sq = nullptr, *d_alb = nullptr, *d_ids = nullptr; // (d_alb: only with opt.orbit_denoise_albedo; d_ids: with opt.orbit_denoise_edges)
+    auto cleanup = [&]() {
+        rt_device_free(0, d_sum); rt_device_free(0, d_sq); rt_device_free(0, d_alb); rt_device_free(0, d_ids);
+        rt_scene_destroy(scene); rt_scene_destroy(albedo); rt_scene_destroy(ids);
+    };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, bytes, &d_sum));
@@ -742,9 +796,20 @@ static std::vector<uint8_t> render_orbit_denoised_rgb8(const rt_scene_desc &desc
         check(rt_device_malloc(0, bytes, &d_alb));
         check(rt_render_views_device(albedo, white.data(), n, &p, static_cast<double *>(d_alb), nullptr));
     }
+    if (opt.orbit_denoise_edges) { // every view's edge guide from one launch over the surface-ID scene, black-background cameras
+        std::vector<rt_view> black(views);
+        for (rt_view &v : black) v.camera.background = rt_vec3{0.0, 0.0, 0.0};
+        check(rt_scene_create_surface_ids(&desc, 0, nullptr, &ids));
+        check(rt_device_malloc(0, bytes, &d_ids));
+        check(rt_render_views_device(ids, black.data(), n, &p, static_cast<double *>(d_ids), nullptr));
+    }
     std::vector<uint8_t> px;
     try { // (the filter's download waits for everything enqueued before it: the scenes are destroyed after it)
-        px = opt.orbit_denoise_albedo
+        px = opt.orbit_denoise_edges
+                 ? denoise_guided_views(cam.image_width, cam.image_height, n, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
+                                        cam.samples_per_pixel, static_cast<const double *>(d_alb), cam.samples_per_pixel,
+                                        static_cast<const double *>(d_ids), cam.samples_per_pixel, opt)
+             : opt.orbit_denoise_albedo
                  ? denoise_albedo_views(cam.image_width, cam.image_height, n, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
                                         cam.samples_per_pixel, static_cast<const double *>(d_alb), cam.samples_per_pixel, opt)
                  : denoise_views(cam.image_width, cam.image_height, n, static_cast<const double *>(d_sum), static_cast<const double *>(d_sq),
@@ -774,7 +839,7 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
     rt_render_params p{};
     p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
     p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
-    if (opt.orbit_denoise || opt.orbit_denoise_albedo) {
+    if (opt.orbit_denoise || opt.orbit_denoise_albedo || opt.orbit_denoise_edges) {
         const std::vector<uint8_t> px = render_orbit_denoised_rgb8(desc, views, p, opt);
         if (!opt.quiet) printf("Render time: %.2fs (%d views, denoised)\n", std::chrono::duration<double>(clock::now() - now).count(), opt.orbit);
         now = clock::now();

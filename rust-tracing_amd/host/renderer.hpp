@@ -40,6 +40,10 @@ struct RenderOptions {
     // frames come from ONE rt_render_views_device over the albedo scene, under the views' cameras with background (1, 1, 1) and their
     // seeds, over the same sample range.
     bool orbit_denoise_albedo = false;
+    // with `orbit`: an edge guide for the stack's filter (rt_denoise_guided_views_device, denoise_edges_sigma), alone — the plain filter
+    // with the edge stop — or beside orbit_denoise / orbit_denoise_albedo.  The guide frames are one rt_render_views_device call over
+    // the surface-ID scene, under the views' cameras with a black background and their seeds.
+    bool orbit_denoise_edges = false;
     // the variance-guided à-trous denoiser (include/rt_amd.h "denoise") over the frame before it is written: a plain render then
     // goes through rt_render_moments_device, an adaptive one hands over its sums, sums of squares and spp map.  One GPU, single pass.
     bool denoise = false;
@@ -68,6 +72,12 @@ struct RenderOptions {
     // spatial_below = this (include/rt_amd.h "spatial variance"): frames of fewer samples take their variance from the spread of the
     // neighbouring pixels, so the first pass is shown filtered too.  0: off, the means forms as they are.
     int live_denoise_spatial = 0;
+    // live_render: an edge guide for every displayed frame's filter (include/rt_amd.h "edge guide on every route"), alone or beside
+    // live_denoise_albedo and live_denoise_spatial; it turns the filter on.  The surface-ID scene is rendered ONCE per session, before
+    // the first pass, as a frame of means (rt_render_mean_device over min(spp - 1, 16) samples under the camera with a black background
+    // and the session's seed), and every pass goes through rt_denoise_guided_mean_device or, with live_denoise_spatial,
+    // rt_denoise_guided_mean_spatial_device; denoise_edges_sigma is the filter's sigma_edge.  Not with `upsample` (live_render throws).
+    bool live_denoise_edges = false;
     int denoise_spatial_radius = 1; // its window_radius, 1..3
     // the tone-mapping stage (include/rt_amd.h "tone mapping") in the output stage's place, on every single-GPU route: the final bytes
     // come from rt_tonemap_device — a plain render's and an unfiltered orbit's from its host mirror rth_tonemap, the same bytes — on the
@@ -130,6 +140,14 @@ std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d
 std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                          const double *d_albedo_mean, const RenderOptions &opt = {});
 
+// rt_denoise_guided_mean_device likewise — with opt.live_denoise_spatial > 0, rt_denoise_guided_mean_spatial_device and its params as
+// below —: d_edge_mean is a DEVICE frame of 3 * w * h doubles, the means of the edge guide; d_albedo_mean may be null (no albedo guide).
+std::vector<uint8_t> denoise_guided_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
+                                         const double *d_albedo_mean, const double *d_edge_mean, const RenderOptions &opt);
+// rt_denoise_guided_views_device likewise, over a stack of n_views frames, view-major in every DEVICE buffer; d_albedo_sum may be null.
+std::vector<uint8_t> denoise_guided_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
+                                          const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
+                                          const RenderOptions &opt);
 // rt_denoise_mean_spatial_device and rt_denoise_albedo_mean_spatial_device likewise, with spatial_below = opt.live_denoise_spatial (0:
 // the library's default) and window_radius = opt.denoise_spatial_radius; d_m2 may be null where samples < spatial_below.
 std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
