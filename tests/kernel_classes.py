@@ -53,6 +53,8 @@ SCENES = {
     "media": (_custom(lambda cam: custom_scenes.media_scene(cam, 0)), 4, None),
     "tie": (_custom(lambda cam: custom_scenes.tie_scene(cam, 2)), 4, None),
     "materials65535": (_custom(lambda cam: custom_scenes.many_materials_scene(cam, 65533, depth=MAX_DEPTH)), 4, None),
+    "textured_flat": (_custom(lambda cam: custom_scenes.textured_scene(cam, False)), 4, None),
+    "textured_frames": (_custom(lambda cam: custom_scenes.textured_scene(cam, True)), 4, None),
     "cornell": (_host(CAMERA_CASE), 4, 30),
     "cornell_smoke": (_host("cornell_smoke_64x64_16spp", width=32), 4, 30),
     "two_perlin_spheres": (_host("two_perlin_spheres_80x45_8spp", width=40), 4, 12),
@@ -138,10 +140,14 @@ CLASSES = {
     "textures-lds3-ref-two_perlin_spheres": ("two_perlin_spheres", REF, _k("spheres_quads_textures", 3, 0, 0, 0, 768)),
     "textures-lds3-ref-simple_light": ("simple_light", REF, _k("spheres_quads_textures", 3, 0, 0, 0, 768)),
     "textures-lds3-ref-earth": ("earth", REF, _k("spheres_quads_textures", 3, 0, 0, 0, 768)),
+    # (hand-made: images on quads, checkers of checkers, two Perlin tables, a textured light — custom_scenes.textured_scene)
+    "textures-lds3-own-wide1-textured_flat": ("textured_flat", OWN1, _k("spheres_quads_textures", 3, 1, 1, 1, 1024)),
+    "textures-lds3-ref-textured_flat": ("textured_flat", REF, _k("spheres_quads_textures", 3, 0, 0, 0, 768)),
     "all-lds3-own-media": ("media", OWN0, _k("all", 3, 1, 0, 1, 1024)),
     "all-lds3-ref-media": ("media", REF, _k("all", 3, 0, 0, 0, 1024)),
     "all-lds3-own-wide1-tie": ("tie", OWN1, _k("all", 3, 1, 1, 1, 1024)),
     "all-lds3-ref-tie": ("tie", REF, _k("all", 3, 0, 0, 0, 1024)),
+    "all-lds3-own-wide1-textured_frames": ("textured_frames", OWN1, _k("all", 3, 1, 1, 1, 1024)),  # (textures inside frames and media)
     "all-lds1-own-wide0": ("spheres1200", OWN0, _k("all", 1, 1, 0, 1, 1024)),
     "all-lds1-own-wide1": ("spheres1200", OWN1, _k("all", 1, 1, 1, 1, 1024)),
     "all-lds1-ref": ("spheres6000", REF, _k("all", 1, 0, 0, 0, 1024)),  # (a flat list is few records in the reference's order: they fit)

@@ -62,6 +62,26 @@ def test_sphere_hit(rt, oracle):
     assert not L.orc_kat_sphere_hit(C.byref(m), v(0, 0, 0), v(0, 0, -1), 1.0, 0.001, math.inf, out)
     assert L.orc_kat_sphere_hit(C.byref(m), v(0, 0, 0), v(0, 0, -1), 0.25, 0.001, math.inf, out)
     assert out[0] == pytest.approx(5 - math.sqrt(0.75))
+    # motion that is not vertical: along (-0.6, 0.2, 0.5), the closed-form first root for the moved centre (src/sphere.rs:53-83)
+    c0, vec, r = np.array([0.3, -1.4, 2.0]), np.array([-0.6, 0.2, 0.5]), 0.7
+    m = make_sphere(rt, tuple(c0), r, moving=tuple(c0 + vec))
+    assert tuple(m.center_vec.tuple()) == tuple((c0 + vec) - c0)
+    o, d = np.array([0.1, 0.2, 9.0]), np.array([0.02, -0.21, -1.0])
+    for time in (0.0, 0.25, 0.999):
+        centre = c0 + vec * time
+        oc = centre - o
+        a, h, cc = d @ d, d @ oc, oc @ oc - r * r
+        assert h * h - a * cc > 0
+        root = (h - math.sqrt(h * h - a * cc)) / a
+        assert L.orc_kat_sphere_hit(C.byref(m), v(*o), v(*d), time, 0.001, math.inf, out), time
+        assert out[0] == pytest.approx(root, rel=1e-13)
+        p = o + root * d
+        assert tuple(out[1:4]) == pytest.approx(tuple(p), rel=1e-13) and tuple(out[4:7]) == pytest.approx(tuple((p - centre) / r), rel=1e-11, abs=1e-13)
+        n = (p - centre) / r
+        assert out[7] == pytest.approx((math.atan2(-n[2], n[0]) + math.pi) / (2 * math.pi), rel=1e-12)   # UV from the MOVED centre
+        assert out[8] == pytest.approx(math.acos(-n[1]) / math.pi, rel=1e-12)
+    # at time 0.999 the still sphere would be hit elsewhere: the three roots differ
+    assert len({round((c0 + vec * t - o) @ d, 9) for t in (0.0, 0.25, 0.999)}) == 3
 
 
 def test_quad_hit(rt, oracle):
@@ -80,6 +100,21 @@ def test_quad_hit(rt, oracle):
     assert not L.orc_kat_quad_hit(C.byref(q), v(0, 0, 0), v(0, 0, -1), 0.001, 2.9999, out)
     # |denom| < 1e-8: parallel rays never hit (src/quad.rs:110)
     assert not L.orc_kat_quad_hit(C.byref(q), v(0, 0, 0), v(1, 0, -1e-9), 0.001, math.inf, out)
+    # a skewed parallelogram (u not perpendicular to v, so w = n / (n . n) matters): (alpha, beta) solve p - Q = alpha u + beta v
+    Q, U, V = np.array([0.2, 0.3, -2.5]), np.array([2.2, 0.5, 0.3]), np.array([0.8, 1.8, -0.4])
+    assert abs(U @ V) > 0.5
+    sk = make_quad(rt, Q, U, V)
+    rng = np.random.default_rng(6)
+    for alpha, beta in [(0.5, 0.5), (0.05, 0.9), (0.9, 0.05), (0.999, 0.999), (0.001, 0.998)] + [tuple(x) for x in rng.uniform(0.01, 0.99, (20, 2))]:
+        target = Q + alpha * U + beta * V
+        origin = np.array([0.3, -0.4, 9.0]) + rng.uniform(-1, 1, 3)
+        assert L.orc_kat_quad_hit(C.byref(sk), v(*origin), v(*(target - origin)), 0.001, math.inf, out)
+        p = np.array(out[1:4])
+        (a, b), *_ = np.linalg.lstsq(np.stack([U, V], axis=1), p - Q, rcond=None)
+        assert out[0] == pytest.approx(1.0, rel=1e-13)
+        assert out[7] == pytest.approx(a, rel=1e-13, abs=1e-15) and out[8] == pytest.approx(b, rel=1e-13, abs=1e-15), (alpha, beta)
+        assert out[7] == pytest.approx(alpha, abs=1e-13) and out[8] == pytest.approx(beta, abs=1e-13)
+    assert not L.orc_kat_quad_hit(C.byref(sk), v(0.3, -0.4, 9.0), v(*(Q + 1.01 * U + 0.5 * V - np.array([0.3, -0.4, 9.0]))), 0.001, math.inf, out)
 
 
 def test_aabb_hit_modes(rt, oracle):
@@ -148,32 +183,55 @@ def perlin_tables(rt, seed=3):
     return p
 
 
+def numpy_noise(p, pt):
+    """independent restatement of src/perlin.rs:27-50,:81-100"""
+    i, j, k = (math.floor(c) for c in pt)
+    u, vv, w = pt[0] - i, pt[1] - j, pt[2] - k
+    uu, vw, ww = (t * t * (3 - 2 * t) for t in (u, vv, w))
+    acc = 0.0
+    for di in range(2):
+        for dj in range(2):
+            for dk in range(2):
+                g = p.ranvec[p.perm_x[(i + di) & 255] ^ p.perm_y[(j + dj) & 255] ^ p.perm_z[(k + dk) & 255]]
+                acc += ((di * uu + (1 - di) * (1 - uu)) * (dj * vw + (1 - dj) * (1 - vw)) * (dk * ww + (1 - dk) * (1 - ww))
+                        * (g.x * (u - di) + g.y * (vv - dj) + g.z * (w - dk)))
+    return acc
+
+
+def check_noise_and_turbulence(L, p, points):
+    for pt in points:
+        assert L.orc_kat_perlin_noise(C.byref(p), v(*pt)) == pytest.approx(numpy_noise(p, pt), rel=1e-13, abs=1e-15)
+        t = 0.0; wgt = 1.0; q = np.array(pt)
+        for _ in range(7):
+            t += wgt * numpy_noise(p, q); wgt *= 0.5; q = q * 2
+        assert L.orc_kat_perlin_turbulence(C.byref(p), v(*pt), 7) == pytest.approx(abs(t), rel=1e-12, abs=1e-15)
+
+
 def test_perlin(rt, oracle):
     L = oracle.lib()
     p = perlin_tables(rt)
     # gradient noise vanishes on the integer lattice (every weight vector there is zero or has zero weight)
     for q in [(0, 0, 0), (3, -2, 7), (-255, 256, 1000)]:
         assert L.orc_kat_perlin_noise(C.byref(p), v(*q)) == 0.0
-    # independent restatement of src/perlin.rs:27-50,:81-100 in numpy
-    def noise(pt):
-        i, j, k = (math.floor(c) for c in pt)
-        u, vv, w = pt[0] - i, pt[1] - j, pt[2] - k
-        uu, vw, ww = (t * t * (3 - 2 * t) for t in (u, vv, w))
-        acc = 0.0
-        for di in range(2):
-            for dj in range(2):
-                for dk in range(2):
-                    g = p.ranvec[p.perm_x[(i + di) & 255] ^ p.perm_y[(j + dj) & 255] ^ p.perm_z[(k + dk) & 255]]
-                    acc += ((di * uu + (1 - di) * (1 - uu)) * (dj * vw + (1 - dj) * (1 - vw)) * (dk * ww + (1 - dk) * (1 - ww))
-                            * (g.x * (u - di) + g.y * (vv - dj) + g.z * (w - dk)))
-        return acc
     rng = np.random.default_rng(4)
-    for pt in rng.uniform(-300, 300, (200, 3)):
-        assert L.orc_kat_perlin_noise(C.byref(p), v(*pt)) == pytest.approx(noise(pt), rel=1e-13, abs=1e-15)
-        t = 0.0; wgt = 1.0; q = np.array(pt)
-        for _ in range(7):
-            t += wgt * noise(q); wgt *= 0.5; q = q * 2
-        assert L.orc_kat_perlin_turbulence(C.byref(p), v(*pt), 7) == pytest.approx(abs(t), rel=1e-12, abs=1e-15)
+    check_noise_and_turbulence(L, p, rng.uniform(-300, 300, (200, 3)))
+
+
+def test_perlin_table_b(rt, oracle):
+    """The second table of the hand-made textured scenes (custom_scenes.perlin_table_b: vectors that are not normalised), where the
+    scenes put it: negative coordinates (`& 255` of a negative lattice index) and large ones (+-300: seven octaves reach +-19 200)."""
+    import custom_scenes
+    L = oracle.lib()
+    p = custom_scenes.perlin_table_b()
+    lengths = np.array([math.sqrt(g.x * g.x + g.y * g.y + g.z * g.z) for g in p.ranvec])
+    assert lengths.min() < 0.5 and lengths.max() > 1.2  # (not the reference's unit vectors)
+    assert all(sorted(getattr(p, name)) == list(range(256)) for name in ("perm_x", "perm_y", "perm_z"))
+    rng = np.random.default_rng(5)
+    points = np.concatenate([rng.uniform(-300, 300, (60, 3)), rng.uniform(-4, 0, (30, 3)), rng.uniform(295, 300, (10, 3)) * rng.choice([-1.0, 1.0], (10, 3)),
+                             np.array([[-0.25, -255.5, 256.75], [-300.0 + 1e-9, 300.0 - 1e-9, -1e-9]])])
+    check_noise_and_turbulence(L, p, points)
+    for q in [(-1, -256, 255), (-300, 300, 0)]:
+        assert L.orc_kat_perlin_noise(C.byref(p), v(*q)) == 0.0
 
 
 def test_textures(rt, oracle):
@@ -199,6 +257,42 @@ def test_textures(rt, oracle):
         L.orc_kat_texture_value(C.byref(de), img, u, vv, v(0, 0, 0), out)
         want = tuple((float(c) / 255.0) ** 2.2 for c in px[j, i])
         assert tuple(out) == pytest.approx(want, rel=1e-15), (u, vv)
+    # the hand-made scenes' textures (custom_scenes.CustomScene): a checker of checkers picks the grandchild by each level's own
+    # inv_scale; images one texel wide or high
+    import custom_scenes
+    s = custom_scenes.CustomScene(hs)
+    leaf = {name: s.solid(*c) for name, c in {"a": (1, 0, 0), "b": (0, 1, 0), "c": (0, 0, 1), "d": (1, 1, 0)}.items()}
+    colour = {"a": (1.0, 0.0, 0.0), "b": (0.0, 1.0, 0.0), "c": (0.0, 0.0, 1.0), "d": (1.0, 1.0, 0.0)}
+    scales = (1.0, 0.25, 0.4)
+    top = s.checker(scales[0], s.checker(scales[1], leaf["a"], leaf["b"]), s.checker(scales[2], leaf["c"], leaf["d"]))
+    sizes = [(1, 1), (1, 9), (17, 1)]
+    imgs = [s.image(s.add_image(custom_scenes.random_image(20 + k, w, h))) for k, (w, h) in enumerate(sizes)]
+    s.finish(s.sphere((0, 0, 0), 1.0, s.lambertian_tex(top)))
+    dn = s.desc
+    assert dn.textures[top].inv_scale == 1.0 and dn.textures[dn.textures[top].even].inv_scale == 4.0 and dn.textures[dn.textures[top].odd].inv_scale == 1.0 / 0.4
+
+    def even(scale, pt):  # src/texture.rs:59-69 with Python's integers
+        return sum(math.floor((1.0 / scale) * c) for c in pt) % 2 == 0
+
+    seen = set()
+    for pt in [(0.1, 0.1, 0.1), (0.3, 0.1, 0.1), (1.1, 0.1, 0.1), (1.5, 0.1, 0.1), (-0.1, 0.1, 0.1), (-0.3, 0.1, 0.1), (-0.1, -0.1, -0.1), (-0.45, -1.3, 2.7),
+               (-1.1, -0.3, 0.1), (-1.5, -0.3, 0.1), (2.05, -3.45, -0.9), (-2.2, 0.61, -0.81)]:
+        name = ("a" if even(scales[1], pt) else "b") if even(scales[0], pt) else ("c" if even(scales[2], pt) else "d")
+        L.orc_kat_texture_value(C.byref(dn), top, 0.0, 0.0, v(*pt), out)
+        assert tuple(out) == colour[name], (pt, name)
+        seen.add(name)
+    assert seen == set("abcd")
+    for t, (w, h) in zip(imgs, sizes):
+        px = s.images[dn.textures[t].image]
+        assert px.shape == (h, w, 3)
+        for u in (0.0, 1.0, 0.5, -3.0, 7.0):
+            for vv in (0.0, 1.0, 0.5, -3.0, 7.0):
+                cu, cv = min(max(u, 0.0), 1.0), 1.0 - min(max(vv, 0.0), 1.0)
+                i, j = int(cu * (w - 1)), int(cv * (h - 1))
+                assert (i == 0 or w > 1) and (j == 0 or h > 1)  # where a side is 1, every u (or v) names texel 0
+                L.orc_kat_texture_value(C.byref(dn), t, u, vv, v(0.3, -0.2, 0.1), out)
+                assert tuple(out) == pytest.approx(tuple((float(c) / 255.0) ** 2.2 for c in px[j, i]), rel=1e-15), (w, h, u, vv)
+        assert {int(0.5 * (w - 1)), int(1.0 * (w - 1))} == ({0} if w == 1 else {(w - 1) // 2, w - 1})
 
 
 def test_furnace(rt, oracle):

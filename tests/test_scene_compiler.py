@@ -76,6 +76,107 @@ def test_refit_only_shrinks_boxes_and_fixes_the_origin_spanning_cubes(rt):
     assert shrunk > 400
 
 
+def _motion_boxes(desc):
+    """per sphere of the description: the box of the sphere at times 0, 0.5 and 1 — from the description alone"""
+    out = []
+    for i in range(desc.n_spheres):
+        s = desc.spheres[i]
+        c, vec, r = np.array(s.center.tuple()), np.array(s.center_vec.tuple()), abs(s.radius)
+        at = [c + vec * t for t in ((0.0, 0.5, 1.0) if s.is_moving else (0.0,))]
+        out.append((np.min([p - r for p in at], axis=0), np.max([p + r for p in at], axis=0)))
+    return out
+
+
+def _described(desc, centre, radius, vec, moving):
+    """the description's spheres with exactly this geometry (coincident copies: more than one)"""
+    return [i for i in range(desc.n_spheres) if desc.spheres[i].center.tuple() == tuple(centre) and desc.spheres[i].radius == radius and
+            bool(desc.spheres[i].is_moving) == bool(moving) and (not moving or desc.spheres[i].center_vec.tuple() == tuple(vec))]
+
+
+@pytest.mark.parametrize("n, frames", [(40, True), (3, False)])
+def test_every_box_above_a_moving_sphere_holds_the_whole_motion(rt, n, frames):
+    """custom_scenes.moving_scene: spheres that move along both directions of every axis and along the eight diagonals, by 1e-3 to 3
+    radii, in the world, inside a frame and as media boundaries.  The box of a moving sphere is worked out HERE, from the description
+    (times 0, 0.5 and 1); every record that holds the sphere, and every record above it, must contain it — in the threaded records, in
+    the library's own trees of two children (leaf_max 1, 2, 4, 8) and of four (1, 3, 8).  (A flat list has no boxes of the
+    reference's to intersect with: the threaded records of this scene carry the primitives' bound, not a box.)"""
+    import custom_scenes
+    import kernel_classes
+    import test_ordered_layout as tol
+    scene = custom_scenes.moving_scene(kernel_classes._Aimed(kernel_classes.aimed_camera(rt, kernel_classes.LOOK_FROM[0])), n=n, frames=frames)
+    d = scene.desc
+    boxes = _motion_boxes(d)
+    n_moving = sum(d.spheres[i].is_moving for i in range(d.n_spheres))
+    assert n_moving >= (n * 8) // 9 + 5 + (2 if frames else 0)
+    moved = {tuple(np.sign(np.round(np.array(d.spheres[i].center_vec.tuple()), 9)).astype(int)) for i in range(d.n_spheres) if d.spheres[i].is_moving}
+    assert n < 14 or len(moved) >= 14, "both directions of every axis and the eight diagonals"
+
+    # the threaded records: the spheres are emitted in scan order, which is the order moving_scene makes them in
+    nodes = list(rt.debug_compiled_nodes(scene, True))
+    leaves = [nd for nd in nodes if nd.kind in (NK_SPHERES, NK_MEDIUM_SPHERE)]
+    assert sum(nd.b if nd.kind == NK_SPHERES else 1 for nd in leaves) == d.n_spheres
+    for nd in sorted(leaves, key=lambda nd: nd.a if nd.kind == NK_SPHERES else -1):
+        if nd.kind != NK_SPHERES:
+            continue
+        lo = np.min([boxes[i][0] for i in range(nd.a, nd.a + nd.b)], axis=0); hi = np.max([boxes[i][1] for i in range(nd.a, nd.a + nd.b)], axis=0)
+        assert (np.array(nd.prim_lo) <= lo).all() and (np.array(nd.prim_hi) >= hi).all(), (nd.a, nd.b)
+        assert np.allclose(nd.prim_lo, lo, rtol=0, atol=1e-12) and np.allclose(nd.prim_hi, hi, rtol=0, atol=1e-12), (nd.a, nd.b)
+        if not nd.no_bbox:
+            assert (np.array(nd.lo) <= lo).all() and (np.array(nd.hi) >= hi).all(), (nd.a, nd.b)
+
+    def check_tree(lay, slots_of, what):
+        """slots_of(record) -> [(reference, f32 box (3, 2))]; returns the number of moving spheres met"""
+        to_desc = [_described(d, row[0:3], row[3], row[4:7], row[8]) for row in lay["spheres"]]
+        assert all(to_desc), (what, "a sphere of the layout is none of the description's: the motion was lost or changed")
+        seen = [0]
+
+        def under(record):
+            lo_all, hi_all = np.full(3, np.inf), np.full(3, -np.inf)
+            for ref, box in slots_of(record):
+                kind, count, index = ref >> 29, ((ref >> 26) & 7) + 1, ref & ((1 << 26) - 1)
+                if kind == tol.KIND_EMPTY:
+                    continue
+                if kind == tol.KIND_INNER:
+                    lo, hi = under(index)
+                elif kind == tol.KIND_INSTANCE:
+                    inst = lay["instances"][index]
+                    lo, hi = tol.to_parent(inst, *under(int(inst[7])))
+                elif kind == tol.KIND_SPHERES:
+                    held = [boxes[to_desc[index + i][0]] for i in range(count)]
+                    lo, hi = np.min([b[0] for b in held], axis=0), np.max([b[1] for b in held], axis=0)
+                    seen[0] += sum(bool(lay["spheres"][index + i, 8]) for i in range(count))
+                else:
+                    held = [tol.prim_bound(lay, kind, index + i) for i in range(count)]
+                    lo, hi = np.min([b[0] for b in held], axis=0), np.max([b[1] for b in held], axis=0)
+                assert (box[:, 0] <= lo).all() and (box[:, 1] >= hi).all(), (what, record, box, lo, hi)
+                lo_all, hi_all = np.minimum(lo_all, lo), np.maximum(hi_all, hi)
+            return lo_all, hi_all
+
+        for step in lay["steps"]:
+            kind, a, b = int(step[0]), int(step[1]), int(step[2])
+            box = tol.f32_box(step[4:10])
+            if kind == 1:  # a medium whose boundary is one sphere: the step's box is the sphere's
+                index = int(lay["media"][a])
+                lo, hi = boxes[to_desc[index][0]]
+                seen[0] += bool(lay["spheres"][index, 8])
+            else:
+                lo, hi = under(a if kind == 0 else b)
+            assert (box[:, 0] <= lo).all() and (box[:, 1] >= hi).all(), (what, "step", kind, box, lo, hi)
+        return seen[0]
+
+    for leaf_max in (1, 2, 4, 8):
+        lay = rt.debug_ordered_layout(scene, walk=rt.RT_WALK_OWN_TREES, wide=0, leaf_max=leaf_max)
+        assert lay["ordered"]
+        two = lambda record: [(int(lay["nodes"][record][12 + k]), tol.f32_box(lay["nodes"][record][6 * k:6 * k + 6])) for k in range(2)]
+        assert check_tree(lay, two, ("two children", leaf_max)) == n_moving
+    for leaf_max in (1, 3, 8):
+        opts = dict(walk=rt.RT_WALK_OWN_TREES, wide=1, leaf_max=leaf_max)
+        lay, rec = rt.debug_ordered_layout(scene, **opts), rt.debug_wide_records(scene, **opts)
+        assert lay["ordered"] and rec["wide"]
+        four = lambda record: [(int(rec["refs"][record][k]), rec["boxes"][record][k].astype(np.float64)) for k in range(4)]
+        assert check_tree(lay, four, ("four children", leaf_max)) == n_moving
+
+
 def test_sphere_bounded_media_become_one_record(rt):
     _, nodes = nodes_of(rt, 8, True)            # final_scene: both media are bounded by a Sphere (src/main.rs:565-587)
     assert sum(nd.kind == NK_MEDIUM_SPHERE for nd in nodes) == 2 and not any(nd.kind == NK_MEDIUM_ENTER for nd in nodes)

@@ -7,6 +7,8 @@ random_scene mixes quads, frames and media into nearly every graph, so its rende
 is one sphere — the only place the inline start test is compiled.  Every eighth seed therefore renders a ground graph as well
 (ground_graph below: spheres only, one big sphere under 1-90 small ones, the camera outside, inside or on it), with start_inline 1
 and 0.  The last line counts, per family, the renders that really ran the inline test (rt_debug_last_start, rt_debug_last_kernel).
+A third family, "textured": random_scene(..., textures=True) — the same graphs with checker, noise and image textures (on Lambertians,
+lights and media) and moving spheres, rendered from a camera turned towards them.
 Usage: python tools/fuzz_parity.py [first_seed] [count]"""
 import importlib, random, sys
 from pathlib import Path
@@ -55,7 +57,8 @@ def ground_graph(seed):
     return s.finish(s.list(items))
 
 
-bad, renders, inline_renders = 0, {"random": 0, "ground": 0}, {"random": 0, "ground": 0}
+bad, renders, inline_renders = 0, {"random": 0, "ground": 0, "textured": 0}, {"random": 0, "ground": 0, "textured": 0}
+aimed = _Aimed(rt.camera_look(cam, (0.0, 0.0, 9.0), (0.0, 0.0, 0.0)))
 
 
 def check(family, scene, seed, start_inline):
@@ -78,6 +81,7 @@ def check(family, scene, seed, start_inline):
 
 for seed in range(first, first + count):
     check("random", custom_scenes.random_scene(cam, seed), seed, (seed >> 5) % 2)
+    check("textured", custom_scenes.random_scene(aimed, seed, textures=True), seed, (seed >> 5) % 2)
     if seed % 8 == 3:
         ground = ground_graph(seed)
         for value in (1, 0):
