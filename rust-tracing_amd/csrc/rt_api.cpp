@@ -273,10 +273,10 @@ struct ViewTable {
     double *d_sum_sq = nullptr; // rt_render_views_moments_device: one frame of sums of squares per view beside the sums, or null
 };
 
-// Live refinement (rt_render_mean_device): the dense render with `d_out` a frame of running means.  Each launch's samples are folded
-// into it by mean_samples_kernel instead of being added by sum_samples_kernel; the last launch of the call also writes the display
+// Live refinement (rt_render_mean_device): the dense render with `d_out` a frame of running means.  Each launch's samples go into it
+// through the reduction's mean fold instead of its sum (rt_kernels.h Reduce); the last launch of the call also writes the display
 // frame.  Everything else — chunks, pipelining, scratch, grid — is the dense render's.  With `d_m2` (rt_render_mean_moments_device) the
-// reduction is mean_moments_samples_kernel, which keeps Welford's M2 in that frame beside the mean.
+// fold keeps Welford's M2 in that frame beside the mean.
 struct MeanOut {
     uint8_t *d_rgba8; // or null
     double *d_m2;     // or null
@@ -502,7 +502,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     if (mean) K.out_sq = mean->d_m2;
     if (views) {
         K.views = ws.views; K.tiles_per_view = (uint32_t)tiles_per_view; K.inv_tiles_per_view = 1.0 / (double)tiles_per_view;
-        K.out_sq = views->d_sum_sq; // (read by sum_view_moments_samples_kernel only)
+        K.out_sq = views->d_sum_sq; // (read by Reduce::ViewsMoments only)
     }
     K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = lds_image_bytes_for(scene, lds);
     K.lds_off_node_b = scene->lds_off_node_b;
@@ -546,9 +546,13 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     // (a lane keeps the instances it has yet to walk as one 32-bit mask of their indices)
     K.defer_instances = (scene->ordered && tn.defer != 0 && scene->insts.bytes / sizeof(Instance) <= 32u) ? 1u : 0u;
 
-    // Launch k renders samples [sb, sb + ns) into its scratch set's sample buffer; sum_samples_kernel then adds them onto `out`
-    // in sample order.  Pipelined: launch k runs on internal stream k % 2; its summation waits for launch k - 1's (the sums
+    // Launch k renders samples [sb, sb + ns) into its scratch set's sample buffer; the route's reduction kernel then folds them into
+    // `out` in sample order.  Pipelined: launch k runs on internal stream k % 2; its reduction waits for launch k - 1's (the folds
     // stay in order) while the render kernel of launch k + 1, on the other stream, takes the CUs that launch k's tail frees.
+    const Reduce reduce = mean    ? (mean->d_m2 ? Reduce::MeanMoments : Reduce::Mean)
+                          : views ? (views->d_sum_sq ? Reduce::ViewsMoments : Reduce::Views)
+                          : list  ? Reduce::Listed
+                                  : Reduce::Sum;
     if (pipelined) {
         HIP_TRY(hipEventRecord(ws.ev_start, stream));
         for (int h = 0; h < 2; ++h) HIP_TRY(hipStreamWaitEvent(ws.aux[h], ws.ev_start, 0));
@@ -587,14 +591,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         }
         HIP_TRY(hipGetLastError());
         if (pipelined && k > 0) HIP_TRY(hipStreamWaitEvent(s, ws.ev_sum[h ^ 1], 0));
-        if (mean) {
-            K.mean_rgba8 = sb + ns >= p.sample_end ? mean->d_rgba8 : nullptr; // (the call's last launch: the frame the caller shows)
-            if (mean->d_m2) launch_mean_moments_samples(K, sum_grid, s);
-            else launch_mean_samples(K, sum_grid, s);
-        } else if (views && views->d_sum_sq) launch_sum_view_moments_samples(K, sum_grid, s);
-        else if (views) launch_sum_view_samples(K, sum_grid, s);
-        else if (list) launch_sum_listed_samples(K, sum_grid, s);
-        else launch_sum_samples(K, sum_grid, s);
+        if (mean) K.mean_rgba8 = sb + ns >= p.sample_end ? mean->d_rgba8 : nullptr; // (the call's last launch: the frame the caller shows)
+        launch_reduce_samples(reduce, K, sum_grid, s);
         HIP_TRY(hipGetLastError());
         if (pipelined) HIP_TRY(hipEventRecord(ws.ev_sum[h], s));
     }

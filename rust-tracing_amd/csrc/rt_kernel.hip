@@ -1387,96 +1387,138 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
     }
 }
 
-// Per-pixel sum of the sample buffer in sample order (src/renderer.rs:35-40: `avg_color += new_color`).
-// One thread per (local tile, pixel of the tile); consecutive threads read consecutive 24-byte samples.
-__global__ void sum_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lt = idx >> 6, p64 = idx & 63u;
-    if (lt >= P.n_local_tiles) return;
-    const int32_t w = P.cam.image_width, h = P.cam.image_height;
-    const uint32_t k = lt * (uint32_t)P.shard_count + (uint32_t)P.shard_index;
-    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
-    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
-    const bool valid = i < w && j < h;
-    double *dst = nullptr;
-    if (P.out_layout == RT_OUT_TILES) dst = P.out + ((size_t)lt * 64u + p64) * 3u;
-    else if (valid) dst = P.out + ((size_t)j * (size_t)w + (size_t)i) * 3u;
-    if (!valid) {
-        if (dst) { dst[0] = 0.0; dst[1] = 0.0; dst[2] = 0.0; }
-        return;
-    }
-    V3 acc = v3(0.0, 0.0, 0.0);
-    if (P.accumulate) acc = v3(dst[0], dst[1], dst[2]);
-    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
-        acc = acc + v3(src[0], src[1], src[2]);
-        src += 64u * 3u;
-    }
-    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
-}
-
-// ---- live refinement (rt_render_mean_device) --------------------------------------------------------------------------------
 // The display bytes of one pixel's mean: color_to_rgb(avg) with alpha 0xff (src/renderer.rs:124-126) as one little-endian word, byte 0
-// red.  Per value this is resolve_rgb8_kernel's code at inv_spp = 1 (x * 1.0 is x); mean_samples_kernel and resolve_rgba8_kernel both
+// red.  Per value this is resolve_rgb8_kernel's code at inv_spp = 1 (x * 1.0 is x); the mean folds below and resolve_rgba8_kernel both
 // call it, so the fused frame and the stand-alone resolve cannot drift.
 __device__ __forceinline__ uint32_t display_rgba8(double r, double g, double b) {
     return (uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(r)) | ((uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(g)) << 8) |
            ((uint32_t)rtm::rt_quantise(rtm::rt_gamma_encode(b)) << 16) | 0xff000000u;
 }
 
-// Per-pixel running mean of the sample buffer in sample order (src/renderer.rs:114: `avg += (new - avg) / num_samples`), dense job
-// mode, RT_OUT_FRAME.  sum_samples_kernel's thread-to-pixel mapping and addressing.  Sample s of the render (absolute index: P.sample_begin
-// is the launch's first) has divisor s + 1: a subtraction, a correctly rounded division and an addition per channel, each rounded on its
-// own (no reciprocal, no contraction).  A launch that starts at sample 0 starts from +0.0 and does not read the frame; any other continues
-// the frame's value, so a call cut into several launches gives one launch's bits.  Padding pixels of edge tiles are not written.  With
-// P.mean_rgba8 set (the last launch of a call) the pixel's display bytes are written in the same pass.
-__global__ void mean_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lt = idx >> 6, p64 = idx & 63u;
-    if (lt >= P.n_local_tiles) return;
+// ---- the per-pixel reduction of the sample buffer ---------------------------------------------------------------------------
+// After every launch of path_kernel one of six kernels folds that launch's samples into the caller's frame: one thread per (sample row,
+// pixel of the row), a row being a local tile or a group of 64 list entries; consecutive threads read consecutive 24-byte samples, and
+// sample s of a row lies 64 * 3 doubles behind sample s - 1.  The six share reduce_samples below and differ in two compile-time policies:
+//   Where: which pixel a thread owns.  visit(P, idx, body) calls body(row, pixel) if thread idx has work: its sample row and the
+//          pixel's index in P.out (and P.out_sq), in pixels;
+//   Fold:  the accumulator — what it starts from and when, the step per sample, what it stores.
+// Every f64 operation is rounded on its own (no contraction, no reciprocal), so each form keeps the CPU oracle's bits.
+
+// Pixel p64 of tile k of the frame: its index in a frame-layout buffer, and whether the frame has it (edge tiles have padding pixels).
+__device__ __forceinline__ bool tile_pixel(const KParams &P, uint32_t k, uint32_t p64, size_t &pixel) {
     const int32_t w = P.cam.image_width, h = P.cam.image_height;
-    const int32_t i = (int32_t)(lt % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
-    const int32_t j = (int32_t)(lt / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
-    if (i >= w || j >= h) return;
-    const size_t pixel = (size_t)j * (size_t)w + (size_t)i;
-    double *dst = P.out + pixel * 3u;
-    V3 m = v3(0.0, 0.0, 0.0);
-    if (P.sample_begin != 0) m = v3(dst[0], dst[1], dst[2]);
-    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
-        const double n = (double)(P.sample_begin + (int32_t)s + 1);
-        m.x = m.x + (src[0] - m.x) / n;
-        m.y = m.y + (src[1] - m.y) / n;
-        m.z = m.z + (src[2] - m.z) / n;
-        src += 64u * 3u;
-    }
-    dst[0] = m.x; dst[1] = m.y; dst[2] = m.z;
-    if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
+    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
+    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
+    pixel = (size_t)j * (size_t)w + (size_t)i;
+    return i < w && j < h;
 }
 
-// mean_samples_kernel with Welford's second moment beside the mean (rt_render_mean_moments_device): its thread-to-pixel mapping and
-// addressing, its recurrence for m word for word — so P.out gets mean_samples_kernel's bits — and per channel M2 = M2 + d * (c - m'),
-// d = c - m the difference before the update and m' the mean after it: the product rounded, then added (no contraction).  d and c - m'
-// have one sign or are zero, so no term is negative.  M2 goes through P.out_sq and starts and continues as the mean does.
-__global__ void mean_moments_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lt = idx >> 6, p64 = idx & 63u;
-    if (lt >= P.n_local_tiles) return;
-    const int32_t w = P.cam.image_width, h = P.cam.image_height;
-    const int32_t i = (int32_t)(lt % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
-    const int32_t j = (int32_t)(lt / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
-    if (i >= w || j >= h) return;
-    const size_t pixel = (size_t)j * (size_t)w + (size_t)i;
-    double *dst = P.out + pixel * 3u, *dm2 = P.out_sq + pixel * 3u;
-    V3 m = v3(0.0, 0.0, 0.0), q = v3(0.0, 0.0, 0.0);
-    if (P.sample_begin != 0) {
-        m = v3(dst[0], dst[1], dst[2]);
-        q = v3(dm2[0], dm2[1], dm2[2]);
+// Dense jobs with shards and both layouts (rt_render[_device]): local tile lt is tile lt * shard_count + shard_index of the frame.
+// RT_OUT_TILES keeps the local tiles whole, so the padding pixels of its edge tiles are zeroed here; RT_OUT_FRAME does not write them.
+struct WhereShards {
+    template <class Body>
+    static __device__ __forceinline__ void visit(const KParams &P, uint32_t idx, Body body) {
+        const uint32_t lt = idx >> 6, p64 = idx & 63u;
+        if (lt >= P.n_local_tiles) return;
+        size_t pixel;
+        const bool valid = tile_pixel(P, lt * (uint32_t)P.shard_count + (uint32_t)P.shard_index, p64, pixel);
+        if (P.out_layout == RT_OUT_TILES) pixel = (size_t)lt * 64u + p64;
+        if (!valid) {
+            if (P.out_layout == RT_OUT_TILES) {
+                double *dst = P.out + pixel * 3u;
+                dst[0] = 0.0; dst[1] = 0.0; dst[2] = 0.0;
+            }
+            return;
+        }
+        body(lt, pixel);
     }
-    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
+};
+// Dense jobs, one shard, RT_OUT_FRAME (the live routes): local tile lt is tile lt.
+struct WhereFrame {
+    template <class Body>
+    static __device__ __forceinline__ void visit(const KParams &P, uint32_t idx, Body body) {
+        const uint32_t lt = idx >> 6;
+        if (lt >= P.n_local_tiles) return;
+        size_t pixel;
+        if (!tile_pixel(P, lt, idx & 63u, pixel)) return;
+        body(lt, pixel);
+    }
+};
+// Views mode: local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view, whose frame starts w * h pixels behind the
+// previous view's.  Nothing behind the last view is written.
+struct WhereViews {
+    template <class Body>
+    static __device__ __forceinline__ void visit(const KParams &P, uint32_t idx, Body body) {
+        const uint32_t lt = idx >> 6;
+        if (lt >= P.n_local_tiles) return;
+        const uint32_t view = lt / P.tiles_per_view;
+        size_t pixel;
+        if (!tile_pixel(P, lt - view * P.tiles_per_view, idx & 63u, pixel)) return;
+        body(lt, (size_t)view * ((size_t)P.cam.image_width * (size_t)P.cam.image_height) + pixel);
+    }
+};
+// List mode: one thread per list entry (group g, entry p of the group).  Pixels not in the list, padding entries and entries that
+// are no pixel of the frame are never written.
+struct WhereList {
+    template <class Body>
+    static __device__ __forceinline__ void visit(const KParams &P, uint32_t idx, Body body) {
+        const uint32_t g = idx >> 6;
+        if (g >= P.n_local_tiles || idx >= P.n_list) return;
+        const uint32_t e = P.pixel_list[idx];
+        if (e >= (uint32_t)P.cam.image_width * (uint32_t)P.cam.image_height) return;
+        body(g, (size_t)e);
+    }
+};
+
+// The sum in sample order (src/renderer.rs:35-40: `avg_color += new_color`) and, per SQ, the sum of squares beside it in P.out_sq:
+// sq = sq + c * c, the product rounded, then added.  Both start from +0.0 or, with P.accumulate, continue what the buffers hold.
+// SQ_IF_SET tests P.out_sq at run time (list mode, with and without squares); its sq is computed in registers either way.
+enum Squares { SQ_NONE, SQ_ALWAYS, SQ_IF_SET };
+template <Squares SQ>
+struct SumFold {
+    double *dst, *dsq;
+    V3 acc, sq;
+    __device__ __forceinline__ void load(const KParams &P, size_t pixel) {
+        dst = P.out + pixel * 3u;
+        dsq = SQ == SQ_NONE || (SQ == SQ_IF_SET && !P.out_sq) ? nullptr : P.out_sq + pixel * 3u;
+        acc = v3(0.0, 0.0, 0.0); sq = v3(0.0, 0.0, 0.0);
+        if (P.accumulate) {
+            acc = v3(dst[0], dst[1], dst[2]);
+            if (squares()) sq = v3(dsq[0], dsq[1], dsq[2]);
+        }
+    }
+    __device__ __forceinline__ bool squares() const { return SQ == SQ_ALWAYS || (SQ == SQ_IF_SET && dsq); }
+    __device__ __forceinline__ void step(const KParams &, uint32_t, const V3 &c) {
+        acc = acc + c;
+        sq = sq + c * c;
+    }
+    __device__ __forceinline__ void store(const KParams &, size_t) {
+        dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
+        if (squares()) { dsq[0] = sq.x; dsq[1] = sq.y; dsq[2] = sq.z; }
+    }
+};
+
+// The running mean in sample order (src/renderer.rs:114: `avg += (new - avg) / num_samples`).  Sample s of the launch has the absolute
+// index P.sample_begin + s and the divisor one more: a subtraction, a correctly rounded division and an addition per channel.  With M2,
+// Welford's second moment beside it in P.out_sq: M2 = M2 + d * (c - m'), d = c - m the difference before the update and m' the mean
+// after it; d and c - m' have one sign or are zero, so no term is negative.  A launch that starts at sample 0 starts from +0.0 and does
+// not read the frames; any other continues their values, so a call cut into several launches gives one launch's bits.  With P.mean_rgba8
+// set (the last launch of a call) the pixel's display bytes are written in the same pass.
+template <bool M2>
+struct MeanFold {
+    double *dst, *dm2;
+    V3 m, q;
+    __device__ __forceinline__ void load(const KParams &P, size_t pixel) {
+        dst = P.out + pixel * 3u;
+        dm2 = M2 ? P.out_sq + pixel * 3u : nullptr;
+        m = v3(0.0, 0.0, 0.0); q = v3(0.0, 0.0, 0.0);
+        if (P.sample_begin != 0) {
+            m = v3(dst[0], dst[1], dst[2]);
+            if (M2) q = v3(dm2[0], dm2[1], dm2[2]);
+        }
+    }
+    __device__ __forceinline__ void step(const KParams &P, uint32_t s, const V3 &c) {
         const double n = (double)(P.sample_begin + (int32_t)s + 1);
-        const V3 c = v3(src[0], src[1], src[2]);
         const V3 d = v3(c.x - m.x, c.y - m.y, c.z - m.z);
         m.x = m.x + d.x / n;
         m.y = m.y + d.y / n;
@@ -1484,92 +1526,36 @@ __global__ void mean_moments_samples_kernel(const KParams P) {
         q.x = q.x + d.x * (c.x - m.x);
         q.y = q.y + d.y * (c.y - m.y);
         q.z = q.z + d.z * (c.z - m.z);
-        src += 64u * 3u;
     }
-    dst[0] = m.x; dst[1] = m.y; dst[2] = m.z;
-    dm2[0] = q.x; dm2[1] = q.y; dm2[2] = q.z;
-    if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
+    __device__ __forceinline__ void store(const KParams &P, size_t pixel) {
+        dst[0] = m.x; dst[1] = m.y; dst[2] = m.z;
+        if (M2) { dm2[0] = q.x; dm2[1] = q.y; dm2[2] = q.z; }
+        if (P.mean_rgba8) ((uint32_t *)P.mean_rgba8)[pixel] = display_rgba8(m.x, m.y, m.z);
+    }
+};
+
+template <class Where, class Fold>
+__device__ __forceinline__ void reduce_samples(const KParams &P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    Where::visit(P, idx, [&](uint32_t row, size_t pixel) {
+        Fold f;
+        f.load(P, pixel);
+        const double *src = P.samples + ((size_t)row * P.n_samples * 64u + (idx & 63u)) * 3u;
+        for (uint32_t s = 0; s < P.n_samples; ++s) {
+            f.step(P, s, v3(src[0], src[1], src[2]));
+            src += 64u * 3u;
+        }
+        f.store(P, pixel);
+    });
 }
 
-// sum_samples_kernel for views mode: local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view, whose frame starts
-// 3 * w * h doubles behind the previous view's.  One thread per (local tile, pixel of the tile); padding pixels of edge tiles are not written.
-__global__ void sum_view_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lt = idx >> 6, p64 = idx & 63u;
-    if (lt >= P.n_local_tiles) return;
-    const int32_t w = P.cam.image_width, h = P.cam.image_height;
-    const uint32_t view = lt / P.tiles_per_view, k = lt - view * P.tiles_per_view;
-    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
-    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
-    if (i >= w || j >= h) return;
-    double *dst = P.out + (size_t)view * ((size_t)w * (size_t)h * 3u) + ((size_t)j * (size_t)w + (size_t)i) * 3u;
-    V3 acc = v3(0.0, 0.0, 0.0);
-    if (P.accumulate) acc = v3(dst[0], dst[1], dst[2]);
-    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
-        acc = acc + v3(src[0], src[1], src[2]);
-        src += 64u * 3u;
-    }
-    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
-}
-
-// sum_view_samples_kernel with the sums of squares beside the sums (rt_render_views_moments_device): its thread-to-pixel mapping and
-// addressing, its additions for the sum word for word — so P.out gets sum_view_samples_kernel's bits — and per channel sq = sq + c * c as
-// sum_listed_samples_kernel keeps it: the product rounded, then added (no contraction).  View v's squares go to P.out_sq at the offset
-// its sums have in P.out; both start from +0.0 or, with P.accumulate, continue.  A kernel of its own: sum_view_samples_kernel stays as it is.
-__global__ void sum_view_moments_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t lt = idx >> 6, p64 = idx & 63u;
-    if (lt >= P.n_local_tiles) return;
-    const int32_t w = P.cam.image_width, h = P.cam.image_height;
-    const uint32_t view = lt / P.tiles_per_view, k = lt - view * P.tiles_per_view;
-    const int32_t i = (int32_t)(k % (uint32_t)P.tiles_x) * RT_TILE_W + (int32_t)(p64 & 7u);
-    const int32_t j = (int32_t)(k / (uint32_t)P.tiles_x) * RT_TILE_H + (int32_t)(p64 >> 3);
-    if (i >= w || j >= h) return;
-    const size_t at = (size_t)view * ((size_t)w * (size_t)h * 3u) + ((size_t)j * (size_t)w + (size_t)i) * 3u;
-    double *dst = P.out + at, *dsq = P.out_sq + at;
-    V3 acc = v3(0.0, 0.0, 0.0), sq = v3(0.0, 0.0, 0.0);
-    if (P.accumulate) {
-        acc = v3(dst[0], dst[1], dst[2]);
-        sq = v3(dsq[0], dsq[1], dsq[2]);
-    }
-    const double *src = P.samples + ((size_t)lt * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
-        const V3 c = v3(src[0], src[1], src[2]);
-        acc = acc + c;
-        sq = sq + c * c;
-        src += 64u * 3u;
-    }
-    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
-    dsq[0] = sq.x; dsq[1] = sq.y; dsq[2] = sq.z;
-}
-
-// sum_samples_kernel for list mode: one thread per list entry (group g, entry p of the group); a listed pixel's samples are added in
-// sample order onto out[pixel] and, when out_sq is set, their squares (each product rounded, then added: no contraction) onto
-// out_sq[pixel].  Pixels not in the list, and padding entries, are never written.
-__global__ void sum_listed_samples_kernel(const KParams P) {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t g = idx >> 6, p64 = idx & 63u;
-    if (g >= P.n_local_tiles || idx >= P.n_list) return;
-    const uint32_t e = P.pixel_list[idx];
-    if (e >= (uint32_t)P.cam.image_width * (uint32_t)P.cam.image_height) return;
-    double *dst = P.out + (size_t)e * 3u;
-    double *dsq = P.out_sq ? P.out_sq + (size_t)e * 3u : nullptr;
-    V3 acc = v3(0.0, 0.0, 0.0), sq = v3(0.0, 0.0, 0.0);
-    if (P.accumulate) {
-        acc = v3(dst[0], dst[1], dst[2]);
-        if (dsq) sq = v3(dsq[0], dsq[1], dsq[2]);
-    }
-    const double *src = P.samples + ((size_t)g * P.n_samples * 64u + p64) * 3u;
-    for (uint32_t s = 0; s < P.n_samples; ++s) {
-        const V3 c = v3(src[0], src[1], src[2]);
-        acc = acc + c;
-        sq = sq + c * c;
-        src += 64u * 3u;
-    }
-    dst[0] = acc.x; dst[1] = acc.y; dst[2] = acc.z;
-    if (dsq) { dsq[0] = sq.x; dsq[1] = sq.y; dsq[2] = sq.z; }
-}
+// The six keep their names (profiles, tools and documents find them by name); each route runs an instantiation of its own.
+__global__ void sum_samples_kernel(const KParams P) { reduce_samples<WhereShards, SumFold<SQ_NONE>>(P); }                  // rt_render[_device]
+__global__ void mean_samples_kernel(const KParams P) { reduce_samples<WhereFrame, MeanFold<false>>(P); }                   // rt_render_mean_device
+__global__ void mean_moments_samples_kernel(const KParams P) { reduce_samples<WhereFrame, MeanFold<true>>(P); }            // rt_render_mean_moments_device
+__global__ void sum_view_samples_kernel(const KParams P) { reduce_samples<WhereViews, SumFold<SQ_NONE>>(P); }              // rt_render_views_device
+__global__ void sum_view_moments_samples_kernel(const KParams P) { reduce_samples<WhereViews, SumFold<SQ_ALWAYS>>(P); }    // rt_render_views_moments_device
+__global__ void sum_listed_samples_kernel(const KParams P) { reduce_samples<WhereList, SumFold<SQ_IF_SET>>(P); }           // rt_render_pixels_device, adaptive
 
 // ---- adaptive sampling (rt_render_adaptive_device) --------------------------------------------------------------
 // The first active list: every pixel in tile order (tile k's 64 entries row-major, 0xffffffff outside the frame), so that its first
@@ -1904,23 +1890,17 @@ const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, 
 #undef RT_PICK
 }
 
-void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(sum_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
-}
-void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(mean_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
-}
-void launch_mean_moments_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(mean_moments_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
-}
-void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(sum_view_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
-}
-void launch_sum_view_moments_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(sum_view_moments_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
-}
-void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(sum_listed_samples_kernel, dim3(grid), dim3(256), 0, stream, K);
+void launch_reduce_samples(Reduce r, const KParams &K, unsigned grid, hipStream_t stream) {
+#define RT_REDUCE(R, KERNEL) case Reduce::R: hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, stream, K); break
+    switch (r) {
+        RT_REDUCE(Sum, sum_samples_kernel);
+        RT_REDUCE(Listed, sum_listed_samples_kernel);
+        RT_REDUCE(Views, sum_view_samples_kernel);
+        RT_REDUCE(ViewsMoments, sum_view_moments_samples_kernel);
+        RT_REDUCE(Mean, mean_samples_kernel);
+        RT_REDUCE(MeanMoments, mean_moments_samples_kernel);
+    }
+#undef RT_REDUCE
 }
 void launch_tile_order_list(int32_t w, int32_t h, uint32_t *list, hipStream_t stream) {
     const int32_t tiles_x = (w + RT_TILE_W - 1) / RT_TILE_W, tiles_y = (h + RT_TILE_H - 1) / RT_TILE_H;

@@ -114,16 +114,15 @@ struct KParams {
     const uint32_t *pixel_list;
     uint32_t n_list;                // entries of pixel_list (the groups beyond it are padding)
     double inv_width;               // 1 / image_width (list mode's pixel -> (i, j) decode; exact for w * h < 2^27)
-    double *out_sq;                 // list mode: per-pixel sums of the squared sample colours beside `out`, or null;
-                                    // mean_moments_samples_kernel: the frame of running M2 beside the running means in `out`;
-                                    // sum_view_moments_samples_kernel: one frame of sums of squares per view, laid out as `out` is
+    double *out_sq;                 // the reduction's second moments beside `out`, laid out as `out` is (launch_reduce_samples): sums of the
+                                    // squared sample colours (list mode: or null; views with moments) or Welford's running M2 (mean with moments)
     // views mode (rt_render_views_device; path_kernel<..., JOBS_VIEWS>): local tile lt is tile lt % tiles_per_view of view lt / tiles_per_view.
     // `cam` then holds what the views share (frame size); camera and seed of a job come from its view's record.  No other instantiation reads these.
     const ViewRec *views;
     double inv_tiles_per_view;      // 1 / tiles_per_view (exact decode for lt < 2^27)
     uint32_t tiles_per_view;
-    // live refinement (rt_render_mean_device; mean_samples_kernel): `out` is the frame of running means and `sample_begin` the number of
-    // samples already in it; the display frame (4 bytes per pixel, 4-byte aligned) that the last launch of a call writes, or null.
+    // live refinement (rt_render_mean_device; the reduction's mean folds): `out` is the frame of running means and `sample_begin` the
+    // number of samples already in it; the display frame (4 bytes per pixel, 4-byte aligned) that the last launch of a call writes, or null.
     // No other kernel reads this.
     uint8_t *mean_rgba8;
 };
@@ -186,12 +185,10 @@ int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered); // work
 const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, int jobs = JOBS_DENSE);
 
 // launches of the small kernels (all asynchronous on `stream`; errors through hipGetLastError)
-void launch_sum_samples(const KParams &K, unsigned grid, hipStream_t stream);
-void launch_sum_listed_samples(const KParams &K, unsigned grid, hipStream_t stream);
-void launch_sum_view_samples(const KParams &K, unsigned grid, hipStream_t stream);
-void launch_sum_view_moments_samples(const KParams &K, unsigned grid, hipStream_t stream); // ... and each view's sums of squares beside them, in K.out_sq
-void launch_mean_samples(const KParams &K, unsigned grid, hipStream_t stream); // live refinement: the running mean instead of the sum
-void launch_mean_moments_samples(const KParams &K, unsigned grid, hipStream_t stream); // ... and Welford's M2 beside it, in K.out_sq
+// the per-pixel reduction of a launch's sample buffer into K.out (rt_kernel.hip reduce_samples), one kernel per route: the sum (dense
+// jobs; a pixel list; views), the sum with each view's sums of squares in K.out_sq, the running mean, the mean with Welford's M2 in K.out_sq
+enum class Reduce { Sum, Listed, Views, ViewsMoments, Mean, MeanMoments };
+void launch_reduce_samples(Reduce r, const KParams &K, unsigned grid, hipStream_t stream); // (grid blocks of 256 threads)
 // adaptive sampling (rt_render_adaptive_device): the list of every pixel in tile order; one convergence step over an active list
 // (spp of the pixels that leave, the survivors compacted in order into list_out, padded to a multiple of 64, their count in *count);
 // the resolve with a per-pixel sample count
