@@ -947,6 +947,72 @@ int rt_upsample_device(int32_t width, int32_t height /* the FULL size */, const 
                        const double *d_edge_sum /* 3*w*h, or NULL */, int32_t edge_spp, const rt_upsample_params *params /* NULL: defaults */,
                        double *d_mean_out /* 3*w*h */, uint8_t *d_rgba8 /* 4*w*h, or NULL */, void *d_workspace, void *hip_stream);
 
+/* ---- robust frames (opt-in; nothing above changes) ---------------------------------------------------------------------------------------
+ * Every route above ends in the plain mean of a pixel's samples, which has no defence against a firefly: one rare path that carries
+ * hundreds of times the pixel's settled value stays a white dot at 4 to 64 samples, and the filters and bloom behind it keep or spread
+ * the dot.  rt_robust_device is the median of means: a pixel's samples arrive as K independent BLOCKS — K sub-frames of one camera under
+ * seeds seed + k, which rt_render_views_device renders in one launch — and the K block means are combined by a trimmed mean whose trim
+ * grows from 0 (the ordinary mean) to the median as the block means become more unequal.
+ *
+ * Normative definition.  The arithmetic rules are those of "Arithmetic" below: f64, every operation rounded on its own, no FMA, IEEE
+ * division.  The input is a block-major stack of K = blocks frames of 3 * w * h doubles, d_stack[k * 3wh + (j*w + i)*3 + c] — what
+ * rt_render_views_device writes — of sums with the uniform per-block count spp, or of means with spp = 1.  Each of the 3 * w * h values
+ * is treated on its own; a pixel's channels never meet.
+ *   Input value.  mu_k = S_k * (1.0 / (double)spp), tone mapping's "Input value"; a mu_k that is a NaN is replaced by THE NaN, the bit
+ *                 pattern 0x7ff8000000000000, so that all NaNs of a value are one.
+ *   Order.        mu_(0) .. mu_(K-1) are the K values sorted ascending; THE NaN sorts behind +inf; -0.0 and +0.0 compare equal.  Values
+ *                 that compare equal differ at most in a zero's sign, and every sum below starts from +0.0, where a zero of either sign
+ *                 adds the same: the order among equal values cannot change a result bit.
+ *   Trim count.   tmax = (K - 1) / 2 (integer division: the median for odd K, the two central values for even K), and by mode
+ *                   RT_ROBUST_MEAN    t = 0
+ *                   RT_ROBUST_TRIM    t = min(trim, tmax)
+ *                   RT_ROBUST_MEDIAN  t = tmax
+ *                   RT_ROBUST_GINI    if any mu_k is not finite, t = tmax.  Otherwise
+ *                                       S = the sum of mu_(i), W = the sum of ((double)(2*i - K + 1)) * mu_(i) (the product rounded, then
+ *                                       added), both over i = 0 .. K-1 in order from +0.0;
+ *                                       if S > 0 and W > 0:  g = (gain * (W / S)) * 0.5;  t = (int32_t)g if g < (double)tmax, else tmax
+ *                                       (so also for a g that is no number); otherwise t = 0.
+ *                 In exact arithmetic W / (K * S) is the Gini coefficient G of the block means, so g = gain * G * K / 2: equal blocks
+ *                 give W = 0 and t = 0, and one block that holds everything gives W / S = K - 1, which at gain 1 is the median.
+ *   Output.       If mu_(t) == mu_(K-1-t) — the kept values are all equal, and no NaN — out = mu_(t) + 0.0 (the value itself; a zero of
+ *                 either sign leaves as +0.0).  Otherwise m = K - 2*t;  acc = +0.0;  for i = t .. K-1-t in order: acc = acc + mu_(i);
+ *                 out = acc / (double)m, THE NaN if a NaN.  (A sum of m equal values need not divide back to the value unless m is a
+ *                 power of two; the first rule keeps a constant pixel constant at any K.)
+ *   M2 (optional) the winsorised second moment: w_i = mu_(t) for i < t, mu_(K-1-t) for i > K-1-t, mu_(i) otherwise;
+ *                 M2 = the sum over i = 0 .. K-1 in order from +0.0 of (w_i - out) * (w_i - out) (the difference rounded, the product
+ *                 rounded, then added), THE NaN if a NaN.  With samples = K, (out, M2) is what rt_denoise_mean_device reads: its Prepare
+ *                 forms M2 / (K - 1) / K, the variance of the combined mean.  M2 is >= +0.0 or THE NaN, never negative.
+ * Consequences.  K = 1: out = mu_0 (a -0.0 leaves as +0.0) and M2 = +0.0 for a finite mu_0.  RT_ROBUST_MEAN is the SORTED-order mean of
+ * the block means: it is not rt_render's sum over the samples in their order and need not equal it to the bit; on K copies of one frame
+ * every mode gives that frame's means exactly.  Where all blocks of a value are equal and finite, M2 = +0.0.  With t >= 1, raising
+ * the t largest values of a pixel to anything larger, +inf and NaN included, or lowering the t smallest, changes no bit of out as long as
+ * t stays what it was — under RT_ROBUST_TRIM and RT_ROBUST_MEDIAN t does not depend on the values; under RT_ROBUST_GINI it does, and a
+ * value that stops being finite makes it tmax.  A NaN or +inf in at most t blocks does not reach out.
+ *
+ * rt_robust_device reads d_stack and writes d_mean_out (3 * w * h doubles of means) and, if it is not NULL, d_m2_out (likewise); with
+ * or without d_m2_out, d_mean_out gets the same bits.  One launch, enqueued on hip_stream; the call does not synchronise, allocates
+ * nothing and has no workspace.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; blocks outside
+ * 1..RT_ROBUST_MAX_BLOCKS; a null d_stack or d_mean_out; spp < 1; a struct_size this library does not know; mode outside 0..3; trim < 0;
+ * gain that is not a finite number > 0; d_mean_out overlapping any of the stack's `blocks` frames, d_m2_out likewise, d_m2_out
+ * overlapping d_mean_out. */
+#define RT_ROBUST_MAX_BLOCKS 32
+#define RT_ROBUST_MEAN 0
+#define RT_ROBUST_TRIM 1
+#define RT_ROBUST_MEDIAN 2
+#define RT_ROBUST_GINI 3
+typedef struct rt_robust_params {
+    uint32_t struct_size;   /* sizeof(rt_robust_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t mode;           /* RT_ROBUST_* (default RT_ROBUST_GINI) */
+    int32_t trim;           /* RT_ROBUST_TRIM only: >= 0, clamped to tmax (default 1) */
+    double gain;            /* RT_ROBUST_GINI only: finite, > 0 (default 1.0) */
+} rt_robust_params;
+/* Fills the defaults into the first struct_size bytes (nothing beyond them is written) and sets struct_size. */
+int rt_robust_params_init_sized(rt_robust_params *params, uint32_t struct_size);
+int rt_robust_device(int32_t width, int32_t height, int32_t blocks, const double *d_stack /* blocks x 3*w*h, block-major */, int32_t spp,
+                     const rt_robust_params *params /* NULL: defaults */, double *d_mean_out /* 3*w*h MEANS */,
+                     double *d_m2_out /* 3*w*h, or NULL */, void *hip_stream);
+
 /* ---- bloom (opt-in; nothing above changes) ------------------------------------------------------------------------------------------------
  * A tone curve works one pixel at a time: a radiance-15 lamp and a radiance-1.5 wall beside it both end near white.  rt_bloom_device
  * spreads the light of the pixels above a luminance threshold over their neighbourhood BEFORE the curve: a bright pass, K levels of the

@@ -232,6 +232,12 @@ int rt_debug_set_tuning(int32_t th_prim, int32_t th_other, int32_t th_shade, int
  * Affects speed only, never results.  Process-wide. */
 int rt_debug_set_bloom_fused(int32_t max_stride);
 
+/* Test / tuning hook: the kernel form of rt_robust_device calls from now on — the number of register slots its sorting network has: 4,
+ * 8, 16 or 32 (any other positive value counts as the next of these above it, 32 at the most); a form with fewer slots than a call has
+ * blocks cannot run it, and that call takes the smallest form that fits.  0 or negative: back to the built-in rule (the smallest form
+ * that fits).  Returns the value in force before the call (0: the built-in rule).  Affects speed only, never results.  Process-wide. */
+int rt_debug_set_robust_form(int32_t slots);
+
 /* Test / tuning hook: the form of the upsample kernel that rt_upsample_device calls from now on launch, whatever the frame: 0 the direct
  * form (every tap read from the workspace's regions in global memory), 1 (or more) the LDS form (a tile's low records staged once);
  * negative: back to the built-in rule (the LDS form, which was the faster one at every size and guide set measured).

@@ -70,6 +70,12 @@ int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, 
 int rth_upsample(int32_t width, int32_t height, const double *low, int32_t spp, const double *albedo_sum /* 3*w*h, or NULL */, int32_t albedo_spp,
                  const double *edge_sum /* 3*w*h, or NULL */, int32_t edge_spp, const rt_upsample_params *params /* NULL: defaults */,
                  double *out_mean, uint8_t *out_rgba8 /* or NULL */);
+/* The host mirror of rt_robust_device (rt_amd.h "robust frames") on host memory: the same per-value body (csrc/rt_robust_shared.h), so
+ * out_mean and, if it is not NULL, out_m2 (3 * w * h doubles each) hold the device's bits.  `stack` is blocks x 3 * w * h doubles, block
+ * after block.  It refuses what the device call refuses, in the same order and with the same words (-1, the field named in
+ * rth_last_error); there is no stream. */
+int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stack, int32_t spp, const rt_robust_params *params /* NULL: defaults */,
+               double *out_mean, double *out_m2 /* or NULL */);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* Deterministic procedural RGB8 map used where assets/earth-large.jpg is unavailable. */

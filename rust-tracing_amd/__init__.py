@@ -324,6 +324,32 @@ def bloom_params(**kw) -> "BloomParams":
     return b
 
 
+RT_ROBUST_MEAN, RT_ROBUST_TRIM, RT_ROBUST_MEDIAN, RT_ROBUST_GINI = 0, 1, 2, 3
+RT_ROBUST_MAX_BLOCKS = 32
+ROBUST_MODES = {"mean": RT_ROBUST_MEAN, "trim": RT_ROBUST_TRIM, "median": RT_ROBUST_MEDIAN, "gini": RT_ROBUST_GINI}
+
+
+class RobustParams(C.Structure):
+    """rt_robust_params (rt_robust_device, rth_robust)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("trim", C.c_int32), ("gain", C.c_double)]
+
+
+def robust_params(**kw) -> "RobustParams":
+    """rt_robust_params_init_sized, then the given fields (mode= an RT_ROBUST_* value or one of "mean", "trim", "median", "gini";
+    trim=, gain=)."""
+    r = RobustParams()
+    _check(amd_lib().rt_robust_params_init_sized(C.byref(r), C.sizeof(r)), "rt_robust_params_init_sized")
+    for k, v in kw.items():
+        if k not in dict(RobustParams._fields_):
+            raise TypeError(f"rt_robust_params has no field {k}")
+        if k == "mode" and isinstance(v, str):
+            if v not in ROBUST_MODES:
+                raise RtError(f"robust_params: no mode {v!r} (mean, trim, median, gini)")
+            v = ROBUST_MODES[v]
+        setattr(r, k, v)
+    return r
+
+
 class UpsampleParams(C.Structure):
     """rt_upsample_params (rt_upsample_device, rth_upsample)."""
     _fields_ = [("struct_size", C.c_uint32), ("factor", C.c_int32), ("sigma_edge", C.c_double), ("sigma_albedo", C.c_double),
@@ -441,6 +467,8 @@ RT_AMD_SYMBOLS = {
     "rt_denoise_guided_views_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_denoise_guided_views_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                                  C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_robust_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_robust_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_bloom_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rt_bloom_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "rt_bloom_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -481,6 +509,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_debug_set_start_inline": (C.c_int, [C.c_int32]),
     "rt_debug_set_bloom_fused": (C.c_int, [C.c_int32]),
+    "rt_debug_set_robust_form": (C.c_int, [C.c_int32]),
     "rt_debug_set_upsample_form": (C.c_int, [C.c_int32]),
     "rt_debug_ordered_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rt_debug_ordered_layout_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -753,6 +782,7 @@ RT_HOST_SYMBOLS = {
     "rth_bloom": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_upsample": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "rth_robust": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_load_image": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
@@ -1004,6 +1034,35 @@ class DeviceScene:
         arr = _view_array(views)
         _check(amd_lib().rt_render_views_device(self._handle, arr, len(arr), C.byref(params), C.c_void_p(d_out_ptr),
                                                 C.c_void_p(stream)), "rt_render_views_device")
+
+    def render_robust(self, params: RenderParams, blocks: int, camera: Camera | None = None, **robust_kw):
+        """A firefly-robust frame: `blocks` sub-frames of this camera under the seeds params.seed + k, each of the samples
+        [0, spp / blocks) — spp is params.sample_end or, if that is 0, the camera's samples_per_pixel, and `blocks` must divide it —
+        from ONE rt_render_views_device launch, combined on the device by rt_robust_device with robust_params(**robust_kw).  Returns
+        (mean, m2), two (h, w, 3) float64 frames: with samples = blocks they are what denoise_mean takes."""
+        import torch
+        cam = camera if camera is not None else self.host_scene.camera
+        spp = params.sample_end if params.sample_end > 0 else cam.samples_per_pixel
+        if not 1 <= blocks <= RT_ROBUST_MAX_BLOCKS:
+            raise RtError(f"render_robust: blocks must be from 1 to {RT_ROBUST_MAX_BLOCKS}")
+        if params.sample_begin != 0 or params.accumulate:
+            raise RtError("render_robust: the sub-frames start at sample 0 and are not accumulated")
+        if spp % blocks != 0:
+            raise RtError(f"render_robust: blocks = {blocks} does not divide the sample count {spp}")
+        rp = robust_params(**robust_kw)
+        sub = RenderParams.from_buffer_copy(params)
+        sub.sample_end = spp // blocks
+        h, w = cam.image_height, cam.image_width
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            d_stack = torch.empty((blocks, h, w, 3), dtype=torch.float64, device="cuda")
+            d_out = torch.empty((2, h, w, 3), dtype=torch.float64, device="cuda")
+            self.render_views_device(sub, [(cam, params.seed + k) for k in range(blocks)], d_stack.data_ptr(), stream)
+            robust_device(w, h, blocks, d_stack.data_ptr(), sub.sample_end, d_out[0].data_ptr(), d_m2_out_ptr=d_out[1].data_ptr(), params=rp,
+                          stream=stream)
+            torch.cuda.synchronize()
+            out = d_out.cpu().numpy()
+        return out[0], out[1]
 
     def render_views_moments(self, params: RenderParams, views, sum=None, sum_sq=None):
         """rt_render_views_moments: (sum, sum_sq), two (n_views, h, w, 3) float64 arrays from one launch: `sum` is render_views' array,
@@ -1738,6 +1797,53 @@ def bloom_host(values, spp, *, spp_map=None, **kw):
                             out.ctypes.data) != 0:
         raise RtError(host_lib().rth_last_error().decode(errors="replace"))
     return out
+
+
+def robust_device(width, height, blocks, d_stack_ptr: int, spp: int, d_mean_out_ptr: int, *, d_m2_out_ptr: int = 0,
+                  params: "RobustParams | None" = None, stream: int = 0):
+    """rt_robust_device: the median of means over `blocks` device frames of 3 w h doubles at d_stack_ptr, block after block — sums with
+    the uniform per-block count `spp`, or means with spp = 1 — into the 3 w h doubles of MEANS at d_mean_out_ptr and, if d_m2_out_ptr is
+    not 0, the winsorised second moments there.  One launch, enqueued on `stream`; no workspace."""
+    _check(amd_lib().rt_robust_device(width, height, blocks, C.c_void_p(d_stack_ptr or None), spp, C.byref(params) if params is not None else None,
+                                      C.c_void_p(d_mean_out_ptr or None), C.c_void_p(d_m2_out_ptr or None), C.c_void_p(stream)), "rt_robust_device")
+
+
+def _robust_stack(who, stack):
+    import numpy as np
+    stack = np.ascontiguousarray(stack, dtype=np.float64)
+    if stack.ndim != 4 or stack.shape[3] != 3 or stack.size == 0:
+        raise RtError(f"{who}: stack must be (blocks, h, w, 3), not {stack.shape}")
+    return stack
+
+
+def robust(stack, spp, *, m2=False, device=0, **kw):
+    """Uploads a (blocks, h, w, 3) stack of sums (with the per-block count `spp`) or of means (spp = 1), runs rt_robust_device with
+    robust_params(**kw) and downloads the (h, w, 3) float64 frame of robust means — with m2=True, (mean, m2)."""
+    stack = _robust_stack("robust", stack)
+    params = robust_params(**kw)
+    k, h, w, _ = stack.shape
+    import torch
+    with torch.cuda.device(device):
+        d_stack = torch.from_numpy(stack).cuda()
+        d_out = torch.empty((2 if m2 else 1, h, w, 3), dtype=torch.float64, device="cuda")
+        robust_device(w, h, k, d_stack.data_ptr(), int(spp), d_out[0].data_ptr(), d_m2_out_ptr=d_out[1].data_ptr() if m2 else 0, params=params,
+                      stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+    return (out[0], out[1]) if m2 else out[0]
+
+
+def robust_host(stack, spp, *, m2=False, **kw):
+    """rth_robust (librt_host, CPU): what rt_robust_device gives, bit for bit, from the same per-value body."""
+    import numpy as np
+    stack = _robust_stack("robust_host", stack)
+    params = robust_params(**kw)
+    k, h, w, _ = stack.shape
+    mean = np.zeros((h, w, 3), dtype=np.float64)
+    second = np.zeros((h, w, 3), dtype=np.float64) if m2 else None
+    if host_lib().rth_robust(w, h, k, stack.ctypes.data, int(spp), C.byref(params), mean.ctypes.data, second.ctypes.data if m2 else None) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return (mean, second) if m2 else mean
 
 
 def camera_scaled(camera: Camera, factor: int) -> Camera:

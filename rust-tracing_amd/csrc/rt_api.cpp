@@ -4,6 +4,7 @@
 #include "rt_qfilt.hpp"
 #include "rt_tonemap_shared.h"
 #include "rt_bloom_shared.h"
+#include "rt_robust_shared.h"
 #include "rt_upsample_shared.h"
 
 #include <algorithm>
@@ -2167,6 +2168,39 @@ int rt_bloom_device(int32_t width, int32_t height, const double *d_values, int32
             HIP_TRY(hipGetLastError());
         }
     }
+    return RT_OK;
+}
+
+// ---- robust frames (rt_robust.hip): K block means per value, combined by a trimmed mean of their sorted order ----
+
+// The kernel form: the slots of its sorting network; 0: the built-in rule, the smallest form that fits (rt_debug_set_robust_form; speed only).
+static std::atomic<int32_t> g_robust_form{0};
+
+int rt_debug_set_robust_form(int32_t slots) {
+    return g_robust_form.exchange(slots <= 0 ? 0 : rtrb::kmax_for(slots > RT_ROBUST_MAX_BLOCKS ? RT_ROBUST_MAX_BLOCKS : slots));
+}
+
+int rt_robust_params_init_sized(rt_robust_params *params, uint32_t struct_size) {
+    if (!params) return fail(RT_ERR_INVALID_ARGUMENT, "rt_robust_params_init_sized: null argument");
+    if (!rtrb::size_known(struct_size)) return fail(RT_ERR_INVALID_ARGUMENT, "rt_robust_params_init_sized: struct_size is not one this library knows");
+    rt_robust_params full;
+    rtrb::defaults(full);
+    full.struct_size = struct_size;
+    memcpy(params, &full, struct_size);
+    return RT_OK;
+}
+
+int rt_robust_device(int32_t width, int32_t height, int32_t blocks, const double *d_stack, int32_t spp, const rt_robust_params *params,
+                     double *d_mean_out, double *d_m2_out, void *hip_stream) {
+    const std::string w("rt_robust_device");
+    rt_robust_params p;
+    if (const char *bad = rtrb::bad_argument(true, width, height, blocks, d_stack, d_mean_out, spp, params, p))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + bad);
+    if (const char *bad = rtrb::bad_overlap(true, width, height, blocks, d_stack, d_mean_out, d_m2_out)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + bad);
+    if (int rc = select_device_of(d_mean_out, "rt_robust_device")) return rc;
+    launch_robust(g_robust_form.load(), 3 * (int64_t)width * height, d_stack, blocks, p.mode, p.trim, p.gain, 1.0 / (double)spp, d_mean_out, d_m2_out,
+                  (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 

@@ -268,6 +268,11 @@ void launch_bloom_level_fused(int32_t w, int32_t h, int32_t stride, const double
                               hipStream_t stream);
 void launch_bloom_h(int32_t w, int32_t h, int32_t stride, const double *b_in, double *h_out, hipStream_t stream);
 void launch_bloom_v(int32_t w, int32_t h, int32_t stride, const double *h_in, double *b_out, double *a, const BloomOutput *last, hipStream_t stream);
+// robust frames (rt_robust.hip; rt_robust_device).  One launch, one thread per value of the 3 w h (`total`): `blocks` frames of `total`
+// doubles at `stack`, block after block, into mean_out and, if not null, m2_out.  kmax picks the kernel form — 4, 8, 16 or 32 register
+// slots; one too small for `blocks` counts as the smallest that fits (what rt_api.cpp passes by itself) — and changes no bit.
+void launch_robust(int32_t kmax, int64_t total, const double *stack, int32_t blocks, int32_t mode, int32_t trim, double gain, double inv_spp,
+                   double *mean_out, double *m2_out, hipStream_t stream);
 // guided upsampling (rt_upsample.hip; rt_upsample_device).  w x h is the FULL size, lw x lh the low one; rec_r, rec_a and rec_g are the
 // workspace's regions of 4 doubles per low pixel (rt_upsample_shared.h).  launch_upsample_prepare writes rec_r and, per guide given
 // (albedo_sum / edge_sum not null), rec_a / rec_g; launch_upsample reads them and writes out (3 w h doubles) and, if not null, rgba (w h

@@ -6,6 +6,7 @@
 #include "scenes.hpp"
 #include "../csrc/rt_tonemap_shared.h"
 #include "../csrc/rt_bloom_shared.h"
+#include "../csrc/rt_robust_shared.h"
 #include "../csrc/rt_upsample_shared.h"
 #include <cstring>
 #include <exception>
@@ -272,6 +273,32 @@ int rth_upsample(int32_t width, int32_t height, const double *low, int32_t spp, 
                 for (int k = 0; k < 4; ++k) out_rgba8[4 * px + (size_t)k] = (uint8_t)(word >> (8 * k));
             }
         }
+    return 0;
+}
+
+// ---- robust frames: the host mirror of rt_robust_device (include/rt_amd.h "robust frames") ----
+
+int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stack, int32_t spp, const rt_robust_params *params, double *out_mean,
+               double *out_m2) {
+    const std::string who("rth_robust");
+    rt_robust_params p;
+    if (const char *bad = rtrb::bad_argument(false, width, height, blocks, stack, out_mean, spp, params, p)) return fail(who + ": " + bad);
+    if (const char *bad = rtrb::bad_overlap(false, width, height, blocks, stack, out_mean, out_m2)) return fail(who + ": " + bad);
+    const size_t total = (size_t)width * (size_t)height * 3u;
+    const rtrb::Rule rule = rtrb::rule_of(p, blocks, spp);
+    // the form the device's built-in rule takes for this K (any larger one gives the same bits)
+    double (*one)(const double *, size_t, const rtrb::Rule &, double *) = nullptr;
+    switch (rtrb::kmax_for(blocks)) {
+    case 4: one = rtrb::combine_strided<4>; break;
+    case 8: one = rtrb::combine_strided<8>; break;
+    case 16: one = rtrb::combine_strided<16>; break;
+    default: one = rtrb::combine_strided<32>; break;
+    }
+    for (size_t e = 0; e < total; ++e) {
+        double m2 = 0.0;
+        out_mean[e] = one(stack + e, total, rule, out_m2 ? &m2 : nullptr);
+        if (out_m2) out_m2[e] = m2;
+    }
     return 0;
 }
 

@@ -35,6 +35,9 @@
 //   width and height, F = 2..4, and brought to full size under the full-size albedo and surface-ID frames asked for; the --denoise
 //   and --live-denoise families then filter the small frame, and bloom and the tone mapping run on the full-size one; --live renders the
 //   guide frames once per session).
+//   --robust K [--robust-mode mean|trim|median|gini] [--robust-trim T] [--robust-gain X] (robust frames of include/rt_amd.h: K sub-frames
+//   of spp / K samples under seeds seed + k in one views launch, combined by the median of means; --denoise filters the result with
+//   samples = K, --bloom and --tonemap run behind it).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -91,6 +94,12 @@ static void usage(const char *argv0) {
             "                         --upsample-edges stops the interpolation at the edges of the full-size surface-ID frame; --denoise* and\n"
             "                         --live-denoise* then filter the small frame, and --live renders the guides once, at up to 16 spp; not with\n"
             "                         --orbit, --adaptive, --gpus > 1 or --progressive)\n"
+            "          [--robust K [--robust-mode mean|trim|median|gini] [--robust-trim T] [--robust-gain X]]   (one GPU, one launch: K = 1..32 sub-frames\n"
+            "                         of spp / K samples each — K must divide spp — under seeds seed + k, combined per value by the median of means:\n"
+            "                         a trimmed mean of the K block means that drops T at each end (trim), all but the centre (median), none (mean),\n"
+            "                         or, default, as many as X times the blocks' Gini coefficient asks for (gini; X > 0, default 1); fireflies stay\n"
+            "                         in their block and are trimmed; --denoise then filters the robust frame with samples = K; also with --tonemap\n"
+            "                         and --bloom; not with -l, --adaptive, --orbit, --progressive, --upsample, --gpus > 1, --denoise-albedo, --denoise-edges)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -98,7 +107,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false, robust_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -213,6 +222,36 @@ int main(int argc, char **argv) {
             if (end == v || *end != 0 || f < 2 || f > 4) { fprintf(stderr, "--upsample needs a factor of 2, 3 or 4\n"); usage(argv[0]); return 2; }
             ro.upsample = (int)f;
         }
+        else if (a == "--robust") {
+            char *end = nullptr;
+            const char *v = need("--robust");
+            const long k = strtol(v, &end, 10);
+            if (end == v || *end != 0 || k < 1 || k > RT_ROBUST_MAX_BLOCKS) { fprintf(stderr, "--robust needs a number of blocks from 1 to 32\n"); usage(argv[0]); return 2; }
+            ro.robust_blocks = (int)k;
+        }
+        else if (a == "--robust-mode") {
+            const std::string m = need("--robust-mode");
+            robust_knob_given = true;
+            if (m == "mean") ro.robust_mode = RT_ROBUST_MEAN;
+            else if (m == "trim") ro.robust_mode = RT_ROBUST_TRIM;
+            else if (m == "median") ro.robust_mode = RT_ROBUST_MEDIAN;
+            else if (m == "gini") ro.robust_mode = RT_ROBUST_GINI;
+            else { fprintf(stderr, "--robust-mode needs a mode: mean, trim, median or gini\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--robust-trim") {
+            char *end = nullptr;
+            const char *v = need("--robust-trim");
+            const long t = strtol(v, &end, 10);
+            robust_knob_given = true;
+            if (end == v || *end != 0 || t < 0 || t > RT_ROBUST_MAX_BLOCKS) { fprintf(stderr, "--robust-trim needs a number of values to drop at each end, from 0 to 32\n"); usage(argv[0]); return 2; }
+            ro.robust_trim = (int)t;
+        }
+        else if (a == "--robust-gain") {
+            char *end = nullptr;
+            const char *v = need("--robust-gain");
+            ro.robust_gain = strtod(v, &end); robust_knob_given = true;
+            if (end == v || *end != 0 || !(ro.robust_gain > 0.0) || !(ro.robust_gain < 1e300)) { fprintf(stderr, "--robust-gain needs a gain above 0\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--upsample-albedo") ro.upsample_albedo = true;
         else if (a == "--upsample-edges") ro.upsample_edges = true;
         else if (a == "--earth") so.earth_image = need("--earth");
@@ -304,6 +343,20 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--upsample traces a smaller frame on a one-GPU route — a plain render, the --denoise family or -l/--live: it cannot be "
                         "combined with --orbit, --adaptive, --gpus > 1 or --progressive\n");
         return 2;
+    }
+    if (robust_knob_given && ro.robust_blocks == 0) {
+        fprintf(stderr, "--robust-mode, --robust-trim and --robust-gain set the combiner of --robust: they need --robust\n");
+        return 2;
+    }
+    if (ro.robust_blocks > 0) {
+        const char *with = live ? "-l/--live" : ro.adaptive ? "--adaptive" : ro.orbit > 0 ? "--orbit" : ro.progressive_spp > 0 ? "--progressive"
+                           : ro.upsample > 0 ? "--upsample" : ro.gpus > 1 ? "--gpus > 1" : ro.denoise_albedo ? "--denoise-albedo"
+                           : ro.denoise_edges ? "--denoise-edges" : nullptr;
+        if (with) {
+            fprintf(stderr, "--robust renders its sub-frames on one GPU in one launch and filters them with the plain --denoise only: it cannot be "
+                            "combined with %s\n", with);
+            return 2;
+        }
     }
     if (white_given && ro.tonemap != RT_TONEMAP_REINHARD) {
         fprintf(stderr, "--tonemap-white sets the white point of --tonemap reinhard: it needs --tonemap reinhard\n");

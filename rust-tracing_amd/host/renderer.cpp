@@ -572,6 +572,62 @@ static std::vector<uint8_t> render_denoised_rgb8(const Camera &camera, const Hit
     return px;
 }
 
+void robust_device(int32_t width, int32_t height, int32_t blocks, const double *d_stack, int32_t spp, double *d_mean_out, double *d_m2_out,
+                   const RenderOptions &opt) {
+    rt_robust_params rp;
+    if (rt_robust_params_init_sized(&rp, sizeof rp) != RT_OK) throw std::runtime_error(std::string("robust: ") + rt_last_error());
+    rp.mode = opt.robust_mode; rp.trim = opt.robust_trim;
+    if (opt.robust_gain > 0.0) rp.gain = opt.robust_gain;
+    if (rt_robust_device(width, height, blocks, d_stack, spp, &rp, d_mean_out, d_m2_out, nullptr) != RT_OK)
+        throw std::runtime_error(std::string("robust: ") + rt_last_error());
+}
+
+// A firefly-robust render on device 0 (opt.robust_blocks = K): K sub-frames of spp / K samples under the camera with seeds seed + k
+// from one rt_render_views_device call, combined on the device by rt_robust_device; the frame of robust means goes through the
+// means-form output — with opt.denoise, with its M2 and samples = K through rt_denoise_mean_device first — and only the bytes come back.
+static std::vector<uint8_t> render_robust_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
+    const rt_camera cam = camera.pod();
+    const int32_t K = opt.robust_blocks, w = cam.image_width, h = cam.image_height;
+    if (K < 1 || K > RT_ROBUST_MAX_BLOCKS) throw std::runtime_error("render: robust_blocks must be from 1 to 32");
+    if (cam.samples_per_pixel % K != 0)
+        throw std::runtime_error("render: robust_blocks = " + std::to_string(K) + " does not divide the " + std::to_string(cam.samples_per_pixel) +
+                                 " samples per pixel: every block takes spp / robust_blocks of them");
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const int64_t n_pix = (int64_t)w * h, frame_bytes = n_pix * 3 * (int64_t)sizeof(double);
+    rt_scene *scene = nullptr;
+    void *d_stack = nullptr, *d_mean = nullptr, *d_m2 = nullptr, *d_rgba8 = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_stack); rt_device_free(0, d_mean); rt_device_free(0, d_m2); rt_device_free(0, d_rgba8); rt_scene_destroy(scene); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    std::vector<rt_view> views((size_t)K);
+    for (int32_t k = 0; k < K; ++k) { views[(size_t)k].camera = cam; views[(size_t)k].seed = opt.seed + (uint64_t)k; }
+    rt_render_params p{};
+    p.sample_begin = 0; p.sample_end = cam.samples_per_pixel / K; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, frame_bytes * K, &d_stack));
+    check(rt_device_malloc(0, frame_bytes, &d_mean));
+    if (opt.denoise) check(rt_device_malloc(0, frame_bytes, &d_m2));
+    check(rt_render_views_device(scene, views.data(), K, &p, static_cast<double *>(d_stack), nullptr));
+    std::vector<uint8_t> px;
+    try {
+        robust_device(w, h, K, static_cast<const double *>(d_stack), p.sample_end, static_cast<double *>(d_mean), static_cast<double *>(d_m2), opt);
+        if (opt.denoise) px = denoise_mean(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), K, opt);
+        else if (tonemapped(opt)) px = staged_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, false, opt);
+    } catch (...) { cleanup(); throw; }
+    if (px.empty()) {
+        check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+        check(rt_resolve_rgba8_device(w, h, static_cast<const double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+        std::vector<uint8_t> rgba((size_t)n_pix * 4u);
+        check(rt_device_download(0, rgba.data(), d_rgba8, n_pix * 4, nullptr));
+        px.resize((size_t)n_pix * 3u);
+        for (size_t q = 0; q < (size_t)n_pix; ++q) { px[3 * q] = rgba[4 * q]; px[3 * q + 1] = rgba[4 * q + 1]; px[3 * q + 2] = rgba[4 * q + 2]; }
+    }
+    cleanup();
+    return px;
+}
+
 // Adaptive sampling on device 0: the frame's sums and per-pixel spp stay on the device, are resolved there with each pixel's own
 // spp, and only the bytes come back.
 static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
@@ -664,6 +720,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     // opt.live_denoise_edges: the surface-ID scene's frame of means d_ids, rendered ONCE, before the first pass, is every pass's edge guide
     const bool edges = opt.live_denoise_edges;
     const bool denoised = opt.live_denoise || opt.live_denoise_albedo || edges, guided = opt.live_denoise_albedo;
+    if (opt.robust_blocks != 0) throw std::runtime_error("live_render: robust_blocks combines the sub-frames of one render() call: it cannot be combined with the live route");
     if (edges && opt.upsample > 0) throw std::runtime_error("live_render: live_denoise_edges cannot be combined with upsample (the guide would have to be made at the low size)");
     const int32_t w = cam.image_width, h = cam.image_height;
     rt_scene *scene = nullptr, *albedo_scene = nullptr;
@@ -885,6 +942,19 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     if (opt.upsample > 0 && (opt.orbit > 0 || opt.adaptive || opt.gpus > 1 || opt.progressive_spp > 0))
         throw std::runtime_error("render: upsample is a one-GPU, one-pass route: it cannot be combined with orbit, adaptive, gpus > 1 or progressive_spp");
     if ((opt.upsample_albedo || opt.upsample_edges) && opt.upsample == 0) throw std::runtime_error("render: upsample_albedo and upsample_edges need upsample");
+    if (opt.robust_blocks != 0) {
+        if (opt.adaptive || opt.orbit > 0 || opt.progressive_spp > 0 || opt.upsample > 0 || opt.gpus > 1)
+            throw std::runtime_error("render: robust_blocks is a one-GPU, one-pass route of its own: it cannot be combined with adaptive, orbit, "
+                                     "progressive_spp, upsample or gpus > 1");
+        if (opt.denoise_albedo || opt.denoise_edges)
+            throw std::runtime_error("render: robust_blocks filters its frame with the plain means form: it cannot be combined with denoise_albedo or denoise_edges");
+        const std::vector<uint8_t> px = render_robust_rgb8(*camera, *world, opt);
+        if (!opt.quiet) printf("Render time: %.2fs (%d robust blocks)\n", std::chrono::duration<double>(clock::now() - now).count(), opt.robust_blocks);
+        now = clock::now();
+        if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");
+        if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+        return;
+    }
     if (opt.orbit > 0) {
         render_orbit(*camera, *world, output_file_name, opt);
         return;

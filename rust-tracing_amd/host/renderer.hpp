@@ -105,6 +105,15 @@ struct RenderOptions {
     int upsample = 0;
     bool upsample_albedo = false;
     bool upsample_edges = false;
+    // robust frames (include/rt_amd.h "robust frames"): robust_blocks = K in 1..32 renders K sub-frames of spp / K samples under the
+    // camera with seeds seed + k in ONE rt_render_views_device call and combines them with rt_robust_device; 0: off.  K must divide the
+    // camera's spp.  The PNG comes from the robust means through the means-form output (rt_resolve_rgba8_device, or bloom and the
+    // tone-mapping stage); with `denoise` the combiner writes M2 as well and the frame goes through rt_denoise_mean_device with
+    // samples = K.  One GPU, one pass; not with adaptive, orbit, progressive_spp, upsample, the guided filters or live_render (they throw).
+    int robust_blocks = 0;
+    int robust_mode = RT_ROBUST_GINI;   // RT_ROBUST_*
+    int robust_trim = 1;                // RT_ROBUST_TRIM's count
+    double robust_gain = 0.0;           // RT_ROBUST_GINI's gain; <= 0: the library's default
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -170,6 +179,12 @@ std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double 
 // std::runtime_error on a library error.
 std::vector<double> bloom_means(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
 void bloom_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double *d_mean_out, const RenderOptions &opt);
+
+// rt_robust_device on device 0 with opt's mode, trim and gain: `blocks` DEVICE frames of 3 * w * h doubles at d_stack, block after
+// block (sums with the per-block count spp; means with spp = 1), into the DEVICE frames d_mean_out and, if not null, d_m2_out.  Enqueued
+// on the null stream, not waited for.  Throws std::runtime_error on a library error.
+void robust_device(int32_t width, int32_t height, int32_t blocks, const double *d_stack, int32_t spp, double *d_mean_out, double *d_m2_out,
+                   const RenderOptions &opt);
 
 // Guided upsampling with opt's factor and the library's default stops; width x height is the FULL size, the low frame holds
 // 3 * ceil(w / F) * ceil(h / F) values (sums with the count spp; means with spp = 1), each guide 3 * w * h sums with its count, or null /
