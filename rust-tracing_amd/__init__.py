@@ -180,16 +180,25 @@ class SceneCreateOptions(C.Structure):
                 ("quad_filter", C.c_int32), ("medium_first", C.c_int32)]
 
 
+def _params(cls, init, c_name, kw, *, sized=True, convert=None):
+    """The body of every *_params(**kw) below: a `cls` filled by the library's `init` (with the struct's size where it takes one),
+    then the given fields, each through its entry in `convert` if it has one."""
+    p = cls()
+    if sized:
+        _check(getattr(amd_lib(), init)(C.byref(p), C.sizeof(p)), init)
+    else:
+        getattr(amd_lib(), init)(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(cls._fields_):
+            raise TypeError(f"{c_name} has no field {k}")
+        setattr(p, k, convert[k](v) if convert and k in convert else v)
+    return p
+
+
 def scene_options(**kw) -> "SceneCreateOptions":
     """rt_scene_options_init, then the given fields (walk=, leaf_max=, flat_max=, refit=, use_lds=, th_*=, sample_buffer_bytes=,
     start_shortcut=, defer_instances=, seq_lookahead=, slow_min=, slow_age=, quad_filter=, medium_first=)."""
-    o = SceneCreateOptions()
-    amd_lib().rt_scene_options_init(C.byref(o))
-    for k, v in kw.items():
-        if k not in dict(SceneCreateOptions._fields_):
-            raise TypeError(f"rt_scene_options has no field {k}")
-        setattr(o, k, v)
-    return o
+    return _params(SceneCreateOptions, "rt_scene_options_init", "rt_scene_options", kw, sized=False)
 
 
 class AdaptiveParams(C.Structure):
@@ -207,13 +216,7 @@ class AdaptiveResult(C.Structure):
 
 def adaptive_params(**kw) -> "AdaptiveParams":
     """rt_adaptive_params_init_sized, then the given fields (min_spp=, batch_spp=, rel_threshold=, abs_threshold=)."""
-    a = AdaptiveParams()
-    _check(amd_lib().rt_adaptive_params_init_sized(C.byref(a), C.sizeof(a)), "rt_adaptive_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(AdaptiveParams._fields_):
-            raise TypeError(f"rt_adaptive_params has no field {k}")
-        setattr(a, k, v)
-    return a
+    return _params(AdaptiveParams, "rt_adaptive_params_init_sized", "rt_adaptive_params", kw)
 
 
 class DenoiseParams(C.Structure):
@@ -223,13 +226,7 @@ class DenoiseParams(C.Structure):
 
 def denoise_params(**kw) -> "DenoiseParams":
     """rt_denoise_params_init_sized, then the given fields (iterations=, sigma=, eps=)."""
-    d = DenoiseParams()
-    _check(amd_lib().rt_denoise_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(DenoiseParams._fields_):
-            raise TypeError(f"rt_denoise_params has no field {k}")
-        setattr(d, k, v)
-    return d
+    return _params(DenoiseParams, "rt_denoise_params_init_sized", "rt_denoise_params", kw)
 
 
 class DenoiseAlbedoParams(C.Structure):
@@ -240,13 +237,7 @@ class DenoiseAlbedoParams(C.Structure):
 
 def denoise_albedo_params(**kw) -> "DenoiseAlbedoParams":
     """rt_denoise_albedo_params_init_sized, then the given fields (iterations=, sigma=, eps=, sigma_albedo=, albedo_floor=)."""
-    d = DenoiseAlbedoParams()
-    _check(amd_lib().rt_denoise_albedo_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_albedo_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(DenoiseAlbedoParams._fields_):
-            raise TypeError(f"rt_denoise_albedo_params has no field {k}")
-        setattr(d, k, v)
-    return d
+    return _params(DenoiseAlbedoParams, "rt_denoise_albedo_params_init_sized", "rt_denoise_albedo_params", kw)
 
 
 class DenoiseGuidedParams(C.Structure):
@@ -257,13 +248,7 @@ class DenoiseGuidedParams(C.Structure):
 
 def denoise_guided_params(**kw) -> "DenoiseGuidedParams":
     """rt_denoise_guided_params_init_sized, then the given fields (iterations=, sigma=, eps=, sigma_albedo=, albedo_floor=, sigma_edge=)."""
-    d = DenoiseGuidedParams()
-    _check(amd_lib().rt_denoise_guided_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_guided_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(DenoiseGuidedParams._fields_):
-            raise TypeError(f"rt_denoise_guided_params has no field {k}")
-        setattr(d, k, v)
-    return d
+    return _params(DenoiseGuidedParams, "rt_denoise_guided_params_init_sized", "rt_denoise_guided_params", kw)
 
 
 class DenoiseSpatialParams(C.Structure):
@@ -273,13 +258,7 @@ class DenoiseSpatialParams(C.Structure):
 
 def denoise_spatial_params(**kw) -> "DenoiseSpatialParams":
     """rt_denoise_spatial_params_init_sized, then the given fields (spatial_below=, window_radius=)."""
-    d = DenoiseSpatialParams()
-    _check(amd_lib().rt_denoise_spatial_params_init_sized(C.byref(d), C.sizeof(d)), "rt_denoise_spatial_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(DenoiseSpatialParams._fields_):
-            raise TypeError(f"rt_denoise_spatial_params has no field {k}")
-        setattr(d, k, v)
-    return d
+    return _params(DenoiseSpatialParams, "rt_denoise_spatial_params_init_sized", "rt_denoise_spatial_params", kw)
 
 
 RT_TONEMAP_CLAMP, RT_TONEMAP_REINHARD, RT_TONEMAP_ACES = range(3)
@@ -292,20 +271,18 @@ class TonemapParams(C.Structure):
                 ("delta", C.c_double), ("white", C.c_double)]
 
 
+def _tonemap_op(v):
+    if isinstance(v, str):
+        if v not in TONEMAP_OPS:
+            raise RtError(f"tonemap_params: no operator {v!r} (clamp, reinhard, aces)")
+        return TONEMAP_OPS[v]
+    return v
+
+
 def tonemap_params(**kw) -> "TonemapParams":
     """rt_tonemap_params_init_sized, then the given fields (op= a number or "clamp" / "reinhard" / "aces", exposure=, auto_key=,
     delta=, white=)."""
-    t = TonemapParams()
-    _check(amd_lib().rt_tonemap_params_init_sized(C.byref(t), C.sizeof(t)), "rt_tonemap_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(TonemapParams._fields_):
-            raise TypeError(f"rt_tonemap_params has no field {k}")
-        if k == "op" and isinstance(v, str):
-            if v not in TONEMAP_OPS:
-                raise RtError(f"tonemap_params: no operator {v!r} (clamp, reinhard, aces)")
-            v = TONEMAP_OPS[v]
-        setattr(t, k, v)
-    return t
+    return _params(TonemapParams, "rt_tonemap_params_init_sized", "rt_tonemap_params", kw, convert={"op": _tonemap_op})
 
 
 class BloomParams(C.Structure):
@@ -315,13 +292,7 @@ class BloomParams(C.Structure):
 
 def bloom_params(**kw) -> "BloomParams":
     """rt_bloom_params_init_sized, then the given fields (levels=, threshold=, strength=)."""
-    b = BloomParams()
-    _check(amd_lib().rt_bloom_params_init_sized(C.byref(b), C.sizeof(b)), "rt_bloom_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(BloomParams._fields_):
-            raise TypeError(f"rt_bloom_params has no field {k}")
-        setattr(b, k, v)
-    return b
+    return _params(BloomParams, "rt_bloom_params_init_sized", "rt_bloom_params", kw)
 
 
 RT_ROBUST_MEAN, RT_ROBUST_TRIM, RT_ROBUST_MEDIAN, RT_ROBUST_GINI = 0, 1, 2, 3
@@ -334,20 +305,18 @@ class RobustParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("trim", C.c_int32), ("gain", C.c_double)]
 
 
+def _robust_mode(v):
+    if isinstance(v, str):
+        if v not in ROBUST_MODES:
+            raise RtError(f"robust_params: no mode {v!r} (mean, trim, median, gini)")
+        return ROBUST_MODES[v]
+    return v
+
+
 def robust_params(**kw) -> "RobustParams":
     """rt_robust_params_init_sized, then the given fields (mode= an RT_ROBUST_* value or one of "mean", "trim", "median", "gini";
     trim=, gain=)."""
-    r = RobustParams()
-    _check(amd_lib().rt_robust_params_init_sized(C.byref(r), C.sizeof(r)), "rt_robust_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(RobustParams._fields_):
-            raise TypeError(f"rt_robust_params has no field {k}")
-        if k == "mode" and isinstance(v, str):
-            if v not in ROBUST_MODES:
-                raise RtError(f"robust_params: no mode {v!r} (mean, trim, median, gini)")
-            v = ROBUST_MODES[v]
-        setattr(r, k, v)
-    return r
+    return _params(RobustParams, "rt_robust_params_init_sized", "rt_robust_params", kw, convert={"mode": _robust_mode})
 
 
 class UpsampleParams(C.Structure):
@@ -358,13 +327,7 @@ class UpsampleParams(C.Structure):
 
 def upsample_params(**kw) -> "UpsampleParams":
     """rt_upsample_params_init_sized, then the given fields (factor=, sigma_edge=, sigma_albedo=, albedo_floor=)."""
-    u = UpsampleParams()
-    _check(amd_lib().rt_upsample_params_init_sized(C.byref(u), C.sizeof(u)), "rt_upsample_params_init_sized")
-    for k, v in kw.items():
-        if k not in dict(UpsampleParams._fields_):
-            raise TypeError(f"rt_upsample_params has no field {k}")
-        setattr(u, k, v)
-    return u
+    return _params(UpsampleParams, "rt_upsample_params_init_sized", "rt_upsample_params", kw)
 
 
 class DebugNode(C.Structure):
@@ -1263,6 +1226,48 @@ def _frame_end(device, inputs, out_shape, rgba8_shape, ws_bytes, call, out_dtype
         return (out, d_rgba.cpu().numpy()) if rgba8_shape else out
 
 
+def _denoise_call(symbol, *args):
+    """One rt_denoise*_device call, `args` in the header's order.  Where the binding takes a pointer, a device address goes as a
+    C.c_void_p (0: null) and a params struct by reference (None: null); the return code is checked under the symbol's name."""
+    fn = getattr(amd_lib(), symbol)
+
+    def pointer(a):
+        return C.byref(a) if isinstance(a, C.Structure) else C.c_void_p(a or None) if a is not None else None
+    _check(fn(*[pointer(a) if t is C.c_void_p else a for t, a in zip(fn.argtypes, args)]), symbol)
+
+
+def _spatial_split(kw):
+    """The keywords of a *_mean_spatial wrapper: (denoise_spatial_params of spatial_below= and window_radius=, every other keyword)."""
+    kw = dict(kw)
+    return denoise_spatial_params(**{k: kw.pop(k) for k in ("spatial_below", "window_radius") if k in kw}), kw
+
+
+def _denoise_blocking(who, frames, rank, shape_error, make_params, kw, ws_bytes, call, *, optional=(), spp_map=None, copy=False, rgba8=False,
+                      device=0):
+    """The body of every blocking denoise wrapper: checks the shapes, builds the params, uploads, runs, downloads.  `frames`: the float64
+    inputs in the order `call` finds their device pointers in (contiguous views, or with `copy` copies); all of one shape, of `rank`
+    dimensions, (h, w, 3) or (n_views, h, w, 3), else `shape_error`; a None is a null pointer at an index in `optional` and refused
+    elsewhere.  `spp_map`: an (h, w) int32 map, whose pointer follows the frames'.  `size` is (w, h) or (w, h, n_views):
+    ws_bytes(*size) sizes the workspace, and call(size, input pointers, output, workspace, keywords) makes the *_device call, the
+    keywords being d_rgba8_ptr=, params= (make_params(**kw)) and stream=.  Returns the filtered means, or (means, display bytes)
+    with rgba8."""
+    import numpy as np
+    inputs = [None if a is None else np.array(a, dtype=np.float64, order="C") if copy else np.ascontiguousarray(a, dtype=np.float64) for a in frames]
+    given = [a for a in inputs if a is not None]
+    if any(a is None and i not in optional for i, a in enumerate(inputs)) or given[0].ndim != rank or given[0].shape[-1] != 3 or \
+            any(a.shape != given[0].shape for a in given):
+        raise RtError(f"{who}: {shape_error}")
+    dims = given[0].shape[:-1]  # (h, w) or (n_views, h, w)
+    if spp_map is not None:
+        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
+        if spp_map.shape != dims:
+            raise RtError(f"{who}: `spp_map` must have shape {dims}")
+    params = make_params(**kw)
+    size = (dims[-1], dims[-2]) + dims[:-2]
+    return _frame_end(device, inputs + [spp_map], dims + (3,), rgba8 and dims + (4,), ws_bytes(*size),
+                      lambda d, out, ws, rgba, stream: call(size, d, out, ws, dict(d_rgba8_ptr=rgba, params=params, stream=stream)))
+
+
 def denoise_workspace_bytes(width, height) -> int:
     return _workspace_bytes("rt_denoise_workspace_bytes", f"a {width}x{height} frame", width, height)
 
@@ -1272,28 +1277,16 @@ def denoise_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d
     """rt_denoise_device: the variance-guided à-trous filter over device frames of sums and sums of squares (3 w h doubles each) with
     the uniform sample count `spp` or, if d_spp_ptr is not 0, a device map of w h int32.  Writes 3 w h doubles of filtered means and,
     if d_rgba8_ptr is not 0, 4 w h display bytes; `d_workspace_ptr`: denoise_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
-                                       C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                       C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)), "rt_denoise_device")
+    _denoise_call("rt_denoise_device", width, height, d_sum_ptr, d_sum_sq_ptr, spp, d_spp_ptr, params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise(sum, sum_sq, spp, *, spp_map=None, rgba8=False, device=0, **kw):
     """Uploads (h, w, 3) frames of sums and sums of squares (and an (h, w) int32 spp map, if given), runs rt_denoise_device with
     denoise_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or (means, (h, w, 4) uint8) with rgba8."""
-    import numpy as np
-    sum = np.ascontiguousarray(sum, dtype=np.float64)
-    sum_sq = np.ascontiguousarray(sum_sq, dtype=np.float64)
-    if sum.ndim != 3 or sum.shape[2] != 3 or sum_sq.shape != sum.shape:
-        raise RtError("denoise: `sum` and `sum_sq` must be (h, w, 3) frames of one shape")
-    h, w = sum.shape[:2]
-    if spp_map is not None:
-        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
-        if spp_map.shape != (h, w):
-            raise RtError(f"denoise: `spp_map` must have shape {(h, w)}")
-    params = denoise_params(**kw)
-    return _frame_end(device, [sum, sum_sq, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_workspace_bytes(w, h),
-                      lambda d, out, ws, rgba, stream: denoise_device(w, h, d[0], d[1], int(spp), out, ws, d_spp_ptr=d[2], d_rgba8_ptr=rgba,
-                                                                      params=params, stream=stream))
+    return _denoise_blocking("denoise", [sum, sum_sq], 3, "`sum` and `sum_sq` must be (h, w, 3) frames of one shape", denoise_params, kw,
+                             denoise_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_device(*size, d[0], d[1], int(spp), out, ws, d_spp_ptr=d[2], **tail),
+                             spp_map=spp_map, rgba8=rgba8, device=device)
 
 
 def albedo_materials(host_scene):
@@ -1323,31 +1316,19 @@ def denoise_albedo_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp:
                           params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
     """rt_denoise_albedo_device: rt_denoise_device with a device frame of albedo sums (3 w h doubles, `albedo_spp` samples of the
     albedo scene) beside the moments; `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_albedo_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
-                                              C.c_void_p(d_albedo_sum_ptr), albedo_spp, C.byref(params) if params is not None else None,
-                                              C.c_void_p(d_mean_out_ptr), C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr),
-                                              C.c_void_p(stream)), "rt_denoise_albedo_device")
+    _denoise_call("rt_denoise_albedo_device", width, height, d_sum_ptr, d_sum_sq_ptr, spp, d_spp_ptr, d_albedo_sum_ptr, albedo_spp, params,
+                 d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_albedo(sum, sum_sq, spp, albedo_sum, albedo_spp, *, spp_map=None, rgba8=False, device=0, **kw):
     """Uploads (h, w, 3) frames of sums, sums of squares and albedo sums (and an (h, w) int32 spp map, if given), runs
     rt_denoise_albedo_device with denoise_albedo_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or
     (means, (h, w, 4) uint8) with rgba8."""
-    import numpy as np
-    sum = np.ascontiguousarray(sum, dtype=np.float64)
-    sum_sq = np.ascontiguousarray(sum_sq, dtype=np.float64)
-    albedo_sum = np.ascontiguousarray(albedo_sum, dtype=np.float64)
-    if sum.ndim != 3 or sum.shape[2] != 3 or sum_sq.shape != sum.shape or albedo_sum.shape != sum.shape:
-        raise RtError("denoise_albedo: `sum`, `sum_sq` and `albedo_sum` must be (h, w, 3) frames of one shape")
-    h, w = sum.shape[:2]
-    if spp_map is not None:
-        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
-        if spp_map.shape != (h, w):
-            raise RtError(f"denoise_albedo: `spp_map` must have shape {(h, w)}")
-    params = denoise_albedo_params(**kw)
-    return _frame_end(device, [sum, sum_sq, albedo_sum, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_albedo_workspace_bytes(w, h),
-                      lambda d, out, ws, rgba, stream: denoise_albedo_device(w, h, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws, d_spp_ptr=d[3],
-                                                                             d_rgba8_ptr=rgba, params=params, stream=stream))
+    return _denoise_blocking("denoise_albedo", [sum, sum_sq, albedo_sum], 3, "`sum`, `sum_sq` and `albedo_sum` must be (h, w, 3) frames of one shape",
+                             denoise_albedo_params, kw, denoise_albedo_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_albedo_device(*size, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws,
+                                                                                  d_spp_ptr=d[3], **tail),
+                             spp_map=spp_map, rgba8=rgba8, device=device)
 
 
 RT_SURFACE_ID_COLOURS = 26
@@ -1386,32 +1367,20 @@ def denoise_guided_device(width, height, d_sum_ptr: int, d_sum_sq_ptr: int, spp:
     """rt_denoise_guided_device: rt_denoise_albedo_device (d_albedo_sum_ptr 0: rt_denoise_device) with a device frame of edge-guide sums
     (3 w h doubles, `edge_spp` samples, e.g. of the surface-ID scene) beside its inputs; `d_workspace_ptr`:
     denoise_guided_workspace_bytes(w, h, d_albedo_sum_ptr != 0) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_guided_device(width, height, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp, C.c_void_p(d_spp_ptr or None),
-                                              C.c_void_p(d_albedo_sum_ptr or None), albedo_spp, C.c_void_p(d_edge_sum_ptr or None), edge_spp,
-                                              C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                              C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_guided_device")
+    _denoise_call("rt_denoise_guided_device", width, height, d_sum_ptr, d_sum_sq_ptr, spp, d_spp_ptr, d_albedo_sum_ptr, albedo_spp, d_edge_sum_ptr,
+                 edge_spp, params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_guided(sum, sum_sq, spp, edge_sum, edge_spp, *, albedo_sum=None, albedo_spp=0, spp_map=None, rgba8=False, device=0, **kw):
     """Uploads (h, w, 3) frames of sums, sums of squares and edge-guide sums (and albedo sums and an (h, w) int32 spp map, if given),
     runs rt_denoise_guided_device with denoise_guided_params(**kw) and downloads: the (h, w, 3) float64 filtered means, or
     (means, (h, w, 4) uint8) with rgba8."""
-    import numpy as np
-    given = [sum, sum_sq, edge_sum] + ([albedo_sum] if albedo_sum is not None else [])
-    frames = [np.ascontiguousarray(a, dtype=np.float64) for a in given]
-    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError("denoise_guided: `sum`, `sum_sq`, `edge_sum` and `albedo_sum` must be (h, w, 3) frames of one shape")
-    h, w = frames[0].shape[:2]
-    if spp_map is not None:
-        spp_map = np.ascontiguousarray(spp_map, dtype=np.int32)
-        if spp_map.shape != (h, w):
-            raise RtError(f"denoise_guided: `spp_map` must have shape {(h, w)}")
-    params = denoise_guided_params(**kw)
-    albedo = frames[3] if albedo_sum is not None else None
-    return _frame_end(device, frames[:3] + [albedo, spp_map], (h, w, 3), rgba8 and (h, w, 4), denoise_guided_workspace_bytes(w, h, albedo is not None),
-                      lambda d, out, ws, rgba, stream: denoise_guided_device(w, h, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2], int(edge_spp), out, ws,
-                                                                             d_spp_ptr=d[4], d_rgba8_ptr=rgba, params=params, stream=stream))
+    return _denoise_blocking("denoise_guided", [sum, sum_sq, edge_sum, albedo_sum], 3,
+                             "`sum`, `sum_sq`, `edge_sum` and `albedo_sum` must be (h, w, 3) frames of one shape", denoise_guided_params, kw,
+                             lambda w, h: denoise_guided_workspace_bytes(w, h, albedo_sum is not None),
+                             lambda size, d, out, ws, tail: denoise_guided_device(*size, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2], int(edge_spp),
+                                                                                  out, ws, d_spp_ptr=d[4], **tail),
+                             optional=(3,), spp_map=spp_map, rgba8=rgba8, device=device)
 
 
 def denoise_views_workspace_bytes(width, height, n_views) -> int:
@@ -1427,10 +1396,8 @@ def denoise_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: i
     """rt_denoise_views_device: denoise_device over a stack of n_views frames in one set of launches; every buffer is view-major
     (n_views frames of 3 w h doubles; d_rgba8_ptr, if not 0, n_views frames of 4 w h bytes), `spp` is uniform, `d_workspace_ptr`:
     denoise_views_workspace_bytes(w, h, n_views) device bytes.  View v equals denoise_device on view v's frames.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
-                                             C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                             C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_views_device")
+    _denoise_call("rt_denoise_views_device", width, height, n_views, d_sum_ptr, d_sum_sq_ptr, spp, params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr,
+                 stream)
 
 
 def denoise_albedo_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq_ptr: int, spp: int, d_albedo_sum_ptr: int, albedo_spp: int,
@@ -1438,40 +1405,25 @@ def denoise_albedo_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq
                                 params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
     """rt_denoise_albedo_views_device: denoise_albedo_device over a stack of n_views frames in one set of launches, the albedo sums
     view-major as well; `d_workspace_ptr`: denoise_albedo_views_workspace_bytes(w, h, n_views) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_albedo_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
-                                                    C.c_void_p(d_albedo_sum_ptr), albedo_spp, C.byref(params) if params is not None else None,
-                                                    C.c_void_p(d_mean_out_ptr), C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr),
-                                                    C.c_void_p(stream)), "rt_denoise_albedo_views_device")
-
-
-def _denoise_views(who, sum, sum_sq, spp, albedo_sum, albedo_spp, rgba8, device, kw):
-    import numpy as np
-    guided = albedo_sum is not None
-    frames = [np.ascontiguousarray(a, dtype=np.float64) for a in ((sum, sum_sq, albedo_sum) if guided else (sum, sum_sq))]
-    if frames[0].ndim != 4 or frames[0].shape[3] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError(f"{who}: the frames must be (n_views, h, w, 3) arrays of one shape")
-    n, h, w = frames[0].shape[:3]
-    params = denoise_albedo_params(**kw) if guided else denoise_params(**kw)
-
-    def call(d, out, ws, rgba, stream):
-        if guided:
-            denoise_albedo_views_device(w, h, n, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
-        else:
-            denoise_views_device(w, h, n, d[0], d[1], int(spp), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
-    ws_bytes = denoise_albedo_views_workspace_bytes(w, h, n) if guided else denoise_views_workspace_bytes(w, h, n)
-    return _frame_end(device, frames, (n, h, w, 3), rgba8 and (n, h, w, 4), ws_bytes, call)
+    _denoise_call("rt_denoise_albedo_views_device", width, height, n_views, d_sum_ptr, d_sum_sq_ptr, spp, d_albedo_sum_ptr, albedo_spp, params,
+                 d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_views(sum, sum_sq, spp, *, rgba8=False, device=0, **kw):
     """Uploads (n_views, h, w, 3) stacks of sums and sums of squares (what render_views_moments returns), runs rt_denoise_views_device
     with denoise_params(**kw) and downloads: the (n_views, h, w, 3) float64 filtered means, or (means, (n_views, h, w, 4) uint8) with rgba8."""
-    return _denoise_views("denoise_views", sum, sum_sq, spp, None, 0, rgba8, device, kw)
+    return _denoise_blocking("denoise_views", [sum, sum_sq], 4, "the frames must be (n_views, h, w, 3) arrays of one shape", denoise_params, kw, denoise_views_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_views_device(*size, d[0], d[1], int(spp), out, ws, **tail),
+                             rgba8=rgba8, device=device)
 
 
 def denoise_albedo_views(sum, sum_sq, spp, albedo_sum, albedo_spp, *, rgba8=False, device=0, **kw):
     """denoise_views with an (n_views, h, w, 3) stack of albedo sums (render_views of the albedo scene): rt_denoise_albedo_views_device
     with denoise_albedo_params(**kw)."""
-    return _denoise_views("denoise_albedo_views", sum, sum_sq, spp, albedo_sum, albedo_spp, rgba8, device, kw)
+    return _denoise_blocking("denoise_albedo_views", [sum, sum_sq, albedo_sum], 4, "the frames must be (n_views, h, w, 3) arrays of one shape", denoise_albedo_params, kw,
+                             denoise_albedo_views_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_albedo_views_device(*size, d[0], d[1], int(spp), d[2], int(albedo_spp), out, ws, **tail),
+                             rgba8=rgba8, device=device)
 
 
 def denoise_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
@@ -1479,50 +1431,32 @@ def denoise_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: 
     """rt_denoise_mean_device: denoise_device over device frames of running means and of M2 (3 w h doubles each, what
     render_mean_moments_device keeps) after `samples` samples of every pixel; `d_workspace_ptr`: denoise_workspace_bytes(w, h) device
     bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples,
-                                            C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                            C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)), "rt_denoise_mean_device")
+    _denoise_call("rt_denoise_mean_device", width, height, d_mean_ptr, d_m2_ptr, samples, params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_albedo_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_mean_out_ptr: int,
                                d_workspace_ptr: int, *, d_rgba8_ptr: int = 0, params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
     """rt_denoise_albedo_mean_device: denoise_mean_device with a device frame of albedo means (3 w h doubles: render_mean_device of the
     albedo scene) beside them; `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_albedo_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples, C.c_void_p(d_albedo_mean_ptr),
-                                                   C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                   C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_albedo_mean_device")
-
-
-def _denoise_means(who, mean, m2, samples, albedo_mean, rgba8, device, kw):
-    """denoise_mean and denoise_albedo_mean: upload, run, download"""
-    import numpy as np
-    frames = [np.array(a, dtype=np.float64, order="C") for a in ((mean, m2) if albedo_mean is None else (mean, m2, albedo_mean))]  # (copies)
-    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
-    h, w = frames[0].shape[:2]
-    params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
-
-    def call(d, out, ws, rgba, stream):
-        if albedo_mean is None:
-            denoise_mean_device(w, h, d[0], d[1], int(samples), out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
-        else:
-            denoise_albedo_mean_device(w, h, d[0], d[1], int(samples), d[2], out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
-    ws_bytes = denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h)
-    return _frame_end(device, frames, (h, w, 3), rgba8 and (h, w, 4), ws_bytes, call)
+    _denoise_call("rt_denoise_albedo_mean_device", width, height, d_mean_ptr, d_m2_ptr, samples, d_albedo_mean_ptr, params, d_mean_out_ptr,
+                 d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_mean(mean, m2, samples, *, rgba8=False, device=0, **kw):
     """Uploads (h, w, 3) frames of running means and of M2 after `samples` samples, runs rt_denoise_mean_device with denoise_params(**kw)
     and downloads: the (h, w, 3) float64 filtered means, or (means, (h, w, 4) uint8) with rgba8."""
-    return _denoise_means("denoise_mean", mean, m2, samples, None, rgba8, device, kw)
+    return _denoise_blocking("denoise_mean", [mean, m2], 3, "the frames must be (h, w, 3) and of one shape", denoise_params, kw, denoise_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_mean_device(*size, d[0], d[1], int(samples), out, ws, **tail),
+                             copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_albedo_mean(mean, m2, samples, albedo_mean, *, rgba8=False, device=0, **kw):
     """denoise_mean with an (h, w, 3) frame of albedo means beside the two: rt_denoise_albedo_mean_device with denoise_albedo_params(**kw)."""
     if albedo_mean is None:
         raise RtError("denoise_albedo_mean: `albedo_mean` is required")
-    return _denoise_means("denoise_albedo_mean", mean, m2, samples, albedo_mean, rgba8, device, kw)
+    return _denoise_blocking("denoise_albedo_mean", [mean, m2, albedo_mean], 3, "the frames must be (h, w, 3) and of one shape", denoise_albedo_params, kw, denoise_albedo_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_albedo_mean_device(*size, d[0], d[1], int(samples), d[2], out, ws, **tail),
+                             copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_mean_out_ptr: int, d_workspace_ptr: int, *,
@@ -1530,11 +1464,8 @@ def denoise_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, s
                                 stream: int = 0):
     """rt_denoise_mean_spatial_device: denoise_mean_device that, for frames of fewer than spatial.spatial_below samples (default 2),
     takes the variance from the spread of the neighbouring pixels' means; `d_m2_ptr` may then be 0.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
-                                                    C.byref(spatial) if spatial is not None else None,
-                                                    C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                    C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_mean_spatial_device")
+    _denoise_call("rt_denoise_mean_spatial_device", width, height, d_mean_ptr, d_m2_ptr, samples, spatial, params, d_mean_out_ptr, d_rgba8_ptr,
+                 d_workspace_ptr, stream)
 
 
 def denoise_albedo_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_mean_out_ptr: int,
@@ -1542,46 +1473,29 @@ def denoise_albedo_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr:
                                        params: "DenoiseAlbedoParams | None" = None, stream: int = 0):
     """rt_denoise_albedo_mean_spatial_device: denoise_mean_spatial_device with a device frame of albedo means beside the two;
     `d_workspace_ptr`: denoise_albedo_workspace_bytes(w, h) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_albedo_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
-                                                           C.c_void_p(d_albedo_mean_ptr), C.byref(spatial) if spatial is not None else None,
-                                                           C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                           C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_albedo_mean_spatial_device")
-
-
-def _denoise_means_spatial(who, mean, m2, samples, albedo_mean, rgba8, device, kw):
-    """denoise_mean_spatial and denoise_albedo_mean_spatial: upload, run, download (m2 None: a null d_m2)"""
-    import numpy as np
-    spatial = denoise_spatial_params(**{k: kw.pop(k) for k in ("spatial_below", "window_radius") if k in kw})
-    given = [a for a in (mean, m2, albedo_mean) if a is not None]
-    frames = [np.array(a, dtype=np.float64, order="C") for a in given]  # (copies)
-    if frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
-    h, w = frames[0].shape[:2]
-    params = denoise_params(**kw) if albedo_mean is None else denoise_albedo_params(**kw)
-    inputs = [frames[0], frames[1] if m2 is not None else None, frames[-1] if albedo_mean is not None else None]
-
-    def call(d, out, ws, rgba, stream):
-        if albedo_mean is None:
-            denoise_mean_spatial_device(w, h, d[0], d[1], int(samples), out, ws, d_rgba8_ptr=rgba, spatial=spatial, params=params, stream=stream)
-        else:
-            denoise_albedo_mean_spatial_device(w, h, d[0], d[1], int(samples), d[2], out, ws, d_rgba8_ptr=rgba, spatial=spatial, params=params,
-                                               stream=stream)
-    ws_bytes = denoise_workspace_bytes(w, h) if albedo_mean is None else denoise_albedo_workspace_bytes(w, h)
-    return _frame_end(device, inputs, (h, w, 3), rgba8 and (h, w, 4), ws_bytes, call)
+    _denoise_call("rt_denoise_albedo_mean_spatial_device", width, height, d_mean_ptr, d_m2_ptr, samples, d_albedo_mean_ptr, spatial, params,
+                 d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_mean_spatial(mean, m2, samples, *, rgba8=False, device=0, **kw):
     """denoise_mean through rt_denoise_mean_spatial_device: `m2` may be None where samples < spatial_below; spatial_below= and
     window_radius= go to denoise_spatial_params, every other keyword to denoise_params."""
-    return _denoise_means_spatial("denoise_mean_spatial", mean, m2, samples, None, rgba8, device, dict(kw))
+    spatial, kw = _spatial_split(kw)
+    return _denoise_blocking("denoise_mean_spatial", [mean, m2], 3, "the frames must be (h, w, 3) and of one shape", denoise_params, kw, denoise_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_mean_spatial_device(*size, d[0], d[1], int(samples), out, ws, spatial=spatial, **tail),
+                             optional=(1,), copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_albedo_mean_spatial(mean, m2, samples, albedo_mean, *, rgba8=False, device=0, **kw):
     """denoise_mean_spatial with an (h, w, 3) frame of albedo means beside the two: rt_denoise_albedo_mean_spatial_device."""
     if albedo_mean is None:
         raise RtError("denoise_albedo_mean_spatial: `albedo_mean` is required")
-    return _denoise_means_spatial("denoise_albedo_mean_spatial", mean, m2, samples, albedo_mean, rgba8, device, dict(kw))
+    spatial, kw = _spatial_split(kw)
+    return _denoise_blocking("denoise_albedo_mean_spatial", [mean, m2, albedo_mean], 3, "the frames must be (h, w, 3) and of one shape", denoise_albedo_params, kw,
+                             denoise_albedo_workspace_bytes,
+                             lambda size, d, out, ws, tail: denoise_albedo_mean_spatial_device(*size, d[0], d[1], int(samples), d[2], out, ws,
+                                                                                               spatial=spatial, **tail),
+                             optional=(1,), copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_guided_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_edge_mean_ptr: int,
@@ -1590,11 +1504,8 @@ def denoise_guided_mean_device(width, height, d_mean_ptr: int, d_m2_ptr: int, sa
     """rt_denoise_guided_mean_device: denoise_albedo_mean_device (d_albedo_mean_ptr 0: denoise_mean_device) with a device frame of
     edge-guide means (3 w h doubles: render_mean_device of the surface-ID scene) beside its inputs; `d_workspace_ptr`:
     denoise_guided_workspace_bytes(w, h, d_albedo_mean_ptr != 0) device bytes.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_guided_mean_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr), samples,
-                                                   C.c_void_p(d_albedo_mean_ptr or None), C.c_void_p(d_edge_mean_ptr or None),
-                                                   C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                   C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_guided_mean_device")
+    _denoise_call("rt_denoise_guided_mean_device", width, height, d_mean_ptr, d_m2_ptr, samples, d_albedo_mean_ptr, d_edge_mean_ptr, params,
+                 d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_guided_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr: int, samples: int, d_albedo_mean_ptr: int, d_edge_mean_ptr: int,
@@ -1602,12 +1513,8 @@ def denoise_guided_mean_spatial_device(width, height, d_mean_ptr: int, d_m2_ptr:
                                        spatial: "DenoiseSpatialParams | None" = None, params: "DenoiseGuidedParams | None" = None, stream: int = 0):
     """rt_denoise_guided_mean_spatial_device: denoise_guided_mean_device that, for frames of fewer than spatial.spatial_below samples,
     takes the variance from the spread of the neighbouring pixels of the same surface; `d_m2_ptr` may then be 0.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_guided_mean_spatial_device(width, height, C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr or None), samples,
-                                                           C.c_void_p(d_albedo_mean_ptr or None), C.c_void_p(d_edge_mean_ptr or None),
-                                                           C.byref(spatial) if spatial is not None else None,
-                                                           C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                           C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_guided_mean_spatial_device")
+    _denoise_call("rt_denoise_guided_mean_spatial_device", width, height, d_mean_ptr, d_m2_ptr, samples, d_albedo_mean_ptr, d_edge_mean_ptr, spatial,
+                 params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_guided_views_workspace_bytes(width, height, n_views, with_albedo) -> int:
@@ -1621,32 +1528,8 @@ def denoise_guided_views_device(width, height, n_views, d_sum_ptr: int, d_sum_sq
     """rt_denoise_guided_views_device: denoise_guided_device over a stack of n_views frames in one set of launches, every buffer
     view-major; `d_workspace_ptr`: denoise_guided_views_workspace_bytes(w, h, n_views, d_albedo_sum_ptr != 0) device bytes.  View v
     equals denoise_guided_device on view v's frames.  Enqueued on `stream`."""
-    _check(amd_lib().rt_denoise_guided_views_device(width, height, n_views, C.c_void_p(d_sum_ptr), C.c_void_p(d_sum_sq_ptr), spp,
-                                                    C.c_void_p(d_albedo_sum_ptr or None), albedo_spp, C.c_void_p(d_edge_sum_ptr or None), edge_spp,
-                                                    C.byref(params) if params is not None else None, C.c_void_p(d_mean_out_ptr),
-                                                    C.c_void_p(d_rgba8_ptr or None), C.c_void_p(d_workspace_ptr), C.c_void_p(stream)),
-           "rt_denoise_guided_views_device")
-
-
-def _denoise_guided_means(who, mean, m2, samples, edge_mean, albedo_mean, spatial, rgba8, device, kw):
-    """denoise_guided_mean and (`spatial`: the route's params) denoise_guided_mean_spatial: upload, run, download (m2 None: a null d_m2)"""
-    import numpy as np
-    if edge_mean is None:
-        raise RtError(f"{who}: `edge_mean` is required")
-    inputs = [None if a is None else np.array(a, dtype=np.float64, order="C") for a in (mean, m2, edge_mean, albedo_mean)]  # (copies)
-    frames = [a for a in inputs if a is not None]
-    if inputs[0] is None or frames[0].ndim != 3 or frames[0].shape[2] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError(f"{who}: the frames must be (h, w, 3) and of one shape")
-    h, w = frames[0].shape[:2]
-    params = denoise_guided_params(**kw)
-
-    def call(d, out, ws, rgba, stream):
-        if spatial is None:
-            denoise_guided_mean_device(w, h, d[0], d[1], int(samples), d[3], d[2], out, ws, d_rgba8_ptr=rgba, params=params, stream=stream)
-        else:
-            denoise_guided_mean_spatial_device(w, h, d[0], d[1], int(samples), d[3], d[2], out, ws, d_rgba8_ptr=rgba, spatial=spatial,
-                                               params=params, stream=stream)
-    return _frame_end(device, inputs, (h, w, 3), rgba8 and (h, w, 4), denoise_guided_workspace_bytes(w, h, albedo_mean is not None), call)
+    _denoise_call("rt_denoise_guided_views_device", width, height, n_views, d_sum_ptr, d_sum_sq_ptr, spp, d_albedo_sum_ptr, albedo_spp, d_edge_sum_ptr,
+                 edge_spp, params, d_mean_out_ptr, d_rgba8_ptr, d_workspace_ptr, stream)
 
 
 def denoise_guided_mean(mean, m2, samples, edge_mean, *, albedo_mean=None, rgba8=False, device=0, **kw):
@@ -1655,34 +1538,38 @@ def denoise_guided_mean(mean, m2, samples, edge_mean, *, albedo_mean=None, rgba8
     (means, (h, w, 4) uint8) with rgba8."""
     if m2 is None:
         raise RtError("denoise_guided_mean: `m2` is required")
-    return _denoise_guided_means("denoise_guided_mean", mean, m2, samples, edge_mean, albedo_mean, None, rgba8, device, dict(kw))
+    if edge_mean is None:
+        raise RtError("denoise_guided_mean: `edge_mean` is required")
+    return _denoise_blocking("denoise_guided_mean", [mean, m2, edge_mean, albedo_mean], 3, "the frames must be (h, w, 3) and of one shape", denoise_guided_params, kw,
+                             lambda w, h: denoise_guided_workspace_bytes(w, h, albedo_mean is not None),
+                             lambda size, d, out, ws, tail: denoise_guided_mean_device(*size, d[0], d[1], int(samples), d[3], d[2], out, ws, **tail),
+                             optional=(3,), copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_guided_mean_spatial(mean, m2, samples, edge_mean, *, albedo_mean=None, rgba8=False, device=0, **kw):
     """denoise_guided_mean through rt_denoise_guided_mean_spatial_device: `m2` may be None where samples < spatial_below; spatial_below=
     and window_radius= go to denoise_spatial_params, every other keyword to denoise_guided_params."""
-    kw = dict(kw)
-    spatial = denoise_spatial_params(**{k: kw.pop(k) for k in ("spatial_below", "window_radius") if k in kw})
-    return _denoise_guided_means("denoise_guided_mean_spatial", mean, m2, samples, edge_mean, albedo_mean, spatial, rgba8, device, kw)
+    spatial, kw = _spatial_split(kw)
+    if edge_mean is None:
+        raise RtError("denoise_guided_mean_spatial: `edge_mean` is required")
+    return _denoise_blocking("denoise_guided_mean_spatial", [mean, m2, edge_mean, albedo_mean], 3, "the frames must be (h, w, 3) and of one shape", denoise_guided_params, kw,
+                             lambda w, h: denoise_guided_workspace_bytes(w, h, albedo_mean is not None),
+                             lambda size, d, out, ws, tail: denoise_guided_mean_spatial_device(*size, d[0], d[1], int(samples), d[3], d[2], out, ws,
+                                                                                               spatial=spatial, **tail),
+                             optional=(1, 3), copy=True, rgba8=rgba8, device=device)
 
 
 def denoise_guided_views(sum, sum_sq, spp, edge_sum, edge_spp, *, albedo_sum=None, albedo_spp=0, rgba8=False, device=0, **kw):
     """Uploads (n_views, h, w, 3) stacks of sums, sums of squares and edge-guide sums (render_views of the surface-ID scene; and of
     albedo sums, if given), runs rt_denoise_guided_views_device with denoise_guided_params(**kw) and downloads: the (n_views, h, w, 3)
     float64 filtered means, or (means, (n_views, h, w, 4) uint8) with rgba8."""
-    import numpy as np
     if edge_sum is None:
         raise RtError("denoise_guided_views: `edge_sum` is required")
-    inputs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (sum, sum_sq, edge_sum, albedo_sum)]
-    frames = [a for a in inputs if a is not None]
-    if inputs[0] is None or inputs[1] is None or frames[0].ndim != 4 or frames[0].shape[3] != 3 or any(a.shape != frames[0].shape for a in frames):
-        raise RtError("denoise_guided_views: the frames must be (n_views, h, w, 3) arrays of one shape")
-    n, h, w = frames[0].shape[:3]
-    params = denoise_guided_params(**kw)
-    return _frame_end(device, inputs, (n, h, w, 3), rgba8 and (n, h, w, 4), denoise_guided_views_workspace_bytes(w, h, n, albedo_sum is not None),
-                      lambda d, out, ws, rgba, stream: denoise_guided_views_device(w, h, n, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2],
-                                                                                   int(edge_spp), out, ws, d_rgba8_ptr=rgba, params=params,
-                                                                                   stream=stream))
+    return _denoise_blocking("denoise_guided_views", [sum, sum_sq, edge_sum, albedo_sum], 4, "the frames must be (n_views, h, w, 3) arrays of one shape", denoise_guided_params, kw,
+                             lambda w, h, n: denoise_guided_views_workspace_bytes(w, h, n, albedo_sum is not None),
+                             lambda size, d, out, ws, tail: denoise_guided_views_device(*size, d[0], d[1], int(spp), d[3], int(albedo_spp), d[2],
+                                                                                        int(edge_spp), out, ws, **tail),
+                             optional=(3,), rgba8=rgba8, device=device)
 
 
 def tonemap_workspace_bytes(width, height) -> int:

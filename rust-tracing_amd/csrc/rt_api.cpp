@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <type_traits>
 
 using namespace rtapi;
@@ -1636,90 +1637,129 @@ bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
-// rt_denoise_device and, with `guide` (what only the guided filter takes; its region is set here), rt_denoise_albedo_device: every check
-// in the header's order, each message under the caller's name `who`, then prepare and the K iterations.  `d` is the caller's resolved
-// params (the fields both structs have), or null where their struct_size was not known: that is refused here, in its place among the checks.
-// `form` is the input form: sums and sums of squares with a sample count or map, or (rt_denoise_mean_device, rt_denoise_albedo_mean_device)
-// running means and M2 after `spp` samples of every pixel, the guide's frame a mean as well; the messages name the inputs as the caller does.
-// `spatial` (rt_denoise_mean_spatial_device, rt_denoise_albedo_mean_spatial_device; means form only) is the route choice: with
-// spp < spatial->params.spatial_below the spatial prepare runs in the elementwise one's place and d_sum_sq (d_m2) is not read and may be
-// null; otherwise the call is the means form's, launch for launch.  Its checks sit behind the sample count's and before the filter's params.
-// `stack` (rt_denoise_views_device, rt_denoise_albedo_views_device; sums form, no map) is a stack of n_views frames, view-major in every
-// buffer and in every region of the workspace, filtered in the same K + 1 launches with the view on the grid's second dimension; its
-// count is checked behind the frame size.  Null is the single frame: a stack of one, launch for launch.
-// `edge` (rt_denoise_guided_device and its _mean, _mean_spatial and _views forms) is the edge guide, with or without `guide`; its region is
-// set here, the third of the workspace alone and the fourth beside the albedo guide's.  Each of its checks sits behind the albedo guide's
-// of the same kind.  In the means forms its frame holds means, as the albedo guide's does, and its count is neither read nor checked.
-enum class DenoiseInput { Sums, Means };
-struct SpatialRoute {
+// Every denoise entry point is one DenoiseCall handed to run_denoise: every check in the header's order, each message under the caller's
+// name `who` and with the inputs named as the caller names them, then prepare and the K iterations.  What a call does not have is a null
+// pointer or an empty optional.  Each check of the edge guide sits behind the albedo guide's of the same kind.
+enum class DenoiseInput { Sums, Means }; // sums and sums of squares with a count or a map, or running means and M2 after `count` samples
+struct GuideFrame {
+    const double *frame; // 3 w h doubles per view, null is refused: sums of `count` samples or, in the means forms, means
+    double count;        // the divisor (means forms: 1.0, neither read nor checked)
+};
+struct SpatialRoute { // with count < spatial_below the spatial prepare runs in the elementwise one's place, and `second` may be null
     rt_denoise_spatial_params params;
     bool known; // its struct_size is one this library knows
 };
-int run_denoise(const char *who, DenoiseInput form, int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp,
-                const int32_t *d_spp, DenoiseGuide *guide, const rt_denoise_params *d, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
-                void *hip_stream, const SpatialRoute *spatial = nullptr, const int32_t *stack = nullptr, DenoiseEdge *edge = nullptr) {
-    const std::string w(who);
-    const bool means = form == DenoiseInput::Means;
+struct DenoiseCall {
+    const char *who;
+    DenoiseInput form;
+    int32_t width, height;
+    std::optional<int32_t> n_views; // the views forms: a stack, view-major in every buffer and every region of the workspace, filtered in the same K + 1 launches
+    const double *first, *second;   // d_sum and d_sum_sq, or d_mean and d_m2
+    int32_t count;                  // spp, or samples
+    const int32_t *spp_map;         // sums form, or null
+    std::optional<GuideFrame> albedo, edge;
+    std::optional<SpatialRoute> spatial; // the *_mean_spatial entry points
+    rt_denoise_guided_params filter;     // the caller's params over the defaults, as denoise_with resolved them; refused in their place among the checks
+    bool filter_known;                   // if their struct_size was not known
+    const char *filter_name;             // the C name of the struct that arrived
+    double *out;
+    uint8_t *rgba8;
+    void *workspace, *stream;
+};
+int run_denoise(const DenoiseCall &c) {
+    const std::string w(c.who);
+    const bool means = c.form == DenoiseInput::Means;
     const char *first = means ? "d_mean" : "d_sum", *second = means ? "d_m2" : "d_sum_sq", *third = means ? "d_albedo_mean" : "d_albedo_sum",
                *fourth = means ? "d_edge_mean" : "d_edge_sum";
+    const rt_denoise_guided_params &d = c.filter;
+    const int32_t width = c.width, height = c.height;
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= ((int64_t)1 << 27)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
-    if (stack && *stack < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
-    if (stack && *stack > RT_DENOISE_MAX_VIEWS)
+    if (c.n_views && *c.n_views < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at least 1");
+    if (c.n_views && *c.n_views > RT_DENOISE_MAX_VIEWS)
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": n_views must be at most " + std::to_string(RT_DENOISE_MAX_VIEWS) + " (the launch grid's second dimension)");
-    const int32_t n_views = stack ? *stack : 1;
-    if (!d_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
-    if (!d_sum_sq && !spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
-    if (guide && !guide->albedo_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
-    if (edge && !edge->edge_sum) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + fourth + " is null");
-    if (!d_mean_out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
-    if (!d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
-    if (means && spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
-    if (!means && !d_spp && spp < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples)" + (stack ? "" : " when d_spp is null"));
-    if (!means && guide && guide->albedo_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
-    if (!means && edge && edge->edge_spp < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": edge_spp must be at least 1");
+    const int32_t n_views = c.n_views.value_or(1);
+    if (!c.first) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + first + " is null");
+    if (!c.second && !c.spatial) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null");
+    if (c.albedo && !c.albedo->frame) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + third + " is null");
+    if (c.edge && !c.edge->frame) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + fourth + " is null");
+    if (!c.out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out is null");
+    if (!c.workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null");
+    if (means && c.count < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": samples must be at least 1 (the number of samples in d_mean)");
+    if (!means && !c.spp_map && c.count < 2) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 2 (a variance needs two samples)" + (c.n_views ? "" : " when d_spp is null"));
+    if (!means && c.albedo && c.albedo->count < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_spp must be at least 1");
+    if (!means && c.edge && c.edge->count < 1.0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": edge_spp must be at least 1");
     bool spatial_route = false;
-    if (spatial) {
-        const rt_denoise_spatial_params &sp = spatial->params;
-        if (!spatial->known) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_spatial_params.struct_size is not one this library knows");
+    if (c.spatial) {
+        const rt_denoise_spatial_params &sp = c.spatial->params;
+        if (!c.spatial->known) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_denoise_spatial_params.struct_size is not one this library knows");
         if (sp.spatial_below < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spatial_below must be at least 1");
         if (sp.window_radius < 1 || sp.window_radius > 3) return fail(RT_ERR_INVALID_ARGUMENT, w + ": window_radius must be 1..3");
-        spatial_route = spp < sp.spatial_below;
-        if (!spatial_route && !d_sum_sq)
+        spatial_route = c.count < sp.spatial_below;
+        if (!spatial_route && !c.second)
             return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + second + " is null (it is read when samples >= spatial_below)");
     }
-    if (!d)
-        return fail(RT_ERR_INVALID_ARGUMENT, w + (edge ? ": rt_denoise_guided_params" : guide ? ": rt_denoise_albedo_params" : ": rt_denoise_params") + ".struct_size is not one this library knows");
-    if (d->iterations < 1 || d->iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
-    if (!(d->sigma > 0.0) || !std::isfinite(d->sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
-    if (!(d->eps > 0.0) || !std::isfinite(d->eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
-    if (guide && (!(guide->sigma_albedo > 0.0) || !std::isfinite(guide->sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
-    if (guide && (!(guide->albedo_floor > 0.0) || !std::isfinite(guide->albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
-    if (edge && (!(edge->sigma_edge > 0.0) || !std::isfinite(edge->sigma_edge))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_edge must be a number > 0");
+    if (!c.filter_known) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + c.filter_name + ".struct_size is not one this library knows");
+    if (d.iterations < 1 || d.iterations > 6) return fail(RT_ERR_INVALID_ARGUMENT, w + ": iterations must be 1..6");
+    if (!(d.sigma > 0.0) || !std::isfinite(d.sigma)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma must be a number > 0");
+    if (!(d.eps > 0.0) || !std::isfinite(d.eps)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": eps must be a number > 0");
+    if (c.albedo && (!(d.sigma_albedo > 0.0) || !std::isfinite(d.sigma_albedo))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_albedo must be a number > 0");
+    if (c.albedo && (!(d.albedo_floor > 0.0) || !std::isfinite(d.albedo_floor))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": albedo_floor must be a number > 0");
+    if (c.edge && (!(d.sigma_edge > 0.0) || !std::isfinite(d.sigma_edge))) return fail(RT_ERR_INVALID_ARGUMENT, w + ": sigma_edge must be a number > 0");
     const size_t n_pix = (size_t)width * (size_t)height, frame_bytes = (size_t)n_views * n_pix * 3u * sizeof(double); // (the whole stack's)
-    if (overlaps(d_mean_out, frame_bytes, d_sum, frame_bytes) || (d_sum_sq && overlaps(d_mean_out, frame_bytes, d_sum_sq, frame_bytes)) ||
-        (guide && overlaps(d_mean_out, frame_bytes, guide->albedo_sum, frame_bytes)))
-        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (guide ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
-    if (edge && overlaps(d_mean_out, frame_bytes, edge->edge_sum, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + fourth);
-    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
-    if (((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
-    if (int rc = select_device_of(d_mean_out, who)) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const size_t region = (size_t)n_views * n_pix * 4u * sizeof(double); // the workspace: two halves and, guided, the guide behind them
-    char *half[2] = {(char *)d_workspace, (char *)d_workspace + region};
-    if (guide) guide->region = (double4 *)((char *)d_workspace + 2u * region);
-    if (edge) edge->region = (double4 *)((char *)d_workspace + (guide ? 3u : 2u) * region); // (alone: the albedo guide's place)
-    if (spatial_route) launch_denoise_prepare_spatial(width, height, spatial->params.window_radius, d_sum, guide, half[0], stream, edge);
-    else launch_denoise_prepare((int64_t)n_pix, n_views, d_sum, d_sum_sq, spp, d_spp, guide, means, half[0], stream, edge);
+    if (overlaps(c.out, frame_bytes, c.first, frame_bytes) || (c.second && overlaps(c.out, frame_bytes, c.second, frame_bytes)) ||
+        (c.albedo && overlaps(c.out, frame_bytes, c.albedo->frame, frame_bytes)))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + first + (c.albedo ? std::string(", ") + second + " or " + third : std::string(" or ") + second));
+    if (c.edge && overlaps(c.out, frame_bytes, c.edge->frame, frame_bytes)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_mean_out must not overlap " + fourth);
+    if (((uintptr_t)c.rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    if (((uintptr_t)c.workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (int rc = select_device_of(c.out, c.who)) return rc;
+    hipStream_t stream = (hipStream_t)c.stream;
+    // the workspace: two halves and behind them the guides' regions, the albedo guide's third; the edge guide's is the third alone and the fourth beside it
+    const size_t region = (size_t)n_views * n_pix * 4u * sizeof(double);
+    char *half[2] = {(char *)c.workspace, (char *)c.workspace + region};
+    DenoiseGuide albedo_guide{};
+    DenoiseEdge edge_guide{};
+    if (c.albedo) albedo_guide = {c.albedo->frame, c.albedo->count, d.albedo_floor, d.sigma_albedo, (double4 *)((char *)c.workspace + 2u * region)};
+    if (c.edge) edge_guide = {c.edge->frame, c.edge->count, d.sigma_edge, (double4 *)((char *)c.workspace + (c.albedo ? 3u : 2u) * region)};
+    const DenoiseGuide *guide = c.albedo ? &albedo_guide : nullptr;
+    const DenoiseEdge *edge = c.edge ? &edge_guide : nullptr;
+    if (spatial_route) launch_denoise_prepare_spatial(width, height, c.spatial->params.window_radius, c.first, guide, half[0], stream, edge);
+    else launch_denoise_prepare((int64_t)n_pix, n_views, c.first, c.second, c.count, c.spp_map, guide, means, half[0], stream, edge);
     HIP_TRY(hipGetLastError());
-    for (int32_t k = 0; k < d->iterations; ++k) {
-        const bool last = k == d->iterations - 1;
-        launch_denoise_atrous(width, height, n_views, (int32_t)1 << k, d->sigma, d->eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
-                              last ? d_mean_out : nullptr, last ? d_rgba8 : nullptr, stream, edge);
+    for (int32_t k = 0; k < d.iterations; ++k) {
+        const bool last = k == d.iterations - 1;
+        launch_denoise_atrous(width, height, n_views, (int32_t)1 << k, d.sigma, d.eps, guide, half[k & 1], last ? nullptr : half[(k + 1) & 1],
+                              last ? c.out : nullptr, last ? c.rgba8 : nullptr, stream, edge);
         HIP_TRY(hipGetLastError());
     }
     return RT_OK;
 }
+// An entry point's call: the caller's filter params — any of the three structs, each the next one's first fields — over the defaults in the
+// description, with whether their size was known and the struct's C name; then the description is run.
+// (Templates, and what the dynamic symbol table is not to list: C++ linkage inside this file's extern "C".)
+extern "C++" {
+constexpr const char *denoise_params_name(const rt_denoise_params *) { return "rt_denoise_params"; }
+constexpr const char *denoise_params_name(const rt_denoise_albedo_params *) { return "rt_denoise_albedo_params"; }
+constexpr const char *denoise_params_name(const rt_denoise_guided_params *) { return "rt_denoise_guided_params"; }
+template <class P> int denoise_with(const P *params, DenoiseCall call) {
+    static_assert(offsetof(rt_denoise_albedo_params, sigma_albedo) == sizeof(rt_denoise_params) &&
+                  offsetof(rt_denoise_guided_params, sigma_edge) == sizeof(rt_denoise_albedo_params), "each params struct extends the one before");
+    P d;
+    call.filter_known = denoise_params_resolve(params, d);
+    call.filter_name = denoise_params_name(params);
+    denoise_defaults(call.filter);
+    memcpy(&call.filter, &d, sizeof d); // the fields P has
+    return run_denoise(call);
+}
+// rt_denoise_guided_*: the albedo guide is there only with its frame (rt_denoise_albedo_*: always, and a null frame is refused)
+std::optional<GuideFrame> guide_if(const double *frame, double count) { return frame ? std::optional<GuideFrame>(GuideFrame{frame, count}) : std::nullopt; }
+SpatialRoute spatial_route_of(const rt_denoise_spatial_params *spatial) {
+    SpatialRoute route;
+    route.known = denoise_params_resolve(spatial, route.params);
+    return route;
+}
+} // extern "C++"
 } // namespace
 
 int rt_render_moments_device(const rt_scene *scene, const rt_camera *camera, const rt_render_params *params, double *d_sum, double *d_sum_sq,
@@ -1748,10 +1788,8 @@ int64_t rt_denoise_workspace_bytes(int32_t width, int32_t height) { return denoi
 
 int rt_denoise_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                       const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_params d;
-    const bool known = denoise_params_resolve(params, d);
-    return run_denoise("rt_denoise_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, nullptr, known ? &d : nullptr, d_mean_out,
-                       d_rgba8, d_workspace, hip_stream);
+    return denoise_with(params, {.who = "rt_denoise_device", .form = DenoiseInput::Sums, .width = width, .height = height, .first = d_sum, .second = d_sum_sq,
+                                 .count = spp, .spp_map = d_spp, .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int64_t rt_denoise_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views) {
@@ -1760,18 +1798,14 @@ int64_t rt_denoise_views_workspace_bytes(int32_t width, int32_t height, int32_t 
 
 int rt_denoise_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                             const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_params d;
-    const bool known = denoise_params_resolve(params, d);
-    return run_denoise("rt_denoise_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, nullptr, known ? &d : nullptr,
-                       d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views);
+    return denoise_with(params, {.who = "rt_denoise_views_device", .form = DenoiseInput::Sums, .width = width, .height = height, .n_views = n_views, .first = d_sum,
+                                 .second = d_sum_sq, .count = spp, .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_denoise_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const rt_denoise_params *params,
                            double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_params d;
-    const bool known = denoise_params_resolve(params, d);
-    return run_denoise("rt_denoise_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, nullptr, known ? &d : nullptr,
-                       d_mean_out, d_rgba8, d_workspace, hip_stream);
+    return denoise_with(params, {.who = "rt_denoise_mean_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean, .second = d_m2,
+                                 .count = samples, .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_denoise_spatial_params_init_sized(rt_denoise_spatial_params *params, uint32_t struct_size) {
@@ -1781,12 +1815,9 @@ int rt_denoise_spatial_params_init_sized(rt_denoise_spatial_params *params, uint
 int rt_denoise_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                    const rt_denoise_spatial_params *spatial, const rt_denoise_params *params, double *d_mean_out, uint8_t *d_rgba8,
                                    void *d_workspace, void *hip_stream) {
-    rt_denoise_params d;
-    const bool known = denoise_params_resolve(params, d);
-    SpatialRoute route;
-    route.known = denoise_params_resolve(spatial, route.params);
-    return run_denoise("rt_denoise_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, nullptr,
-                       known ? &d : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route);
+    return denoise_with(params, {.who = "rt_denoise_mean_spatial_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean,
+                                 .second = d_m2, .count = samples, .spatial = spatial_route_of(spatial), .out = d_mean_out, .rgba8 = d_rgba8,
+                                 .workspace = d_workspace, .stream = hip_stream});
 }
 
 // ---- albedo scene and the albedo-guided filter (rt_denoise.hip, with a guide) ----
@@ -1869,12 +1900,9 @@ int64_t rt_denoise_albedo_workspace_bytes(int32_t width, int32_t height) { retur
 int rt_denoise_albedo_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                              const double *d_albedo_sum, int32_t albedo_spp, const rt_denoise_albedo_params *params, double *d_mean_out,
                              uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_albedo_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
-    return run_denoise("rt_denoise_albedo_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, &guide, known ? &shared : nullptr,
-                       d_mean_out, d_rgba8, d_workspace, hip_stream);
+    return denoise_with(params, {.who = "rt_denoise_albedo_device", .form = DenoiseInput::Sums, .width = width, .height = height, .first = d_sum, .second = d_sum_sq,
+                                 .count = spp, .spp_map = d_spp, .albedo = GuideFrame{d_albedo_sum, (double)albedo_spp}, .out = d_mean_out, .rgba8 = d_rgba8,
+                                 .workspace = d_workspace, .stream = hip_stream});
 }
 
 int64_t rt_denoise_albedo_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views) {
@@ -1884,35 +1912,24 @@ int64_t rt_denoise_albedo_views_workspace_bytes(int32_t width, int32_t height, i
 int rt_denoise_albedo_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                    const double *d_albedo_sum, int32_t albedo_spp, const rt_denoise_albedo_params *params, double *d_mean_out,
                                    uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_albedo_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
-    return run_denoise("rt_denoise_albedo_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, &guide,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views);
+    return denoise_with(params, {.who = "rt_denoise_albedo_views_device", .form = DenoiseInput::Sums, .width = width, .height = height, .n_views = n_views,
+                                 .first = d_sum, .second = d_sum_sq, .count = spp, .albedo = GuideFrame{d_albedo_sum, (double)albedo_spp}, .out = d_mean_out,
+                                 .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_denoise_albedo_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const double *d_albedo_mean,
                                   const rt_denoise_albedo_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_albedo_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr}; // (a frame of means: no count, nothing is divided)
-    return run_denoise("rt_denoise_albedo_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream);
+    return denoise_with(params, {.who = "rt_denoise_albedo_mean_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean,
+                                 .second = d_m2, .count = samples, .albedo = GuideFrame{d_albedo_mean, 1.0}, .out = d_mean_out, .rgba8 = d_rgba8,
+                                 .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_denoise_albedo_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                           const double *d_albedo_mean, const rt_denoise_spatial_params *spatial, const rt_denoise_albedo_params *params,
                                           double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_albedo_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr};
-    SpatialRoute route;
-    route.known = denoise_params_resolve(spatial, route.params);
-    return run_denoise("rt_denoise_albedo_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, &guide,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route);
+    return denoise_with(params, {.who = "rt_denoise_albedo_mean_spatial_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean,
+                                 .second = d_m2, .count = samples, .albedo = GuideFrame{d_albedo_mean, 1.0}, .spatial = spatial_route_of(spatial), .out = d_mean_out,
+                                 .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 // ---- surface-ID scene and the edge-guided filter (rt_denoise.hip, with an edge guide) ----
@@ -1995,41 +2012,27 @@ int64_t rt_denoise_guided_workspace_bytes(int32_t width, int32_t height, int32_t
 int rt_denoise_guided_device(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                              const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
                              const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_guided_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr}; // (used only with an albedo frame)
-    DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
-    return run_denoise("rt_denoise_guided_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum ? &guide : nullptr,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
+    return denoise_with(params, {.who = "rt_denoise_guided_device", .form = DenoiseInput::Sums, .width = width, .height = height, .first = d_sum, .second = d_sum_sq,
+                                 .count = spp, .spp_map = d_spp, .albedo = guide_if(d_albedo_sum, albedo_spp), .edge = GuideFrame{d_edge_sum, (double)edge_spp},
+                                 .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 // the edge guide on the other routes (include/rt_amd.h "edge guide on every route"): the means, spatial-variance and views forms
 int rt_denoise_guided_mean_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const double *d_albedo_mean,
                                   const double *d_edge_mean, const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8,
                                   void *d_workspace, void *hip_stream) {
-    rt_denoise_guided_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr}; // (used only with an albedo frame)
-    DenoiseEdge edge{d_edge_mean, 1.0, d.sigma_edge, nullptr};
-    return run_denoise("rt_denoise_guided_mean_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr, d_albedo_mean ? &guide : nullptr,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, nullptr, &edge);
+    return denoise_with(params, {.who = "rt_denoise_guided_mean_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean,
+                                 .second = d_m2, .count = samples, .albedo = guide_if(d_albedo_mean, 1.0), .edge = GuideFrame{d_edge_mean, 1.0}, .out = d_mean_out,
+                                 .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_denoise_guided_mean_spatial_device(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                           const double *d_albedo_mean, const double *d_edge_mean, const rt_denoise_spatial_params *spatial,
                                           const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace,
                                           void *hip_stream) {
-    rt_denoise_guided_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_mean, 1.0, d.albedo_floor, d.sigma_albedo, nullptr};
-    DenoiseEdge edge{d_edge_mean, 1.0, d.sigma_edge, nullptr};
-    SpatialRoute route;
-    route.known = denoise_params_resolve(spatial, route.params);
-    return run_denoise("rt_denoise_guided_mean_spatial_device", DenoiseInput::Means, width, height, d_mean, d_m2, samples, nullptr,
-                       d_albedo_mean ? &guide : nullptr, known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, &route, nullptr, &edge);
+    return denoise_with(params, {.who = "rt_denoise_guided_mean_spatial_device", .form = DenoiseInput::Means, .width = width, .height = height, .first = d_mean,
+                                 .second = d_m2, .count = samples, .albedo = guide_if(d_albedo_mean, 1.0), .edge = GuideFrame{d_edge_mean, 1.0},
+                                 .spatial = spatial_route_of(spatial), .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int64_t rt_denoise_guided_views_workspace_bytes(int32_t width, int32_t height, int32_t n_views, int32_t with_albedo) {
@@ -2039,13 +2042,10 @@ int64_t rt_denoise_guided_views_workspace_bytes(int32_t width, int32_t height, i
 int rt_denoise_guided_views_device(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                    const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
                                    const rt_denoise_guided_params *params, double *d_mean_out, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    rt_denoise_guided_params d;
-    const bool known = denoise_params_resolve(params, d);
-    const rt_denoise_params shared{d.struct_size, d.iterations, d.sigma, d.eps};
-    DenoiseGuide guide{d_albedo_sum, (double)albedo_spp, d.albedo_floor, d.sigma_albedo, nullptr};
-    DenoiseEdge edge{d_edge_sum, (double)edge_spp, d.sigma_edge, nullptr};
-    return run_denoise("rt_denoise_guided_views_device", DenoiseInput::Sums, width, height, d_sum, d_sum_sq, spp, nullptr, d_albedo_sum ? &guide : nullptr,
-                       known ? &shared : nullptr, d_mean_out, d_rgba8, d_workspace, hip_stream, nullptr, &n_views, &edge);
+    return denoise_with(params, {.who = "rt_denoise_guided_views_device", .form = DenoiseInput::Sums, .width = width, .height = height, .n_views = n_views,
+                                 .first = d_sum, .second = d_sum_sq, .count = spp, .albedo = guide_if(d_albedo_sum, albedo_spp),
+                                 .edge = GuideFrame{d_edge_sum, (double)edge_spp}, .out = d_mean_out, .rgba8 = d_rgba8, .workspace = d_workspace,
+                                 .stream = hip_stream});
 }
 
 // ---- tone mapping (rt_tonemap.hip): exposure and a tone curve in front of the output stage's gamma, auto-exposure from a device reduction ----

@@ -5,7 +5,9 @@
 #include "rt_host.h"
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <thread>
 
@@ -254,12 +256,103 @@ void upsample_device(int32_t width, int32_t height, const double *d_low, int32_t
     rt_device_free(0, d_work);
 }
 
-// what denoise and denoise_albedo share: the outputs and the workspace on device 0, the call, the display bytes back as RGB
-// (n_frames: the views forms' stack of frames, one behind the other in every buffer).  With the tone-mapping stage on, the filter
-// writes no bytes (a null d_rgba8) and the stage makes them from the filtered means, every frame of a stack as a frame of its own.
-static std::vector<uint8_t> run_denoise(const char *who, const RenderOptions &opt, int32_t width, int32_t height, int64_t work,
-                                        const std::function<int(double *, uint8_t *, void *)> &call, int32_t n_frames = 1) {
-    const int64_t n_pix = (int64_t)width * height * n_frames;
+// One description of a denoise request on device 0, behind every rt::denoise* below, live_render and the upsample route.
+enum class DenoiseForm { Sums, Means, Views };   // Views: a stack of n_views frames of sums, one behind the other in every buffer
+enum class DenoiseGuides { None, Albedo, Edge }; // Edge: rt_denoise_guided_*, with the albedo guide as well where its frame is not null
+struct DenoiseRequest {
+    DenoiseForm form;
+    DenoiseGuides guides;
+    int32_t width, height;
+    const double *first, *second;     // sums and sums of squares, or running means and M2
+    int32_t count;                    // spp, or samples
+    const int32_t *spp_map = nullptr; // Sums only
+    const double *albedo = nullptr;   // (the counts: Sums and Views only)
+    int32_t albedo_count = 0;
+    const double *edge = nullptr;
+    int32_t edge_count = 0;
+    bool spatial = false; // Means only: through the *_mean_spatial entry points
+    int32_t n_views = 1;  // Views only
+};
+
+// the spatial route's params from the options (live_denoise_spatial 0: the library's threshold)
+static int spatial_params(const RenderOptions &opt, rt_denoise_spatial_params *sp) {
+    if (int rc = rt_denoise_spatial_params_init_sized(sp, sizeof *sp)) return rc;
+    if (opt.live_denoise_spatial > 0) sp->spatial_below = opt.live_denoise_spatial;
+    sp->window_radius = opt.denoise_spatial_radius;
+    return RT_OK;
+}
+
+// the albedo-guided and the plain filter's params from the edge-guided one's: each struct is the next one's first fields
+static_assert(offsetof(rt_denoise_albedo_params, sigma_albedo) == sizeof(rt_denoise_params) &&
+              offsetof(rt_denoise_guided_params, sigma_edge) == sizeof(rt_denoise_albedo_params), "the denoise params structs extend one another");
+template <class P> static P narrowed(const rt_denoise_guided_params &gp) {
+    P p;
+    memcpy(&p, &gp, sizeof p);
+    p.struct_size = (uint32_t)sizeof p;
+    return p;
+}
+
+// The request's workspace in bytes (-1: a size the library refuses), and the request itself into device buffers: the filter's params from
+// the options, and the C entry point of the request's form and guides.  Returns the library's code; rt_last_error() has the text.
+static int64_t denoise_workspace_bytes(const DenoiseRequest &r) {
+    const bool views = r.form == DenoiseForm::Views;
+    switch (r.guides) {
+    case DenoiseGuides::None: return views ? rt_denoise_views_workspace_bytes(r.width, r.height, r.n_views) : rt_denoise_workspace_bytes(r.width, r.height);
+    case DenoiseGuides::Albedo:
+        return views ? rt_denoise_albedo_views_workspace_bytes(r.width, r.height, r.n_views) : rt_denoise_albedo_workspace_bytes(r.width, r.height);
+    default:
+        return views ? rt_denoise_guided_views_workspace_bytes(r.width, r.height, r.n_views, r.albedo != nullptr)
+                     : rt_denoise_guided_workspace_bytes(r.width, r.height, r.albedo != nullptr);
+    }
+}
+static int denoise_into(const DenoiseRequest &r, const RenderOptions &opt, double *d_out, uint8_t *d_rgba8, void *d_work) {
+    rt_denoise_guided_params gp;
+    if (int rc = rt_denoise_guided_params_init_sized(&gp, sizeof gp)) return rc;
+    gp.iterations = opt.denoise_iters; gp.sigma = opt.denoise_sigma; gp.sigma_albedo = opt.denoise_albedo_sigma; gp.sigma_edge = opt.denoise_edges_sigma;
+    const rt_denoise_albedo_params ap = narrowed<rt_denoise_albedo_params>(gp);
+    const rt_denoise_params pp = narrowed<rt_denoise_params>(gp);
+    rt_denoise_spatial_params sp{};
+    if (r.spatial)
+        if (int rc = spatial_params(opt, &sp)) return rc;
+    const int32_t w = r.width, h = r.height, n = r.count;
+    const double *A = r.albedo, *E = r.edge;
+    switch (r.form) {
+    case DenoiseForm::Sums:
+        switch (r.guides) {
+        case DenoiseGuides::None: return rt_denoise_device(w, h, r.first, r.second, n, r.spp_map, &pp, d_out, d_rgba8, d_work, nullptr);
+        case DenoiseGuides::Albedo: return rt_denoise_albedo_device(w, h, r.first, r.second, n, r.spp_map, A, r.albedo_count, &ap, d_out, d_rgba8, d_work, nullptr);
+        default: return rt_denoise_guided_device(w, h, r.first, r.second, n, r.spp_map, A, r.albedo_count, E, r.edge_count, &gp, d_out, d_rgba8, d_work, nullptr);
+        }
+    case DenoiseForm::Views:
+        switch (r.guides) {
+        case DenoiseGuides::None: return rt_denoise_views_device(w, h, r.n_views, r.first, r.second, n, &pp, d_out, d_rgba8, d_work, nullptr);
+        case DenoiseGuides::Albedo:
+            return rt_denoise_albedo_views_device(w, h, r.n_views, r.first, r.second, n, A, r.albedo_count, &ap, d_out, d_rgba8, d_work, nullptr);
+        default:
+            return rt_denoise_guided_views_device(w, h, r.n_views, r.first, r.second, n, A, r.albedo_count, E, r.edge_count, &gp, d_out, d_rgba8, d_work, nullptr);
+        }
+    default:
+        switch (r.guides) {
+        case DenoiseGuides::None:
+            return r.spatial ? rt_denoise_mean_spatial_device(w, h, r.first, r.second, n, &sp, &pp, d_out, d_rgba8, d_work, nullptr)
+                             : rt_denoise_mean_device(w, h, r.first, r.second, n, &pp, d_out, d_rgba8, d_work, nullptr);
+        case DenoiseGuides::Albedo:
+            return r.spatial ? rt_denoise_albedo_mean_spatial_device(w, h, r.first, r.second, n, A, &sp, &ap, d_out, d_rgba8, d_work, nullptr)
+                             : rt_denoise_albedo_mean_device(w, h, r.first, r.second, n, A, &ap, d_out, d_rgba8, d_work, nullptr);
+        default:
+            return r.spatial ? rt_denoise_guided_mean_spatial_device(w, h, r.first, r.second, n, A, E, &sp, &gp, d_out, d_rgba8, d_work, nullptr)
+                             : rt_denoise_guided_mean_device(w, h, r.first, r.second, n, A, E, &gp, d_out, d_rgba8, d_work, nullptr);
+        }
+    }
+}
+
+// what every rt::denoise* is: the output and the workspace on device 0, the request run into them, the display bytes back as RGB, every
+// frame of a stack behind the one before.  With the tone-mapping stage on, the filter writes no bytes (a null d_rgba8) and the stage makes
+// them from the filtered means, every frame of a stack as a frame of its own.
+static std::vector<uint8_t> run_denoise(const char *who, const DenoiseRequest &r, const RenderOptions &opt) {
+    const int32_t width = r.width, height = r.height, n_frames = r.n_views;
+    if (n_frames < 1) throw std::runtime_error(std::string(who) + ": n_views must be at least 1");
+    const int64_t n_pix = (int64_t)width * height * n_frames, work = denoise_workspace_bytes(r);
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_work = nullptr;
     auto cleanup = [&]() { rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_work); };
     auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error(std::string(who) + ": " + msg); } };
@@ -267,7 +360,7 @@ static std::vector<uint8_t> run_denoise(const char *who, const RenderOptions &op
     check(rt_device_malloc(0, n_pix * 3 * (int64_t)sizeof(double), &d_mean));
     if (!tonemapped(opt)) check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
     check(rt_device_malloc(0, work, &d_work));
-    check(call(static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work));
+    check(denoise_into(r, opt, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work));
     if (tonemapped(opt)) {
         std::vector<uint8_t> rgb;
         try {
@@ -290,148 +383,72 @@ static std::vector<uint8_t> run_denoise(const char *who, const RenderOptions &op
 
 std::vector<uint8_t> denoise(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                              const RenderOptions &opt) {
-    rt_denoise_params dp;
-    if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise: ") + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
-    return run_denoise("denoise", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_device(width, height, d_sum, d_sum_sq, spp, d_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
-    });
+    return run_denoise("denoise", {.form = DenoiseForm::Sums, .guides = DenoiseGuides::None, .width = width, .height = height, .first = d_sum,
+                                   .second = d_sum_sq, .count = spp, .spp_map = d_spp}, opt);
 }
 
 std::vector<uint8_t> denoise_albedo(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                                     const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt) {
-    rt_denoise_albedo_params dp;
-    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo: ") + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
-    return run_denoise("denoise_albedo", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_albedo_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
-    });
+    return run_denoise("denoise_albedo", {.form = DenoiseForm::Sums, .guides = DenoiseGuides::Albedo, .width = width, .height = height, .first = d_sum,
+                                          .second = d_sum_sq, .count = spp, .spp_map = d_spp, .albedo = d_albedo_sum, .albedo_count = albedo_spp}, opt);
 }
 
 std::vector<uint8_t> denoise_guided(int32_t width, int32_t height, const double *d_sum, const double *d_sum_sq, int32_t spp, const int32_t *d_spp,
                                     const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp, const RenderOptions &opt) {
-    rt_denoise_guided_params dp;
-    if (rt_denoise_guided_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_guided: ") + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
-    return run_denoise("denoise_guided", opt, width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_sum != nullptr),
-                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-                           return rt_denoise_guided_device(width, height, d_sum, d_sum_sq, spp, d_spp, d_albedo_sum, albedo_spp, d_edge_sum, edge_spp, &dp,
-                                                           d_mean, d_rgba8, d_work, nullptr);
-                       });
+    return run_denoise("denoise_guided", {.form = DenoiseForm::Sums, .guides = DenoiseGuides::Edge, .width = width, .height = height, .first = d_sum,
+                                          .second = d_sum_sq, .count = spp, .spp_map = d_spp, .albedo = d_albedo_sum, .albedo_count = albedo_spp,
+                                          .edge = d_edge_sum, .edge_count = edge_spp}, opt);
 }
 
 std::vector<uint8_t> denoise_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                    const RenderOptions &opt) {
-    rt_denoise_params dp;
-    if (rt_denoise_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_views: ") + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma;
-    if (n_views < 1) throw std::runtime_error("denoise_views: n_views must be at least 1");
-    return run_denoise("denoise_views", opt, width, height, rt_denoise_views_workspace_bytes(width, height, n_views), [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_views_device(width, height, n_views, d_sum, d_sum_sq, spp, &dp, d_mean, d_rgba8, d_work, nullptr);
-    }, n_views);
+    return run_denoise("denoise_views", {.form = DenoiseForm::Views, .guides = DenoiseGuides::None, .width = width, .height = height, .first = d_sum,
+                                         .second = d_sum_sq, .count = spp, .n_views = n_views}, opt);
 }
 
 std::vector<uint8_t> denoise_albedo_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                           const double *d_albedo_sum, int32_t albedo_spp, const RenderOptions &opt) {
-    rt_denoise_albedo_params dp;
-    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string("denoise_albedo_views: ") + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
-    if (n_views < 1) throw std::runtime_error("denoise_albedo_views: n_views must be at least 1");
-    return run_denoise("denoise_albedo_views", opt, width, height, rt_denoise_albedo_views_workspace_bytes(width, height, n_views),
-                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-                           return rt_denoise_albedo_views_device(width, height, n_views, d_sum, d_sum_sq, spp, d_albedo_sum, albedo_spp, &dp, d_mean,
-                                                                 d_rgba8, d_work, nullptr);
-                       }, n_views);
-}
-
-// the params of the two filters from the options (the plain filter's are the guided one's first fields)
-static rt_denoise_albedo_params filter_params(const char *who, const RenderOptions &opt) {
-    rt_denoise_albedo_params dp;
-    if (rt_denoise_albedo_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma;
-    return dp;
-}
-static rt_denoise_params plain_params(const rt_denoise_albedo_params &dp) {
-    return rt_denoise_params{(uint32_t)sizeof(rt_denoise_params), dp.iterations, dp.sigma, dp.eps};
+    return run_denoise("denoise_albedo_views", {.form = DenoiseForm::Views, .guides = DenoiseGuides::Albedo, .width = width, .height = height,
+                                                .first = d_sum, .second = d_sum_sq, .count = spp, .albedo = d_albedo_sum, .albedo_count = albedo_spp,
+                                                .n_views = n_views}, opt);
 }
 
 std::vector<uint8_t> denoise_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples, const RenderOptions &opt) {
-    const rt_denoise_params dp = plain_params(filter_params("denoise_mean", opt));
-    return run_denoise("denoise_mean", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_mean_device(width, height, d_mean, d_m2, samples, &dp, d_out, d_rgba8, d_work, nullptr);
-    });
+    return run_denoise("denoise_mean", {.form = DenoiseForm::Means, .guides = DenoiseGuides::None, .width = width, .height = height, .first = d_mean,
+                                        .second = d_m2, .count = samples}, opt);
 }
 
 std::vector<uint8_t> denoise_albedo_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                          const double *d_albedo_mean, const RenderOptions &opt) {
-    const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean", opt);
-    return run_denoise("denoise_albedo_mean", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_albedo_mean_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &dp, d_out, d_rgba8, d_work, nullptr);
-    });
-}
-
-// the spatial route's params from the options (live_denoise_spatial 0: the library's threshold)
-static rt_denoise_spatial_params spatial_params(const char *who, const RenderOptions &opt) {
-    rt_denoise_spatial_params sp;
-    if (rt_denoise_spatial_params_init_sized(&sp, sizeof sp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
-    if (opt.live_denoise_spatial > 0) sp.spatial_below = opt.live_denoise_spatial;
-    sp.window_radius = opt.denoise_spatial_radius;
-    return sp;
+    return run_denoise("denoise_albedo_mean", {.form = DenoiseForm::Means, .guides = DenoiseGuides::Albedo, .width = width, .height = height,
+                                               .first = d_mean, .second = d_m2, .count = samples, .albedo = d_albedo_mean}, opt);
 }
 
 std::vector<uint8_t> denoise_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                           const RenderOptions &opt) {
-    const rt_denoise_params dp = plain_params(filter_params("denoise_mean_spatial", opt));
-    const rt_denoise_spatial_params sp = spatial_params("denoise_mean_spatial", opt);
-    return run_denoise("denoise_mean_spatial", opt, width, height, rt_denoise_workspace_bytes(width, height), [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
-        return rt_denoise_mean_spatial_device(width, height, d_mean, d_m2, samples, &sp, &dp, d_out, d_rgba8, d_work, nullptr);
-    });
+    return run_denoise("denoise_mean_spatial", {.form = DenoiseForm::Means, .guides = DenoiseGuides::None, .width = width, .height = height,
+                                                .first = d_mean, .second = d_m2, .count = samples, .spatial = true}, opt);
 }
 
 std::vector<uint8_t> denoise_albedo_mean_spatial(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                                  const double *d_albedo_mean, const RenderOptions &opt) {
-    const rt_denoise_albedo_params dp = filter_params("denoise_albedo_mean_spatial", opt);
-    const rt_denoise_spatial_params sp = spatial_params("denoise_albedo_mean_spatial", opt);
-    return run_denoise("denoise_albedo_mean_spatial", opt, width, height, rt_denoise_albedo_workspace_bytes(width, height),
-                       [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
-                           return rt_denoise_albedo_mean_spatial_device(width, height, d_mean, d_m2, samples, d_albedo_mean, &sp, &dp, d_out, d_rgba8,
-                                                                        d_work, nullptr);
-                       });
-}
-
-// the edge-guided filter's params from the options
-static rt_denoise_guided_params guided_params(const char *who, const RenderOptions &opt) {
-    rt_denoise_guided_params dp;
-    if (rt_denoise_guided_params_init_sized(&dp, sizeof dp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
-    dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
-    return dp;
+    return run_denoise("denoise_albedo_mean_spatial", {.form = DenoiseForm::Means, .guides = DenoiseGuides::Albedo, .width = width, .height = height,
+                                                       .first = d_mean, .second = d_m2, .count = samples, .albedo = d_albedo_mean, .spatial = true}, opt);
 }
 
 std::vector<uint8_t> denoise_guided_mean(int32_t width, int32_t height, const double *d_mean, const double *d_m2, int32_t samples,
                                          const double *d_albedo_mean, const double *d_edge_mean, const RenderOptions &opt) {
-    const rt_denoise_guided_params dp = guided_params("denoise_guided_mean", opt);
-    const bool spatial = opt.live_denoise_spatial > 0;
-    rt_denoise_spatial_params sp{};
-    if (spatial) sp = spatial_params("denoise_guided_mean", opt);
-    return run_denoise("denoise_guided_mean", opt, width, height, rt_denoise_guided_workspace_bytes(width, height, d_albedo_mean != nullptr),
-                       [&](double *d_out, uint8_t *d_rgba8, void *d_work) {
-                           return spatial ? rt_denoise_guided_mean_spatial_device(width, height, d_mean, d_m2, samples, d_albedo_mean, d_edge_mean, &sp, &dp,
-                                                                                  d_out, d_rgba8, d_work, nullptr)
-                                          : rt_denoise_guided_mean_device(width, height, d_mean, d_m2, samples, d_albedo_mean, d_edge_mean, &dp, d_out,
-                                                                          d_rgba8, d_work, nullptr);
-                       });
+    return run_denoise("denoise_guided_mean", {.form = DenoiseForm::Means, .guides = DenoiseGuides::Edge, .width = width, .height = height,
+                                               .first = d_mean, .second = d_m2, .count = samples, .albedo = d_albedo_mean, .edge = d_edge_mean,
+                                               .spatial = opt.live_denoise_spatial > 0}, opt);
 }
 
 std::vector<uint8_t> denoise_guided_views(int32_t width, int32_t height, int32_t n_views, const double *d_sum, const double *d_sum_sq, int32_t spp,
                                           const double *d_albedo_sum, int32_t albedo_spp, const double *d_edge_sum, int32_t edge_spp,
                                           const RenderOptions &opt) {
-    const rt_denoise_guided_params dp = guided_params("denoise_guided_views", opt);
-    if (n_views < 1) throw std::runtime_error("denoise_guided_views: n_views must be at least 1");
-    return run_denoise("denoise_guided_views", opt, width, height, rt_denoise_guided_views_workspace_bytes(width, height, n_views, d_albedo_sum != nullptr),
-                       [&](double *d_mean, uint8_t *d_rgba8, void *d_work) {
-                           return rt_denoise_guided_views_device(width, height, n_views, d_sum, d_sum_sq, spp, d_albedo_sum, albedo_spp, d_edge_sum,
-                                                                 edge_spp, &dp, d_mean, d_rgba8, d_work, nullptr);
-                       }, n_views);
+    return run_denoise("denoise_guided_views", {.form = DenoiseForm::Views, .guides = DenoiseGuides::Edge, .width = width, .height = height,
+                                                .first = d_sum, .second = d_sum_sq, .count = spp, .albedo = d_albedo_sum, .albedo_count = albedo_spp,
+                                                .edge = d_edge_sum, .edge_count = edge_spp, .n_views = n_views}, opt);
 }
 
 // The albedo frame of a render (opt.denoise_albedo): the albedo scene of `desc` on device 0, rendered over the samples [0, spp) of
@@ -494,25 +511,14 @@ static std::vector<uint8_t> render_upsampled_rgb8(const Camera &camera, const Hi
         check(rt_render_moments_device(scene, &low, &p, static_cast<double *>(d_sum), static_cast<double *>(d_sq), nullptr));
         if (opt.denoise_albedo) check(render_albedo_sums(desc, low, opt.seed, spp, &d_low_alb));
         if (opt.denoise_edges) check(render_albedo_sums(desc, low, opt.seed, spp, &d_low_ids, true));
-        rt_denoise_guided_params dp;
-        check(rt_denoise_guided_params_init_sized(&dp, sizeof dp));
-        dp.iterations = opt.denoise_iters; dp.sigma = opt.denoise_sigma; dp.sigma_albedo = opt.denoise_albedo_sigma; dp.sigma_edge = opt.denoise_edges_sigma;
-        const int64_t work = opt.denoise_edges ? rt_denoise_guided_workspace_bytes(lw, lh, opt.denoise_albedo)
-                             : opt.denoise_albedo ? rt_denoise_albedo_workspace_bytes(lw, lh) : rt_denoise_workspace_bytes(lw, lh);
+        const DenoiseRequest r{.form = DenoiseForm::Sums, .guides = opt.denoise_edges ? DenoiseGuides::Edge : opt.denoise_albedo ? DenoiseGuides::Albedo : DenoiseGuides::None,
+                               .width = lw, .height = lh, .first = static_cast<const double *>(d_sum), .second = static_cast<const double *>(d_sq), .count = spp,
+                               .albedo = static_cast<const double *>(d_low_alb), .albedo_count = spp, .edge = static_cast<const double *>(d_low_ids), .edge_count = spp};
+        const int64_t work = denoise_workspace_bytes(r);
         if (work < 0) { cleanup(); throw std::runtime_error("render: no denoise workspace for a frame of this size"); }
         check(rt_device_malloc(0, work, &d_work));
-        const double *S = static_cast<const double *>(d_sum), *Q = static_cast<const double *>(d_sq);
         double *out = static_cast<double *>(d_low_mean);
-        if (opt.denoise_edges) {
-            check(rt_denoise_guided_device(lw, lh, S, Q, spp, nullptr, static_cast<const double *>(d_low_alb), spp, static_cast<const double *>(d_low_ids), spp,
-                                           &dp, out, nullptr, d_work, nullptr));
-        } else if (opt.denoise_albedo) {
-            const rt_denoise_albedo_params ap{(uint32_t)sizeof(rt_denoise_albedo_params), dp.iterations, dp.sigma, dp.eps, dp.sigma_albedo, dp.albedo_floor};
-            check(rt_denoise_albedo_device(lw, lh, S, Q, spp, nullptr, static_cast<const double *>(d_low_alb), spp, &ap, out, nullptr, d_work, nullptr));
-        } else {
-            const rt_denoise_params pp{(uint32_t)sizeof(rt_denoise_params), dp.iterations, dp.sigma, dp.eps};
-            check(rt_denoise_device(lw, lh, S, Q, spp, nullptr, &pp, out, nullptr, d_work, nullptr));
-        }
+        check(denoise_into(r, opt, out, nullptr, d_work));
         d_low = out;
         low_spp = 1; // the filter writes means
     } else {
@@ -747,30 +753,25 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         if (opt.upsample_albedo) check(render_albedo_sums(desc, full, opt.seed, guide_spp, &d_up_alb));
         if (opt.upsample_edges) check(render_albedo_sums(desc, full, opt.seed, guide_spp, &d_up_ids, true));
     }
-    rt_denoise_albedo_params dp{};
-    rt_denoise_guided_params gp{};
-    rt_denoise_spatial_params sp{};
-    const bool spatial = opt.live_denoise_spatial > 0; // every pass through the spatial entry points: the first one is filtered too
     rt_camera white = cam;
     white.background = rt_vec3{1.0, 1.0, 1.0};
+    // every pass's filter; opt.live_denoise_spatial > 0: through the spatial entry points, so that the first pass is filtered too
+    DenoiseRequest filter{.form = DenoiseForm::Means, .guides = edges ? DenoiseGuides::Edge : guided ? DenoiseGuides::Albedo : DenoiseGuides::None,
+                          .width = w, .height = h, .first = nullptr, .second = nullptr, .count = 0, .spatial = opt.live_denoise_spatial > 0};
     if (denoised) {
-        try {
-            dp = filter_params("live_render", opt);
-            if (spatial) sp = spatial_params("live_render", opt);
-            if (edges) gp = guided_params("live_render", opt);
-        } catch (...) { cleanup(); throw; }
-        const int64_t work = edges ? rt_denoise_guided_workspace_bytes(w, h, guided) : guided ? rt_denoise_albedo_workspace_bytes(w, h) : rt_denoise_workspace_bytes(w, h);
-        if (work < 0) { cleanup(); throw std::runtime_error("live_render: no denoise workspace for a frame of this size"); }
-        check(rt_device_malloc(0, frame_bytes, &d_m2));
-        check(rt_device_malloc(0, frame_bytes, &d_shown));
-        check(rt_device_malloc(0, work, &d_work));
         if (guided) {
             check(rt_scene_create_albedo(&desc, 0, nullptr, &albedo_scene));
             check(rt_device_malloc(0, frame_bytes, &d_alb));
         }
+        filter.albedo = static_cast<const double *>(d_alb); // (null without the albedo guide: the plain filter with the edge guide)
+        const int64_t work = denoise_workspace_bytes(filter);
+        if (work < 0) { cleanup(); throw std::runtime_error("live_render: no denoise workspace for a frame of this size"); }
+        check(rt_device_malloc(0, frame_bytes, &d_m2));
+        check(rt_device_malloc(0, frame_bytes, &d_shown));
+        check(rt_device_malloc(0, work, &d_work));
         if (edges) check(render_albedo_sums(desc, cam, opt.seed, guide_spp, &d_ids, true, true));
+        filter.first = static_cast<const double *>(d_mean); filter.second = static_cast<const double *>(d_m2); filter.edge = static_cast<const double *>(d_ids);
     }
-    const rt_denoise_params plain = plain_params(dp);
     // with the tone-mapping stage on, the pass and the filters write no bytes (a null d_rgba8): the stage makes the frame shown from
     // the running mean — or, filtered, from d_shown — and the mean itself is never touched
     // ... and with the upsampler on it is the upsampler that writes the bytes, at the full size
@@ -785,26 +786,8 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         } else {
             check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
             if (guided) check(rt_render_mean_device(albedo_scene, &white, &p, static_cast<double *>(d_alb), nullptr, nullptr));
-            if (edges) { // (d_alb is null without the albedo guide: the plain filter with the edge guide)
-                check(spatial ? rt_denoise_guided_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
-                                                                      static_cast<const double *>(d_alb), static_cast<const double *>(d_ids), &sp, &gp,
-                                                                      static_cast<double *>(d_shown), d_bytes, d_work, nullptr)
-                              : rt_denoise_guided_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
-                                                              static_cast<const double *>(d_alb), static_cast<const double *>(d_ids), &gp,
-                                                              static_cast<double *>(d_shown), d_bytes, d_work, nullptr));
-            } else if (guided) {
-                check(spatial ? rt_denoise_albedo_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
-                                                                      static_cast<const double *>(d_alb), &sp, &dp, static_cast<double *>(d_shown),
-                                                                      d_bytes, d_work, nullptr)
-                              : rt_denoise_albedo_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end,
-                                                              static_cast<const double *>(d_alb), &dp, static_cast<double *>(d_shown),
-                                                              d_bytes, d_work, nullptr));
-            } else {
-                check(spatial ? rt_denoise_mean_spatial_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &sp,
-                                                               &plain, static_cast<double *>(d_shown), d_bytes, d_work, nullptr)
-                              : rt_denoise_mean_device(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, &plain,
-                                                       static_cast<double *>(d_shown), d_bytes, d_work, nullptr));
-            }
+            filter.count = end;
+            check(denoise_into(filter, opt, static_cast<double *>(d_shown), d_bytes, d_work));
         }
         const double *d_means = static_cast<const double *>(denoised ? d_shown : d_mean); // the pass's frame of means, at the traced size
         if (upsampled) {
