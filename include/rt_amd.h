@@ -1133,6 +1133,45 @@ int rt_log_average_luminance_device(int32_t width, int32_t height, const double 
                                     const int32_t *d_spp /* NULL: uniform */, double delta, double *d_out4 /* log_mean, Lavg, count, 0 */,
                                     void *d_workspace, void *hip_stream);
 
+/* ---- film output (opt-in; nothing above changes) -------------------------------------------------------------------------------------------
+ * Every stage above ends in eight-bit gamma bytes.  rt_film_device is the tone-mapping stage with another last step: the value the stage
+ * would gamma-encode and quantise is written in a format that keeps it — the shared-exponent pixels of a Radiance .hdr file, floats for
+ * a PFM, or sixteen-bit gamma samples for a PNG — so that radiance above 1 leaves the device unclipped in 4 or 12 bytes per pixel
+ * instead of the sums' 24.
+ *
+ * Normative definition.  d_values, spp and d_spp are tone mapping's, and so is the value before encoding, bit for bit:
+ *     m = tone mapping's "Input value";  x = m * scale;  y = rt_tonemap(op, x, w2)
+ * with scale = exposure, or with auto_key > 0 the scale of tone mapping's "Auto-exposure": the same reduction tree in the same workspace
+ * (rt_tonemap_workspace_bytes), whose first four doubles are afterwards log_mean, Lavg, (double)count and scale.  With the defaults
+ * (clamp, exposure 1, no key) y == m exactly: the linear formats then hold the frame's radiance.
+ *   RT_FILM_RGBE   4 bytes per pixel, Radiance's shared exponent (Ward's float2rgbe with its one inexact step, m * 256 / v, made exact),
+ *                  one 32-bit store per pixel, R in the lowest byte as rt_resolve_rgba8_device packs, the exponent byte on top.
+ *                  Per channel c = y where y > 0 (+inf included), else c = 0: zero, negatives and NaN give 0.  c = min(c, 255 * 2^119),
+ *                  the largest value the format holds.  v = max(c_r, c_g, c_b).  v < 2^-128: the pixel is 0, 0, 0, 0.  Otherwise e is the
+ *                  integer with 2^(e-1) <= v < 2^e, taken from the exponent field of v's bits (v is normal here; no library frexp);
+ *                  b_k = (uint8_t)(c_k * 2^(8-e)), an exact multiplication by a power of two built from bits, then truncated;
+ *                  E = e + 128, in 1..255.  Hence b_k * 2^(E-136) <= c_k < (b_k + 1) * 2^(E-136), and the largest byte is >= 128.
+ *   RT_FILM_F32    3 floats per pixel: y rounded to f32, to nearest, ties to even.  Overflow gives +-inf, signs are kept, values below
+ *                  f32's normal range become f32 subnormals or +-0, and every NaN becomes the one bit pattern 0x7fc00000.
+ *   RT_FILM_RGB16  3 native-endian uint16_t per pixel: g = rt_gamma_encode(y); NaN gives 0, otherwise
+ *                  (uint16_t)(65536.0 * clamp(g, 0, 0.99999)).  The high byte of every value is the byte rt_tonemap_device writes for the
+ *                  same input and params: the scalings by 256 and 65536 are exact and both clamps land in 255.
+ *
+ * rt_film_device reads d_values and writes rt_film_bytes(w, h, format) bytes at d_out; d_values is not written.  The call is enqueued
+ * on hip_stream, does not synchronise and allocates nothing.  rt_film_bytes is w * h * (4, 12 or 6); -1 for a frame or a format the
+ * call refuses.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; a null d_values; a
+ * null d_out; spp < 1; format outside 0..2; the rt_tonemap_params checks of tone mapping, in its order; with auto_key > 0 a null
+ * d_workspace or one that is not 16-byte aligned; a d_out that is not 4-byte aligned (RT_FILM_RGB16: 2-byte); d_out overlapping
+ * d_values. */
+#define RT_FILM_RGBE 0
+#define RT_FILM_F32 1
+#define RT_FILM_RGB16 2
+int64_t rt_film_bytes(int32_t width, int32_t height, int32_t format);
+int rt_film_device(int32_t width, int32_t height, const double *d_values /* 3*w*h */, int32_t spp, const int32_t *d_spp /* NULL: uniform */,
+                   const rt_tonemap_params *tone /* NULL: defaults */, int32_t format /* RT_FILM_* */, void *d_out /* rt_film_bytes */,
+                   void *d_workspace /* may be NULL when auto_key == 0 */, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done. */

@@ -57,6 +57,12 @@ int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp
                 const rt_tonemap_params *params /* NULL: defaults */, uint8_t *out_rgb8, uint8_t *out_rgba8);
 int rth_log_average_luminance(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
                               double delta, double *out4);
+/* The host mirror of rt_film_device (rt_amd.h "film output") on host memory: the same shared encoders behind the same value, auto-exposure
+ * through rth_log_average_luminance's tree, so `out` (rt_film_bytes(w, h, format) bytes, any alignment) holds the device's bytes, bit for
+ * bit.  `values` as rth_tonemap takes them.  It refuses what the device call refuses of these arguments, in the same order and with the
+ * same words (-1, the field named in rth_last_error); there is no workspace and no stream. */
+int rth_film(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
+             const rt_tonemap_params *tone /* NULL: defaults */, int32_t format /* RT_FILM_* */, void *out);
 /* The host mirror of rt_bloom_device (rt_amd.h "bloom") on host memory: the same shared per-value functions in the same order, so
  * out_mean (3 * w * h doubles, a frame of means) holds the device's bits.  `values` as rth_tonemap takes them.  It refuses what the
  * device call refuses of these arguments, in the same order and with the same words (-1, the field named in rth_last_error); there is
@@ -78,6 +84,16 @@ int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stac
                double *out_mean, double *out_m2 /* or NULL */);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
+/* The film formats' files, each from a frame in its format (rt_amd.h "film output"), row 0 on top:
+ *   rth_write_hdr    RT_FILM_RGBE bytes as a Radiance picture: "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y h +X w\n", then the scanlines in
+ *                    the new-style run-length code where 8 <= w <= 32767 (2 2 hi lo, then the four byte planes: a run is 128 + length and
+ *                    the value, a literal its length, at most 128, and the bytes), as flat pixels otherwise;
+ *   rth_write_pfm    RT_FILM_F32 floats as "PF\nw h\n-1.0\n", little-endian, the bottom row first;
+ *   rth_write_png16  RT_FILM_RGB16 samples as a PNG of colour type 2 and bit depth 16 (big-endian in the file), through the filter and
+ *                    zlib path of rth_write_png. */
+int rth_write_hdr(const char *path, int32_t width, int32_t height, const uint8_t *rgbe);
+int rth_write_pfm(const char *path, int32_t width, int32_t height, const float *rgb_f32);
+int rth_write_png16(const char *path, int32_t width, int32_t height, const uint16_t *rgb16);
 /* Deterministic procedural RGB8 map used where assets/earth-large.jpg is unavailable. */
 int rth_synthetic_earth(int32_t width, int32_t height, uint8_t *out_rgb8);
 /* Image ingest used by ImageTexture (PPM / JPEG, sequential or progressive / PNG / synthetic:WxH); out_rgb8 may be NULL to query size. */

@@ -446,6 +446,8 @@ RT_AMD_SYMBOLS = {
                                     C.c_void_p]),
     "rt_log_average_luminance_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]),
+    "rt_film_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "rt_film_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -742,11 +744,15 @@ RT_HOST_SYMBOLS = {
     "rth_resolve_rgb8": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
     "rth_tonemap": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_log_average_luminance": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p]),
+    "rth_film": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "rth_bloom": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_upsample": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "rth_robust": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
+    "rth_write_hdr": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rth_write_pfm": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rth_write_png16": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rth_synthetic_earth": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_load_image": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8),
                                  C.c_int64]),
@@ -1649,6 +1655,87 @@ def log_average_luminance_host(values, spp, *, spp_map=None, delta=1e-4):
                                             out.ctypes.data) != 0:
         raise RtError(host_lib().rth_last_error().decode(errors="replace"))
     return tuple(float(x) for x in out)
+
+
+# film output (include/rt_amd.h "film output"): the formats, and the (trailing shape, dtype) of a frame in each
+RT_FILM_RGBE, RT_FILM_F32, RT_FILM_RGB16 = 0, 1, 2
+_FILM_LAYOUT = {RT_FILM_RGBE: ((4,), "uint8"), RT_FILM_F32: ((3,), "float32"), RT_FILM_RGB16: ((3,), "uint16")}
+
+
+def _film_format(v):
+    if isinstance(v, str):
+        if v.lower() not in ("rgbe", "f32", "rgb16"):
+            raise RtError(f"film: no format {v!r} (rgbe, f32, rgb16)")
+        return ("rgbe", "f32", "rgb16").index(v.lower())
+    return int(v)
+
+
+def film_bytes(width, height, format) -> int:
+    """rt_film_bytes: the bytes of a w x h frame in `format` (a number or "rgbe" / "f32" / "rgb16"); an RtError where the call refuses."""
+    n = int(amd_lib().rt_film_bytes(width, height, _film_format(format)))
+    if n < 0:
+        raise RtError(f"rt_film_bytes: no {width}x{height} frame in format {format!r}")
+    return n
+
+
+def film_device(width, height, d_values_ptr: int, spp: int, format, d_out_ptr: int, *, d_spp_ptr: int = 0, d_workspace_ptr: int = 0,
+                params: "TonemapParams | None" = None, stream: int = 0):
+    """rt_film_device: the tone-mapping stage's value over a device frame, as tonemap_device takes it, written in `format` to
+    film_bytes(w, h, format) device bytes at d_out_ptr.  With params.auto_key > 0 the exposure comes from the frame's log-average
+    luminance, reduced in `d_workspace_ptr` (tonemap_workspace_bytes(w, h) device bytes).  Enqueued on `stream`."""
+    _check(amd_lib().rt_film_device(width, height, C.c_void_p(d_values_ptr), spp, C.c_void_p(d_spp_ptr or None),
+                                    C.byref(params) if params is not None else None, _film_format(format), C.c_void_p(d_out_ptr or None),
+                                    C.c_void_p(d_workspace_ptr or None), C.c_void_p(stream)), "rt_film_device")
+
+
+def film(values, spp, format, *, spp_map=None, device=0, **kw):
+    """Uploads a frame as tonemap() takes it, runs rt_film_device with tonemap_params(**kw) and downloads the frame in `format`:
+    (h, w, 4) uint8 R, G, B, E for "rgbe", (h, w, 3) float32 for "f32", (h, w, 3) uint16 for "rgb16"."""
+    values, spp_map, w, h = _tonemap_frame("film", values, spp_map)
+    params, fmt = tonemap_params(**kw), _film_format(format)
+    film_bytes(w, h, fmt)
+    tail, dtype = _FILM_LAYOUT[fmt]
+    return _frame_end(device, [values, spp_map], (h, w) + tail, None, tonemap_workspace_bytes(w, h),
+                      lambda d, out, ws, rgba, stream: film_device(w, h, d[0], int(spp), fmt, out, d_spp_ptr=d[1], d_workspace_ptr=ws, params=params,
+                                                                   stream=stream), out_dtype=dtype)
+
+
+def film_host(values, spp, format, *, spp_map=None, **kw):
+    """rth_film (librt_host, CPU): the bytes rt_film_device gives, from the same shared encoders and the same reduction tree."""
+    import numpy as np
+    values, spp_map, w, h = _tonemap_frame("film_host", values, spp_map)
+    params, fmt = tonemap_params(**kw), _film_format(format)
+    tail, dtype = _FILM_LAYOUT.get(fmt, ((4,), "uint8"))  # (a format out of range is refused below, by the library)
+    out = np.zeros((h, w) + tail, dtype=dtype)
+    if host_lib().rth_film(w, h, values.ctypes.data, int(spp), spp_map.ctypes.data if spp_map is not None else None, C.byref(params), fmt,
+                           out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return out
+
+
+def _write_film(symbol, path, frame, channels, dtype):
+    import numpy as np
+    frame = np.ascontiguousarray(frame, dtype=dtype)
+    if frame.ndim != 3 or frame.shape[2] != channels:
+        raise RtError(f"{symbol}: the frame must have shape (h, w, {channels})")
+    h, w, _ = frame.shape
+    if getattr(host_lib(), symbol)(os.fsencode(path), w, h, frame.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+
+
+def write_hdr(path, rgbe):
+    """rth_write_hdr: an (h, w, 4) uint8 frame of R, G, B, E bytes ("rgbe") as a Radiance .hdr picture."""
+    _write_film("rth_write_hdr", path, rgbe, 4, "uint8")
+
+
+def write_pfm(path, rgb_f32):
+    """rth_write_pfm: an (h, w, 3) float32 frame ("f32") as a colour PFM."""
+    _write_film("rth_write_pfm", path, rgb_f32, 3, "float32")
+
+
+def write_png16(path, rgb16):
+    """rth_write_png16: an (h, w, 3) uint16 frame ("rgb16") as a PNG with 16 bits per sample."""
+    _write_film("rth_write_png16", path, rgb16, 3, "uint16")
 
 
 def bloom_workspace_bytes(width, height) -> int:

@@ -2056,43 +2056,86 @@ int rt_tonemap_params_init_sized(rt_tonemap_params *params, uint32_t struct_size
 
 int64_t rt_tonemap_workspace_bytes(int32_t width, int32_t height) { return rttm::workspace_bytes(width, height); }
 
-int rt_tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const rt_tonemap_params *params,
-                      uint8_t *d_rgb8, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
-    const std::string w("rt_tonemap_device");
+// What rt_tonemap_device and rt_film_device are: one frame of values through the exposure and the operator into bytes — the tone-mapping
+// stage's RGB8 / RGBA8, or (film != null) one film format.  The checks in the headers' order, the reduction if auto_key > 0, the launches.
+struct OutputStageCall {
+    const char *who;
+    int32_t width, height;
+    const double *values;
+    int32_t spp;
+    const int32_t *spp_map;
+    const rt_tonemap_params *params;
+    uint8_t *rgb8 = nullptr, *rgba8 = nullptr; // the tone-mapping stage's outputs
+    bool film = false;                         // rt_film_device: `out` in `format`
+    int32_t format = 0;
+    void *out = nullptr;
+    void *workspace;
+    void *stream;
+};
+
+static int output_stage(const OutputStageCall &c) {
+    const std::string w(c.who);
+    const int32_t width = c.width, height = c.height;
     if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width and height must be positive");
     if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(RT_ERR_INVALID_ARGUMENT, w + ": width x height must be below 2^27 pixels");
-    if (!d_values) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_values is null");
-    if (!d_rgb8 && !d_rgba8) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgb8 and d_rgba8 are both null");
-    if (spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 1");
+    if (!c.values) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_values is null");
+    if (c.film && !c.out) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_out is null");
+    if (!c.film && !c.rgb8 && !c.rgba8) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgb8 and d_rgba8 are both null");
+    if (c.spp < 1) return fail(RT_ERR_INVALID_ARGUMENT, w + ": spp must be at least 1");
+    if (c.film && !rttm::film_pixel_bytes(c.format))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": format must be RT_FILM_RGBE, RT_FILM_F32 or RT_FILM_RGB16 (0..2)");
     rt_tonemap_params p;
-    if (!rttm::resolve(params, p)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_tonemap_params.struct_size is not one this library knows");
+    if (!rttm::resolve(c.params, p)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": rt_tonemap_params.struct_size is not one this library knows");
     if (const char *bad = rttm::bad_field(p)) return fail(RT_ERR_INVALID_ARGUMENT, w + ": " + bad);
     const bool automatic = p.auto_key > 0.0;
-    if (automatic && !d_workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null (auto_key > 0 needs it)");
-    if (automatic && ((uintptr_t)d_workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
-    if (((uintptr_t)d_rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
-    const size_t n_pix = (size_t)width * (size_t)height;
-    if ((d_rgb8 && overlaps(d_rgb8, n_pix * 3u, d_values, n_pix * 3u * sizeof(double))) ||
-        (d_rgba8 && overlaps(d_rgba8, n_pix * 4u, d_values, n_pix * 3u * sizeof(double))))
+    if (automatic && !c.workspace) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace is null (auto_key > 0 needs it)");
+    if (automatic && ((uintptr_t)c.workspace & 15u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_workspace must be 16-byte aligned");
+    if (((uintptr_t)c.rgba8 & 3u) != 0) return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_rgba8 must be 4-byte aligned");
+    if (c.film && ((uintptr_t)c.out & (rttm::film_alignment(c.format) - 1u)) != 0)
+        return fail(RT_ERR_INVALID_ARGUMENT, w + (c.format == RT_FILM_RGB16 ? ": d_out must be 2-byte aligned" : ": d_out must be 4-byte aligned"));
+    const size_t n_pix = (size_t)width * (size_t)height, value_bytes = n_pix * 3u * sizeof(double);
+    if (c.film && overlaps(c.out, n_pix * (size_t)rttm::film_pixel_bytes(c.format), c.values, value_bytes))
+        return fail(RT_ERR_INVALID_ARGUMENT, w + ": d_out must not overlap d_values");
+    if ((c.rgb8 && overlaps(c.rgb8, n_pix * 3u, c.values, value_bytes)) || (c.rgba8 && overlaps(c.rgba8, n_pix * 4u, c.values, value_bytes)))
         return fail(RT_ERR_INVALID_ARGUMENT, w + ": an output must not overlap d_values");
-    if (int rc = select_device_of(d_rgb8 ? d_rgb8 : d_rgba8, "rt_tonemap_device")) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const double inv_spp = 1.0 / (double)spp, w2 = p.white * p.white;
-    double *out4 = (double *)d_workspace;
+    if (int rc = select_device_of(c.film ? c.out : c.rgb8 ? (void *)c.rgb8 : (void *)c.rgba8, c.who)) return rc;
+    hipStream_t stream = (hipStream_t)c.stream;
+    const double inv_spp = 1.0 / (double)c.spp, w2 = p.white * p.white;
+    double *out4 = (double *)c.workspace;
     if (automatic) {
-        launch_log_average((int64_t)n_pix, d_values, inv_spp, d_spp, p.delta, (TonemapPartial *)(out4 + 4), p.exposure, p.auto_key, out4, stream);
+        launch_log_average((int64_t)n_pix, c.values, inv_spp, c.spp_map, p.delta, (TonemapPartial *)(out4 + 4), p.exposure, p.auto_key, out4, stream);
         HIP_TRY(hipGetLastError());
     }
     const double *d_scale = automatic ? out4 + 3 : nullptr;
-    if (d_rgb8) {
-        launch_tonemap_rgb8((int64_t)n_pix, d_values, inv_spp, d_spp, p.exposure, d_scale, p.op, w2, d_rgb8, stream);
+    if (c.film) {
+        launch_film(c.format, (int64_t)n_pix, c.values, inv_spp, c.spp_map, p.exposure, d_scale, p.op, w2, c.out, stream);
         HIP_TRY(hipGetLastError());
     }
-    if (d_rgba8) {
-        launch_tonemap_rgba8((int64_t)n_pix, d_values, inv_spp, d_spp, p.exposure, d_scale, p.op, w2, d_rgba8, stream);
+    if (c.rgb8) {
+        launch_tonemap_rgb8((int64_t)n_pix, c.values, inv_spp, c.spp_map, p.exposure, d_scale, p.op, w2, c.rgb8, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (c.rgba8) {
+        launch_tonemap_rgba8((int64_t)n_pix, c.values, inv_spp, c.spp_map, p.exposure, d_scale, p.op, w2, c.rgba8, stream);
         HIP_TRY(hipGetLastError());
     }
     return RT_OK;
+}
+
+int rt_tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const rt_tonemap_params *params,
+                      uint8_t *d_rgb8, uint8_t *d_rgba8, void *d_workspace, void *hip_stream) {
+    return output_stage({.who = "rt_tonemap_device", .width = width, .height = height, .values = d_values, .spp = spp, .spp_map = d_spp, .params = params,
+                         .rgb8 = d_rgb8, .rgba8 = d_rgba8, .workspace = d_workspace, .stream = hip_stream});
+}
+
+// ---- film output (rt_film.hip): the tone-mapping stage's value in a file's format — shared-exponent RGBE, f32 or 16-bit gamma ----
+
+int64_t rt_film_bytes(int32_t width, int32_t height, int32_t format) { return rttm::film_bytes(width, height, format); }
+
+int rt_film_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const rt_tonemap_params *tone,
+                   int32_t format, void *d_out, void *d_workspace, void *hip_stream) {
+    return output_stage({.who = "rt_film_device", .width = width, .height = height, .values = d_values, .spp = spp, .spp_map = d_spp, .params = tone,
+                         .film = true, .format = format, .out = d_out, .workspace = d_workspace, .stream = hip_stream});
 }
 
 int rt_log_average_luminance_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, double delta,

@@ -253,6 +253,10 @@ void launch_tonemap_rgb8(int64_t n_pixels, const double *values, double inv_spp,
                          double w2, uint8_t *rgb, hipStream_t stream);
 void launch_tonemap_rgba8(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double scale, const double *d_scale, int32_t op,
                           double w2, uint8_t *rgba, hipStream_t stream);
+// the film stage (rt_film.hip; rt_film_device): the tone-mapping value kernels' arguments, and `out` in the layout of `format`
+// (RT_FILM_RGBE: n_pixels words; RT_FILM_F32: 3 n_pixels floats; RT_FILM_RGB16: 3 n_pixels uint16)
+void launch_film(int32_t format, int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, double scale, const double *d_scale,
+                 int32_t op, double w2, void *out, hipStream_t stream);
 // bloom (rt_bloom.hip; rt_bloom_device).  Frames are 3 doubles per pixel, row after row.  launch_bloom_bright writes every pixel's B0
 // to b0 and +0.0 to a.  A level at `stride` reads b_in and leaves B_k+1 in b_out and A += B_k+1 in a; on the last level it writes
 // out = m + strength * (A / levels) instead, from values / inv_spp / spp_map, and neither b_out nor a.  launch_bloom_level_fused is

@@ -6,6 +6,7 @@
 //   rt_gamma_encode   x^(1/2.2), the output stage's linear_to_gamma (src/color.rs:3-6)
 //   rt_quantise       (256 * clamp(g, 0, 0.999)) as u8 (src/color.rs:12-19)
 //   rt_tonemap, rt_luminance, rt_log_luminance_term, rt_log_average_result   the tone-mapping stage's operator and auto-exposure's terms
+//   rt_rgbe_pack, rt_f32_of, rt_quantise16   the film formats' encoders: shared-exponent RGBE, f32 bits and the 16-bit gamma quantiser
 //   rt_bloom_bright, rt_bloom_taps, rt_bloom_output   bloom's bright pass, one five-tap accumulation and its output value
 //   rt_adaptive_converged   adaptive sampling's per-pixel stopping rule
 // Coefficients: FreeBSD msun e_log.c / e_exp.c (public constants of the published algorithms).
@@ -125,6 +126,51 @@ RT_HD double rt_tonemap(int32_t op, double x, double w2) {
         return num / den;
     }
     return x;
+}
+
+// The film formats' encoders (include/rt_amd.h "film output"), on the tone-mapped value y.  Bit moves and exact multiplications by powers
+// of two only: no rounding mode, denormal mode or library call that could differ between the two sides.
+// RT_FILM_RGBE: Radiance's shared exponent, R in the low byte and the exponent byte on top.  c = y where y > 0 (+inf included), else 0;
+// c = min(c, 255 * 2^119); v = the largest c; v < 2^-128: the zero pixel.  Else e with 2^(e-1) <= v < 2^e from v's exponent field (v is
+// normal), b_k = (u8)(c_k * 2^(8-e)) — exact, then truncated — and E = e + 128 in 1..255.
+RT_HD uint32_t rt_rgbe_pack(double yr, double yg, double yb) {
+    const double top = 255.0 * u2f((uint64_t)(119 + 1023) << 52);
+    double c[3] = {yr > 0.0 ? yr : 0.0, yg > 0.0 ? yg : 0.0, yb > 0.0 ? yb : 0.0};
+    for (int k = 0; k < 3; ++k) c[k] = c[k] > top ? top : c[k];
+    double v = c[0];
+    if (c[1] > v) v = c[1];
+    if (c[2] > v) v = c[2];
+    if (v < u2f((uint64_t)(1023 - 128) << 52)) return 0u;
+    const int32_t e = (int32_t)((f2u(v) >> 52) & 0x7ff) - 1022; // -127 .. 127
+    const double s = u2f((uint64_t)(8 - e + 1023) << 52);       // 2^(8-e), a normal number
+    return (uint32_t)(uint8_t)(c[0] * s) | ((uint32_t)(uint8_t)(c[1] * s) << 8) | ((uint32_t)(uint8_t)(c[2] * s) << 16) | ((uint32_t)(e + 128) << 24);
+}
+
+// RT_FILM_F32: the bits of (float)y rounded to nearest, ties to even: overflow gives +-inf, signs are kept (-0.0 too), what lies below
+// f32's normal range becomes an f32 subnormal or +-0, and every NaN becomes 0x7fc00000.
+RT_HD uint32_t rt_f32_of(double y) {
+    const uint64_t b = f2u(y);
+    const uint32_t sign = (uint32_t)(b >> 63) << 31, ef = (uint32_t)(b >> 52) & 0x7ffu;
+    const uint64_t man = b & 0x000fffffffffffffull;
+    if (ef == 0x7ffu) return man ? 0x7fc00000u : sign | 0x7f800000u;
+    const int32_t e = (int32_t)ef - 1023 + 127; // the f32 exponent field of a normal result
+    if (e >= 255) return sign | 0x7f800000u;
+    if (ef == 0 || e < -30) return sign;        // (below 2^-157: far under half of f32's smallest subnormal, 2^-150)
+    const int shift = e >= 1 ? 29 : 29 + (1 - e); // 52 - 23 bits go; a subnormal result loses 1 - e more
+    const uint64_t sig = man | (1ull << 52), half = 1ull << (shift - 1), rem = sig & ((half << 1) - 1u);
+    uint64_t q = sig >> shift;
+    if (rem > half || (rem == half && (q & 1u))) ++q;
+    // a normal q holds the implicit bit, which counts as one step of the exponent field; a carry out of the mantissa is the next step
+    // (up to the field of +inf), and a subnormal that rounds up to 2^23 is the smallest normal
+    return sign | (((uint32_t)(e >= 1 ? e - 1 : 0) << 23) + (uint32_t)q);
+}
+
+// RT_FILM_RGB16: (u16)(65536 * clamp(g, 0, 0.99999)), NaN -> 0.  Its high byte is rt_quantise(g): both scalings are exact and both
+// clamps land in 255.
+RT_HD uint16_t rt_quantise16(double g) {
+    if (g != g) return 0;
+    const double c = g < 0.0 ? 0.0 : (g > 0.99999 ? 0.99999 : g);
+    return (uint16_t)(65536.0 * c);
 }
 
 // Rec. 709 luminance of a linear colour, in this order: ((0.2126 r + 0.7152 g) + 0.0722 b)

@@ -1,6 +1,7 @@
 // rt_tonemap_shared.h — what both libraries need of rt_tonemap_params on the host side (include/rt_amd.h "tone mapping"): the defaults,
 // the struct sizes known, and the checks in the header's order, so that rt_tonemap_device (rt_api.cpp) and its host mirror rth_tonemap
-// (host/capi.cpp) refuse the same things with the same words.  Plain C++, no device code; the arithmetic itself is rt_shared_math.h's.
+// (host/capi.cpp) refuse the same things with the same words; rt_film_device and rth_film ("film output") take the same params and
+// checks, and their formats' sizes are here.  Plain C++, no device code; the arithmetic itself is rt_shared_math.h's.
 #pragma once
 #include "rt_amd.h"
 
@@ -42,6 +43,13 @@ inline const char *bad_field(const rt_tonemap_params &p) {
     if (!(p.white > 0.0)) return "white must be > 0 (+inf allowed)";
     return nullptr;
 }
+// film output (include/rt_amd.h "film output"): bytes per pixel of a format (0: not a format), the frame's bytes (-1: refused), and the
+// alignment the format's stores need of the output
+inline int32_t film_pixel_bytes(int32_t format) { return format == RT_FILM_RGBE ? 4 : format == RT_FILM_F32 ? 12 : format == RT_FILM_RGB16 ? 6 : 0; }
+inline int64_t film_bytes(int32_t w, int32_t h, int32_t format) {
+    return frame_ok(w, h) && film_pixel_bytes(format) ? (int64_t)w * h * film_pixel_bytes(format) : -1;
+}
+inline uintptr_t film_alignment(int32_t format) { return format == RT_FILM_RGB16 ? 2u : 4u; }
 // blocks of the level that reduces n entries
 inline int64_t level_blocks(int64_t n) { return (n + LEVEL_BLOCK - 1) / LEVEL_BLOCK; }
 // the workspace: four doubles of results, then 16 bytes (T, count) per block of every level, level 0 first

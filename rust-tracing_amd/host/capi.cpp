@@ -191,6 +191,52 @@ int rth_tonemap(int32_t width, int32_t height, const double *values, int32_t spp
     return 0;
 }
 
+// ---- film output: the host mirror of rt_film_device (include/rt_amd.h "film output") ----
+
+int rth_film(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, const rt_tonemap_params *tone,
+             int32_t format, void *out) {
+    const std::string w("rth_film");
+    if (width <= 0 || height <= 0) return fail(w + ": width and height must be positive");
+    if ((int64_t)width * height >= rttm::MAX_PIXELS) return fail(w + ": width x height must be below 2^27 pixels");
+    if (!values) return fail(w + ": values is null");
+    if (!out) return fail(w + ": out is null");
+    if (spp < 1) return fail(w + ": spp must be at least 1");
+    if (!rttm::film_pixel_bytes(format)) return fail(w + ": format must be RT_FILM_RGBE, RT_FILM_F32 or RT_FILM_RGB16 (0..2)");
+    rt_tonemap_params p;
+    if (!rttm::resolve(tone, p)) return fail(w + ": rt_tonemap_params.struct_size is not one this library knows");
+    if (const char *bad = rttm::bad_field(p)) return fail(w + ": " + bad);
+    const size_t n = (size_t)width * (size_t)height;
+    double scale = p.exposure;
+    if (p.auto_key > 0.0) {
+        double out4[4];
+        log_average(n, values, spp, spp_map, p.delta, p.exposure, p.auto_key, out4);
+        scale = out4[3];
+    }
+    const double w2 = p.white * p.white;
+    uint8_t *bytes = static_cast<uint8_t *>(out); // (written through memcpy: the host mirror asks no alignment of `out`)
+    for (size_t i = 0; i < n; ++i) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
+        double y[3];
+        for (size_t c = 0; c < 3; ++c) {
+            const double m = values[3 * i + c] * inv;
+            const double x = m * scale;
+            y[c] = rtm::rt_tonemap(p.op, x, w2);
+        }
+        if (format == RT_FILM_RGBE) {
+            const uint32_t word = rtm::rt_rgbe_pack(y[0], y[1], y[2]);
+            memcpy(bytes + 4 * i, &word, 4);
+        } else if (format == RT_FILM_F32) {
+            const uint32_t bits[3] = {rtm::rt_f32_of(y[0]), rtm::rt_f32_of(y[1]), rtm::rt_f32_of(y[2])};
+            memcpy(bytes + 12 * i, bits, 12);
+        } else {
+            const uint16_t q[3] = {rtm::rt_quantise16(rtm::rt_gamma_encode(y[0])), rtm::rt_quantise16(rtm::rt_gamma_encode(y[1])),
+                                   rtm::rt_quantise16(rtm::rt_gamma_encode(y[2]))};
+            memcpy(bytes + 6 * i, q, 6);
+        }
+    }
+    return 0;
+}
+
 // ---- bloom: the host mirror of rt_bloom_device (include/rt_amd.h "bloom") ----
 
 int rth_bloom(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, const rt_bloom_params *params,
@@ -305,6 +351,21 @@ int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stac
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8) {
     if (!path || !rgb8) return fail("rth_write_png: null argument");
     return write_png_rgb8(path, width, height, rgb8) ? 0 : fail(std::string("rth_write_png: cannot write ") + path);
+}
+
+int rth_write_hdr(const char *path, int32_t width, int32_t height, const uint8_t *rgbe) {
+    if (!path || !rgbe) return fail("rth_write_hdr: null argument");
+    return write_hdr_rgbe(path, width, height, rgbe) ? 0 : fail(std::string("rth_write_hdr: cannot write ") + path);
+}
+
+int rth_write_pfm(const char *path, int32_t width, int32_t height, const float *rgb_f32) {
+    if (!path || !rgb_f32) return fail("rth_write_pfm: null argument");
+    return write_pfm_rgb(path, width, height, rgb_f32) ? 0 : fail(std::string("rth_write_pfm: cannot write ") + path);
+}
+
+int rth_write_png16(const char *path, int32_t width, int32_t height, const uint16_t *rgb16) {
+    if (!path || !rgb16) return fail("rth_write_png16: null argument");
+    return write_png_rgb16(path, width, height, rgb16) ? 0 : fail(std::string("rth_write_png16: cannot write ") + path);
 }
 
 int rth_synthetic_earth(int32_t width, int32_t height, uint8_t *out_rgb8) {

@@ -275,6 +275,13 @@ ImageRGB8 load_image_rgb8(const std::string &path) {
 static void put_u32(std::vector<uint8_t> &v, uint32_t x) {
     v.push_back((uint8_t)(x >> 24)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x);
 }
+static bool write_file(const std::string &path, const std::vector<uint8_t> &bytes) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    ok = (fclose(f) == 0) && ok;
+    return ok;
+}
 static void put_chunk(std::vector<uint8_t> &out, const char type[4], const uint8_t *data, size_t len) {
     put_u32(out, (uint32_t)len);
     size_t start = out.size();
@@ -283,46 +290,36 @@ static void put_chunk(std::vector<uint8_t> &out, const char type[4], const uint8
     uint32_t crc = (uint32_t)crc32(0L, out.data() + start, (uInt)(len + 4));
     put_u32(out, crc);
 }
-static inline int paeth(int a, int b, int c) { return paeth_predictor(a, b, c); }
+// the residual of byte x of a row under filter f (ISO 15948 section 9); bpp: how far back "the corresponding byte of the pixel to the left" lies
+static inline uint8_t filter_residual(int f, const uint8_t *cur, const uint8_t *up, size_t x, size_t bpp) {
+    const int a = x >= bpp ? cur[x - bpp] : 0, b = up[x], c = x >= bpp ? up[x - bpp] : 0, v = cur[x];
+    switch (f) {
+    case 0: return (uint8_t)v;
+    case 1: return (uint8_t)(v - a);
+    case 2: return (uint8_t)(v - b);
+    case 3: return (uint8_t)(v - ((a + b) >> 1));
+    default: return (uint8_t)(v - paeth_predictor(a, b, c));
+    }
+}
 
-bool write_png_rgb8(const std::string &path, int32_t width, int32_t height, const uint8_t *rgb) {
-    if (width <= 0 || height <= 0 || !rgb) return false;
-    const size_t stride = (size_t)width * 3u;
+// A colour-type-2 PNG of `depth` bits per sample from rows of width * bpp bytes as the file stores them (16-bit samples big-endian),
+// zlib-deflated, every row under the filter with the smallest sum of absolute (signed) residuals.
+static bool write_png_rgb(const std::string &path, int32_t width, int32_t height, const uint8_t *bytes, size_t bpp, uint8_t depth) {
+    const size_t stride = (size_t)width * bpp;
     std::vector<uint8_t> raw((stride + 1u) * (size_t)height);
-    std::vector<uint8_t> cand(stride), zero(stride, 0);
+    std::vector<uint8_t> zero(stride, 0);
     for (int32_t y = 0; y < height; ++y) {
-        const uint8_t *cur = rgb + (size_t)y * stride;
-        const uint8_t *up = y ? rgb + (size_t)(y - 1) * stride : zero.data();
-        // adaptive filter: minimum sum of absolute (signed) residuals
+        const uint8_t *cur = bytes + (size_t)y * stride;
+        const uint8_t *up = y ? bytes + (size_t)(y - 1) * stride : zero.data();
         int best_f = 0; uint64_t best_cost = ~0ull;
         for (int f = 0; f < 5; ++f) {
             uint64_t cost = 0;
-            for (size_t x = 0; x < stride; ++x) {
-                int a = x >= 3 ? cur[x - 3] : 0, b = up[x], c = x >= 3 ? up[x - 3] : 0, v = cur[x], r;
-                switch (f) {
-                case 0: r = v; break;
-                case 1: r = v - a; break;
-                case 2: r = v - b; break;
-                case 3: r = v - ((a + b) >> 1); break;
-                default: r = v - paeth(a, b, c); break;
-                }
-                cost += (uint64_t)std::abs((int)(int8_t)(uint8_t)r);
-            }
+            for (size_t x = 0; x < stride; ++x) cost += (uint64_t)std::abs((int)(int8_t)filter_residual(f, cur, up, x, bpp));
             if (cost < best_cost) { best_cost = cost; best_f = f; }
         }
         uint8_t *dst = raw.data() + (size_t)y * (stride + 1u);
         dst[0] = (uint8_t)best_f;
-        for (size_t x = 0; x < stride; ++x) {
-            int a = x >= 3 ? cur[x - 3] : 0, b = up[x], c = x >= 3 ? up[x - 3] : 0, v = cur[x], r;
-            switch (best_f) {
-            case 0: r = v; break;
-            case 1: r = v - a; break;
-            case 2: r = v - b; break;
-            case 3: r = v - ((a + b) >> 1); break;
-            default: r = v - paeth(a, b, c); break;
-            }
-            dst[1 + x] = (uint8_t)r;
-        }
+        for (size_t x = 0; x < stride; ++x) dst[1 + x] = filter_residual(best_f, cur, up, x, bpp);
     }
     uLongf zlen = compressBound((uLong)raw.size());
     std::vector<uint8_t> z(zlen);
@@ -331,15 +328,86 @@ bool write_png_rgb8(const std::string &path, int32_t width, int32_t height, cons
     std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     std::vector<uint8_t> ihdr;
     put_u32(ihdr, (uint32_t)width); put_u32(ihdr, (uint32_t)height);
-    ihdr.push_back(8); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
+    ihdr.push_back(depth); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
     put_chunk(out, "IHDR", ihdr.data(), ihdr.size());
     put_chunk(out, "IDAT", z.data(), (size_t)zlen);
     put_chunk(out, "IEND", nullptr, 0);
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) return false;
-    bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
-    ok = (fclose(f) == 0) && ok;
-    return ok;
+    return write_file(path, out);
+}
+
+bool write_png_rgb8(const std::string &path, int32_t width, int32_t height, const uint8_t *rgb) {
+    if (width <= 0 || height <= 0 || !rgb) return false;
+    return write_png_rgb(path, width, height, rgb, 3u, 8);
+}
+
+bool write_png_rgb16(const std::string &path, int32_t width, int32_t height, const uint16_t *rgb) {
+    if (width <= 0 || height <= 0 || !rgb) return false;
+    std::vector<uint8_t> be((size_t)width * (size_t)height * 6u); // the file's samples are big-endian
+    for (size_t i = 0; i < be.size() / 2u; ++i) { be[2 * i] = (uint8_t)(rgb[i] >> 8); be[2 * i + 1] = (uint8_t)rgb[i]; }
+    return write_png_rgb(path, width, height, be.data(), 6u, 16);
+}
+
+// ---- Radiance .hdr and PFM ------------------------------------------------------------------------------
+// One byte plane of a scanline in Radiance's new-style run-length code: a run of 4 .. 127 equal bytes is (128 + length, value), what
+// lies between two runs goes out as literals of at most 128 bytes, (length, bytes...).
+static void put_rle_plane(std::vector<uint8_t> &out, const uint8_t *plane, size_t n) {
+    const size_t MIN_RUN = 4;
+    for (size_t cur = 0; cur < n;) {
+        size_t beg = cur, run = 0; // the next run of at least MIN_RUN starts at beg (n: there is none)
+        while (beg < n) {
+            run = 1;
+            while (beg + run < n && run < 127 && plane[beg + run] == plane[beg]) ++run;
+            if (run >= MIN_RUN) break;
+            beg += run;
+        }
+        while (cur < beg) {
+            const size_t len = beg - cur < 128 ? beg - cur : 128;
+            out.push_back((uint8_t)len);
+            out.insert(out.end(), plane + cur, plane + cur + len);
+            cur += len;
+        }
+        if (beg < n) {
+            out.push_back((uint8_t)(128 + run));
+            out.push_back(plane[beg]);
+            cur += run;
+        }
+    }
+}
+
+bool write_hdr_rgbe(const std::string &path, int32_t width, int32_t height, const uint8_t *rgbe) {
+    if (width <= 0 || height <= 0 || !rgbe) return false;
+    const std::string head = "#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " + std::to_string(height) + " +X " + std::to_string(width) + "\n";
+    std::vector<uint8_t> out(head.begin(), head.end());
+    const size_t w = (size_t)width;
+    if (width < 8 || width > 32767) { // the run-length form does not exist at these widths: flat pixels
+        out.insert(out.end(), rgbe, rgbe + w * (size_t)height * 4u);
+        return write_file(path, out);
+    }
+    std::vector<uint8_t> plane(w);
+    for (int32_t y = 0; y < height; ++y) {
+        const uint8_t *row = rgbe + (size_t)y * w * 4u;
+        out.push_back(2); out.push_back(2); out.push_back((uint8_t)(width >> 8)); out.push_back((uint8_t)(width & 0xff));
+        for (size_t c = 0; c < 4; ++c) {
+            for (size_t x = 0; x < w; ++x) plane[x] = row[4 * x + c];
+            put_rle_plane(out, plane.data(), w);
+        }
+    }
+    return write_file(path, out);
+}
+
+bool write_pfm_rgb(const std::string &path, int32_t width, int32_t height, const float *rgb) {
+    if (width <= 0 || height <= 0 || !rgb) return false;
+    const std::string head = "PF\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    std::vector<uint8_t> out(head.begin(), head.end());
+    const size_t row = (size_t)width * 3u;
+    out.reserve(out.size() + row * (size_t)height * 4u);
+    for (int32_t y = height - 1; y >= 0; --y) // the bottom row first
+        for (size_t x = 0; x < row; ++x) {
+            uint32_t bits;
+            memcpy(&bits, rgb + (size_t)y * row + x, 4);
+            out.push_back((uint8_t)bits); out.push_back((uint8_t)(bits >> 8)); out.push_back((uint8_t)(bits >> 16)); out.push_back((uint8_t)(bits >> 24));
+        }
+    return write_file(path, out);
 }
 
 } // namespace rt

@@ -1,5 +1,5 @@
 // Image ingest for ImageTexture (reference: image::io::Reader::open(path).decode(), src/texture.rs:78) and
-// PNG output for render() (reference: image::codecs::png::PngEncoder, src/renderer.rs:59-72).
+// PNG, Radiance .hdr and PFM output for render() (reference: image::codecs::png::PngEncoder, src/renderer.rs:59-72).
 #pragma once
 #include <cstdint>
 #include <memory>
@@ -26,5 +26,15 @@ ImageRGB8 synthetic_earth(int32_t width, int32_t height);
 
 // RGB8 PNG, zlib-deflated, adaptive per-row filter.  Returns false on I/O failure.
 bool write_png_rgb8(const std::string &path, int32_t width, int32_t height, const uint8_t *rgb);
+
+// The film formats' files (include/rt_amd.h "film output"), each from the frame rt_film_device / rth_film writes in its format; false on
+// I/O failure.
+//   write_png_rgb16: native-endian uint16 samples as a PNG of colour type 2 and bit depth 16, through write_png_rgb8's filter and zlib path.
+//   write_hdr_rgbe:  R, G, B, E bytes as a Radiance picture, "#?RADIANCE / FORMAT=32-bit_rle_rgbe / -Y h +X w", top row first; scanlines
+//                    of 8 .. 32767 pixels in the new-style run-length code (2 2 hi lo, then the four byte planes), others as flat pixels.
+//   write_pfm_rgb:   floats as a colour PFM, "PF / w h / -1.0": little-endian, the bottom row first.
+bool write_png_rgb16(const std::string &path, int32_t width, int32_t height, const uint16_t *rgb);
+bool write_hdr_rgbe(const std::string &path, int32_t width, int32_t height, const uint8_t *rgbe);
+bool write_pfm_rgb(const std::string &path, int32_t width, int32_t height, const float *rgb);
 
 } // namespace rt

@@ -38,6 +38,9 @@
 //   --robust K [--robust-mode mean|trim|median|gini] [--robust-trim T] [--robust-gain X] (robust frames of include/rt_amd.h: K sub-frames
 //   of spp / K samples under seeds seed + k in one views launch, combined by the median of means; --denoise filters the result with
 //   samples = K, --bloom and --tonemap run behind it).
+//   --format png|png16|hdr|pfm (film output of include/rt_amd.h: the frame of every single-GPU, one-pass route — each file of --orbit,
+//   the last frame of --live — as a 16-bit PNG, a Radiance OUTPUT.hdr or a float OUTPUT.pfm; --tonemap, --exposure, --auto-exposure,
+//   --tonemap-white and --bloom apply in front of every format, and with none of them .hdr and .pfm hold the linear means).
 #include "image_io.hpp"
 #include "renderer.hpp"
 #include "scenes.hpp"
@@ -100,6 +103,10 @@ static void usage(const char *argv0) {
             "                         or, default, as many as X times the blocks' Gini coefficient asks for (gini; X > 0, default 1); fireflies stay\n"
             "                         in their block and are trimmed; --denoise then filters the robust frame with samples = K; also with --tonemap\n"
             "                         and --bloom; not with -l, --adaptive, --orbit, --progressive, --upsample, --gpus > 1, --denoise-albedo, --denoise-edges)\n"
+            "          [--format png|png16|hdr|pfm]   (one GPU, any route but --progressive: the file written — each file of --orbit, the last frame\n"
+            "                         of --live — is OUTPUT.png with 8-bit samples, default, or 16-bit ones (png16), a Radiance OUTPUT.hdr with shared-\n"
+            "                         exponent pixels (hdr) or a float OUTPUT.pfm (pfm); --tonemap, --exposure, --auto-exposure, --tonemap-white and\n"
+            "                         --bloom apply in front of every format: with none of them hdr and pfm hold the linear means, unclipped)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -252,6 +259,14 @@ int main(int argc, char **argv) {
             ro.robust_gain = strtod(v, &end); robust_knob_given = true;
             if (end == v || *end != 0 || !(ro.robust_gain > 0.0) || !(ro.robust_gain < 1e300)) { fprintf(stderr, "--robust-gain needs a gain above 0\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--format") {
+            const std::string f = need("--format");
+            if (f == "png") ro.format = FILM_PNG;
+            else if (f == "png16") ro.format = FILM_PNG16;
+            else if (f == "hdr") ro.format = FILM_HDR;
+            else if (f == "pfm") ro.format = FILM_PFM;
+            else { fprintf(stderr, "--format needs a file format: png, png16, hdr or pfm\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--upsample-albedo") ro.upsample_albedo = true;
         else if (a == "--upsample-edges") ro.upsample_edges = true;
         else if (a == "--earth") so.earth_image = need("--earth");
@@ -331,6 +346,16 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--bloom runs in front of the tone mapping of a one-GPU, one-pass route: it cannot be combined with --gpus > 1 or --progressive\n");
         return 2;
     }
+    if (ro.format != FILM_PNG && ro.gpus > 1) {
+        fprintf(stderr, "--format other than png is written by the film stage of a one-GPU route: it cannot be combined with --gpus > 1 (the gather "
+                        "carries 8-bit tiles)\n");
+        return 2;
+    }
+    if (ro.format != FILM_PNG && ro.progressive_spp > 0) {
+        fprintf(stderr, "--format other than png is written by the film stage of a one-pass route: it cannot be combined with --progressive (the "
+                        "passes rewrite an 8-bit PNG)\n");
+        return 2;
+    }
     if (bloom_knob_given && ro.bloom < 0.0) {
         fprintf(stderr, "--bloom-threshold and --bloom-levels set the glow of --bloom: they need --bloom\n");
         return 2;
@@ -384,9 +409,14 @@ int main(int argc, char **argv) {
         if (live) {
             now = std::chrono::steady_clock::now();
             int frames = 0, samples = 0;
-            const std::vector<uint8_t> rgba = live_render(camera, *bvh, ro, [&](const std::vector<uint8_t> &, int n) { ++frames; samples = n; });
+            std::vector<uint8_t> film;
+            const std::vector<uint8_t> rgba = live_render(camera, *bvh, ro, [&](const std::vector<uint8_t> &, int n) { ++frames; samples = n; }, &film);
             printf("Live: %d frames, %d samples per pixel in the last, %.2fs\n", frames, samples,
                    std::chrono::duration<double>(std::chrono::steady_clock::now() - now).count());
+            if (ro.format != FILM_PNG) { // the last frame in the film format, from the means it was shown from
+                write_film_frame(output, (int32_t)camera.image_width, (int32_t)camera.image_height, film, ro);
+                return 0;
+            }
             std::vector<uint8_t> rgb(rgba.size() / 4u * 3u);
             for (size_t p = 0; p < rgba.size() / 4u; ++p) { rgb[3 * p] = rgba[4 * p]; rgb[3 * p + 1] = rgba[4 * p + 1]; rgb[3 * p + 2] = rgba[4 * p + 2]; }
             if (!write_png_rgb8(output + ".png", (int32_t)camera.image_width, (int32_t)camera.image_height, rgb.data()))

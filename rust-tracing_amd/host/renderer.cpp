@@ -134,7 +134,10 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp) 
 
 // The tone-mapping stage (include/rt_amd.h "tone mapping") is on when any of its options was given: opt.tonemap >= 0 — or when bloom
 // is on (opt.bloom >= 0), which runs in front of it: the stage then has the clamp unless an operator was chosen.
-static bool tonemapped(const RenderOptions &opt) { return opt.tonemap >= 0 || opt.bloom >= 0.0; }
+// A film format (opt.format other than FILM_PNG; include/rt_amd.h "film output") turns the stage on as well: the film stage is the
+// tone-mapping stage with another last step, and with nothing else given it runs with the clamp and exposure 1, where its value is the mean.
+static bool filmed(const RenderOptions &opt) { return opt.format != FILM_PNG; }
+static bool tonemapped(const RenderOptions &opt) { return opt.tonemap >= 0 || opt.bloom >= 0.0 || filmed(opt); }
 static rt_tonemap_params tonemap_params(const char *who, const RenderOptions &opt) {
     rt_tonemap_params tp;
     if (rt_tonemap_params_init_sized(&tp, sizeof tp) != RT_OK) throw std::runtime_error(std::string(who) + ": " + rt_last_error());
@@ -162,6 +165,35 @@ std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double 
     if (tp.auto_key > 0.0) check(rt_device_malloc(0, work, &d_work));
     check(rt_tonemap_device(width, height, d_values, spp, d_spp, &tp, rgba ? nullptr : static_cast<uint8_t *>(d_out),
                             rgba ? static_cast<uint8_t *>(d_out) : nullptr, d_work, nullptr));
+    std::vector<uint8_t> px((size_t)bytes);
+    check(rt_device_download(0, px.data(), d_out, bytes, nullptr)); // (waits for the stage: the buffers are freed behind it)
+    cleanup();
+    return px;
+}
+
+// The film stage with opt's operator, exposure, key and white, in the format opt.format's file takes.
+static int32_t film_format(const RenderOptions &opt) { return opt.format == FILM_HDR ? RT_FILM_RGBE : opt.format == FILM_PFM ? RT_FILM_F32 : RT_FILM_RGB16; }
+
+std::vector<uint8_t> film_host(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
+    const rt_tonemap_params tp = tonemap_params("film", opt);
+    const int64_t bytes = rt_film_bytes(width, height, film_format(opt));
+    if (bytes < 0) throw std::runtime_error("film: no frame of this size");
+    if (values.size() != (size_t)width * (size_t)height * 3u) throw std::runtime_error("film: the frame does not hold 3 * width * height values");
+    std::vector<uint8_t> px((size_t)bytes);
+    if (rth_film(width, height, values.data(), spp, nullptr, &tp, film_format(opt), px.data()) != 0) throw std::runtime_error(rth_last_error());
+    return px;
+}
+
+std::vector<uint8_t> film_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const RenderOptions &opt) {
+    const rt_tonemap_params tp = tonemap_params("film", opt);
+    const int64_t bytes = rt_film_bytes(width, height, film_format(opt)), work = rt_tonemap_workspace_bytes(width, height);
+    void *d_out = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_out); rt_device_free(0, d_work); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("film: " + msg); } };
+    if (bytes < 0 || work < 0) throw std::runtime_error("film: no frame of this size");
+    check(rt_device_malloc(0, bytes, &d_out));
+    if (tp.auto_key > 0.0) check(rt_device_malloc(0, work, &d_work));
+    check(rt_film_device(width, height, d_values, spp, d_spp, &tp, film_format(opt), d_out, d_work, nullptr));
     std::vector<uint8_t> px((size_t)bytes);
     check(rt_device_download(0, px.data(), d_out, bytes, nullptr)); // (waits for the stage: the buffers are freed behind it)
     cleanup();
@@ -198,25 +230,48 @@ void bloom_device(int32_t width, int32_t height, const double *d_values, int32_t
     rt_device_free(0, d_work);
 }
 
-// the output stage of a HOST frame of sums when the tone-mapping stage is on: bloom first if it is on, then the stage on its means
+// the output stage of a HOST frame of sums when the tone-mapping stage is on: bloom first if it is on, then the stage on its means —
+// or, with a film format, the film stage in its place: the bytes are then the frame in that format, what write_frame takes
 static std::vector<uint8_t> staged_rgb8(const std::vector<double> &sums, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
-    if (!bloomed(opt)) return tonemap_rgb8(sums, width, height, spp, opt);
-    return tonemap_rgb8(bloom_means(sums, width, height, spp, opt), width, height, 1, opt);
+    const auto stage = filmed(opt) ? film_host : tonemap_rgb8;
+    if (!bloomed(opt)) return stage(sums, width, height, spp, opt);
+    return stage(bloom_means(sums, width, height, spp, opt), width, height, 1, opt);
 }
 
 // ... and of a DEVICE frame
 static std::vector<uint8_t> staged_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
                                           const RenderOptions &opt) {
-    if (!bloomed(opt)) return tonemap_device(width, height, d_values, spp, d_spp, rgba, opt);
+    auto stage = [&](const double *d_frame, int32_t n, const int32_t *d_map) { // (a film format has one layout: `rgba` is the display bytes' choice)
+        return filmed(opt) ? film_device(width, height, d_frame, n, d_map, opt) : tonemap_device(width, height, d_frame, n, d_map, rgba, opt);
+    };
+    if (!bloomed(opt)) return stage(d_values, spp, d_spp);
     void *d_bloomed = nullptr;
     if (rt_device_malloc(0, (int64_t)width * height * 3 * (int64_t)sizeof(double), &d_bloomed) != RT_OK) throw std::runtime_error(std::string("bloom: ") + rt_last_error());
     std::vector<uint8_t> px;
     try {
         bloom_device(width, height, d_values, spp, d_spp, static_cast<double *>(d_bloomed), opt);
-        px = tonemap_device(width, height, static_cast<const double *>(d_bloomed), 1, nullptr, rgba, opt);
+        px = stage(static_cast<const double *>(d_bloomed), 1, nullptr);
     } catch (...) { rt_device_free(0, d_bloomed); throw; }
     rt_device_free(0, d_bloomed);
     return px;
+}
+
+// The frame's file: NAME.png from RGB bytes, or with a film format NAME.hdr / NAME.pfm / NAME.png from the bytes the staging made in it.
+static void write_frame(const std::string &name, int32_t width, int32_t height, const std::vector<uint8_t> &px, const RenderOptions &opt) {
+    const int64_t want = filmed(opt) ? rt_film_bytes(width, height, film_format(opt)) : (int64_t)width * height * 3;
+    bool ok = want >= 0 && px.size() >= (size_t)want;
+    if (!ok) throw std::runtime_error("render: the frame's bytes do not fit its format");
+    switch (opt.format) {
+    case FILM_HDR: ok = write_hdr_rgbe(name + ".hdr", width, height, px.data()); break;
+    case FILM_PFM: ok = write_pfm_rgb(name + ".pfm", width, height, reinterpret_cast<const float *>(px.data())); break;
+    case FILM_PNG16: ok = write_png_rgb16(name + ".png", width, height, reinterpret_cast<const uint16_t *>(px.data())); break;
+    default: ok = write_png_rgb8(name + ".png", width, height, px.data()); break;
+    }
+    if (!ok) throw std::runtime_error("Should've encoded the image into a file."); // src/renderer.rs:72
+}
+
+void write_film_frame(const std::string &name, int32_t width, int32_t height, const std::vector<uint8_t> &film, const RenderOptions &opt) {
+    write_frame(name, width, height, film, opt);
 }
 
 // Guided upsampling (include/rt_amd.h "guided upsampling") is on when opt.upsample is a factor, 2..4.
@@ -702,8 +757,12 @@ constexpr int32_t LIVE_UPSAMPLE_GUIDE_SPP = 16;
 
 // The running mean and its display frame stay on the device; every pass is one rt_render_mean_device call (the render launches and one
 // reduction that also writes the RGBA8 frame), and only the bytes to show come back.
-std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt,
-                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame) {
+std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &asked,
+                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame, std::vector<uint8_t> *final_film) {
+    // every frame shown is RGBA8 whatever asked.format says: the passes run under `opt`, the options without the film format, and the
+    // format shapes only *final_film, made from the last pass's means
+    RenderOptions opt = asked;
+    opt.format = FILM_PNG;
     SceneDescriber sd;
     const rt_ref root = world.describe(sd);
     const rt_scene_desc desc = sd.desc(root);
@@ -719,7 +778,10 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     std::vector<uint8_t> frame((size_t)n_shown * 4u, 0);
     for (size_t k = 3; k < frame.size(); k += 4) frame[k] = 0xff; // color_to_rgb(Color::ZERO), alpha 0xff
     const int last = cam.samples_per_pixel - 1; // `if num_samples < spp` (src/renderer.rs:104): divisors 1 .. spp - 1
-    if (last <= 0) return frame;
+    if (last <= 0) {
+        if (final_film && filmed(asked)) *final_film = film_host(std::vector<double>((size_t)n_shown * 3u, 0.0), fw, fh, 1, asked);
+        return frame;
+    }
     const int pass = opt.live_spp > 0 ? opt.live_spp : 1;
     // opt.live_denoise: the pass keeps M2 beside the mean, and the frame shown is the filter's, written to d_shown and its bytes to
     // d_rgba8: the running frames (d_mean, d_m2, and the guided filter's running albedo mean d_alb) are the filter's inputs only
@@ -804,6 +866,10 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         if (on_frame) {
             try { on_frame(frame, end); } catch (...) { cleanup(); throw; }
         }
+        if (end == last && final_film && filmed(asked)) { // the frame just shown, in the film format: bloom and the stage on the same means
+            try { *final_film = staged_device(fw, fh, d_means, 1, nullptr, false, asked); }
+            catch (...) { cleanup(); throw; }
+        }
     }
     cleanup();
     return frame;
@@ -883,11 +949,12 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
         const std::vector<uint8_t> px = render_orbit_denoised_rgb8(desc, views, p, opt);
         if (!opt.quiet) printf("Render time: %.2fs (%d views, denoised)\n", std::chrono::duration<double>(clock::now() - now).count(), opt.orbit);
         now = clock::now();
+        const size_t one = px.size() / (size_t)opt.orbit; // a view's bytes, in the format asked for
         for (int k = 0; k < opt.orbit; ++k) {
             char suffix[16];
-            snprintf(suffix, sizeof suffix, "_%03d.png", k);
-            if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, px.data() + frame * (size_t)k))
-                throw std::runtime_error("Should've encoded the image into a file.");
+            snprintf(suffix, sizeof suffix, "_%03d", k);
+            write_frame(output_file_name + suffix, cam.image_width, cam.image_height,
+                        std::vector<uint8_t>(px.begin() + (ptrdiff_t)(one * (size_t)k), px.begin() + (ptrdiff_t)(one * (size_t)(k + 1))), opt);
         }
         if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         return;
@@ -907,11 +974,10 @@ static void render_orbit(const Camera &camera, const Hittable &world, const std:
     for (int k = 0; k < opt.orbit; ++k) {
         const std::vector<double> one(sums.begin() + (ptrdiff_t)(frame * (size_t)k), sums.begin() + (ptrdiff_t)(frame * (size_t)(k + 1)));
         char suffix[16];
-        snprintf(suffix, sizeof suffix, "_%03d.png", k);
+        snprintf(suffix, sizeof suffix, "_%03d", k);
         const std::vector<uint8_t> px = tonemapped(opt) ? staged_rgb8(one, cam.image_width, cam.image_height, cam.samples_per_pixel, opt) // (each view its own frame)
                                                         : resolve_rgb8(one, cam.samples_per_pixel);
-        if (!write_png_rgb8(output_file_name + suffix, cam.image_width, cam.image_height, px.data()))
-            throw std::runtime_error("Should've encoded the image into a file.");
+        write_frame(output_file_name + suffix, cam.image_width, cam.image_height, px, opt);
     }
     if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
 }
@@ -921,6 +987,10 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     using clock = std::chrono::steady_clock;
     auto now = clock::now();
     const int32_t w = (int32_t)camera->image_width, h = (int32_t)camera->image_height;
+    if (opt.format < FILM_PNG || opt.format > FILM_PFM) throw std::runtime_error("render: format must be FILM_PNG, FILM_PNG16, FILM_HDR or FILM_PFM");
+    if (filmed(opt) && (opt.gpus > 1 || opt.progressive_spp > 0))
+        throw std::runtime_error("render: a format other than png is written by the film stage of a one-GPU, one-pass route: it cannot be combined with "
+                                 "gpus > 1 or progressive_spp (the gather and the passes carry 8-bit frames)");
     if (opt.upsample != 0 && (opt.upsample < 2 || opt.upsample > 4)) throw std::runtime_error("render: upsample must be 0 (off), 2, 3 or 4");
     if (opt.upsample > 0 && (opt.orbit > 0 || opt.adaptive || opt.gpus > 1 || opt.progressive_spp > 0))
         throw std::runtime_error("render: upsample is a one-GPU, one-pass route: it cannot be combined with orbit, adaptive, gpus > 1 or progressive_spp");
@@ -934,7 +1004,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
         const std::vector<uint8_t> px = render_robust_rgb8(*camera, *world, opt);
         if (!opt.quiet) printf("Render time: %.2fs (%d robust blocks)\n", std::chrono::duration<double>(clock::now() - now).count(), opt.robust_blocks);
         now = clock::now();
-        if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");
+        write_frame(output_file_name, w, h, px, opt);
         if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         return;
     }
@@ -948,7 +1018,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
                                                          : render_denoised_rgb8(*camera, *world, opt);
         if (!opt.quiet) printf("Render time: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         now = clock::now();
-        if (!write_png_rgb8(output_file_name + ".png", w, h, px.data())) throw std::runtime_error("Should've encoded the image into a file.");
+        write_frame(output_file_name, w, h, px, opt);
         if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
         return;
     }
@@ -968,9 +1038,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
 
     now = clock::now();
     const std::vector<uint8_t> px = tonemapped(opt) ? staged_rgb8(sums, w, h, camera->samples_per_pixel, opt) : resolve_rgb8(sums, camera->samples_per_pixel);
-    if (!write_png_rgb8(output_file_name + ".png", (int32_t)camera->image_width, (int32_t)camera->image_height,
-                        px.data()))
-        throw std::runtime_error("Should've encoded the image into a file."); // src/renderer.rs:72
+    write_frame(output_file_name, w, h, px, opt);
     if (!opt.quiet)
         printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
 }

@@ -15,6 +15,9 @@
 
 namespace rt {
 
+// The file render() writes (RenderOptions::format): the reference's 8-bit PNG, or one of the film formats of include/rt_amd.h "film output".
+enum FilmFile { FILM_PNG = 0, FILM_PNG16 = 1, FILM_HDR = 2, FILM_PFM = 3 };
+
 struct RenderOptions {
     uint64_t seed = 1; // render seed (the reference's RNG is unseeded; see include/rt_amd.h "RNG")
     int gpus = 1;      // framebuffer tiles are dealt round-robin to this many devices
@@ -114,6 +117,13 @@ struct RenderOptions {
     int robust_mode = RT_ROBUST_GINI;   // RT_ROBUST_*
     int robust_trim = 1;                // RT_ROBUST_TRIM's count
     double robust_gain = 0.0;           // RT_ROBUST_GINI's gain; <= 0: the library's default
+    // film output (include/rt_amd.h "film output"): FILM_PNG16, FILM_HDR or FILM_PFM sends the frame of every single-GPU, one-pass route
+    // — plain, adaptive, the denoise family, robust, upsample, each view of orbit and live_render's final frame — through the film stage
+    // (rt_film_device; a plain render's and an unfiltered orbit's through its host mirror rth_film, the same bytes) in the tone-mapping
+    // stage's place, behind bloom, with that stage's operator, exposure and key, and writes NAME.png (16-bit), NAME.hdr or NAME.pfm.  With
+    // no tonemap, exposure or bloom given the stage runs with the clamp and exposure 1: .hdr and .pfm hold the linear means.  Not with
+    // gpus > 1 or progressive_spp (render() throws).
+    int format = FILM_PNG;
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -172,6 +182,13 @@ std::vector<uint8_t> tonemap_rgb8(const std::vector<double> &values, int32_t wid
 std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, bool rgba,
                                     const RenderOptions &opt);
 
+// The film stage likewise, in the format of opt.format's file (FILM_HDR: RT_FILM_RGBE, FILM_PFM: RT_FILM_F32, FILM_PNG16: RT_FILM_RGB16):
+// film_host through the host mirror rth_film on a HOST frame, film_device through rt_film_device on device 0 over a DEVICE frame; both
+// return rt_film_bytes(w, h, format) bytes.  write_film_frame writes such a frame to NAME.hdr / NAME.pfm / NAME.png.
+std::vector<uint8_t> film_host(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
+std::vector<uint8_t> film_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const RenderOptions &opt);
+void write_film_frame(const std::string &name, int32_t width, int32_t height, const std::vector<uint8_t> &film, const RenderOptions &opt);
+
 // Bloom with opt's strength, threshold and levels.  bloom_means: on a HOST frame (sums with the uniform count spp; means with spp = 1),
 // through the host mirror; returns the 3 * w * h bloomed means.  bloom_device: rt_bloom_device on device 0 over a DEVICE frame (sums with
 // spp or, if d_spp is not null, a device map; means with spp = 1) into the DEVICE frame d_mean_out (3 * w * h doubles, not d_values):
@@ -214,8 +231,11 @@ std::vector<uint8_t> resolve_rgb8(const std::vector<double> &sums, int32_t spp);
 // the reference's zeroed raw_pixels, when spp <= 1 leaves nothing to draw).  Throws std::runtime_error on a GPU library error.
 // With opt.live_denoise the frame handed over is the filtered one (above); the loop still settles on spp - 1 samples.  With
 // opt.live_denoise_spatial as well, that holds from the first pass on.
+// The frames shown are RGBA8 whatever opt.format says; with a film format and final_film not null, *final_film receives the last
+// frame in that format (bloom and the film stage over the means the last frame shown was made from).
 std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, const RenderOptions &opt = {},
-                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame = nullptr);
+                                 const std::function<void(const std::vector<uint8_t> &, int)> &on_frame = nullptr,
+                                 std::vector<uint8_t> *final_film = nullptr);
 
 void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, const std::string &output_file_name,
             const RenderOptions &opt = {});
