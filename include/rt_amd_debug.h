@@ -138,6 +138,40 @@ typedef struct rt_debug_wide {
 } rt_debug_wide;
 int rt_debug_wide_records(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_wide *io);
 
+/* Test hook (no GPU needed): the plan of the scene rt_scene_create_ex would make of `desc` under `options` — everything scene creation
+ * decides and every byte it uploads (csrc/rt_scene_plan.hpp; the same options check, the same planner).
+ * In: oimage, lds_image, aux_image, mats, insts with their capacities in bytes (any may be null: only sizes and digests are returned).
+ * Out: the layout's scalars under the names rt_scene's launches read them by (o_root 0xfffffffe: no own tree to start in;
+ * o_start_direct 0xffffffff: none; lds_off_qfilt 0: no filter records); the scene's stats as rt_scene_get_stats returns them;
+ * level[0] / level[1]: a launch at LDS level 0 and at the scene's lds_level (what rt_scene_options.use_lds chooses between) — the
+ * kernel's feature mask, its workgroup threads, whether the small tables (AUX) and the parked world rays go into the LDS, where the
+ * regions of the dynamic LDS start (stacks, sequence, AUX, world rays, profile rows) and its size, plain and for the instrumented
+ * kernel; images[0..3]: byte count and 64-bit FNV-1a digest of the node tables' global form, the LDS image, the AUX image and the
+ * material table; tables[0..10]: the same for the tables uploaded as they are — nodes, sequence, spheres, quads, instances, media,
+ * textures, Perlin tables, image records, texels, sRGB table. */
+typedef struct rt_debug_plan_level {
+    uint32_t lds_level, features, threads, aux_in_lds, world_in_lds;
+    uint32_t stack_off, seq_off, aux_off, world_off, prof_off;
+    uint32_t dynamic_lds_bytes, dynamic_lds_bytes_counted;
+} rt_debug_plan_level;
+typedef struct rt_debug_plan_bytes {
+    uint64_t bytes, digest;
+} rt_debug_plan_bytes;
+typedef struct rt_debug_plan {
+    int64_t cap_oimage, cap_lds_image, cap_aux_image, cap_mats, cap_insts;
+    uint8_t *oimage, *lds_image, *aux_image, *mats, *insts;
+    uint32_t features, parks_colours, has_instances, ordered, wide, o_root, n_oseq, o_stack, n_nodes;
+    uint32_t o_start_stage, o_start_prim, o_start_end, o_start_rest, o_start_slot, o_start_direct;
+    float box_extent;
+    uint32_t lds_level, lds_off_node_b, lds_off_spheres, lds_off_quads, lds_off_qfilt, lds_prefix_bytes[4];
+    uint32_t aux_bytes, aux_off[5];
+    rt_scene_stats stats;
+    rt_debug_plan_level level[2];
+    rt_debug_plan_bytes images[4];
+    rt_debug_plan_bytes tables[11];
+} rt_debug_plan;
+int rt_debug_scene_plan(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_plan *io);
+
 /* Test hook: the visit of a four-child record as the render kernels make it (rt_device_scene.h: make_ray_pair32, load_oquad,
  * box_quad_f32 on the interval converted outward, wide_verdict with the ray's degenerate flag, wide_nearest), on n cases.
  * Per case: rays = (origin xyz, direction xyz), the interval (tmin[i], tmax[i]), todo[i] = the mask of the slots to look at.

@@ -470,6 +470,7 @@ RT_AMD_DEBUG_SYMBOLS = {
     "rt_debug_wide_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "rt_debug_wide_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_wide_visits": (C.c_int, [C.c_void_p, C.c_int]),
+    "rt_debug_scene_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_debug_set_traversal": (C.c_int, [C.c_int32, C.c_int32]),
     "rt_debug_set_walk_shortcuts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rt_debug_set_start_inline": (C.c_int, [C.c_int32]),
@@ -578,6 +579,29 @@ class DebugWide(C.Structure):
                 ("lds_image", C.c_void_p), ("step_boxes", C.c_void_p)]
 
 
+class DebugPlanLevel(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("lds_level", "features", "threads", "aux_in_lds", "world_in_lds", "stack_off", "seq_off", "aux_off",
+                                          "world_off", "prof_off", "dynamic_lds_bytes", "dynamic_lds_bytes_counted")]
+
+
+class DebugPlanBytes(C.Structure):
+    _fields_ = [("bytes", C.c_uint64), ("digest", C.c_uint64)]
+
+
+PLAN_IMAGES = ("oimage", "lds_image", "aux_image", "mats")  # what scene creation builds; then the tables it uploads as they are
+PLAN_TABLES = ("nodes", "oseq", "spheres", "quads", "insts", "media", "texs", "perlins", "images", "texels", "lut")
+PLAN_SCALARS = ("features", "parks_colours", "has_instances", "ordered", "wide", "o_root", "n_oseq", "o_stack", "n_nodes", "o_start_stage",
+                "o_start_prim", "o_start_end", "o_start_rest", "o_start_slot", "o_start_direct", "box_extent", "lds_level", "lds_off_node_b",
+                "lds_off_spheres", "lds_off_quads", "lds_off_qfilt", "lds_prefix_bytes", "aux_bytes", "aux_off")
+
+
+class DebugPlan(C.Structure):
+    _fields_ = [("cap_" + n, C.c_int64) for n in PLAN_IMAGES + ("insts",)] + [(n, C.c_void_p) for n in PLAN_IMAGES + ("insts",)] + \
+               [(n, C.c_uint32) for n in PLAN_SCALARS[:15]] + [("box_extent", C.c_float)] + [(n, C.c_uint32) for n in PLAN_SCALARS[16:21]] + \
+               [("lds_prefix_bytes", C.c_uint32 * 4), ("aux_bytes", C.c_uint32), ("aux_off", C.c_uint32 * 5), ("stats", SceneStats),
+                ("level", DebugPlanLevel * 2), ("image_bytes", DebugPlanBytes * 4), ("table_bytes", DebugPlanBytes * 11)]
+
+
 class DebugWideCases(C.Structure):
     _fields_ = [("n", C.c_int64), ("rays", C.c_void_p), ("tmin", C.c_void_p), ("tmax", C.c_void_p), ("todo", C.c_void_p),
                 ("boxes", C.c_void_p), ("refs", C.c_void_p), ("global_image", C.c_void_p), ("lds_image", C.c_void_p),
@@ -604,6 +628,35 @@ def debug_wide_records(host_scene, **option_fields) -> dict:
     assert (int(io.n_records), int(io.n_steps)) == (n, ns)
     return {"wide": bool(io.wide), "box_extent": float(io.box_extent), "table_bytes": int(io.table_bytes), "boxes": boxes[:n], "refs": refs[:n],
             "bounds": bounds[:n], "global_image": glob[:n], "lds_image": lds[:n * 208], "step_boxes": steps[:ns]}
+
+
+def debug_scene_plan(host_scene, options: "SceneCreateOptions | None" = None, **option_fields) -> dict:
+    """rt_debug_scene_plan: what rt_scene_create_ex would decide and upload for this scene under these options (CPU only).  The layout's
+    scalars by name (box_extent a float, lds_prefix_bytes and aux_off lists); "stats" as DeviceScene.stats(); "levels": {0: ...,
+    lds_level: ...}, a launch at either LDS level; "sizes" and "digests" (64-bit FNV-1a) of the four images and the eleven tables by name
+    (PLAN_IMAGES, PLAN_TABLES); the four images and the instance table as uint8 arrays."""
+    import numpy as np
+    io = DebugPlan()
+    if option_fields:
+        assert options is None
+        options = scene_options(**option_fields)
+    call = lambda: amd_lib().rt_debug_scene_plan(C.addressof(host_scene.desc), C.addressof(options) if options is not None else None, C.addressof(io))
+    _check(call(), "rt_debug_scene_plan")
+    sized = dict(zip(PLAN_IMAGES, (int(b.bytes) for b in io.image_bytes)), insts=int(io.table_bytes[PLAN_TABLES.index("insts")].bytes))
+    bufs = {n: np.zeros(max(size, 1), dtype=np.uint8) for n, size in sized.items()}
+    for n, a in bufs.items():
+        setattr(io, "cap_" + n, a.size)
+        setattr(io, n, a.ctypes.data)
+    _check(call(), "rt_debug_scene_plan")
+    out = {n: (list(getattr(io, n)) if n in ("lds_prefix_bytes", "aux_off") else float(io.box_extent) if n == "box_extent" else int(getattr(io, n)))
+           for n in PLAN_SCALARS}
+    out["stats"] = io.stats.as_dict()
+    out["levels"] = {int(v.lds_level): {n: int(getattr(v, n)) for n, _ in DebugPlanLevel._fields_} for v in io.level}
+    named = list(zip(PLAN_IMAGES, io.image_bytes)) + list(zip(PLAN_TABLES, io.table_bytes))
+    out["sizes"] = {n: int(b.bytes) for n, b in named}
+    out["digests"] = {n: f"{int(b.digest):016x}" for n, b in named}
+    out.update({n: a[:sized[n]] for n, a in bufs.items()})
+    return out
 
 
 def debug_wide_visits(rays, tmin, tmax, todo, boxes=None, refs=None, records=None, record=None, extent=0.0, lds=0, device=0) -> dict:

@@ -20,7 +20,6 @@ using namespace rtapi;
 
 namespace rtapi {
 
-thread_local std::string g_last_error;
 thread_local uint32_t g_last_launch[4] = {0, 0, 0, 0};
 thread_local uint32_t g_last_kernel[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 thread_local uint32_t g_last_start[4] = {0, 0, 0, 0};
@@ -28,23 +27,6 @@ std::mutex g_stage_profile_mu;
 unsigned long long g_stage_profile[PROF_SLOTS * 3] = {0};
 unsigned long long g_visit_stats[VISIT_STATS] = {0};
 
-int fail(int status, const std::string &msg) {
-    g_last_error = msg;
-    return status;
-}
-
-Tuning::Tuning() {
-    auto env = [](const char *name, int &v) { if (const char *e = getenv(name)) v = atoi(e); };
-    env("RT_TH_PRIM", forced[0]); env("RT_TH_OTHER", forced[1]); env("RT_TH_SHADE", forced[2]); env("RT_TH_BOX", forced[3]); env("RT_TH_NEW", forced[4]);
-    env("RT_USE_LDS", use_lds); env("RT_REFIT", refit); env("RT_ORDERED", ordered); env("RT_JOBS_PER_GRAB", jobs_per_grab); env("RT_GRAB_TAPER", grab_taper); env("RT_DEFER", defer); env("RT_START_SHORTCUT", start_shortcut); env("RT_START_INLINE", start_inline); env("RT_SEQ_LOOKAHEAD", seq_lookahead); env("RT_SLOW_MIN", slow_min); env("RT_SLOW_AGE", slow_age); env("RT_OVERLAP", overlap);
-    env("RT_WIDE", wide); env("RT_WIDE_SETASIDE", wide_setaside); env("RT_QUAD_FILTER", quad_filter); env("RT_MEDIUM_FIRST", medium_first);
-    if (const char *e = getenv("RT_SAH_LEAF")) ordered_options.leaf_max = (uint32_t)atoi(e);
-    if (const char *e = getenv("RT_FLAT_MAX")) ordered_options.flat_max = (uint32_t)atoi(e);
-    if (const char *e = getenv("RT_SAH_SPHERE")) ordered_options.cost_sphere = atof(e);
-    if (const char *e = getenv("RT_SAH_QUAD")) ordered_options.cost_quad = atof(e);
-    if (const char *e = getenv("RT_SAH_INSTANCE")) ordered_options.cost_instance = atof(e);
-    if (const char *e = getenv("RT_SAMPLE_BUFFER_MB")) sample_buffer_bytes = (size_t)strtoull(e, nullptr, 10) << 20;
-}
 namespace {
 std::mutex g_tuning_mu;
 Tuning &tuning_locked() { static Tuning t; return t; } // call with g_tuning_mu held
@@ -69,36 +51,6 @@ uint64_t host_mix64(uint64_t z) {
     return z;
 }
 
-uint32_t lds_image_bytes_for(const rt_scene *s, int lds) { return s->lds_prefix_bytes[lds]; }
-// the LDS image, then (ordered walk) the per-lane stacks: 2-byte entries beside an LDS-resident scene, else 4-byte
-int block_threads(const rt_scene *s, int lds) { return kernel_threads_for(kernel_features_for(s->features, lds, s->ordered), lds, s->ordered); }
-size_t stack_bytes(const rt_scene *s, int lds) {
-    if (!s->ordered) return 0;
-    return (size_t)s->o_stack * (size_t)block_threads(s, lds) * (lds ? 2u : 4u);
-}
-size_t prof_bytes(const rt_scene *s, int lds) { return (size_t)(block_threads(s, lds) / 64) * PROF_SLOTS * 3u * sizeof(unsigned long long); }
-// behind the image and the stacks: the world's sequence | the small tables (AUX kernels) | parked world rays | profile rows —
-// the optional parts are taken in this order for as long as the CU's LDS has room (the instrumented kernel's rows included,
-// so that it has the layout of the one it stands in for)
-size_t align16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-size_t seq_offset(const rt_scene *s, int lds) { return align16(lds_image_bytes_for(s, lds) + stack_bytes(s, lds)); }
-size_t aux_offset(const rt_scene *s, int lds) { return align16(seq_offset(s, lds) + (s->ordered ? (size_t)s->n_oseq * sizeof(OSeq) : 0u)); }
-bool aux_in_lds(const rt_scene *s, int lds) {
-    return s->ordered && s->aux_bytes != 0 && aux_offset(s, lds) + s->aux_bytes + prof_bytes(s, lds) <= LDS_BUDGET_BYTES;
-}
-size_t world_offset(const rt_scene *s, int lds) { return align16(aux_offset(s, lds) + (aux_in_lds(s, lds) ? s->aux_bytes : 0u)); }
-size_t world_bytes(const rt_scene *s, int lds) { return (size_t)6 * sizeof(double) * (size_t)block_threads(s, lds); }
-bool world_in_lds(const rt_scene *s, int lds) {
-    return s->has_instances && world_offset(s, lds) + world_bytes(s, lds) + prof_bytes(s, lds) <= LDS_BUDGET_BYTES;
-}
-size_t prof_offset(const rt_scene *s, int lds) { return world_offset(s, lds) + (world_in_lds(s, lds) ? world_bytes(s, lds) : 0u); }
-size_t dynamic_lds_bytes(const rt_scene *s, int lds, bool counted) {
-    return prof_offset(s, lds) + (counted ? prof_bytes(s, lds) : 0);
-}
-// rt_scene::blocks_per_cu's second index: every instantiation a render may launch has its own occupancy figure (only the dense
-// kernel has an instrumented twin)
-int kernel_variant(bool counted, int jobs) { return jobs == JOBS_VIEWS ? 3 : jobs == JOBS_LIST ? 2 : counted ? 1 : 0; }
-
 template <class T> int upload(DeviceArray<T> &dst, const std::vector<T> &src) {
     dst.bytes = src.size() * sizeof(T);
     // never hand the kernel a null table: allocate at least one element
@@ -107,23 +59,6 @@ template <class T> int upload(DeviceArray<T> &dst, const std::vector<T> &src) {
     if (dst.bytes) HIP_TRY(hipMemcpy(dst.ptr, src.data(), dst.bytes, hipMemcpyHostToDevice));
     else HIP_TRY(hipMemset(dst.ptr, 0, alloc));
     return RT_OK;
-}
-
-bool texture_needs_uv(const std::vector<rt_texture> &texs, int32_t t, int depth = 0) {
-    if (t < 0 || depth > 16) return false;
-    const rt_texture &x = texs[(size_t)t];
-    if (x.kind == RT_TEXTURE_IMAGE) return true;
-    if (x.kind == RT_TEXTURE_CHECKER) return texture_needs_uv(texs, x.even, depth + 1) || texture_needs_uv(texs, x.odd, depth + 1);
-    return false;
-}
-
-// Perlin turbulence anywhere under texture t (seven noise evaluations per lookup: by far the dearest thing a hit can ask for)
-bool texture_has_noise(const std::vector<rt_texture> &texs, int32_t t, int depth = 0) {
-    if (t < 0 || depth > 16) return false;
-    const rt_texture &x = texs[(size_t)t];
-    if (x.kind == RT_TEXTURE_NOISE) return true;
-    if (x.kind == RT_TEXTURE_CHECKER) return texture_has_noise(texs, x.even, depth + 1) || texture_has_noise(texs, x.odd, depth + 1);
-    return false;
 }
 
 } // namespace
@@ -284,6 +219,53 @@ struct MeanOut {
     double *d_m2;     // or null
 };
 
+// The scene-constant part of a launch's parameters at LDS level `lds` under `tn`: the tables, where the regions of the dynamic LDS start
+// (rt_scene_plan.hpp), where a query starts.  The per-call and per-launch words are launch_render's.
+int scene_params(KParams &K, const rt_scene *scene, int lds, const Tuning &tn) {
+    const Layout &L = scene->layout;
+    K.nodes = scene->nodes.ptr; K.spheres = scene->spheres.ptr; K.quads = scene->quads.ptr; K.insts = scene->insts.ptr;
+    K.media = scene->media.ptr; K.mats = scene->mats.ptr; K.texs = scene->texs.ptr; K.perlins = scene->perlins.ptr;
+    K.images = scene->images.ptr; K.texels = scene->texels.ptr; K.srgb_lut = scene->lut.ptr;
+    K.n_nodes = L.n_nodes;
+    K.id_one = (uint32_t)(scene->mats.bytes / sizeof(DMaterial)) - 1u;
+    K.ids_ok = K.id_one < 0xffffu ? 1u : 0u;
+    K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = L.lds.prefix_bytes[lds];
+    K.lds_off_node_b = L.lds.off_node_b;
+    K.lds_off_spheres = L.lds.off_spheres; K.lds_off_quads = L.lds.off_quads;
+    K.lds_off_qfilt = (lds == 3 && tn.quad_filter != 0 && L.lds.off_qfilt != 0) ? L.lds.off_qfilt : 0xffffffffu;
+    K.lds_world_off = world_in_lds(L, lds) ? (uint32_t)world_offset(L, lds) : 0xffffffffu;
+    K.box_extent = L.box_extent;
+    K.seq_lookahead = tn.seq_lookahead ? 1u : 0u;
+    K.medium_first = tn.medium_first ? 1u : 0u;
+    K.inst_shortcut = tn.start_shortcut ? 1u : 0u;
+    K.slow_min = (uint32_t)tn.slow_min; K.slow_age = (uint32_t)tn.slow_age;
+    K.o_start_stage = tn.start_shortcut ? L.start.stage : 0u; K.o_start_prim = L.start.prim; K.o_start_end = L.start.end;
+    K.o_start_rest = L.start.rest; K.o_start_slot = L.start.slot;
+    K.setaside_direct = tn.wide_setaside != 0 ? 1u : 0u;
+    // the inline start test (path_kernel): the shortcut's leaf is one sphere (OrderedKind SPHERES = Stage ST_SPHERE = 1)
+    K.start_inline = (tn.start_inline != 0 && K.o_start_stage == (uint32_t)OK_SPHERES && K.o_start_end == K.o_start_prim + 1u) ? 1u : 0u;
+    if (L.wide) { // the start shortcut's entry as the kernel pushes it (rt_kernel.hip W_SHIFT: 2-byte entries in the LDS kernels)
+        // An entry is a record's index and, above it, the mask of its children NOT to be looked at: an inner record set aside as itself is
+        // its bare index.  No entry at all is all ones, which no entry is (one with all four children gone is never made).
+        const uint32_t w_shift = lds != 0 ? 12u : 26u;
+        if (K.setaside_direct && L.start.direct != 0xffffffffu) K.o_start_rest = L.start.direct;
+        else if (L.start.rest != 0u) K.o_start_rest = L.o_root | ((~L.start.rest & 0xfu) << w_shift);
+        else K.o_start_rest = 0xffffffffu;
+        // (no real entry may read as S_EXIT, all ones in the entry's width)
+        if (K.o_start_rest != 0xffffffffu && (K.o_start_rest & (lds != 0 ? 0xffffu : 0xffffffffu)) == (lds != 0 ? 0xffffu : 0xffffffffu))
+            return fail(RT_ERR_INVALID_ARGUMENT, "start shortcut: entry reads as S_EXIT");
+    }
+    K.oimage = scene->oimage.ptr; K.o_root = L.o_root; K.oseq = scene->oseq.ptr; K.n_oseq = L.n_oseq; K.lds_stack_off = L.lds.prefix_bytes[lds];
+    K.lds_seq_off = (uint32_t)seq_offset(L, lds);
+    K.aux_image = scene->aux_image.ptr; K.aux_bytes = L.aux.bytes; K.lds_aux_off = (uint32_t)aux_offset(L, lds);
+    K.aux_off_mats = L.aux.off[0]; K.aux_off_texs = L.aux.off[1]; K.aux_off_insts = L.aux.off[2];
+    K.aux_off_media = L.aux.off[3]; K.aux_off_perlins = L.aux.off[4];
+    K.lds_prof_off = (uint32_t)prof_offset(L, lds);
+    // (a lane keeps the instances it has yet to walk as one 32-bit mask of their indices)
+    K.defer_instances = (L.ordered && tn.defer != 0 && scene->insts.bytes / sizeof(Instance) <= 32u) ? 1u : 0u;
+    return RT_OK;
+}
+
 int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, double *d_out, hipStream_t stream,
                   rt_counters *out_counters, const PixelList *list = nullptr, const ViewTable *views = nullptr, const MeanOut *mean = nullptr) {
     int rc = normalise_params(camera, p);
@@ -319,11 +301,12 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     bool pipelined = !counted && tn.overlap != 0 && chunk < n_samples_total && chunk_for(tn.sample_buffer_bytes / 2) >= 1;
     if (pipelined) chunk = chunk_for(tn.sample_buffer_bytes / 2);
 
-    const int lds = tn.use_lds != 0 ? scene->lds_level : 0;
-    const int threads = block_threads(scene, lds);
+    const Layout &L = scene->layout;
+    const int lds = tn.use_lds != 0 ? L.lds.level : 0;
+    const int threads = block_threads(L, lds);
     const int jobs = views ? JOBS_VIEWS : list ? JOBS_LIST : JOBS_DENSE;
     const int bpc = scene->blocks_per_cu[lds][kernel_variant(counted, jobs)];
-    const size_t dyn_lds = dynamic_lds_bytes(scene, lds, counted);
+    const size_t dyn_lds = dynamic_lds_bytes(L, lds, counted);
     // persistent grid: every resident wave pulls jobs until none are left
     int64_t grid = (int64_t)scene->n_cus * bpc;
     const int64_t waves_per_block = threads / 64;
@@ -377,7 +360,7 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     }
     if (!evicted.empty()) (void)hipGetLastError();
     evicted.clear();
-    const bool colours = scene->parks_colours;
+    const bool colours = L.parks_colours;
     std::unique_lock<std::mutex> slot_lock(slot->mu); // held to the end of the enqueues
     {
         Workspace &w = slot->w;
@@ -481,17 +464,12 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     }
 
     KParams K{};
-    K.nodes = scene->nodes.ptr; K.spheres = scene->spheres.ptr; K.quads = scene->quads.ptr; K.insts = scene->insts.ptr;
-    K.media = scene->media.ptr; K.mats = scene->mats.ptr; K.texs = scene->texs.ptr; K.perlins = scene->perlins.ptr;
-    K.images = scene->images.ptr; K.texels = scene->texels.ptr; K.srgb_lut = scene->lut.ptr;
+    if ((rc = scene_params(K, scene, lds, tn)) != RT_OK) return rc;
     K.out = d_out;
     K.counters = counted ? ws.counters : nullptr;
     K.cam = *camera;
     K.seed_mixed = host_mix64(p.seed + 0x9E3779B97F4A7C15ull);
-    K.n_nodes = scene->n_nodes;
     K.n_threads = n_threads;
-    K.id_one = (uint32_t)(scene->mats.bytes / sizeof(DMaterial)) - 1u;
-    K.ids_ok = K.id_one < 0xffffu ? 1u : 0u;
     K.max_depth = p.max_depth;
     K.shard_index = p.shard_index; K.shard_count = p.shard_count; K.out_layout = p.out_layout;
     K.tiles_x = (camera->image_width + RT_TILE_W - 1) / RT_TILE_W;
@@ -506,47 +484,13 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         K.views = ws.views; K.tiles_per_view = (uint32_t)tiles_per_view; K.inv_tiles_per_view = 1.0 / (double)tiles_per_view;
         K.out_sq = views->d_sum_sq; // (read by Reduce::ViewsMoments only)
     }
-    K.lds_image = scene->lds_image.ptr; K.lds_image_bytes = lds_image_bytes_for(scene, lds);
-    K.lds_off_node_b = scene->lds_off_node_b;
-    K.lds_off_spheres = scene->lds_off_spheres; K.lds_off_quads = scene->lds_off_quads;
-    K.lds_off_qfilt = (lds == 3 && tn.quad_filter != 0 && scene->lds_off_qfilt != 0) ? scene->lds_off_qfilt : 0xffffffffu;
-    K.lds_world_off = world_in_lds(scene, lds) ? (uint32_t)world_offset(scene, lds) : 0xffffffffu;
-    K.box_extent = scene->box_extent;
-    K.seq_lookahead = tn.seq_lookahead ? 1u : 0u;
-    K.medium_first = tn.medium_first ? 1u : 0u;
-    K.inst_shortcut = tn.start_shortcut ? 1u : 0u;
-    K.slow_min = (uint32_t)tn.slow_min; K.slow_age = (uint32_t)tn.slow_age;
-    K.o_start_stage = tn.start_shortcut ? scene->o_start_stage : 0u; K.o_start_prim = scene->o_start_prim; K.o_start_end = scene->o_start_end;
-    K.o_start_rest = scene->o_start_rest; K.o_start_slot = scene->o_start_slot;
-    K.setaside_direct = tn.wide_setaside != 0 ? 1u : 0u;
-    // the inline start test (path_kernel): the shortcut's leaf is one sphere (OrderedKind SPHERES = Stage ST_SPHERE = 1)
-    K.start_inline = (tn.start_inline != 0 && K.o_start_stage == (uint32_t)OK_SPHERES && K.o_start_end == K.o_start_prim + 1u) ? 1u : 0u;
-    if (scene->wide) { // the start shortcut's entry as the kernel pushes it (rt_kernel.hip W_SHIFT: 2-byte entries in the LDS kernels)
-        // An entry is a record's index and, above it, the mask of its children NOT to be looked at: an inner record set aside as itself is
-        // its bare index.  No entry at all is all ones, which no entry is (one with all four children gone is never made).
-        const uint32_t w_shift = lds != 0 ? 12u : 26u;
-        if (K.setaside_direct && scene->o_start_direct != 0xffffffffu) K.o_start_rest = scene->o_start_direct;
-        else if (scene->o_start_rest != 0u) K.o_start_rest = scene->o_root | ((~scene->o_start_rest & 0xfu) << w_shift);
-        else K.o_start_rest = 0xffffffffu;
-        // (no real entry may read as S_EXIT, all ones in the entry's width)
-        if (K.o_start_rest != 0xffffffffu && (K.o_start_rest & (lds != 0 ? 0xffffu : 0xffffffffu)) == (lds != 0 ? 0xffffu : 0xffffffffu))
-            return fail(RT_ERR_INVALID_ARGUMENT, "start shortcut: entry reads as S_EXIT");
-    }
-    K.oimage = scene->oimage.ptr; K.o_root = scene->o_root; K.oseq = scene->oseq.ptr; K.n_oseq = scene->n_oseq; K.lds_stack_off = lds_image_bytes_for(scene, lds);
-    K.lds_seq_off = (uint32_t)seq_offset(scene, lds);
-    K.aux_image = scene->aux_image.ptr; K.aux_bytes = scene->aux_bytes; K.lds_aux_off = (uint32_t)aux_offset(scene, lds);
-    K.aux_off_mats = scene->aux_off[0]; K.aux_off_texs = scene->aux_off[1]; K.aux_off_insts = scene->aux_off[2];
-    K.aux_off_media = scene->aux_off[3]; K.aux_off_perlins = scene->aux_off[4];
-    K.lds_prof_off = (uint32_t)prof_offset(scene, lds);
     {
-        const uint32_t kf = kernel_features_for(scene->features, lds, scene->ordered);
-        const Thresholds th = tn.pick(kf == FEAT_SPHERES_SOLID ? (scene->ordered ? tn.spheres_solid : tn.spheres_threaded) : (kf == FEAT_QUADS_FRAMES ? (scene->insts.bytes ? tn.quads_frames : tn.quads_only) : (scene->ordered ? (lds == 0 ? tn.ordered_global : tn.ordered_general) : tn.general)));
+        const uint32_t kf = kernel_features_for(L.features, lds, L.ordered);
+        const Thresholds th = tn.pick(kf == FEAT_SPHERES_SOLID ? (L.ordered ? tn.spheres_solid : tn.spheres_threaded) : (kf == FEAT_QUADS_FRAMES ? (scene->insts.bytes ? tn.quads_frames : tn.quads_only) : (L.ordered ? (lds == 0 ? tn.ordered_global : tn.ordered_general) : tn.general)));
         K.th_prim = th.prim; K.th_other = th.other; K.th_shade = th.shade; K.th_box = th.box; K.th_new = th.newjob;
         auto byte = [](uint32_t v) { return v > 255u ? 255u : v; };
         K.th_pack = byte(th.prim) | (byte(th.other) << 8) | (byte(th.shade) << 16) | (byte(th.box) << 24);
     }
-    // (a lane keeps the instances it has yet to walk as one 32-bit mask of their indices)
-    K.defer_instances = (scene->ordered && tn.defer != 0 && scene->insts.bytes / sizeof(Instance) <= 32u) ? 1u : 0u;
 
     // Launch k renders samples [sb, sb + ns) into its scratch set's sample buffer; the route's reduction kernel then folds them into
     // `out` in sample order.  Pipelined: launch k runs on internal stream k % 2; its reduction waits for launch k - 1's (the folds
@@ -587,8 +531,8 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
         HIP_TRY(hipMemsetAsync(x.job_counter, 0, sizeof(uint32_t), s));
         {
             void *args[] = {(void *)&K};
-            const uint32_t kf = kernel_features_for(scene->features, lds, scene->ordered);
-            const void *fn = path_kernel_for(lds, counted, kf, scene->ordered, aux_in_lds(scene, lds), scene->wide, jobs);
+            const uint32_t kf = kernel_features_for(L.features, lds, L.ordered);
+            const void *fn = path_kernel_for(lds, counted, kf, L.ordered, aux_in_lds(L, lds), L.wide, jobs);
             HIP_TRY(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(threads), args, dyn_lds, s));
         }
         HIP_TRY(hipGetLastError());
@@ -602,10 +546,10 @@ int launch_render(rt_scene *scene, const rt_camera *camera, rt_render_params p, 
     HIP_TRY(hipEventRecord(ws.ev_done, stream));
     release.completed = true;
     g_last_launch[0] = (uint32_t)k; g_last_launch[1] = (uint32_t)lds; g_last_launch[2] = (uint32_t)threads; g_last_launch[3] = (uint32_t)grid;
-    g_last_kernel[0] = kernel_features_for(scene->features, lds, scene->ordered); g_last_kernel[1] = (uint32_t)lds;
-    g_last_kernel[2] = scene->ordered ? 1u : 0u; g_last_kernel[3] = scene->wide ? 1u : 0u; g_last_kernel[4] = aux_in_lds(scene, lds) ? 1u : 0u;
+    g_last_kernel[0] = kernel_features_for(L.features, lds, L.ordered); g_last_kernel[1] = (uint32_t)lds;
+    g_last_kernel[2] = L.ordered ? 1u : 0u; g_last_kernel[3] = L.wide ? 1u : 0u; g_last_kernel[4] = aux_in_lds(L, lds) ? 1u : 0u;
     g_last_kernel[5] = (uint32_t)jobs; g_last_kernel[6] = K.ids_ok; g_last_kernel[7] = (uint32_t)threads;
-    g_last_start[0] = scene->ordered ? K.o_start_stage : 0u; g_last_start[1] = K.o_start_prim; g_last_start[2] = K.o_start_end; g_last_start[3] = scene->ordered ? K.start_inline : 0u;
+    g_last_start[0] = L.ordered ? K.o_start_stage : 0u; g_last_start[1] = K.o_start_prim; g_last_start[2] = K.o_start_end; g_last_start[3] = L.ordered ? K.start_inline : 0u;
 
     if (counted) {
         unsigned long long host[COUNTER_WORDS];
@@ -748,79 +692,6 @@ int resolve_scene_options(const rt_scene_options *options, rt_scene_options &opt
     if (opt.walk < RT_WALK_DEFAULT || opt.walk > RT_WALK_OWN_TREES) return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": unknown walk");
     return RT_OK;
 }
-// Which walk for this scene?  Measured on MI355X at the in-code cameras (tools/scene_speed.py, profiles/r02_scene_speed.txt), own trees
-// vs reference order, Msamples/s: random_balls 4416 / 2128, two_spheres 8739 / 7281, earth 22557 / 22523 (one primitive: a tree and a
-// stack are pure overhead), two_perlin_spheres 4821 / 3288, quads 12860 / 12612, simple_light 5845 / 4894, cornell_box 3224 / 2102,
-// cornell_smoke 1261 / 966 (a tie until its frames' primitives went into flat leaves, rt_ordered.hpp flat_max), final_scene 983 / 643.
-static bool ordered_walk_pays(const CompiledScene &cs) {
-    return cs.spheres.size() + cs.quads.size() > 1;
-}
-
-// The scene as rt_scene_create_ex compiles it under `opt` (already resolved) and the process defaults in force now (RT_* variables,
-// rt_debug_set_*): which walk, which boxes, which records.  Shared with rt_debug_wide_records, so that the hook shows what a scene gets.
-int compile_for_scene(const rt_scene_desc &desc, const rt_scene_options &opt, CompiledScene &cs, const char *who) {
-    const Tuning tn = tuning_snapshot();
-    const int walk = opt.walk != RT_WALK_DEFAULT ? opt.walk : tn.ordered;
-    const bool refit = opt.refit >= 0 ? opt.refit != 0 : tn.refit != 0;
-    OrderedOptions oopt = tn.ordered_options;
-    if (opt.leaf_max > 0) oopt.leaf_max = (uint32_t)opt.leaf_max < OREF_MAX_LEAF ? (uint32_t)opt.leaf_max : OREF_MAX_LEAF;
-    if (opt.flat_max >= 0) oopt.flat_max = (uint32_t)opt.flat_max;
-    const int want_wide = opt.wide >= 0 ? opt.wide : tn.wide; // (-1: where it measured faster, below)
-    try {
-        cs = compile_scene(desc, refit);
-        // Four children per record where the trees are big enough for the halved number of visits to pay for the dearer visit
-        // (MI355X, Msamples/s two / four children: random-spheres 5428 / 5437, final_scene 1049 / 1088; Cornell's 4 records: 2438 / 2345)
-        oopt.wide = want_wide >= 0 ? want_wide != 0 : cs.spheres.size() + cs.quads.size() >= 64;
-        if (walk == RT_WALK_OWN_TREES || (walk == RT_WALK_AUTO && ordered_walk_pays(cs))) build_ordered(cs, oopt);
-    } catch (const CompileError &e) {
-        return fail(e.status, e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + e.what());
-    }
-    return RT_OK;
-}
-
-// The largest |coordinate| of any box an ordered walk tests (box_pair_f32's and box_quad_f32's B): the children's boxes of the binary
-// records — a wide record's slots are copies of those (rt_ordered.hpp widen) — and the boxes of the world's sequence.
-float ordered_box_extent(const CompiledScene &cs) {
-    float extent = 0.0f;
-    for (const ONode &nd : cs.onodes)
-        for (int k = 0; k < 6; ++k) {
-            if ((nd.c[0] >> OREF_KIND_SHIFT) != OK_EMPTY) extent = std::fmax(extent, std::fabs(nd.b0[k]));
-            if ((nd.c[1] >> OREF_KIND_SHIFT) != OK_EMPTY) extent = std::fmax(extent, std::fabs(nd.b1[k]));
-        }
-    for (const OSeq &st : cs.oseq)
-        for (int k = 0; k < 6; ++k) extent = std::fmax(extent, std::fabs(st.box[k]));
-    return extent;
-}
-
-WideImage pack_wide_records(const std::vector<ONode4> &recs) {
-    const size_t n = recs.size(), off_b = n * 32;
-    WideImage img;
-    img.table_bytes = off_b;
-    img.tables.resize(n * 13); // 6 x 32 + 16 bytes per record
-    img.lines.resize(n * 16);
-    unsigned char *base = reinterpret_cast<unsigned char *>(img.tables.data());
-    for (size_t i = 0; i < n; ++i) {
-        const ONode4 &nd = recs[i];
-        for (int ax = 0; ax < 3; ++ax) {
-            float plus[8], minus[8];
-            for (int k = 0; k < 4; ++k) {
-                plus[k] = nd.b[k][2 * ax]; plus[4 + k] = nd.b[k][2 * ax + 1];   // enter through lo, leave through hi
-                minus[k] = nd.b[k][2 * ax + 1]; minus[4 + k] = nd.b[k][2 * ax];
-            }
-            memcpy(base + (size_t)(2 * ax) * off_b + i * 32, plus, 32);
-            memcpy(base + (size_t)(2 * ax + 1) * off_b + i * 32, minus, 32);
-        }
-        memcpy(base + 6 * off_b + i * 16, nd.c, 16);
-    }
-    unsigned char *dst = reinterpret_cast<unsigned char *>(img.lines.data());
-    for (size_t i = 0; i < n; ++i) {
-        for (size_t q = 0; q < 6; ++q) memcpy(dst + i * 256 + q * 32, base + q * off_b + i * 32, 32);
-        memcpy(dst + i * 256 + 192, base + 6 * off_b + i * 16, 16);
-    }
-    return img;
-}
 } // namespace rtapi
 
 extern "C" {
@@ -875,276 +746,62 @@ int rt_scene_create_ex(const rt_scene_desc *desc, int device, const rt_scene_opt
     *out_scene = nullptr;
     rt_scene_options opt;
     if (int orc = resolve_scene_options(options, opt, "rt_scene_create_ex")) return orc;
-    CompiledScene cs;
-    if (int crc = compile_for_scene(*desc, opt, cs, "rt_scene_create")) return crc;
+    ScenePlan plan; // (a description that does not compile is refused before the device is looked at)
+    if (int prc = plan_scene(*desc, opt, tuning_snapshot(), plan, "rt_scene_create")) return prc;
     const int ndev = rt_device_count();
     if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "rt_scene_create: no HIP device is visible (this library has no CPU path)");
     if (device < 0 || device >= ndev) return fail(RT_ERR_NO_DEVICE, "rt_scene_create: device ordinal out of range");
     HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail(RT_ERR_HIP, "hipGetDeviceProperties failed");
 
-    rt_scene *s = new rt_scene();
+    std::unique_ptr<rt_scene, void (*)(rt_scene *)> scene(new (std::nothrow) rt_scene(), free_scene);
+    if (!scene) return fail(RT_ERR_OUT_OF_MEMORY, "rt_scene_create: out of memory");
+    rt_scene *s = scene.get();
     s->device = device;
     s->options = opt;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete s; return fail(RT_ERR_HIP, "hipGetDeviceProperties failed"); }
     s->n_cus = prop.multiProcessorCount;
-    s->has_instances = !cs.instances.empty();
-    s->features = (cs.spheres.empty() ? 0u : F_SPHERES) | (cs.quads.empty() ? 0u : F_QUADS) | (cs.instances.empty() ? 0u : F_FRAMES) |
-                  (cs.media.empty() ? 0u : F_MEDIA);
-    for (const auto &t : cs.textures)
-        if (t.kind != RT_TEXTURE_SOLID) s->features |= F_TEXTURES;
-    // attenuations are parked as material indices unless the colour is a texture's value, or the indices do not fit 16 bits: such a
-    // scene is rendered by the kernels that can park colours, i.e. those with textures
-    if (cs.materials.size() >= 0xffffu) s->features |= F_TEXTURES;
-    s->parks_colours = (s->features & F_TEXTURES) != 0;
-    s->ordered = cs.ordered;
-    // a walk starts in the first step's tree; a sequence that starts with a medium goes through ST_OTHER first
-    s->o_root = cs.ordered && cs.oseq[0].kind == OSEQ_TREE ? cs.oseq[0].a : 0xfffffffeu;
-    s->n_oseq = (uint32_t)cs.oseq.size();
-    // Start shortcut.  random-spheres' ground sphere (r = 1000) spans the scene, so the sweep puts it directly under the root and every
-    // ray's origin lies inside its box — the walk visits the root, finds that leaf "nearest", tests the sphere, comes back for the other
-    // child; a frame of a few primitives keeps them in one leaf under its root (rt_ordered.hpp flat_max: Cornell's walls).  When the root
-    // has such a child (a leaf whose box has at least half the area of the root's), a query starts in the leaf's primitive stage with the
-    // other child already set aside: the same tests, minus the visit of the root record, and the lanes that start together stay together.
-    s->wide = cs.ordered && cs.wide;
-    if (cs.ordered && cs.media.empty() && cs.oseq.size() == 1 && cs.oseq[0].kind == OSEQ_TREE) {
-        auto half_area = [](const float *b) { const double x = (double)b[1] - b[0], y = (double)b[3] - b[2], z = (double)b[5] - b[4]; return x * y + y * z + z * x; };
-        // the root's children: (box, reference) in slot order — two of a binary record, up to four of a wide one
-        std::vector<std::pair<const float *, uint32_t>> kids;
-        if (s->wide) {
-            const ONode4 &root = cs.onodes4[s->o_root];
-            for (int k = 0; k < 4; ++k) kids.emplace_back(root.b[k], root.c[k]);
-        } else {
-            const ONode &root = cs.onodes[s->o_root];
-            kids.emplace_back(root.b0, root.c[0]);
-            kids.emplace_back(root.b1, root.c[1]);
-        }
-        float all[6] = {INFINITY, -INFINITY, INFINITY, -INFINITY, INFINITY, -INFINITY};
-        for (const auto &kid : kids)
-            if ((kid.second >> OREF_KIND_SHIFT) != OK_EMPTY)
-                for (int k = 0; k < 6; k += 2) { all[k] = std::fmin(all[k], kid.first[k]); all[k + 1] = std::fmax(all[k + 1], kid.first[k + 1]); }
-        for (uint32_t slot = 0; slot < kids.size(); ++slot) {
-            const uint32_t ref = kids[slot].second, kind = ref >> OREF_KIND_SHIFT;
-            if ((kind == OK_SPHERES || kind == OK_QUADS) && half_area(kids[slot].first) >= 0.5 * half_area(all)) {
-                s->o_start_stage = kind; // (OrderedKind SPHERES / QUADS = Stage ST_SPHERE / ST_QUAD)
-                s->o_start_prim = ref & OREF_INDEX_MASK;
-                s->o_start_end = s->o_start_prim + ((ref >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) + 1u;
-                s->o_start_slot = slot;
-                if (s->wide) { // what is set aside: the root record with the mask of its other children, or the one other child itself
-                    uint32_t mask = 0;
-                    for (uint32_t k = 0; k < 4; ++k)
-                        if (k != slot && (kids[k].second >> OREF_KIND_SHIFT) != OK_EMPTY) mask |= 1u << k;
-                    s->o_start_rest = mask;
-                    if (mask != 0u && (mask & (mask - 1u)) == 0u) {
-                        const uint32_t other = kids[__builtin_ctz(mask)].second;
-                        if ((other >> OREF_KIND_SHIFT) == OK_INNER) s->o_start_direct = other & OREF_INDEX_MASK;
-                    }
-                } else {
-                    s->o_start_rest = kids[slot ^ 1u].second;
-                }
-                break;
-            }
-        }
-    }
-    // The same for a Translate / RotateY frame whose tree is a single leaf (a box's six faces in a flat leaf): a walk that enters the frame
-    // starts with the leaf's primitives; the visit of a root record with one child is skipped (Cornell: 2.6 of 9.2 record visits per sample).
-    if (cs.ordered)
-        for (Instance &in : cs.instances) {
-            uint32_t only = 0, n = 0;
-            const float *box = nullptr;
-            auto look = [&](uint32_t ref, const float *b) { if ((ref >> OREF_KIND_SHIFT) != OK_EMPTY) { ++n; only = ref; box = b; } };
-            if (s->wide) for (int k = 0; k < 4; ++k) look(cs.onodes4[in.root].c[k], cs.onodes4[in.root].b[k]);
-            else { look(cs.onodes[in.root].c[0], cs.onodes[in.root].b0); look(cs.onodes[in.root].c[1], cs.onodes[in.root].b1); }
-            const uint32_t kind = only >> OREF_KIND_SHIFT;
-            in.start_ref = (n == 1 && (kind == OK_SPHERES || kind == OK_QUADS)) ? only : 0u;
-            if (in.start_ref) memcpy(in.start_box, box, sizeof in.start_box);
-        }
-    s->box_extent = ordered_box_extent(cs);
-    s->o_stack = cs.ordered_stack;
-    // Node tables (load_node / load_opair): threaded records as two 16-byte halves, ordered records as six 16-byte plane
-    // tables and an 8-byte reference table.  LDS image = node tables | spheres | quads; every LDS level copies a prefix.
-    {
-        const bool wide = cs.ordered && cs.wide;
-        const size_t n = wide ? cs.onodes4.size() : (cs.ordered ? cs.onodes.size() : cs.nodes32.size());
-        const size_t off_b = wide ? n * 32 : n * 16; // bytes of one plane table (16 bytes per record; wide records: 32)
-        const size_t off_sph = wide ? n * (6 * 32 + 16) : (cs.ordered ? ((n * (6 * 16 + 8) + 15u) & ~(size_t)15u) : n * 32);
-        WideImage wimg;
-        if (wide) wimg = pack_wide_records(cs.onodes4); // (rt_device_scene.h load_oquad)
-        std::vector<uint4> local_tables(wide ? 0 : off_sph / 16);
-        std::vector<uint4> &tables = wide ? wimg.tables : local_tables;
-        if (!wide) {
-            unsigned char *base = reinterpret_cast<unsigned char *>(tables.data());
-            if (cs.ordered) {
-                for (size_t i = 0; i < n; ++i) {
-                    const ONode &nd = cs.onodes[i];
-                    for (int ax = 0; ax < 3; ++ax) {
-                        const float lo0 = nd.b0[2 * ax], hi0 = nd.b0[2 * ax + 1], lo1 = nd.b1[2 * ax], hi1 = nd.b1[2 * ax + 1];
-                        const float plus[4] = {lo0, lo1, hi0, hi1}, minus[4] = {hi0, hi1, lo0, lo1};
-                        memcpy(base + (size_t)(2 * ax) * off_b + i * 16, plus, 16);
-                        memcpy(base + (size_t)(2 * ax + 1) * off_b + i * 16, minus, 16);
-                    }
-                    memcpy(base + 6 * off_b + i * 8, nd.c, 8);
-                }
-            } else {
-                const unsigned char *src = reinterpret_cast<const unsigned char *>(cs.nodes32.data());
-                for (size_t i = 0; i < n; ++i)
-                    for (size_t q = 0; q < 2; ++q) memcpy(base + q * off_b + i * 16, src + (i * 2 + q) * 16, 16);
-            }
-        }
-        if (wide) { // the global copy: 256 bytes per record (load_oquad<0>)
-            int urc = upload(s->oimage, wimg.lines);
-            if (urc != RT_OK) { free_scene(s); return urc; }
-        } else if (cs.ordered) { // the global copy: one 128-byte line per record (load_opair<0>)
-            std::vector<uint4> lines(n * 8);
-            unsigned char *dst = reinterpret_cast<unsigned char *>(lines.data());
-            const unsigned char *tab = reinterpret_cast<const unsigned char *>(tables.data());
-            for (size_t i = 0; i < n; ++i) {
-                for (size_t q = 0; q < 6; ++q) memcpy(dst + i * 128 + q * 16, tab + q * off_b + i * 16, 16);
-                memcpy(dst + i * 128 + 96, tab + 6 * off_b + i * 8, 8);
-            }
-            int urc = upload(s->oimage, lines);
-            if (urc != RT_OK) { free_scene(s); return urc; }
-        }
-        s->lds_off_node_b = (uint32_t)off_b;
-        const size_t off_quads = off_sph + cs.spheres.size() * sizeof(Sphere);
-        // behind the quads: their f32 filter records (rt_qfilt.hpp) — if some leaf of the library's own trees holds more than one quad
-        // (a single quad's exact test runs in its round anyway) and the LDS has room for them
-        bool flat_quads = false;
-        if (cs.ordered) {
-            auto multi = [](uint32_t ref) { return (ref >> OREF_KIND_SHIFT) == OK_QUADS && ((ref >> OREF_COUNT_SHIFT) & OREF_COUNT_MASK) != 0u; };
-            for (const ONode &nd : cs.onodes) flat_quads = flat_quads || multi(nd.c[0]) || multi(nd.c[1]);
-            for (const ONode4 &nd : cs.onodes4) for (int k = 0; k < 4; ++k) flat_quads = flat_quads || multi(nd.c[k]);
-        }
-        const size_t off_qfilt = (off_quads + cs.quads.size() * sizeof(Quad) + 15u) & ~(size_t)15u;
-        const size_t total_plain = off_qfilt, total_filt = off_qfilt + cs.quads.size() * sizeof(QFiltPair);
-        const size_t stack3 = stack_bytes(s, 3), stack1 = stack_bytes(s, 1); // (the two levels' kernels differ in workgroup size)
-        // level 2 (nodes + spheres) exists but is not selected: on final_scene it measured 10 % slower than level 1
-        // (behind the stacks: the world's sequence, and the instrumented kernels' profile rows)
-        const size_t budget = LDS_BUDGET_BYTES - 4096 - cs.oseq.size() * sizeof(OSeq);
-        const bool with_filter = flat_quads && total_filt + stack3 <= budget;
-        const size_t total = with_filter ? total_filt : total_plain;
-        s->lds_level = total + stack3 <= budget ? 3 : (off_sph + stack1 <= budget ? 1 : 0);
-        if (cs.ordered && n >= (wide ? (size_t)WIDE_MAX_LDS_RECORDS : (size_t)0x3fffu)) s->lds_level = 0; // 2-byte stack entries: a record index in 14 bits + two skip bits (wide: 12 + 4 mask bits)
-        if (s->lds_level) {
-            const size_t used = s->lds_level == 3 ? total : (s->lds_level == 2 ? ((off_quads + 15u) & ~(size_t)15u) : off_sph);
-            std::vector<uint4> img(used / 16);
-            unsigned char *base = reinterpret_cast<unsigned char *>(img.data());
-            memcpy(base, tables.data(), off_sph);
-            if (s->lds_level >= 2 && !cs.spheres.empty()) memcpy(base + off_sph, cs.spheres.data(), cs.spheres.size() * sizeof(Sphere));
-            if (s->lds_level == 3 && !cs.quads.empty()) memcpy(base + off_quads, cs.quads.data(), cs.quads.size() * sizeof(Quad));
-            if (s->lds_level == 3 && with_filter) {
-                const std::vector<QFiltPair> qf = qfilt_table(cs.quads);
-                memcpy(base + off_qfilt, qf.data(), qf.size() * sizeof(QFiltPair));
-                s->lds_off_qfilt = (uint32_t)off_qfilt;
-            }
-            int urc = upload(s->lds_image, img);
-            if (urc != RT_OK) { free_scene(s); return urc; }
-            s->lds_off_spheres = (uint32_t)off_sph; s->lds_off_quads = (uint32_t)off_quads;
-            s->lds_image_bytes = (uint32_t)used;
-            s->lds_prefix_bytes[1] = (uint32_t)off_sph;
-            s->lds_prefix_bytes[2] = (uint32_t)((off_quads + 15u) & ~(size_t)15u);
-            s->lds_prefix_bytes[3] = (uint32_t)total;
-            for (int l = s->lds_level + 1; l < 4; ++l) s->lds_prefix_bytes[l] = 0;
-        }
-    }
-    // (one entry more than the scene has materials: Color::ONE, what the path end multiplies by for a level a path does not have;
-    // two more where the one's index would be 0xffff, the mark of a parked colour)
-    const size_t n_mats = cs.materials.size();
-    std::vector<DMaterial> mats(n_mats + (n_mats == 0xffffu ? 2u : 1u));
-    for (size_t i = n_mats; i < mats.size(); ++i) {
-        mats[i].albedo[0] = mats[i].albedo[1] = mats[i].albedo[2] = 1.0;
-        mats[i].solid = 1u;
-    }
-    for (size_t i = 0; i < n_mats; ++i) {
-        const rt_material &m = cs.materials[i];
-        DMaterial d{};
-        d.kind = (uint32_t)m.kind;
-        d.texture = m.texture >= 0 ? (uint32_t)m.texture : 0u;
-        d.needs_uv = texture_needs_uv(cs.textures, m.texture) ? 1u : 0u;
-        d.slow = (m.kind != RT_MATERIAL_METAL && m.kind != RT_MATERIAL_DIELECTRIC && texture_has_noise(cs.textures, m.texture)) ? 1u : 0u;
-        d.albedo[0] = m.albedo.x; d.albedo[1] = m.albedo.y; d.albedo[2] = m.albedo.z;
-        if (m.kind != RT_MATERIAL_METAL && m.kind != RT_MATERIAL_DIELECTRIC && m.texture >= 0 &&
-            cs.textures[(size_t)m.texture].kind == RT_TEXTURE_SOLID) {
-            const rt_vec3 &c = cs.textures[(size_t)m.texture].color;
-            d.solid = 1u;
-            d.albedo[0] = c.x; d.albedo[1] = c.y; d.albedo[2] = c.z;
-        }
-        d.fuzz = m.fuzz;
-        d.ir = m.ir;
-        if (m.kind == RT_MATERIAL_DIELECTRIC) {
-            // a Dielectric attenuates by Color::ONE and reads no albedo: the three doubles carry what its scatter() divides out on every
-            // hit (src/material.rs:86, :75-77) — the same IEEE operations, done once here: 1 / ir, and Schlick's r0 for either face
-            const double inv_ir = 1.0 / m.ir;
-            double r0_front = (1.0 - inv_ir) / (1.0 + inv_ir), r0_back = (1.0 - m.ir) / (1.0 + m.ir);
-            r0_front = r0_front * r0_front; r0_back = r0_back * r0_back;
-            d.albedo[0] = inv_ir; d.albedo[1] = r0_front; d.albedo[2] = r0_back;
-        }
-        mats[i] = d;
-    }
-
-    // AUX image (path_kernel's AUX): the small tables an ordered scene's kernel reads per hit — materials, frames, media, and
-    // (only when some texture is not a SolidColor: otherwise the colours sit in the material records) textures and Perlin
-    // tables; copied into the LDS wherever it fits (aux_in_lds)
-    {
-        const bool with_textures = (s->features & F_TEXTURES) != 0;
-        const size_t o_mats = 0, o_texs = align16(o_mats + mats.size() * sizeof(DMaterial)),
-                     o_insts = align16(o_texs + (with_textures ? cs.textures.size() * sizeof(rt_texture) : 0u)),
-                     o_media = align16(o_insts + cs.instances.size() * sizeof(Instance)),
-                     o_perlins = align16(o_media + cs.media.size() * sizeof(Medium)),
-                     total = align16(o_perlins + (with_textures ? cs.perlins.size() * sizeof(rt_perlin) : 0u));
-        if (s->ordered && total > 0 && total <= 48 * 1024) {
-            std::vector<uint4> img(total / 16);
-            unsigned char *base = reinterpret_cast<unsigned char *>(img.data());
-            if (!mats.empty()) memcpy(base + o_mats, mats.data(), mats.size() * sizeof(DMaterial));
-            if (with_textures && !cs.textures.empty()) memcpy(base + o_texs, cs.textures.data(), cs.textures.size() * sizeof(rt_texture));
-            if (!cs.instances.empty()) memcpy(base + o_insts, cs.instances.data(), cs.instances.size() * sizeof(Instance));
-            if (!cs.media.empty()) memcpy(base + o_media, cs.media.data(), cs.media.size() * sizeof(Medium));
-            if (with_textures && !cs.perlins.empty()) memcpy(base + o_perlins, cs.perlins.data(), cs.perlins.size() * sizeof(rt_perlin));
-            int urc = upload(s->aux_image, img);
-            if (urc != RT_OK) { free_scene(s); return urc; }
-            s->aux_bytes = (uint32_t)total;
-            s->aux_off[0] = (uint32_t)o_mats; s->aux_off[1] = (uint32_t)o_texs; s->aux_off[2] = (uint32_t)o_insts;
-            s->aux_off[3] = (uint32_t)o_media; s->aux_off[4] = (uint32_t)o_perlins;
-        }
-    }
+    s->layout = plan.layout;
+    s->stats = plan.stats;
+    const Layout &L = s->layout;
+    // every table a kernel reads: (wanted, device array <- host vector); the three images only where the plan made them
+    struct Upload { bool wanted; int (*run)(rt_scene &, const ScenePlan &); };
+    const Upload uploads[] = {
+        {L.ordered, [](rt_scene &d, const ScenePlan &p) { return upload(d.oimage, p.oimage); }},
+        {L.lds.level != 0, [](rt_scene &d, const ScenePlan &p) { return upload(d.lds_image, p.lds_image); }},
+        {L.aux.bytes != 0, [](rt_scene &d, const ScenePlan &p) { return upload(d.aux_image, p.aux_image); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.nodes, p.cs.nodes32); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.oseq, p.cs.oseq); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.spheres, p.cs.spheres); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.quads, p.cs.quads); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.insts, p.cs.instances); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.media, p.cs.media); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.mats, p.mats); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.texs, p.cs.textures); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.perlins, p.cs.perlins); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.images, p.cs.images); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.texels, p.cs.texels); }},
+        {true, [](rt_scene &d, const ScenePlan &p) { return upload(d.lut, p.cs.srgb_lut); }},
+    };
+    for (const Upload &u : uploads)
+        if (u.wanted)
+            if (int urc = u.run(*s, plan)) return urc;
     // every kernel a render of this scene may launch — dense, its instrumented twin, the list and the views twin — gets its LDS
     // attribute set and its own occupancy figure: the twins are code objects of their own, with their own register counts
     for (int lds = 0; lds < 4; ++lds)
         for (int variant = 0; variant < 4; ++variant) {
-            if (lds && lds != s->lds_level) { s->blocks_per_cu[lds][variant] = 0; continue; }
+            if (lds && lds != L.lds.level) { s->blocks_per_cu[lds][variant] = 0; continue; }
             const bool counted = variant == 1;
             const int jobs = variant == 3 ? JOBS_VIEWS : variant == 2 ? JOBS_LIST : JOBS_DENSE;
-            const void *fn = path_kernel_for(lds, counted, kernel_features_for(s->features, lds, s->ordered), s->ordered, aux_in_lds(s, lds), s->wide, jobs);
-            const int threads = block_threads(s, lds);
-            const size_t dyn = dynamic_lds_bytes(s, lds, counted);
+            const void *fn = path_kernel_for(lds, counted, kernel_features_for(L.features, lds, L.ordered), L.ordered, aux_in_lds(L, lds), L.wide, jobs);
+            const int threads = block_threads(L, lds);
+            const size_t dyn = dynamic_lds_bytes(L, lds, counted);
             if (dyn > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
             int b = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, fn, threads, dyn) != hipSuccess || b < 1) b = 1;
             s->blocks_per_cu[lds][variant] = b;
         }
-
-    int rc = RT_OK;
-    if ((rc = upload(s->nodes, cs.nodes32)) != RT_OK || (rc = upload(s->oseq, cs.oseq)) != RT_OK ||
-        (rc = upload(s->spheres, cs.spheres)) != RT_OK ||
-        (rc = upload(s->quads, cs.quads)) != RT_OK || (rc = upload(s->insts, cs.instances)) != RT_OK ||
-        (rc = upload(s->media, cs.media)) != RT_OK || (rc = upload(s->mats, mats)) != RT_OK ||
-        (rc = upload(s->texs, cs.textures)) != RT_OK || (rc = upload(s->perlins, cs.perlins)) != RT_OK ||
-        (rc = upload(s->images, cs.images)) != RT_OK || (rc = upload(s->texels, cs.texels)) != RT_OK ||
-        (rc = upload(s->lut, cs.srgb_lut)) != RT_OK) {
-        free_scene(s);
-        return rc;
-    }
-    s->n_nodes = (uint32_t)cs.nodes.size();
-    rt_scene_stats &st = s->stats;
-    st.node_bytes = cs.ordered ? s->oimage.bytes : s->nodes.bytes; st.sphere_bytes = s->spheres.bytes; st.quad_bytes = s->quads.bytes;
-    st.instance_bytes = s->insts.bytes; st.medium_bytes = s->media.bytes; st.material_bytes = s->mats.bytes;
-    st.texture_bytes = s->texs.bytes; st.perlin_bytes = s->perlins.bytes; st.image_bytes = s->texels.bytes;
-    st.n_nodes = (uint32_t)(cs.ordered ? (cs.wide ? cs.onodes4.size() : cs.onodes.size()) : cs.nodes.size()); st.n_spheres = (uint32_t)cs.spheres.size(); st.n_quads = (uint32_t)cs.quads.size();
-    st.n_instances = (uint32_t)cs.instances.size(); st.n_media = (uint32_t)cs.media.size();
-    st.max_instance_depth = cs.max_instance_depth;
-    st.lds_nodes = s->lds_level ? st.n_nodes : 0; st.lds_bytes = s->lds_level ? (uint32_t)dynamic_lds_bytes(s, s->lds_level, false) : 0;
-    st.ordered = cs.ordered ? 1u : 0u; st.stack_entries = cs.ordered ? cs.ordered_stack : 0u;
-    *out_scene = s;
+    *out_scene = scene.release();
     return RT_OK;
 }
 

@@ -62,10 +62,7 @@ int rt_debug_ordered_layout_ex(const rt_scene_desc *desc, const rt_scene_options
     CompiledScene cs;
     try {
         cs = compile_scene(*desc, true);
-        OrderedOptions oopt = tuning_snapshot().ordered_options;
-        if (opt.leaf_max > 0) oopt.leaf_max = (uint32_t)opt.leaf_max < OREF_MAX_LEAF ? (uint32_t)opt.leaf_max : OREF_MAX_LEAF;
-        if (opt.flat_max >= 0) oopt.flat_max = (uint32_t)opt.flat_max;
-        build_ordered(cs, oopt);
+        build_ordered(cs, ordered_options_for(opt, tuning_snapshot()));
     } catch (const CompileError &e) {
         return fail(e.status, e.what());
     } catch (const std::exception &e) {
@@ -131,9 +128,7 @@ int rt_debug_wide_layout(const rt_scene_desc *desc, const rt_scene_options *opti
     CompiledScene cs;
     try {
         cs = compile_scene(*desc, true);
-        OrderedOptions oopt = tuning_snapshot().ordered_options;
-        if (opt.leaf_max > 0) oopt.leaf_max = (uint32_t)opt.leaf_max < OREF_MAX_LEAF ? (uint32_t)opt.leaf_max : OREF_MAX_LEAF;
-        if (opt.flat_max >= 0) oopt.flat_max = (uint32_t)opt.flat_max;
+        OrderedOptions oopt = ordered_options_for(opt, tuning_snapshot());
         oopt.wide = true;
         build_ordered(cs, oopt);
     } catch (const CompileError &e) {
@@ -225,7 +220,7 @@ int rt_debug_wide_records(const rt_scene_desc *desc, const rt_scene_options *opt
     rt_scene_options opt;
     if (int orc = resolve_scene_options(options, opt, "rt_debug_wide_records")) return orc;
     CompiledScene cs;
-    if (int crc = compile_for_scene(*desc, opt, cs, "rt_debug_wide_records")) return crc;
+    if (int crc = compile_for_scene(*desc, opt, tuning_snapshot(), cs, "rt_debug_wide_records")) return crc;
     const bool wide = cs.ordered && cs.wide;
     const size_t n = wide ? cs.onodes4.size() : 0;
     io->wide = wide ? 1u : 0u;
@@ -254,11 +249,59 @@ int rt_debug_wide_records(const rt_scene_desc *desc, const rt_scene_options *opt
         }
     }
     if (io->global_image || io->lds_image) {
-        const WideImage img = pack_wide_records(cs.onodes4);
+        const NodeTables img = pack_wide_records(cs.onodes4);
         if (io->global_image) memcpy(io->global_image, img.lines.data(), n * 256);
         if (io->lds_image) memcpy(io->lds_image, img.tables.data(), n * 208);
     }
     return RT_OK;
+}
+
+int rt_debug_scene_plan(const rt_scene_desc *desc, const rt_scene_options *options, rt_debug_plan *io) {
+    if (!desc || !io) return fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_scene_plan: null argument");
+    rt_scene_options opt;
+    if (int orc = resolve_scene_options(options, opt, "rt_debug_scene_plan")) return orc;
+    ScenePlan plan;
+    if (int prc = plan_scene(*desc, opt, tuning_snapshot(), plan, "rt_debug_scene_plan")) return prc;
+    const Layout &l = plan.layout;
+    io->features = l.features; io->parks_colours = l.parks_colours; io->has_instances = l.has_instances; io->ordered = l.ordered; io->wide = l.wide;
+    io->o_root = l.o_root; io->n_oseq = l.n_oseq; io->o_stack = l.o_stack; io->n_nodes = l.n_nodes;
+    io->o_start_stage = l.start.stage; io->o_start_prim = l.start.prim; io->o_start_end = l.start.end; io->o_start_rest = l.start.rest;
+    io->o_start_slot = l.start.slot; io->o_start_direct = l.start.direct;
+    io->box_extent = l.box_extent;
+    io->lds_level = (uint32_t)l.lds.level; io->lds_off_node_b = l.lds.off_node_b; io->lds_off_spheres = l.lds.off_spheres;
+    io->lds_off_quads = l.lds.off_quads; io->lds_off_qfilt = l.lds.off_qfilt;
+    for (int k = 0; k < 4; ++k) io->lds_prefix_bytes[k] = l.lds.prefix_bytes[k];
+    io->aux_bytes = l.aux.bytes;
+    for (int k = 0; k < 5; ++k) io->aux_off[k] = l.aux.off[k];
+    io->stats = plan.stats;
+    for (int k = 0; k < 2; ++k) { // the two levels a scene may be launched at (rt_scene_options.use_lds = 0: level 0)
+        const int lds = k ? l.lds.level : 0;
+        rt_debug_plan_level &v = io->level[k];
+        v.lds_level = (uint32_t)lds; v.features = kernel_features_for(l.features, lds, l.ordered); v.threads = (uint32_t)block_threads(l, lds);
+        v.aux_in_lds = aux_in_lds(l, lds) ? 1u : 0u; v.world_in_lds = world_in_lds(l, lds) ? 1u : 0u;
+        v.stack_off = l.lds.prefix_bytes[lds]; v.seq_off = (uint32_t)seq_offset(l, lds); v.aux_off = (uint32_t)aux_offset(l, lds);
+        v.world_off = (uint32_t)world_offset(l, lds); v.prof_off = (uint32_t)prof_offset(l, lds);
+        v.dynamic_lds_bytes = (uint32_t)dynamic_lds_bytes(l, lds, false); v.dynamic_lds_bytes_counted = (uint32_t)dynamic_lds_bytes(l, lds, true);
+    }
+    auto fnv1a = [](const void *data, size_t n) {
+        uint64_t h = 0xcbf29ce484222325ull;
+        for (size_t i = 0; i < n; ++i) { h ^= static_cast<const unsigned char *>(data)[i]; h *= 0x100000001b3ull; }
+        return h;
+    };
+    int rc = RT_OK;
+    auto give = [&](rt_debug_plan_bytes &out, const auto &v, uint8_t *buf = nullptr, int64_t cap = 0) {
+        out.bytes = v.size() * sizeof(v[0]);
+        out.digest = fnv1a(v.data(), out.bytes);
+        if (buf && cap < (int64_t)out.bytes) rc = fail(RT_ERR_INVALID_ARGUMENT, "rt_debug_scene_plan: image buffer too small");
+        else if (buf && out.bytes) memcpy(buf, v.data(), out.bytes);
+    };
+    const CompiledScene &cs = plan.cs;
+    give(io->images[0], plan.oimage, io->oimage, io->cap_oimage); give(io->images[1], plan.lds_image, io->lds_image, io->cap_lds_image);
+    give(io->images[2], plan.aux_image, io->aux_image, io->cap_aux_image); give(io->images[3], plan.mats, io->mats, io->cap_mats);
+    give(io->tables[0], cs.nodes32); give(io->tables[1], cs.oseq); give(io->tables[2], cs.spheres); give(io->tables[3], cs.quads);
+    give(io->tables[4], cs.instances, io->insts, io->cap_insts); give(io->tables[5], cs.media); give(io->tables[6], cs.textures);
+    give(io->tables[7], cs.perlins); give(io->tables[8], cs.images); give(io->tables[9], cs.texels); give(io->tables[10], cs.srgb_lut);
+    return rc;
 }
 
 int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device) {
@@ -293,7 +336,7 @@ int rt_debug_wide_visits(const rt_debug_wide_cases *io, int device) {
         boxes64.assign((size_t)m * 24, 0.0);
         extents.assign((size_t)m, 0.0f);
         const unsigned char *image = nullptr;
-        WideImage img;
+        NodeTables img;
         if (!packed) {
             for (int64_t i = 0; i < m; ++i) {
                 const double *src = io->boxes + (first + i) * 24;

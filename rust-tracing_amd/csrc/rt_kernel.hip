@@ -1844,20 +1844,6 @@ __global__ void debug_eval_kernel(int32_t op, int64_t n, const double *__restric
 // =====================================================================================================
 namespace rtk {
 
-uint32_t kernel_features_for(uint32_t scene_features, int lds, bool ordered) {
-    (void)ordered;
-    if (lds == 3) { // the specialised instantiations exist for scenes that live in the LDS whole
-        for (uint32_t f : {FEAT_SPHERES_SOLID, FEAT_QUADS_FRAMES, FEAT_QUADS_FRAMES_MEDIA, FEAT_SPHERES_QUADS_TEXTURES})
-            if ((scene_features & ~f) == 0) return f;
-    }
-    return F_ALL;
-}
-int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered) {
-    if (lds == 0) return GLOBAL_THREADS;
-    if (kernel_features == FEAT_QUADS_FRAMES) return QUADS_FRAMES_THREADS;
-    if (kernel_features == FEAT_SPHERES_QUADS_TEXTURES && !ordered) return REFERENCE_TEXTURES_THREADS;
-    return kernel_features == FEAT_SPHERES_SOLID ? LDS_THREADS : LDS_THREADS_GENERAL;
-}
 const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, int jobs) {
 // (list mode: rt_render_pixels_device; views mode: rt_render_views_device; neither is ever counted)
     const bool list = jobs == JOBS_LIST, views = jobs == JOBS_VIEWS;

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 #include <cstdint>
+#include <initializer_list>
 
 namespace rtk {
 using namespace rtd;
@@ -180,8 +181,20 @@ constexpr uint32_t FEAT_QUADS_FRAMES = F_QUADS | F_FRAMES;  // Cornell box: quad
 // two more, at 768 threads (3 waves per SIMD), which need no spill there: 156 and 150 registers (the every-feature kernel: 168 + 16..38 spilled)
 constexpr uint32_t FEAT_QUADS_FRAMES_MEDIA = F_QUADS | F_FRAMES | F_MEDIA;              // cornell_smoke
 constexpr uint32_t FEAT_SPHERES_QUADS_TEXTURES = F_SPHERES | F_QUADS | F_TEXTURES;    // two_spheres, earth, two_perlin_spheres, simple_light
-uint32_t kernel_features_for(uint32_t scene_features, int lds, bool ordered);
-int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered); // workgroup size of that instantiation
+inline uint32_t kernel_features_for(uint32_t scene_features, int lds, bool ordered) {
+    (void)ordered;
+    if (lds == 3) { // the specialised instantiations exist for scenes that live in the LDS whole
+        for (uint32_t f : {FEAT_SPHERES_SOLID, FEAT_QUADS_FRAMES, FEAT_QUADS_FRAMES_MEDIA, FEAT_SPHERES_QUADS_TEXTURES})
+            if ((scene_features & ~f) == 0) return f;
+    }
+    return F_ALL;
+}
+inline int kernel_threads_for(uint32_t kernel_features, int lds, bool ordered) { // workgroup size of that instantiation
+    if (lds == 0) return GLOBAL_THREADS;
+    if (kernel_features == FEAT_QUADS_FRAMES) return QUADS_FRAMES_THREADS;
+    if (kernel_features == FEAT_SPHERES_QUADS_TEXTURES && !ordered) return REFERENCE_TEXTURES_THREADS;
+    return kernel_features == FEAT_SPHERES_SOLID ? LDS_THREADS : LDS_THREADS_GENERAL;
+}
 const void *path_kernel_for(int lds, bool counted, uint32_t feat, bool ordered, bool aux, bool wide, int jobs = JOBS_DENSE);
 
 // launches of the small kernels (all asynchronous on `stream`; errors through hipGetLastError)

@@ -1,12 +1,14 @@
 // CPU.  Scene-description fuzzer: the nine reference scenes' rt_scene_desc (built by the host library), copied into mutable arrays and
 // damaged — indices, counts, kinds; NaN, inf, 0, 1e300 in the doubles — then through the part of rt_scene_create that needs no GPU:
-// compile_scene, build_ordered (two- and four-child records, random leaf sizes), qfilt_table.  Built with AddressSanitizer + UBSan
+// compile_scene, build_ordered (two- and four-child records, random leaf sizes), qfilt_table, and — for every description that
+// compiles — plan_scene (rt_scene_plan.hpp: the layout and every image scene creation uploads).  Built with AddressSanitizer + UBSan
 // (+ float-cast-overflow) by tools/fuzz_scene_compiler.sh: a damaged description must end in an exception (rt_scene_create turns it
 // into RT_ERR_INVALID_ARGUMENT), never in a fault.  Images are left alone: a pointer and its extent are the caller's word.
 // Round 4: 27 000 damaged descriptions, half refused, half compiled, no finding.
 #include "rt_host.h"
 #include "rt_ordered.hpp"
 #include "rt_qfilt.hpp"
+#include "rt_scene_plan.hpp"
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -34,7 +36,8 @@ int main(int argc, char **argv) {
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1;
     const int per_scene = argc > 2 ? atoi(argv[2]) : 200;
     std::mt19937_64 rng(seed);
-    long ok = 0, refused = 0;
+    long ok = 0, refused = 0, planned = 0, plan_refused = 0;
+    const rtapi::Tuning tn;
     for (int scene = 0; scene <= 8; ++scene) {
         rth_scene_options o{};
         o.scene = scene; o.scene_seed = seed; o.image_width = 64; o.samples_per_pixel = 1; o.max_depth = 4; o.earth_image = "synthetic:64x32";
@@ -77,11 +80,22 @@ int main(int argc, char **argv) {
                     build_ordered(cs, oo);
                     const std::vector<QFiltPair> qf = qfilt_table(cs.quads);
                     ok += (long)(qf.size() >= 0);
+                    // the same description as a scene gets it: no exception may leave plan_scene, and a plan has its images
+                    rt_scene_options so;
+                    memset(&so, 0xff, sizeof so); // (every field -1: unset)
+                    so.struct_size = (uint32_t)sizeof so; so.sample_buffer_bytes = 0;
+                    so.walk = (int32_t)(rng() % 3); so.refit = it & 1; so.leaf_max = (int32_t)oo.leaf_max; so.flat_max = (int32_t)oo.flat_max; so.wide = wide;
+                    rtapi::ScenePlan plan;
+                    if (rtapi::plan_scene(m.d, so, tn, plan, "fuzz") == RT_OK) {
+                        ++planned;
+                        if (plan.mats.empty() || (plan.layout.lds.level != 0) != !plan.lds_image.empty() || plan.layout.ordered != !plan.oimage.empty() ||
+                            plan.layout.aux.bytes != plan.aux_image.size() * 16) { fprintf(stderr, "scene %d it %d wide %d: inconsistent plan\n", scene, it, wide); return 3; }
+                    } else ++plan_refused;
                 } catch (const std::exception &e) { ++refused; if (refused < 12 || it == 0) fprintf(stderr, "scene %d it %d wide %d: %s\n", scene, it, wide, e.what()); }
             }
         }
         rth_scene_destroy(hs);
     }
-    printf("compiled %ld, refused %ld\n", ok, refused);
+    printf("compiled %ld, refused %ld; planned %ld, plan refused %ld\n", ok, refused, planned, plan_refused);
     return 0;
 }
