@@ -1,4 +1,4 @@
-"""Shared by tests/test_gpu_job_modes.py (not a test module): one small scene per class of render kernel (rt_kernel.hip path_kernel's
+"""Shared by tests/test_gpu_job_modes.py, tests/test_gpu_schedule.py and others (not a test module): one small scene per class of render kernel (rt_kernel.hip path_kernel's
 LDS level x feature set x walk x record width x AUX, as rt_kernels.h path_kernel_for picks it), what rt_debug_last_kernel must report
 for it, three views of every scene, and the pixel list of the list-mode stress shape.
 
