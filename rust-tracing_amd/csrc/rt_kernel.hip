@@ -1002,24 +1002,36 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                 const uint32_t park_id = (!HAS_TEXTURES || (P.ids_ok != 0u && (mk == RT_MATERIAL_METAL || m->solid != 0u))) ? mat : ID_COLOUR;
                 bool unit_attenuation = false;
                 V3 new_dir = normal;
-                // Metal and Dielectric both start from the unit direction: one square root and one division for the two branches of a round
-                V3 unit_d = d;
-                if (mk == RT_MATERIAL_METAL || mk == RT_MATERIAL_DIELECTRIC) unit_d = normalize(d);
+                // A wave runs every branch that one of its lanes takes, and a round nearly always holds every material.  Each branch but
+                // the light's normalizes one vector — Lambertian and Isotropic the unit-sphere sample, Metal and Dielectric the ray's
+                // direction —: ONE normalize for the round, ahead of the branches, on the operand selected per lane.  The same function of
+                // the same operand as before, issued once instead of once per branch.  (A light reads neither; its lanes take the
+                // direction.  Spelled the other way round — `Metal or Dielectric ? d : rs` — the flagship kernel takes 105 registers,
+                // spelled like this 102.)  In the spheres-only kernels: Cornell's quads + frames kernel, at the register ceiling, lost
+                // 2.3 % with it, so every other family keeps the two normalizes, Metal's and Dielectric's shared as before.
+                // (Isotropic is a medium's phase function: it never occurs where ONE_NORMALIZE holds — no media there —, so its term of
+                // from_sample and its arm's `unit` are dead in those kernels; they are written out so that the block reads the same
+                // whichever families the merge is compiled into.)
+                constexpr bool ONE_NORMALIZE = !HAS_QUADS && !HAS_OTHER && !HAS_TEXTURES;
+                const bool from_sample = mk == RT_MATERIAL_LAMBERTIAN || mk == RT_MATERIAL_ISOTROPIC;
+                V3 unit = d;
+                if constexpr (ONE_NORMALIZE) unit = normalize(from_sample ? rs : d);
+                else if (mk == RT_MATERIAL_METAL || mk == RT_MATERIAL_DIELECTRIC) unit = normalize(d);
                 if (mk == RT_MATERIAL_DIFFUSE_LIGHT) { // emitted, no scatter (src/material.rs:114-122)
                     result = tex;
                     path_done = true;
                 } else if (mk == RT_MATERIAL_LAMBERTIAN) { // src/material.rs:26-42
-                    const V3 scatter_direction = normal + normalize(rs);
+                    const V3 scatter_direction = normal + (ONE_NORMALIZE ? unit : normalize(rs));
                     new_dir = near_zero(scatter_direction) ? normal : scatter_direction;
                 } else if (mk == RT_MATERIAL_METAL) { // src/material.rs:53-64
-                    const V3 refl = reflect(unit_d, normal);
+                    const V3 refl = reflect(unit, normal);
                     const V3 reflected = refl + rs * m->fuzz;
                     if (!(dot(reflected, normal) > 0.0)) path_done = true; // absorbed: emission (zero) only
                     new_dir = reflected;
                     attenuation = ld3(m->albedo);
                 } else if (mk == RT_MATERIAL_DIELECTRIC) { // src/material.rs:80-104
                     const double refraction_ratio = front_face ? m->albedo[0] : m->ir; // (1.0 / ir and both r0 were divided out when the table was built)
-                    const V3 unit_direction = unit_d;
+                    const V3 unit_direction = unit;
                     const double cos_theta = __builtin_fmin(dot(-unit_direction, normal), 1.0);
                     const double sin_theta = __builtin_sqrt(1.0 - cos_theta * cos_theta);
                     bool do_reflect = refraction_ratio * sin_theta > 1.0;
@@ -1032,7 +1044,7 @@ __global__ __launch_bounds__(THREADS, LDS ? 1 : RT_MIN_WAVES) void path_kernel(c
                     new_dir = do_reflect ? reflect(unit_direction, normal) : refract(unit_direction, normal, refraction_ratio);
                     unit_attenuation = true; // Color::ONE: multiplying by it is the identity, nothing to park
                 } else { // RT_MATERIAL_ISOTROPIC, src/material.rs:132-138
-                    new_dir = normalize(rs);
+                    new_dir = ONE_NORMALIZE ? unit : normalize(rs);
                 }
                 if (!path_done) {
                     if (!unit_attenuation) park(park_id, attenuation);
