@@ -1172,12 +1172,79 @@ int rt_film_device(int32_t width, int32_t height, const double *d_values /* 3*w*
                    const rt_tonemap_params *tone /* NULL: defaults */, int32_t format /* RT_FILM_* */, void *d_out /* rt_film_bytes */,
                    void *d_workspace /* may be NULL when auto_key == 0 */, void *hip_stream);
 
+/* ---- panoramas (opt-in; nothing above changes) ----------------------------------------------------------------------------------------------
+ * A full 360 x 180 degree picture of a scene from one point: the six faces of a cube map are six views of ONE rt_render_views_device
+ * launch, and rt_panorama_device resamples them into an equirectangular frame of means, which bloom, tone mapping and the film stage
+ * take as any frame of means (spp = 1) — the equirectangular .hdr is what viewers and image-based lighting read.
+ *
+ * Cube-face cameras.  rt_camera_cube_faces (no device) fills six square pinhole cameras of F = face_size pixels (defocus_angle 0, both
+ * disk vectors 0) centred at `center` (NULL: like->center); samples_per_pixel, max_depth and background are like's.  The inner
+ * (F - 2 g)^2 texels of a face (g = guard) cover exactly 90 degrees and the g texels around them continue the same grid outwards, so
+ * with g >= 1 a bilinear tap near a seam stays inside its own face and reads what the neighbouring face would show.  World axes, +Y up,
+ * right = forward x up (the reference camera's vup x w):
+ *       face   forward n   up u   right r
+ *        0       +X         +Y     +Z
+ *        1       -X         +Y     -Z
+ *        2       +Y         +Z     +X
+ *        3       -Y         -Z     +X
+ *        4       +Z         +Y     -X
+ *        5       -Z         +Y     +X
+ *   Plain f64, each operation rounded on its own, no trigonometry and no normalisation:
+ *       delta = 2.0 / (double)(F - 2 g);   hh = (double)F / (double)(F - 2 g);   e = 0.5 * delta - hh
+ *       pixel_delta_u = r * delta;   pixel_delta_v = u * (-delta)          (every component is +-delta or 0)
+ *       pixel00_loc_c = center_c + t_c,  t = n + r * e - u * e              (three different axes: every t_c is exactly one of +-1, +-e)
+ *   so that texel (i, j) of a face looks along n + r * ((2 i + 1 - F) / (F - 2 g)) - u * ((2 j + 1 - F) / (F - 2 g)).
+ *   RT_ERR_INVALID_ARGUMENT (the field named), in this order: a null like or out; face_size outside 2..16384; guard < 0;
+ *   face_size - 2 * guard < 1.
+ *
+ * Tables.  rt_panorama_tables (no device) writes 2 w + 2 h doubles to HOST memory, column entries first, then row entries:
+ *       tables[2 i]       = sin(lambda_i),  tables[2 i + 1]       = cos(lambda_i),   lambda_i = (((double)i + 0.5) / (double)w - 0.5) * 2 pi
+ *       tables[2 w + 2 j] = sin(phi_j),     tables[2 w + 2 j + 1] = cos(phi_j),      phi_j = (0.5 - ((double)j + 0.5) / (double)h) * pi
+ *   for the rows j with 2 j < h; row h - 1 - j is its mirror image (-sin(phi_j), cos(phi_j)), so the two hemispheres are each other's
+ *   reflection to the bit (the formula itself rounds differently above and below the equator).  The centre column looks along -Z, the
+ *   reference camera's default direction; longitude grows towards +X; row 0 is up.  The tables are DATA the caller uploads once per
+ *   size, and the only place a transcendental enters (the host's libm): the kernel and the host mirror read the same tables, so their
+ *   outputs agree bit for bit whatever libm made them.  The resampler does not require them to be normalised.
+ *   RT_ERR_INVALID_ARGUMENT: w or h < 1, or w * h >= 2^27; a null tables.
+ *
+ * The resampler, normative definition.  The arithmetic rules are those of "Arithmetic" below: f64, every operation rounded on its own,
+ * no FMA, IEEE division.  d_faces are six frames of 3 F F doubles, face-major — what rt_render_views_device writes for the six cameras
+ * above — of sums with the uniform count spp, or of means with spp = 1.  Per output pixel (i, j), with (sl, cl) column i's entries and
+ * (sp, cp) row j's:
+ *   Direction.    dx = cp * sl;  dy = sp;  dz = -(cp * cl).
+ *   Face.         ax, ay, az the absolute values.  ax >= ay and ax >= az: face 0 if dx > 0, else 1, m = ax.  Else ay >= az: face 2 if
+ *                 dy > 0, else 3, m = ay.  Otherwise face 4 if dz > 0, else 5, m = az.  Ties go to X over Y over Z.
+ *   Face coords.  a = (d . r) / m;  b = (d . u) / m — each dot product is one signed component of d, exact, so |a|, |b| <= 1.
+ *   Texel coords. s = (double)(F - 2 g) * 0.5;  c = (double)F * 0.5 - 0.5;  x = a * s + c;  y = c - b * s;
+ *                 x0 = min(max((int32_t)floor(x), 0), F - 2);  fx = min(max(x - (double)x0, 0.0), 1.0);  y0 and fy likewise.
+ *                 With g >= 1 no clamp ever acts; with g = 0 they are clamp-to-edge.
+ *   Taps.         T = S * (1.0 / (double)spp), tone mapping's "Input value", at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1)
+ *                 of the chosen face: T00, T10, T01, T11.
+ *   Output.       Per channel:  top = T00 + (T10 - T00) * fx;  bot = T01 + (T11 - T01) * fx;  out = top + (bot - top) * fy.
+ * Consequences.  A stack of one finite value gives that value bit for bit (every difference is +0.0).  A non-finite texel reaches
+ * exactly the output pixels that tap it, also at weight 0 (0 * inf and 0 * NaN are NaN), and no other.  With g = 2 the outermost texel
+ * ring of every face is never read: |a| <= 1 puts x in [g - 0.5, F - g - 0.5], whose taps are columns g - 1 .. F - g.
+ *
+ * rt_panorama_device reads d_tables (2 w + 2 h doubles, DEVICE memory) and d_faces and writes d_mean_out (3 w h doubles of means); no
+ * input is written.  One launch, enqueued on hip_stream; the call does not synchronise, allocates nothing and has no workspace.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; face_size and guard
+ * as rt_camera_cube_faces refuses them; a null d_tables, d_faces or d_mean_out; spp < 1; d_mean_out overlapping d_tables or any of
+ * the six faces. */
+int rt_camera_cube_faces(const rt_camera *like, const double center[3] /* NULL: like->center */, int32_t face_size, int32_t guard,
+                         rt_camera out[6]);
+int rt_panorama_tables(int32_t width, int32_t height, double *tables /* HOST, 2*width + 2*height doubles */);
+int rt_panorama_device(int32_t width, int32_t height, const double *d_tables /* 2w + 2h, device */,
+                       const double *d_faces /* 6 frames of 3*F*F doubles, face-major */, int32_t face_size, int32_t guard,
+                       int32_t spp /* sums with a count; means: 1 */, double *d_mean_out /* 3*w*h MEANS */, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
- * the copy — and everything enqueued on hip_stream before it — is done. */
+ * the copy — and everything enqueued on hip_stream before it — is done; rt_device_upload is the other direction (small inputs such as
+ * rt_panorama_tables' doubles) and returns when the host memory may be reused. */
 int rt_device_malloc(int device, int64_t bytes, void **out_device_ptr);
 int rt_device_free(int device, void *device_ptr);
 int rt_device_download(int device, void *dst_host, const void *src_device, int64_t bytes, void *hip_stream);
+int rt_device_upload(int device, void *dst_device, const void *src_host, int64_t bytes, void *hip_stream);
 
 /* ---- frame-end gather over RCCL / xGMI ----------------------------------------------------------
  * One communicator handle per rank (= per GPU).  Create it either

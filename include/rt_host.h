@@ -82,6 +82,12 @@ int rth_upsample(int32_t width, int32_t height, const double *low, int32_t spp, 
  * rth_last_error); there is no stream. */
 int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stack, int32_t spp, const rt_robust_params *params /* NULL: defaults */,
                double *out_mean, double *out_m2 /* or NULL */);
+/* The host mirror of rt_panorama_device (rt_amd.h "panoramas") on host memory: the same per-pixel body over the same tables
+ * (rt_panorama_tables' 2 w + 2 h doubles) and the six faces (3 * F * F doubles each, face-major: sums with the count spp, or means with
+ * spp = 1), so out_mean (3 * w * h doubles, a frame of means) holds the device's bits.  It refuses what the device call refuses, in the
+ * same order and with the same words (-1, the field named in rth_last_error); there is no stream. */
+int rth_panorama(int32_t width, int32_t height, const double *tables, const double *faces, int32_t face_size, int32_t guard, int32_t spp,
+                 double *out_mean);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* The film formats' files, each from a frame in its format (rt_amd.h "film output"), row 0 on top:

@@ -361,6 +361,7 @@ RT_AMD_SYMBOLS = {
     "rt_device_malloc": (C.c_int, [C.c_int, C.c_int64, C.POINTER(C.c_void_p)]),
     "rt_device_free": (C.c_int, [C.c_int, C.c_void_p]),
     "rt_device_download": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rt_device_upload": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "rt_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "rt_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "rt_comm_create_all": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
@@ -448,6 +449,9 @@ RT_AMD_SYMBOLS = {
                                                   C.c_void_p]),
     "rt_film_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "rt_film_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_camera_cube_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_panorama_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
+    "rt_panorama_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -802,6 +806,7 @@ RT_HOST_SYMBOLS = {
     "rth_upsample": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "rth_robust": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rth_panorama": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_write_hdr": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rth_write_pfm": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -1085,6 +1090,35 @@ class DeviceScene:
             torch.cuda.synchronize()
             out = d_out.cpu().numpy()
         return out[0], out[1]
+
+    def panorama_views(self, face_size: int, guard: int = 1, center=None, seed: int = 1):
+        """The six views render_panorama launches: the cube-face cameras about `center` (None: the scene camera's centre), face f with
+        seed + f."""
+        cams = cube_face_cameras(self.host_scene.camera, center, face_size, guard)
+        return _view_array([(cams[f], seed + f) for f in range(6)])
+
+    def render_panorama(self, width: int, height: "int | None" = None, center=None, face_size: "int | None" = None, guard: int = 1,
+                        spp: "int | None" = None, seed: int = 1):
+        """A full 360 x 180 degree equirectangular frame of the scene seen from `center` (None: the scene camera's centre): the six
+        cube faces (face_size pixels wide, default width // 4 + 2 * guard — the cube's texel density at the equator) under seeds
+        seed + f from ONE rt_render_views_device launch of `spp` samples (None: the camera's samples_per_pixel), resampled on the device
+        by rt_panorama_device.  `height` defaults to width // 2.  Returns the (height, width, 3) float64 frame of means: what bloom,
+        tonemap and film take with spp = 1."""
+        import torch
+        height = width // 2 if height is None else height
+        face_size = width // 4 + 2 * guard if face_size is None else face_size
+        views = self.panorama_views(face_size, guard, center, seed)
+        n = spp if spp is not None else self.host_scene.camera.samples_per_pixel
+        tables = panorama_tables(width, height)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            d_tables = torch.from_numpy(tables).cuda()
+            d_faces = torch.empty((6, face_size, face_size, 3), dtype=torch.float64, device="cuda")
+            d_out = torch.empty((height, width, 3), dtype=torch.float64, device="cuda")
+            self.render_views_device(render_params(sample_end=n), views, d_faces.data_ptr(), stream)
+            panorama_device(width, height, d_tables.data_ptr(), d_faces.data_ptr(), face_size, guard, n, d_out.data_ptr(), stream=stream)
+            torch.cuda.synchronize()
+            return d_out.cpu().numpy()
 
     def render_views_moments(self, params: RenderParams, views, sum=None, sum_sq=None):
         """rt_render_views_moments: (sum, sum_sq), two (n_views, h, w, 3) float64 arrays from one launch: `sum` is render_views' array,
@@ -1878,6 +1912,65 @@ def camera_scaled(camera: Camera, factor: int) -> Camera:
     factor x factor block of `camera`'s."""
     out = Camera()
     _check(amd_lib().rt_camera_scaled(C.byref(camera), int(factor), C.byref(out)), "rt_camera_scaled")
+    return out
+
+
+def cube_face_cameras(like: Camera, center=None, face_size: int = 0, guard: int = 1):
+    """rt_camera_cube_faces (GPU-free): a ctypes array of the six square pinhole cameras of a cube map about `center` (None: like's
+    centre), faces +X, -X, +Y, -Y, +Z, -Z, each `face_size` pixels wide with `guard` texels beyond the 90 degrees on every side;
+    samples_per_pixel, max_depth and background are like's."""
+    out = (Camera * 6)()
+    c = None if center is None else (C.c_double * 3)(*[float(x) for x in center])
+    _check(amd_lib().rt_camera_cube_faces(C.byref(like), c, int(face_size), int(guard), out), "rt_camera_cube_faces")
+    return out
+
+
+def panorama_tables(width, height):
+    """rt_panorama_tables (GPU-free): the 2 w + 2 h float64 of a w x h equirectangular frame — (sin, cos) of every column's longitude,
+    then of every row's latitude.  Data for panorama_device / panorama_host, reusable for every frame of that size."""
+    import numpy as np
+    n = 2 * width + 2 * height if width > 0 and height > 0 and width * height < 1 << 27 else 1
+    t = np.zeros(n, dtype=np.float64)
+    _check(amd_lib().rt_panorama_tables(int(width), int(height), t.ctypes.data), "rt_panorama_tables")
+    return t
+
+
+def panorama_device(width, height, d_tables_ptr: int, d_faces_ptr: int, face_size: int, guard: int, spp: int, d_mean_out_ptr: int, *,
+                    stream: int = 0):
+    """rt_panorama_device: the six device frames of 3 F F doubles at d_faces_ptr, face after face — sums with the count `spp`, or means
+    with spp = 1 — resampled through the device copy of panorama_tables(w, h) at d_tables_ptr into the 3 w h doubles of MEANS at
+    d_mean_out_ptr.  One launch, enqueued on `stream`; no workspace."""
+    _check(amd_lib().rt_panorama_device(width, height, C.c_void_p(d_tables_ptr or None), C.c_void_p(d_faces_ptr or None), face_size, guard, spp,
+                                        C.c_void_p(d_mean_out_ptr or None), C.c_void_p(stream)), "rt_panorama_device")
+
+
+def _panorama_inputs(who, width, height, faces, tables):
+    import numpy as np
+    faces = np.ascontiguousarray(faces, dtype=np.float64)
+    if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+        raise RtError(f"{who}: faces must be (6, F, F, 3), not {faces.shape}")
+    tables = panorama_tables(width, height) if tables is None else np.ascontiguousarray(tables, dtype=np.float64)
+    if tables.shape != (2 * width + 2 * height,):
+        raise RtError(f"{who}: tables must hold 2 * width + 2 * height values")
+    return faces, tables
+
+
+def panorama(width, height, faces, guard, spp, *, tables=None, device=0):
+    """Uploads a (6, F, F, 3) stack of cube faces (sums with the count `spp`, or means with spp = 1) and the tables (None:
+    panorama_tables(width, height)), runs rt_panorama_device and downloads the (height, width, 3) float64 frame of means."""
+    faces, tables = _panorama_inputs("panorama", width, height, faces, tables)
+    F = faces.shape[1]
+    return _frame_end(device, [tables, faces], (height, width, 3), None, 0,
+                      lambda d, out, ws, rgba, stream: panorama_device(width, height, d[0], d[1], F, int(guard), int(spp), out, stream=stream))
+
+
+def panorama_host(width, height, faces, guard, spp, *, tables=None):
+    """rth_panorama (librt_host, CPU): what rt_panorama_device gives, bit for bit, from the same per-pixel body and the same tables."""
+    import numpy as np
+    faces, tables = _panorama_inputs("panorama_host", width, height, faces, tables)
+    out = np.zeros((height, width, 3), dtype=np.float64)
+    if host_lib().rth_panorama(width, height, tables.ctypes.data, faces.ctypes.data, faces.shape[1], int(guard), int(spp), out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
     return out
 
 

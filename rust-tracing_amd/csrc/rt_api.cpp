@@ -5,6 +5,7 @@
 #include "rt_tonemap_shared.h"
 #include "rt_bloom_shared.h"
 #include "rt_robust_shared.h"
+#include "rt_panorama_shared.h"
 #include "rt_upsample_shared.h"
 
 #include <algorithm>
@@ -895,6 +896,15 @@ int rt_device_download(int device, void *dst_host, const void *src_device, int64
     if (device < 0 || device >= rt_device_count()) return fail(RT_ERR_NO_DEVICE, "rt_device_download: device ordinal out of range");
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipMemcpyAsync(dst_host, src_device, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
+    return RT_OK;
+}
+
+int rt_device_upload(int device, void *dst_device, const void *src_host, int64_t bytes, void *hip_stream) {
+    if (!dst_device || !src_host || bytes <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_device_upload: bad argument");
+    if (device < 0 || device >= rt_device_count()) return fail(RT_ERR_NO_DEVICE, "rt_device_upload: device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipMemcpyAsync(dst_device, src_host, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
     return RT_OK;
 }
@@ -1969,6 +1979,34 @@ int rt_upsample_device(int32_t width, int32_t height, const double *d_low, int32
     HIP_TRY(hipGetLastError());
     const int32_t form = g_upsample_form.load();
     launch_upsample(u, form != 0, stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- panoramas (rt_panorama.hip): six cube-face cameras, the longitude and latitude tables, and the cube-to-equirectangular resampler ----
+
+int rt_camera_cube_faces(const rt_camera *like, const double center[3], int32_t face_size, int32_t guard, rt_camera out[6]) {
+    if (!like) return fail(RT_ERR_INVALID_ARGUMENT, "rt_camera_cube_faces: like is null");
+    if (!out) return fail(RT_ERR_INVALID_ARGUMENT, "rt_camera_cube_faces: out is null");
+    if (const char *bad = rtpn::bad_face(face_size, guard)) return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_camera_cube_faces: ") + bad);
+    rtpn::cube_faces(*like, center, face_size, guard, out);
+    return RT_OK;
+}
+
+int rt_panorama_tables(int32_t width, int32_t height, double *tables) {
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID_ARGUMENT, "rt_panorama_tables: width and height must be positive");
+    if ((int64_t)width * height >= rtpn::MAX_PIXELS) return fail(RT_ERR_INVALID_ARGUMENT, "rt_panorama_tables: width x height must be below 2^27 pixels");
+    if (!tables) return fail(RT_ERR_INVALID_ARGUMENT, "rt_panorama_tables: tables is null");
+    rtpn::tables(width, height, tables);
+    return RT_OK;
+}
+
+int rt_panorama_device(int32_t width, int32_t height, const double *d_tables, const double *d_faces, int32_t face_size, int32_t guard, int32_t spp,
+                       double *d_mean_out, void *hip_stream) {
+    if (const char *bad = rtpn::bad_argument(true, width, height, d_tables, d_faces, face_size, guard, spp, d_mean_out))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_panorama_device: ") + bad);
+    if (int rc = select_device_of(d_mean_out, "rt_panorama_device")) return rc;
+    launch_panorama(width, height, d_tables, d_faces, face_size, guard, 1.0 / (double)spp, d_mean_out, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }

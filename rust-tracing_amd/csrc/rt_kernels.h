@@ -305,7 +305,11 @@ struct UpsampleArgs {
 };
 void launch_upsample_prepare(const UpsampleArgs &u, hipStream_t stream);
 void launch_upsample(const UpsampleArgs &u, bool lds, hipStream_t stream);
-void launch_debug_box(int64_t n, const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
+// panoramas (rt_panorama.hip; rt_panorama_device).  One launch, one thread per output pixel of the w x h frame: `tables` are the 2 w + 2 h
+// doubles of rt_panorama_tables, `faces` six frames of 3 F F doubles, face-major; `out` gets 3 w h means.
+void launch_panorama(int32_t w, int32_t h, const double *tables, const double *faces, int32_t face_size, int32_t guard, double inv_spp, double *out,
+                     hipStream_t stream);
+void launch_debug_box(int64_t n,const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)
 struct DebugWideArgs {

@@ -8,6 +8,7 @@
 #include "../csrc/rt_bloom_shared.h"
 #include "../csrc/rt_robust_shared.h"
 #include "../csrc/rt_upsample_shared.h"
+#include "../csrc/rt_panorama_shared.h"
 #include <cstring>
 #include <exception>
 #include <string>
@@ -345,6 +346,16 @@ int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stac
         out_mean[e] = one(stack + e, total, rule, out_m2 ? &m2 : nullptr);
         if (out_m2) out_m2[e] = m2;
     }
+    return 0;
+}
+
+// ---- panoramas: the host mirror of rt_panorama_device (include/rt_amd.h "panoramas") ----
+
+int rth_panorama(int32_t width, int32_t height, const double *tables, const double *faces, int32_t face_size, int32_t guard, int32_t spp,
+                 double *out_mean) {
+    if (const char *bad = rtpn::bad_argument(false, width, height, tables, faces, face_size, guard, spp, out_mean))
+        return fail(std::string("rth_panorama: ") + bad);
+    rtpn::resample(width, height, tables, faces, face_size, guard, spp, out_mean);
     return 0;
 }
 

@@ -38,6 +38,9 @@
 //   --robust K [--robust-mode mean|trim|median|gini] [--robust-trim T] [--robust-gain X] (robust frames of include/rt_amd.h: K sub-frames
 //   of spp / K samples under seeds seed + k in one views launch, combined by the median of means; --denoise filters the result with
 //   samples = K, --bloom and --tonemap run behind it).
+//   --panorama W [--panorama-face F] [--panorama-guard G] [--panorama-at x,y,z] (panoramas of include/rt_amd.h: the six cube-face views
+//   about a point in one views launch, resampled on the device into a W x W / 2 equirectangular frame of means; --bloom, --tonemap and
+//   --format run behind it).
 //   --format png|png16|hdr|pfm (film output of include/rt_amd.h: the frame of every single-GPU, one-pass route — each file of --orbit,
 //   the last frame of --live — as a 16-bit PNG, a Radiance OUTPUT.hdr or a float OUTPUT.pfm; --tonemap, --exposure, --auto-exposure,
 //   --tonemap-white and --bloom apply in front of every format, and with none of them .hdr and .pfm hold the linear means).
@@ -45,6 +48,7 @@
 #include "renderer.hpp"
 #include "scenes.hpp"
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -107,6 +111,12 @@ static void usage(const char *argv0) {
             "                         of --live — is OUTPUT.png with 8-bit samples, default, or 16-bit ones (png16), a Radiance OUTPUT.hdr with shared-\n"
             "                         exponent pixels (hdr) or a float OUTPUT.pfm (pfm); --tonemap, --exposure, --auto-exposure, --tonemap-white and\n"
             "                         --bloom apply in front of every format: with none of them hdr and pfm hold the linear means, unclipped)\n"
+            "          [--panorama W [--panorama-face F] [--panorama-guard G] [--panorama-at x,y,z]]   (one GPU, one launch: a 360 x 180 degree\n"
+            "                         equirectangular frame of W x W / 2 pixels, W even, seen from x,y,z (default: the scene camera's centre): the six\n"
+            "                         faces of a cube map, F pixels wide (default W / 4 + 2 G) with G guard texels beyond the 90 degrees (default 1),\n"
+            "                         under seeds seed + face, resampled bilinearly; the frame of means goes on through --bloom, --tonemap, --exposure,\n"
+            "                         --auto-exposure and --format as any other: --format hdr is what viewers and image-based lighting read; not with\n"
+            "                         -l, --adaptive, --orbit, --progressive, --upsample, --robust, --gpus > 1 or the --denoise family)\n"
             "  scenes: 0 random balls, 1 two spheres, 2 earth, 3 perlin spheres, 4 quads, 5 simple light,\n"
             "          6 cornell box, 7 cornell smoke, 8 final scene\n",
             argv0);
@@ -114,7 +124,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false, robust_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false, robust_knob_given = false, panorama_knob_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -267,6 +277,42 @@ int main(int argc, char **argv) {
             else if (f == "pfm") ro.format = FILM_PFM;
             else { fprintf(stderr, "--format needs a file format: png, png16, hdr or pfm\n"); usage(argv[0]); return 2; }
         }
+        else if (a == "--panorama") {
+            char *end = nullptr;
+            const char *v = need("--panorama");
+            const long pw = strtol(v, &end, 10);
+            if (end == v || *end != 0 || pw < 2 || pw > 32768 || pw % 2 != 0) { fprintf(stderr, "--panorama needs an even width from 2 to 32768\n"); usage(argv[0]); return 2; }
+            ro.panorama_width = (int)pw;
+        }
+        else if (a == "--panorama-face") {
+            char *end = nullptr;
+            const char *v = need("--panorama-face");
+            const long f = strtol(v, &end, 10);
+            panorama_knob_given = true;
+            if (end == v || *end != 0 || f < 2 || f > 16384) { fprintf(stderr, "--panorama-face needs a face size from 2 to 16384\n"); usage(argv[0]); return 2; }
+            ro.panorama_face = (int)f;
+        }
+        else if (a == "--panorama-guard") {
+            char *end = nullptr;
+            const char *v = need("--panorama-guard");
+            const long g = strtol(v, &end, 10);
+            panorama_knob_given = true;
+            if (end == v || *end != 0 || g < 0 || g > 8191) { fprintf(stderr, "--panorama-guard needs a number of guard texels from 0 to 8191\n"); usage(argv[0]); return 2; }
+            ro.panorama_guard = (int)g;
+        }
+        else if (a == "--panorama-at") {
+            const char *v = need("--panorama-at");
+            char *end = nullptr;
+            bool ok = true;
+            panorama_knob_given = true;
+            for (int c = 0; c < 3 && ok; ++c) {
+                ro.panorama_at[c] = strtod(v, &end);
+                ok = end != v && std::isfinite(ro.panorama_at[c]) && *end == (c < 2 ? ',' : 0);
+                v = end + 1;
+            }
+            if (!ok) { fprintf(stderr, "--panorama-at needs a point x,y,z\n"); usage(argv[0]); return 2; }
+            ro.panorama_at_given = true;
+        }
         else if (a == "--upsample-albedo") ro.upsample_albedo = true;
         else if (a == "--upsample-edges") ro.upsample_edges = true;
         else if (a == "--earth") so.earth_image = need("--earth");
@@ -380,6 +426,20 @@ int main(int argc, char **argv) {
         if (with) {
             fprintf(stderr, "--robust renders its sub-frames on one GPU in one launch and filters them with the plain --denoise only: it cannot be "
                             "combined with %s\n", with);
+            return 2;
+        }
+    }
+    if (panorama_knob_given && ro.panorama_width == 0) {
+        fprintf(stderr, "--panorama-face, --panorama-guard and --panorama-at set the cube map of --panorama: they need --panorama\n");
+        return 2;
+    }
+    if (ro.panorama_width > 0) {
+        const char *with = live ? "-l/--live" : ro.adaptive ? "--adaptive" : ro.orbit > 0 ? "--orbit" : ro.progressive_spp > 0 ? "--progressive"
+                           : ro.upsample > 0 ? "--upsample" : ro.robust_blocks > 0 ? "--robust" : ro.gpus > 1 ? "--gpus > 1"
+                           : ro.denoise_albedo ? "--denoise-albedo" : ro.denoise_edges ? "--denoise-edges" : ro.denoise ? "--denoise" : nullptr;
+        if (with) {
+            fprintf(stderr, "--panorama renders its six cube faces on one GPU in one launch and resamples them unfiltered: it cannot be combined "
+                            "with %s\n", with);
             return 2;
         }
     }

@@ -689,6 +689,67 @@ static std::vector<uint8_t> render_robust_rgb8(const Camera &camera, const Hitta
     return px;
 }
 
+void panorama_device(int32_t width, int32_t height, const double *d_faces, int32_t face_size, int32_t guard, int32_t spp, double *d_mean_out) {
+    if (width < 1 || height < 1 || (int64_t)width * height >= ((int64_t)1 << 27)) throw std::runtime_error("panorama: no frame of this size");
+    std::vector<double> tables(2u * (size_t)width + 2u * (size_t)height);
+    if (rt_panorama_tables(width, height, tables.data()) != RT_OK) throw std::runtime_error(std::string("panorama: ") + rt_last_error());
+    const int64_t bytes = (int64_t)(tables.size() * sizeof(double));
+    void *d_tables = nullptr;
+    int rc = rt_device_malloc(0, bytes, &d_tables);
+    if (rc == RT_OK) rc = rt_device_upload(0, d_tables, tables.data(), bytes, nullptr);
+    if (rc == RT_OK) rc = rt_panorama_device(width, height, static_cast<const double *>(d_tables), d_faces, face_size, guard, spp, d_mean_out, nullptr);
+    double done = 0.0; // (waits for the launch: the tables are freed behind it)
+    if (rc == RT_OK) rc = rt_device_download(0, &done, d_mean_out, (int64_t)sizeof done, nullptr);
+    const std::string msg = rc == RT_OK ? "" : rt_last_error();
+    rt_device_free(0, d_tables);
+    if (rc != RT_OK) throw std::runtime_error("panorama: " + msg);
+}
+
+// A panorama on device 0 (opt.panorama_width = W): the six cube-face views about the point from one rt_render_views_device call,
+// resampled on the device by rt_panorama_device; the W x W / 2 frame of means goes through the means-form output and only the bytes
+// come back.
+static std::vector<uint8_t> render_panorama_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt, int32_t &w, int32_t &h) {
+    const rt_camera cam = camera.pod();
+    w = opt.panorama_width; h = w / 2;
+    if (w < 2 || w % 2 != 0 || w > 32768) throw std::runtime_error("render: panorama_width must be an even number from 2 to 32768");
+    const int32_t g = opt.panorama_guard, F = opt.panorama_face > 0 ? opt.panorama_face : w / 4 + 2 * g;
+    rt_camera faces[6];
+    if (rt_camera_cube_faces(&cam, opt.panorama_at_given ? opt.panorama_at : nullptr, F, g, faces) != RT_OK)
+        throw std::runtime_error(std::string("render: ") + rt_last_error());
+    SceneDescriber sd;
+    const rt_ref root = world.describe(sd);
+    const rt_scene_desc desc = sd.desc(root);
+    const int64_t n_pix = (int64_t)w * h, frame_bytes = n_pix * 3 * (int64_t)sizeof(double), face_bytes = (int64_t)F * F * 3 * (int64_t)sizeof(double);
+    rt_scene *scene = nullptr;
+    void *d_faces = nullptr, *d_mean = nullptr, *d_rgba8 = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_faces); rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_scene_destroy(scene); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("render: " + msg); } };
+    std::vector<rt_view> views(6);
+    for (int f = 0; f < 6; ++f) { views[(size_t)f].camera = faces[f]; views[(size_t)f].seed = opt.seed + (uint64_t)f; }
+    rt_render_params p{};
+    p.sample_begin = 0; p.sample_end = cam.samples_per_pixel; p.max_depth = cam.max_depth;
+    p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
+    check(rt_scene_create(&desc, 0, &scene));
+    check(rt_device_malloc(0, face_bytes * 6, &d_faces));
+    check(rt_device_malloc(0, frame_bytes, &d_mean));
+    check(rt_render_views_device(scene, views.data(), 6, &p, static_cast<double *>(d_faces), nullptr));
+    std::vector<uint8_t> px;
+    try {
+        panorama_device(w, h, static_cast<const double *>(d_faces), F, g, p.sample_end, static_cast<double *>(d_mean));
+        if (tonemapped(opt)) px = staged_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, false, opt);
+    } catch (...) { cleanup(); throw; }
+    if (px.empty()) {
+        check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
+        check(rt_resolve_rgba8_device(w, h, static_cast<const double *>(d_mean), static_cast<uint8_t *>(d_rgba8), nullptr));
+        std::vector<uint8_t> rgba((size_t)n_pix * 4u);
+        check(rt_device_download(0, rgba.data(), d_rgba8, n_pix * 4, nullptr));
+        px.resize((size_t)n_pix * 3u);
+        for (size_t q = 0; q < (size_t)n_pix; ++q) { px[3 * q] = rgba[4 * q]; px[3 * q + 1] = rgba[4 * q + 1]; px[3 * q + 2] = rgba[4 * q + 2]; }
+    }
+    cleanup();
+    return px;
+}
+
 // Adaptive sampling on device 0: the frame's sums and per-pixel spp stay on the device, are resolved there with each pixel's own
 // spp, and only the bytes come back.
 static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hittable &world, const RenderOptions &opt) {
@@ -788,6 +849,7 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     // opt.live_denoise_edges: the surface-ID scene's frame of means d_ids, rendered ONCE, before the first pass, is every pass's edge guide
     const bool edges = opt.live_denoise_edges;
     const bool denoised = opt.live_denoise || opt.live_denoise_albedo || edges, guided = opt.live_denoise_albedo;
+    if (opt.panorama_width != 0) throw std::runtime_error("live_render: panorama_width resamples the cube faces of one render() call: it cannot be combined with the live route");
     if (opt.robust_blocks != 0) throw std::runtime_error("live_render: robust_blocks combines the sub-frames of one render() call: it cannot be combined with the live route");
     if (edges && opt.upsample > 0) throw std::runtime_error("live_render: live_denoise_edges cannot be combined with upsample (the guide would have to be made at the low size)");
     const int32_t w = cam.image_width, h = cam.image_height;
@@ -995,6 +1057,18 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     if (opt.upsample > 0 && (opt.orbit > 0 || opt.adaptive || opt.gpus > 1 || opt.progressive_spp > 0))
         throw std::runtime_error("render: upsample is a one-GPU, one-pass route: it cannot be combined with orbit, adaptive, gpus > 1 or progressive_spp");
     if ((opt.upsample_albedo || opt.upsample_edges) && opt.upsample == 0) throw std::runtime_error("render: upsample_albedo and upsample_edges need upsample");
+    if (opt.panorama_width != 0) {
+        if (opt.adaptive || opt.orbit > 0 || opt.progressive_spp > 0 || opt.upsample > 0 || opt.robust_blocks != 0 || opt.denoise || opt.gpus > 1)
+            throw std::runtime_error("render: panorama_width is a one-GPU, one-pass route of its own: it cannot be combined with adaptive, orbit, "
+                                     "progressive_spp, upsample, robust_blocks, denoise or gpus > 1");
+        int32_t pw = 0, ph = 0;
+        const std::vector<uint8_t> px = render_panorama_rgb8(*camera, *world, opt, pw, ph);
+        if (!opt.quiet) printf("Render time: %.2fs (panorama %d x %d)\n", std::chrono::duration<double>(clock::now() - now).count(), pw, ph);
+        now = clock::now();
+        write_frame(output_file_name, pw, ph, px, opt);
+        if (!opt.quiet) printf("PNG encoding: %.2fs\n", std::chrono::duration<double>(clock::now() - now).count());
+        return;
+    }
     if (opt.robust_blocks != 0) {
         if (opt.adaptive || opt.orbit > 0 || opt.progressive_spp > 0 || opt.upsample > 0 || opt.gpus > 1)
             throw std::runtime_error("render: robust_blocks is a one-GPU, one-pass route of its own: it cannot be combined with adaptive, orbit, "

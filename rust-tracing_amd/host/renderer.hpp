@@ -124,6 +124,16 @@ struct RenderOptions {
     // no tonemap, exposure or bloom given the stage runs with the clamp and exposure 1: .hdr and .pfm hold the linear means.  Not with
     // gpus > 1 or progressive_spp (render() throws).
     int format = FILM_PNG;
+    // panoramas (include/rt_amd.h "panoramas"): panorama_width = W > 0 (even) renders the six cube-face views about panorama_at (or, not
+    // given, the camera's centre) — panorama_face pixels wide (0: W / 4 + 2 * panorama_guard) with panorama_guard guard texels, under seeds
+    // seed + face — in ONE rt_render_views_device call and resamples them with rt_panorama_device into a W x W / 2 equirectangular frame of
+    // means, which goes through bloom, the tone-mapping stage and the film formats as any frame of means.  The scene camera's image size is
+    // not used.  Not with adaptive, orbit, progressive_spp, upsample, robust_blocks, denoise or gpus > 1 (render() throws), nor live_render.
+    int panorama_width = 0;
+    int panorama_face = 0;
+    int panorama_guard = 1;
+    bool panorama_at_given = false;
+    double panorama_at[3] = {0.0, 0.0, 0.0};
 };
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
@@ -188,6 +198,11 @@ std::vector<uint8_t> tonemap_device(int32_t width, int32_t height, const double 
 std::vector<uint8_t> film_host(const std::vector<double> &values, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt);
 std::vector<uint8_t> film_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const RenderOptions &opt);
 void write_film_frame(const std::string &name, int32_t width, int32_t height, const std::vector<uint8_t> &film, const RenderOptions &opt);
+
+// rt_panorama_device on device 0: the six DEVICE frames of 3 * F * F doubles at d_faces (sums with the count spp, or means with spp = 1),
+// F = face_size with `guard` guard texels, into the DEVICE frame d_mean_out (3 * width * height doubles of means).  The tables of the
+// size are made and uploaded by the call and freed behind it.  Throws std::runtime_error on a library error.
+void panorama_device(int32_t width, int32_t height, const double *d_faces, int32_t face_size, int32_t guard, int32_t spp, double *d_mean_out);
 
 // Bloom with opt's strength, threshold and levels.  bloom_means: on a HOST frame (sums with the uniform count spp; means with spp = 1),
 // through the host mirror; returns the 3 * w * h bloomed means.  bloom_device: rt_bloom_device on device 0 over a DEVICE frame (sums with
