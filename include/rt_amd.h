@@ -1237,6 +1237,81 @@ int rt_panorama_device(int32_t width, int32_t height, const double *d_tables /* 
                        const double *d_faces /* 6 frames of 3*F*F doubles, face-major */, int32_t face_size, int32_t guard,
                        int32_t spp /* sums with a count; means: 1 */, double *d_mean_out /* 3*w*h MEANS */, void *hip_stream);
 
+/* ---- frame metrics (opt-in; nothing above changes) -------------------------------------------------------------------------------------------
+ * How good is a frame?  rt_frame_error_device measures a frame against a reference frame of the same size (MSE, relative MSE, mean
+ * absolute error, bias, largest error, PSNR); rt_frame_noise_device estimates a frame's own noise from its second moments, so that a
+ * refining loop can stop when the picture has settled.  Both are one reduction over the pixels, on the device, without a host round trip.
+ *
+ * Normative definition.  The arithmetic rules are those of "Arithmetic" below: f64, every operation rounded on its own, no FMA, IEEE
+ * division and square root, rt_log where a logarithm is needed.  max(a, b) = (a < b ? b : a).
+ *   Reduction.    Exactly tone mapping's tree: one entry per pixel in index order j * w + i, padded to a multiple of 256 with the
+ *                 neutral entry; each block of 256 consecutive entries is reduced by
+ *                     for stride = 128, 64, ..., 1:   e[i] = e[i] (+) e[i + stride]   for i < stride
+ *                 the block results, in block order, are the entries of the next level; levels repeat until one entry is left.  An
+ *                 entry is a record of several accumulators: (+) adds sums, takes max of maxima and adds the integer counts.  The
+ *                 neutral entry is all +0.0 with count 0.  No floating-point atomics, and no summation order that depends on the
+ *                 launch shape.  w * h < 2^27, as there.
+ *   Input value.  As in "tone mapping".  Sums form: m = S * (1.0 / (double)n), n uniform or d_spp[pixel].  Means form: m = S.
+ *
+ * rt_frame_error_device.  d_values is a frame of sums with the count spp or the map d_spp, or of means with spp = 1; d_ref a frame of
+ * sums with the uniform count ref_spp, or of means with ref_spp = 1: r = R * (1.0 / (double)ref_spp).
+ *   Counting.     A pixel COUNTS iff its three m and three r are all finite.  Any other pixel is the neutral entry.
+ *   Per channel of a counting pixel.   d = m - r;  sq = d * d;  ab = |d|;  den = (r * r) + eps;  rel = sq / den.
+ *   Pixel entry.  T_sq, T_rel, T_ab, T_d: (t_r + t_g) + t_b of sq, rel, ab and d;  Tmax = max(max(ab_r, ab_g), ab_b);  count 1.
+ *   Final values, with N = (double)(3 * count), written to d_out8 in this order:
+ *                 count (as a double);  mse = T_sq / N;  rmse = sqrt(mse);  rel_mse = T_rel / N;  mae = T_ab / N;  bias = T_d / N;
+ *                 max_abs = Tmax;  psnr = 4.342944819032518 * rt_log((peak * peak) / mse)  (the constant is 10 / ln 10), and +inf where
+ *                 mse == 0.  With count == 0 all eight are 0.
+ *
+ * rt_frame_noise_device.  form RT_METRICS_SUMS: d_a holds per-pixel sums S and d_b sums of squares Q (rt_render_moments_device), with
+ * the count n or the map d_spp.  form RT_METRICS_MEANS: d_a holds the running means and d_b Welford's M2 after n samples of every
+ * pixel (rt_render_mean_moments_device); uniform n only.
+ *   Counting.     A pixel COUNTS iff its n >= 2 and its six values are finite.  Any other pixel is the neutral entry.
+ *   Variance.     Per channel, with dn = (double)n, the variance of the mean as the denoisers' Prepare step has it before it takes the
+ *                 largest channel — "denoise": m_c = S_c / dn, v_c = (Q_c - S_c * m_c) / (dn - 1); "live denoise": v_c = M2_c / (dn - 1) —
+ *                 then var_c = (0 > v_c ? 0 : v_c) / dn.  The largest var_c of a pixel is Prepare's V0 bit for bit.
+ *   Per channel.  mean = the "Input value" above;  rel = var / ((mean * mean) + eps).
+ *   Pixel entry.  V = (var_r + var_g) + var_b;  R = (rel_r + rel_g) + rel_b;  Rmax = max(max(rel_r, rel_g), rel_b);  count 1.
+ *   Final values, with N = (double)(3 * count), written to d_out4 in this order:
+ *                 count (as a double);  mean_var = V / N;  noise = sqrt(R / N), the RMS relative standard error;
+ *                 max_noise = sqrt(Rmax).  With count == 0: mean_var = 0 and noise = max_noise = +inf, so that a test
+ *                 `noise <= threshold` never passes on a frame that says nothing (every pixel at n = 1).
+ *
+ * Both calls read their inputs and write only the output doubles (DEVICE memory) and d_workspace: rt_metrics_workspace_bytes(w, h)
+ * bytes of device memory, 16-byte aligned, the caller's — 48 bytes per block of every level; -1 for a size the calls refuse.  They are
+ * enqueued on hip_stream, do not synchronise and allocate nothing.  spp / n must be >= 1 even where d_spp is given (it is then not read).
+ * The entries of d_spp are the caller's to keep >= 1, as in "tone mapping": they are not checked.  An entry of 0 makes 1.0 / 0 = +inf, so the
+ * error call's m is +-inf or NaN and the pixel does not count; a negative entry negates m, and the pixel counts with it; in the noise call
+ * an entry below 2 does not count.
+ * RT_ERR_INVALID_ARGUMENT (the field named) before any device work, in this order: w or h < 1, or w * h >= 2^27; a null d_values,
+ * d_ref, d_out8 (d_a, d_b, d_out4); spp < 1, ref_spp < 1 (n < 1); a struct_size this library does not know; form outside 0..1, or a
+ * d_spp map with RT_METRICS_MEANS; eps (and peak) that is not a finite number > 0; a null d_workspace or one that is not 16-byte
+ * aligned; the output overlapping an input frame. */
+#define RT_METRICS_SUMS 0
+#define RT_METRICS_MEANS 1
+typedef struct rt_frame_error_params {
+    uint32_t struct_size;   /* sizeof(rt_frame_error_params) as the CALLER was compiled (grows like rt_scene_options) */
+    int32_t _pad;
+    double eps;             /* added to the squared reference in rel's denominator (default 1e-2), finite, > 0 */
+    double peak;            /* the signal peak of psnr (default 1.0), finite, > 0 */
+} rt_frame_error_params;
+typedef struct rt_frame_noise_params {
+    uint32_t struct_size;   /* sizeof(rt_frame_noise_params) as the CALLER was compiled */
+    int32_t _pad;
+    double eps;             /* added to the squared mean in rel's denominator (default 1e-2), finite, > 0 */
+} rt_frame_noise_params;
+/* Fill the defaults into the first struct_size bytes (nothing beyond them is written) and set struct_size. */
+int rt_frame_error_params_init_sized(rt_frame_error_params *params, uint32_t struct_size);
+int rt_frame_noise_params_init_sized(rt_frame_noise_params *params, uint32_t struct_size);
+int64_t rt_metrics_workspace_bytes(int32_t width, int32_t height);
+int rt_frame_error_device(int32_t width, int32_t height, const double *d_values /* 3*w*h */, int32_t spp, const int32_t *d_spp /* NULL: uniform */,
+                          const double *d_ref /* 3*w*h */, int32_t ref_spp, const rt_frame_error_params *params /* NULL: defaults */,
+                          double *d_out8 /* count, mse, rmse, rel_mse, mae, bias, max_abs, psnr */, void *d_workspace, void *hip_stream);
+int rt_frame_noise_device(int32_t width, int32_t height, int32_t form /* RT_METRICS_* */, const double *d_a /* 3*w*h */,
+                          const double *d_b /* 3*w*h */, int32_t n, const int32_t *d_spp /* NULL: uniform; sums form only */,
+                          const rt_frame_noise_params *params /* NULL: defaults */, double *d_out4 /* count, mean_var, noise, max_noise */,
+                          void *d_workspace, void *hip_stream);
+
 /* Device memory for hosts that do not link the HIP runtime themselves (the Rust binding, host/renderer.cpp): the buffers
  * rt_render_device, the gather and the frame-end kernels work on.  rt_device_download copies to host memory and returns when
  * the copy — and everything enqueued on hip_stream before it — is done; rt_device_upload is the other direction (small inputs such as

@@ -88,6 +88,21 @@ int rth_robust(int32_t width, int32_t height, int32_t blocks, const double *stac
  * same order and with the same words (-1, the field named in rth_last_error); there is no stream. */
 int rth_panorama(int32_t width, int32_t height, const double *tables, const double *faces, int32_t face_size, int32_t guard, int32_t spp,
                  double *out_mean);
+/* The host mirrors of rt_frame_error_device and rt_frame_noise_device (rt_amd.h "frame metrics") on host memory: the same shared pixel
+ * term, combine and final values through the same reduction tree, so out8 (count, mse, rmse, rel_mse, mae, bias, max_abs, psnr) and
+ * out4 (count, mean_var, noise, max_noise) hold the device's bits.  They refuse what the device calls refuse of these arguments, in the
+ * same order and with the same words (-1, the field named in rth_last_error); there is no workspace and no stream. */
+int rth_frame_error(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map /* NULL: uniform */,
+                    const double *ref, int32_t ref_spp, const rt_frame_error_params *params /* NULL: defaults */, double *out8);
+int rth_frame_noise(int32_t width, int32_t height, int32_t form /* RT_METRICS_* */, const double *a, const double *b, int32_t n,
+                    const int32_t *spp_map /* NULL: uniform; sums form only */, const rt_frame_noise_params *params /* NULL: defaults */,
+                    double *out4);
+/* rth_write_pfm's counterpart: a colour PFM ("PF", either byte order by the scale's sign, the bottom row first) as 3 * w * h doubles,
+ * row 0 on top, each the file's f32 widened; the scale's magnitude is not applied.  out_rgb may be NULL to query the size; `capacity`
+ * is its room in doubles.  Every header number is bounded before it is multiplied: -1 (the reason in rth_last_error) for a width or
+ * height < 1, w * h >= 2^27, a scale that is zero, not finite or not a number, trailing characters in a header field, or a body shorter
+ * than the header announces.  Nothing beyond the file's bytes is read. */
+int rth_read_pfm(const char *path, int32_t *out_width, int32_t *out_height, double *out_rgb, int64_t capacity);
 /* RGB8 PNG writer (src/renderer.rs:59-72). */
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8);
 /* The film formats' files, each from a frame in its format (rt_amd.h "film output"), row 0 on top:

@@ -285,6 +285,32 @@ def tonemap_params(**kw) -> "TonemapParams":
     return _params(TonemapParams, "rt_tonemap_params_init_sized", "rt_tonemap_params", kw, convert={"op": _tonemap_op})
 
 
+RT_METRICS_SUMS, RT_METRICS_MEANS = 0, 1
+METRICS_FORMS = {"sums": RT_METRICS_SUMS, "means": RT_METRICS_MEANS}
+FRAME_ERROR_FIELDS = ("count", "mse", "rmse", "rel_mse", "mae", "bias", "max_abs", "psnr")
+FRAME_NOISE_FIELDS = ("count", "mean_var", "noise", "max_noise")
+
+
+class FrameErrorParams(C.Structure):
+    """rt_frame_error_params (rt_frame_error_device, rth_frame_error)."""
+    _fields_ = [("struct_size", C.c_uint32), ("_pad", C.c_int32), ("eps", C.c_double), ("peak", C.c_double)]
+
+
+def frame_error_params(**kw) -> "FrameErrorParams":
+    """rt_frame_error_params_init_sized, then the given fields (eps=, peak=)."""
+    return _params(FrameErrorParams, "rt_frame_error_params_init_sized", "rt_frame_error_params", kw)
+
+
+class FrameNoiseParams(C.Structure):
+    """rt_frame_noise_params (rt_frame_noise_device, rth_frame_noise)."""
+    _fields_ = [("struct_size", C.c_uint32), ("_pad", C.c_int32), ("eps", C.c_double)]
+
+
+def frame_noise_params(**kw) -> "FrameNoiseParams":
+    """rt_frame_noise_params_init_sized, then the given fields (eps=)."""
+    return _params(FrameNoiseParams, "rt_frame_noise_params_init_sized", "rt_frame_noise_params", kw)
+
+
 class BloomParams(C.Structure):
     """rt_bloom_params (rt_bloom_device, rth_bloom)."""
     _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_int32), ("threshold", C.c_double), ("strength", C.c_double)]
@@ -452,6 +478,13 @@ RT_AMD_SYMBOLS = {
     "rt_camera_cube_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rt_panorama_tables": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p]),
     "rt_panorama_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rt_frame_error_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_frame_noise_params_init_sized": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rt_metrics_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rt_frame_error_device": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "rt_frame_noise_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
 }
 
 # every symbol include/rt_amd_debug.h declares (test and tuning hooks; not part of the drop-in boundary)
@@ -807,6 +840,9 @@ RT_HOST_SYMBOLS = {
                                C.c_void_p]),
     "rth_robust": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rth_panorama": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "rth_frame_error": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rth_frame_noise": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rth_read_pfm": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64]),
     "rth_write_png": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rth_write_hdr": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
     "rth_write_pfm": (C.c_int, [C.c_char_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -1197,6 +1233,38 @@ class DeviceScene:
         cam = camera if camera is not None else self.host_scene.camera
         _check(amd_lib().rt_render_mean_moments_device(self._handle, C.byref(cam), C.byref(params), C.c_void_p(d_mean_ptr), C.c_void_p(d_m2_ptr),
                                                        C.c_void_p(d_rgba8_ptr or None), C.c_void_p(stream)), "rt_render_mean_moments_device")
+
+    def render_until(self, noise: float, *, max_spp: int, pass_spp: int = 1, min_samples: int = 16, seed: int = 1, camera: Camera | None = None,
+                     eps: "float | None" = None):
+        """Refines a running mean and M2 on the device in passes of `pass_spp` samples (the last one cut at max_spp), each a
+        render_mean_moments_device over the next sample range, and evaluates frame_noise_device (means form) after every pass.  Stops at
+        the first pass with samples >= min_samples and noise <= `noise`, or at max_spp.  Returns (mean, m2, samples, noise): the two
+        (h, w, 3) float64 frames — bit for bit render_mean_moments' over [0, samples) —, the sample count reached and the last pass's
+        noise.  `eps`: frame_noise_params' (None: its default)."""
+        import torch
+        if max_spp < 1 or pass_spp < 1:
+            raise RtError("render_until: max_spp and pass_spp must be at least 1")
+        cam = camera if camera is not None else self.host_scene.camera
+        h, w = cam.image_height, cam.image_width
+        np_params = frame_noise_params(**({} if eps is None else {"eps": eps}))
+        with torch.cuda.device(self.device):
+            d_mean = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda")
+            d_m2 = torch.zeros((h, w, 3), dtype=torch.float64, device="cuda")
+            d_out4 = torch.zeros(4, dtype=torch.float64, device="cuda")
+            d_ws = torch.empty(metrics_workspace_bytes(w, h), dtype=torch.uint8, device="cuda")
+            stream = torch.cuda.current_stream().cuda_stream
+            samples, level = 0, float("inf")
+            while samples < max_spp:
+                end = min(samples + pass_spp, max_spp)
+                self.render_mean_moments_device(render_params(seed=seed, sample_begin=samples, sample_end=end), d_mean.data_ptr(), d_m2.data_ptr(),
+                                                stream=stream, camera=cam)
+                samples = end
+                frame_noise_device(w, h, RT_METRICS_MEANS, d_mean.data_ptr(), d_m2.data_ptr(), samples, d_out4.data_ptr(), d_ws.data_ptr(),
+                                   params=np_params, stream=stream)
+                level = float(d_out4.cpu()[2])  # (the download waits for the pass and the reduction; this loop hands no frame to the host, so it is its only wait)
+                if samples >= min_samples and level <= noise:
+                    break
+            return d_mean.cpu().numpy(), d_m2.cpu().numpy(), samples, level
 
     def render_moments(self, params: RenderParams, camera: Camera | None = None, sum=None, sum_sq=None):
         """rt_render_moments: (sum, sum_sq), two (h, w, 3) float64 frames: the per-pixel sums rt_render gives and the in-order sums of
@@ -1744,6 +1812,103 @@ def log_average_luminance_host(values, spp, *, spp_map=None, delta=1e-4):
     return tuple(float(x) for x in out)
 
 
+# frame metrics (include/rt_amd.h "frame metrics")
+def _metrics_form(v):
+    if isinstance(v, str):
+        if v not in METRICS_FORMS:
+            raise RtError(f"frame_noise: no form {v!r} (sums, means)")
+        return METRICS_FORMS[v]
+    return int(v)
+
+
+def metrics_workspace_bytes(width, height) -> int:
+    return _workspace_bytes("rt_metrics_workspace_bytes", f"a {width}x{height} frame", width, height)
+
+
+def frame_error_device(width, height, d_values_ptr: int, spp: int, d_ref_ptr: int, ref_spp: int, d_out8_ptr: int, d_workspace_ptr: int, *,
+                       d_spp_ptr: int = 0, params: "FrameErrorParams | None" = None, stream: int = 0):
+    """rt_frame_error_device: count, mse, rmse, rel_mse, mae, bias, max_abs and psnr of a device frame (sums with `spp` or the device map
+    d_spp_ptr; means with spp = 1) against a reference frame (sums with ref_spp; means with 1) into eight device doubles, reduced in
+    `d_workspace_ptr` (metrics_workspace_bytes(w, h) device bytes).  Enqueued on `stream`."""
+    _check(amd_lib().rt_frame_error_device(width, height, C.c_void_p(d_values_ptr or None), spp, C.c_void_p(d_spp_ptr or None),
+                                           C.c_void_p(d_ref_ptr or None), ref_spp, C.byref(params) if params is not None else None,
+                                           C.c_void_p(d_out8_ptr or None), C.c_void_p(d_workspace_ptr or None), C.c_void_p(stream)),
+           "rt_frame_error_device")
+
+
+def frame_noise_device(width, height, form, d_a_ptr: int, d_b_ptr: int, n: int, d_out4_ptr: int, d_workspace_ptr: int, *, d_spp_ptr: int = 0,
+                       params: "FrameNoiseParams | None" = None, stream: int = 0):
+    """rt_frame_noise_device: count, mean_var, noise and max_noise of a device frame's moments — form "sums": sums and sums of squares with
+    the count `n` or the device map d_spp_ptr; "means": running means and M2 after n samples — into four device doubles, reduced in
+    `d_workspace_ptr` (metrics_workspace_bytes(w, h) device bytes).  Enqueued on `stream`."""
+    _check(amd_lib().rt_frame_noise_device(width, height, _metrics_form(form), C.c_void_p(d_a_ptr or None), C.c_void_p(d_b_ptr or None), n,
+                                           C.c_void_p(d_spp_ptr or None), C.byref(params) if params is not None else None,
+                                           C.c_void_p(d_out4_ptr or None), C.c_void_p(d_workspace_ptr or None), C.c_void_p(stream)),
+           "rt_frame_noise_device")
+
+
+def _metrics_frames(who, first, second, spp_map):
+    import numpy as np
+    first, spp_map, w, h = _tonemap_frame(who, first, spp_map)
+    second = np.ascontiguousarray(second, dtype=np.float64)
+    if second.shape != first.shape:
+        raise RtError(f"{who}: both frames must have shape {first.shape}")
+    return first, second, spp_map, w, h
+
+
+def frame_error(values, spp, ref, ref_spp, *, spp_map=None, device=0, **kw) -> dict:
+    """Uploads an (h, w, 3) frame as tonemap() takes it and a reference frame of the same shape (sums with ref_spp, or means with 1), runs
+    rt_frame_error_device with frame_error_params(**kw) and downloads the eight values as a dict (FRAME_ERROR_FIELDS; count an int)."""
+    values, ref, spp_map, w, h = _metrics_frames("frame_error", values, ref, spp_map)
+    params = frame_error_params(**kw)
+    out = _frame_end(device, [values, ref, spp_map], (8,), None, metrics_workspace_bytes(w, h),
+                     lambda d, out, ws, rgba, stream: frame_error_device(w, h, d[0], int(spp), d[1], int(ref_spp), out, ws, d_spp_ptr=d[2],
+                                                                         params=params, stream=stream))
+    return _metrics_dict(FRAME_ERROR_FIELDS, out)
+
+
+def frame_noise(a, b, n, *, form="sums", spp_map=None, device=0, **kw) -> dict:
+    """Uploads two (h, w, 3) frames of moments — form "sums": sums and sums of squares with the count n or an (h, w) int32 map; "means":
+    running means and M2 after n samples —, runs rt_frame_noise_device with frame_noise_params(**kw) and downloads the four values as a
+    dict (FRAME_NOISE_FIELDS; count an int)."""
+    a, b, spp_map, w, h = _metrics_frames("frame_noise", a, b, spp_map)
+    params, form = frame_noise_params(**kw), _metrics_form(form)
+    out = _frame_end(device, [a, b, spp_map], (4,), None, metrics_workspace_bytes(w, h),
+                     lambda d, out, ws, rgba, stream: frame_noise_device(w, h, form, d[0], d[1], int(n), out, ws, d_spp_ptr=d[2], params=params,
+                                                                         stream=stream))
+    return _metrics_dict(FRAME_NOISE_FIELDS, out)
+
+
+def _metrics_dict(fields, out):
+    d = {k: float(x) for k, x in zip(fields, out)}
+    d["count"] = int(d["count"])
+    return d
+
+
+def frame_error_host(values, spp, ref, ref_spp, *, spp_map=None, **kw) -> dict:
+    """rth_frame_error (librt_host, CPU): the eight values rt_frame_error_device gives, bit for bit."""
+    import numpy as np
+    values, ref, spp_map, w, h = _metrics_frames("frame_error_host", values, ref, spp_map)
+    params = frame_error_params(**kw)
+    out = np.zeros(8, dtype=np.float64)
+    if host_lib().rth_frame_error(w, h, values.ctypes.data, int(spp), spp_map.ctypes.data if spp_map is not None else None, ref.ctypes.data,
+                                  int(ref_spp), C.byref(params), out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return _metrics_dict(FRAME_ERROR_FIELDS, out)
+
+
+def frame_noise_host(a, b, n, *, form="sums", spp_map=None, **kw) -> dict:
+    """rth_frame_noise (librt_host, CPU): the four values rt_frame_noise_device gives, bit for bit."""
+    import numpy as np
+    a, b, spp_map, w, h = _metrics_frames("frame_noise_host", a, b, spp_map)
+    params = frame_noise_params(**kw)
+    out = np.zeros(4, dtype=np.float64)
+    if host_lib().rth_frame_noise(w, h, _metrics_form(form), a.ctypes.data, b.ctypes.data, int(n),
+                                  spp_map.ctypes.data if spp_map is not None else None, C.byref(params), out.ctypes.data) != 0:
+        raise RtError(host_lib().rth_last_error().decode(errors="replace"))
+    return _metrics_dict(FRAME_NOISE_FIELDS, out)
+
+
 # film output (include/rt_amd.h "film output"): the formats, and the (trailing shape, dtype) of a frame in each
 RT_FILM_RGBE, RT_FILM_F32, RT_FILM_RGB16 = 0, 1, 2
 _FILM_LAYOUT = {RT_FILM_RGBE: ((4,), "uint8"), RT_FILM_F32: ((3,), "float32"), RT_FILM_RGB16: ((3,), "uint16")}
@@ -1818,6 +1983,20 @@ def write_hdr(path, rgbe):
 def write_pfm(path, rgb_f32):
     """rth_write_pfm: an (h, w, 3) float32 frame ("f32") as a colour PFM."""
     _write_film("rth_write_pfm", path, rgb_f32, 3, "float32")
+
+
+def read_pfm(path):
+    """rth_read_pfm: a colour PFM of either byte order as an (h, w, 3) float64 frame, row 0 on top, each value the file's f32 widened;
+    an RtError for a file the reader refuses."""
+    import numpy as np
+    lib = host_lib()
+    w, h = C.c_int32(0), C.c_int32(0)
+    if lib.rth_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), None, 0) != 0:
+        raise RtError(lib.rth_last_error().decode(errors="replace"))
+    out = np.zeros((h.value, w.value, 3), dtype=np.float64)
+    if lib.rth_read_pfm(os.fsencode(path), C.byref(w), C.byref(h), out.ctypes.data, out.size) != 0:
+        raise RtError(lib.rth_last_error().decode(errors="replace"))
+    return out
 
 
 def write_png16(path, rgb16):

@@ -6,6 +6,7 @@
 #include "rt_bloom_shared.h"
 #include "rt_robust_shared.h"
 #include "rt_panorama_shared.h"
+#include "rt_metrics_shared.h"
 #include "rt_upsample_shared.h"
 
 #include <algorithm>
@@ -2007,6 +2008,41 @@ int rt_panorama_device(int32_t width, int32_t height, const double *d_tables, co
         return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_panorama_device: ") + bad);
     if (int rc = select_device_of(d_mean_out, "rt_panorama_device")) return rc;
     launch_panorama(width, height, d_tables, d_faces, face_size, guard, 1.0 / (double)spp, d_mean_out, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- frame metrics (rt_metrics.hip): a frame's error against a reference and its own noise estimate, each one tree reduction ----
+
+int rt_frame_error_params_init_sized(rt_frame_error_params *params, uint32_t struct_size) {
+    return params_init_sized<rt_frame_error_params>(params, struct_size, "rt_frame_error_params_init_sized", rtmt::error_size_known, rtmt::defaults);
+}
+
+int rt_frame_noise_params_init_sized(rt_frame_noise_params *params, uint32_t struct_size) {
+    return params_init_sized<rt_frame_noise_params>(params, struct_size, "rt_frame_noise_params_init_sized", rtmt::noise_size_known, rtmt::defaults);
+}
+
+int64_t rt_metrics_workspace_bytes(int32_t width, int32_t height) { return rtmt::workspace_bytes(width, height); }
+
+int rt_frame_error_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const double *d_ref, int32_t ref_spp,
+                          const rt_frame_error_params *params, double *d_out8, void *d_workspace, void *hip_stream) {
+    rt_frame_error_params p;
+    if (const char *bad = rtmt::bad_error_argument(true, width, height, d_values, spp, d_ref, ref_spp, params, d_out8, d_workspace, p))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_frame_error_device: ") + bad);
+    if (int rc = select_device_of(d_out8, "rt_frame_error_device")) return rc;
+    launch_frame_error((int64_t)width * height, d_values, 1.0 / (double)spp, d_spp, d_ref, 1.0 / (double)ref_spp, p.eps, p.peak, (double *)d_workspace,
+                       d_out8, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+int rt_frame_noise_device(int32_t width, int32_t height, int32_t form, const double *d_a, const double *d_b, int32_t n, const int32_t *d_spp,
+                          const rt_frame_noise_params *params, double *d_out4, void *d_workspace, void *hip_stream) {
+    rt_frame_noise_params p;
+    if (const char *bad = rtmt::bad_noise_argument(true, width, height, form, d_a, d_b, n, d_spp, params, d_out4, d_workspace, p))
+        return fail(RT_ERR_INVALID_ARGUMENT, std::string("rt_frame_noise_device: ") + bad);
+    if (int rc = select_device_of(d_out4, "rt_frame_noise_device")) return rc;
+    launch_frame_noise((int64_t)width * height, form == RT_METRICS_MEANS, d_a, d_b, n, d_spp, p.eps, (double *)d_workspace, d_out4, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }

@@ -309,6 +309,14 @@ void launch_upsample(const UpsampleArgs &u, bool lds, hipStream_t stream);
 // doubles of rt_panorama_tables, `faces` six frames of 3 F F doubles, face-major; `out` gets 3 w h means.
 void launch_panorama(int32_t w, int32_t h, const double *tables, const double *faces, int32_t face_size, int32_t guard, double inv_spp, double *out,
                      hipStream_t stream);
+// frame metrics (rt_metrics.hip; rt_frame_error_device, rt_frame_noise_device).  Each runs every level of the normative 256-tree over
+// the n_pixels entries that level 0 makes from the frames; `partials` has room for METRICS_ENTRY_DOUBLES 8-byte words per block of every
+// level, level 0's first (rt_metrics_workspace_bytes); the last level writes the eight (four) final values to out8 (out4).
+constexpr int METRICS_ENTRY_DOUBLES = 6; // a block's record: up to five accumulators and the count (a uint64) in the last word
+void launch_frame_error(int64_t n_pixels, const double *values, double inv_spp, const int32_t *spp_map, const double *ref, double inv_ref, double eps,
+                        double peak, double *partials, double *out8, hipStream_t stream);
+void launch_frame_noise(int64_t n_pixels, bool means, const double *first, const double *second, int32_t n, const int32_t *spp_map, double eps,
+                        double *partials, double *out4, hipStream_t stream);
 void launch_debug_box(int64_t n,const double *rays, const double *boxes, double tmin, double tmax, uint8_t *exact_hit, uint8_t *f32_hit);
 void launch_debug_quad(int64_t n, const double *rays, const Quad *quads, const QFiltPair *filt, double tmin, double tmax, uint8_t *exact_hit, uint8_t *keep);
 // the wide visit on n cases whose records are image rows 0 .. n - 1 (lds == 0: 256-byte records; else the seven tables, n * 32 bytes per plane table)

@@ -9,6 +9,7 @@
 #include "../csrc/rt_robust_shared.h"
 #include "../csrc/rt_upsample_shared.h"
 #include "../csrc/rt_panorama_shared.h"
+#include "../csrc/rt_metrics_shared.h"
 #include <cstring>
 #include <exception>
 #include <string>
@@ -357,6 +358,82 @@ int rth_panorama(int32_t width, int32_t height, const double *tables, const doub
         return fail(std::string("rth_panorama: ") + bad);
     rtpn::resample(width, height, tables, faces, face_size, guard, spp, out_mean);
     return 0;
+}
+
+// ---- frame metrics: the host mirrors of rt_frame_error_device and rt_frame_noise_device (include/rt_amd.h "frame metrics") ----
+
+extern "C++" {
+namespace {
+template <int A> struct MetricsEntry { double e[A]; uint32_t count; };
+
+// the normative reduction over records: 256 entries per block (the last one padded with the neutral entry), each block by the tree
+// `for stride = 128 .. 1: e[i] = e[i] (+) e[i + stride]`, the block results the next level's entries, until one is left
+template <int A, class Combine>
+MetricsEntry<A> reduce_metrics(std::vector<MetricsEntry<A>> entries, Combine combine) {
+    for (;;) {
+        const size_t blocks = (entries.size() + 255u) / 256u;
+        std::vector<MetricsEntry<A>> next(blocks);
+        for (size_t b = 0; b < blocks; ++b) {
+            MetricsEntry<A> e[256];
+            for (size_t i = 0; i < 256; ++i) e[i] = b * 256u + i < entries.size() ? entries[b * 256u + i] : MetricsEntry<A>{};
+            for (size_t stride = 128; stride >= 1; stride >>= 1)
+                for (size_t i = 0; i < stride; ++i) combine(e[i].e, &e[i].count, e[i + stride].e, e[i + stride].count);
+            next[b] = e[0];
+        }
+        if (blocks == 1) return next[0];
+        entries.swap(next);
+    }
+}
+} // namespace
+} // extern "C++"
+
+int rth_frame_error(int32_t width, int32_t height, const double *values, int32_t spp, const int32_t *spp_map, const double *ref, int32_t ref_spp,
+                    const rt_frame_error_params *params, double *out8) {
+    rt_frame_error_params p;
+    if (const char *bad = rtmt::bad_error_argument(false, width, height, values, spp, ref, ref_spp, params, out8, nullptr, p))
+        return fail(std::string("rth_frame_error: ") + bad);
+    const size_t n = (size_t)width * (size_t)height;
+    const double inv_ref = 1.0 / (double)ref_spp;
+    std::vector<MetricsEntry<rtm::RT_ERROR_ACCS>> terms(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double inv = 1.0 / (double)(spp_map ? spp_map[i] : spp);
+        const double m[3] = {values[3 * i] * inv, values[3 * i + 1] * inv, values[3 * i + 2] * inv};
+        const double r[3] = {ref[3 * i] * inv_ref, ref[3 * i + 1] * inv_ref, ref[3 * i + 2] * inv_ref};
+        rtm::rt_error_term(m, r, p.eps, terms[i].e, &terms[i].count);
+    }
+    const auto total = reduce_metrics<rtm::RT_ERROR_ACCS>(std::move(terms), rtm::rt_error_combine);
+    rtm::rt_error_result(total.e, total.count, p.peak, out8);
+    return 0;
+}
+
+int rth_frame_noise(int32_t width, int32_t height, int32_t form, const double *a, const double *b, int32_t n, const int32_t *spp_map,
+                    const rt_frame_noise_params *params, double *out4) {
+    rt_frame_noise_params p;
+    if (const char *bad = rtmt::bad_noise_argument(false, width, height, form, a, b, n, spp_map, params, out4, nullptr, p))
+        return fail(std::string("rth_frame_noise: ") + bad);
+    const size_t pixels = (size_t)width * (size_t)height;
+    std::vector<MetricsEntry<rtm::RT_NOISE_ACCS>> terms(pixels);
+    for (size_t i = 0; i < pixels; ++i)
+        rtm::rt_noise_term(form == RT_METRICS_MEANS, a + 3 * i, b + 3 * i, spp_map ? spp_map[i] : n, p.eps, terms[i].e, &terms[i].count);
+    const auto total = reduce_metrics<rtm::RT_NOISE_ACCS>(std::move(terms), rtm::rt_noise_combine);
+    rtm::rt_noise_result(total.e, total.count, out4);
+    return 0;
+}
+
+int rth_read_pfm(const char *path, int32_t *out_width, int32_t *out_height, double *out_rgb, int64_t capacity) {
+    if (!path || !out_width || !out_height) return fail("rth_read_pfm: null argument");
+    try {
+        std::vector<double> px;
+        const std::string bad = read_pfm_rgb(path, *out_width, *out_height, out_rgb ? &px : nullptr);
+        if (!bad.empty()) return fail("rth_read_pfm: " + bad);
+        if (out_rgb) {
+            if ((int64_t)px.size() > capacity) return fail("rth_read_pfm: buffer too small");
+            memcpy(out_rgb, px.data(), px.size() * sizeof(double));
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(std::string("rth_read_pfm: ") + e.what());
+    }
 }
 
 int rth_write_png(const char *path, int32_t width, int32_t height, const uint8_t *rgb8) {

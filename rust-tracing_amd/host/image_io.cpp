@@ -410,4 +410,88 @@ bool write_pfm_rgb(const std::string &path, int32_t width, int32_t height, const
     return write_file(path, out);
 }
 
+// ---- the PFM reader: a file a user hands in, so every header number is bounded before anything is multiplied or allocated ----
+namespace {
+bool pfm_space(uint8_t c) { return c == ' ' || c == '\n' || c == '\t' || c == '\r'; }
+// a decimal number of 1..9 digits at `at` (so it fits an int32 whatever the digits are); false: none, or a longer one
+bool pfm_number(const uint8_t *data, size_t size, size_t &at, int32_t &out) {
+    int64_t v = 0;
+    size_t digits = 0;
+    while (at < size && data[at] >= '0' && data[at] <= '9') {
+        if (++digits > 9) return false;
+        v = v * 10 + (data[at++] - '0');
+    }
+    out = (int32_t)v;
+    return digits > 0;
+}
+// one or more white-space characters at `at`
+bool pfm_gap(const uint8_t *data, size_t size, size_t &at) {
+    const size_t from = at;
+    while (at < size && pfm_space(data[at])) ++at;
+    return at > from;
+}
+} // namespace
+
+std::string parse_pfm_rgb(const uint8_t *data, size_t size, int32_t &width, int32_t &height, std::vector<double> *out) {
+    width = height = 0;
+    if (!data || size < 2 || data[0] != 'P' || data[1] != 'F') return "not a colour PFM (no \"PF\" magic)";
+    size_t at = 2;
+    int32_t w = 0, h = 0;
+    if (!pfm_gap(data, size, at) || !pfm_number(data, size, at, w) || !pfm_gap(data, size, at) || !pfm_number(data, size, at, h) || !pfm_gap(data, size, at))
+        return "malformed PFM header (\"PF\", width, height and scale, separated by white space)";
+    if (w < 1 || h < 1) return "PFM width and height must be at least 1";
+    if ((int64_t)w * h >= PFM_MAX_PIXELS) return "PFM width x height must be below 2^27 pixels";
+    // the scale: one token of at most 31 characters that must parse as a number to its end, then exactly one white-space character
+    char token[32];
+    size_t len = 0;
+    while (at < size && !pfm_space(data[at])) {
+        if (len + 1 >= sizeof token) return "malformed PFM header (the scale is too long)";
+        token[len++] = (char)data[at++];
+    }
+    token[len] = 0;
+    char *end = nullptr;
+    const double scale = len ? strtod(token, &end) : 0.0;
+    if (len == 0 || end != token + len) return "malformed PFM header (the scale is not a number)";
+    if (!(scale == scale) || scale == 0.0 || scale - scale != 0.0) return "PFM scale must be a finite number other than 0";
+    if (at >= size || !pfm_space(data[at])) return "malformed PFM header (no white space behind the scale)";
+    ++at;
+    const size_t values = (size_t)w * (size_t)h * 3u; // < 2^27 * 3
+    if ((size - at) / 4u < values) return "PFM body is shorter than width x height x 3 floats";
+    width = w;
+    height = h;
+    if (!out) return "";
+    out->resize(values);
+    const bool little = scale < 0.0;
+    const size_t row = (size_t)w * 3u;
+    for (int32_t y = 0; y < h; ++y) { // the file's first row is the bottom one
+        const uint8_t *src = data + at + (size_t)(h - 1 - y) * row * 4u;
+        for (size_t x = 0; x < row; ++x) {
+            const uint8_t *b = src + x * 4u;
+            const uint32_t bits = little ? (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24)
+                                         : (uint32_t)b[3] | ((uint32_t)b[2] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[0] << 24);
+            float f;
+            memcpy(&f, &bits, 4);
+            (*out)[(size_t)y * row + x] = (double)f;
+        }
+    }
+    return "";
+}
+
+std::string read_pfm_rgb(const std::string &path, int32_t &width, int32_t &height, std::vector<double> *out) {
+    width = height = 0;
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return "cannot open " + path;
+    // the file as it is, in pieces: its own length bounds the memory, never a number from its header
+    const size_t cap = (size_t)PFM_MAX_PIXELS * 12u + 256u;
+    std::vector<uint8_t> bytes;
+    uint8_t piece[65536];
+    size_t n;
+    while ((n = fread(piece, 1, sizeof piece, f)) > 0) {
+        if (bytes.size() + n > cap) { fclose(f); return "PFM file is larger than any frame this library takes"; }
+        bytes.insert(bytes.end(), piece, piece + n);
+    }
+    fclose(f);
+    return parse_pfm_rgb(bytes.data(), bytes.size(), width, height, out);
+}
+
 } // namespace rt

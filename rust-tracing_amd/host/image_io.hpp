@@ -37,4 +37,14 @@ bool write_png_rgb16(const std::string &path, int32_t width, int32_t height, con
 bool write_hdr_rgbe(const std::string &path, int32_t width, int32_t height, const uint8_t *rgbe);
 bool write_pfm_rgb(const std::string &path, int32_t width, int32_t height, const float *rgb);
 
+// write_pfm_rgb's counterpart, for a reference frame a user hands in (include/rt_amd.h "frame metrics"): a colour PFM ("PF", width,
+// height and scale separated by white space, exactly one white-space character behind the scale, then rows of RGB f32, the bottom row
+// first; a negative scale means little-endian, a positive one big-endian; its magnitude is not applied).  `out`, if not null, receives
+// 3 * w * h doubles, row 0 on top, each the file's f32 widened.  Every header number is bounded before it is multiplied: refused are a
+// width or height < 1 or of more than nine digits, width x height >= 2^27, a scale that is zero, not finite or not a number to its last
+// character, and a body shorter than the header announces; nothing beyond `size` is read.  Returns "" or the reason.
+constexpr int64_t PFM_MAX_PIXELS = (int64_t)1 << 27;
+std::string parse_pfm_rgb(const uint8_t *data, size_t size, int32_t &width, int32_t &height, std::vector<double> *out);
+std::string read_pfm_rgb(const std::string &path, int32_t &width, int32_t &height, std::vector<double> *out);
+
 } // namespace rt

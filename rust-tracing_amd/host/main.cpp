@@ -35,6 +35,8 @@
 //   width and height, F = 2..4, and brought to full size under the full-size albedo and surface-ID frames asked for; the --denoise
 //   and --live-denoise families then filter the small frame, and bloom and the tone mapping run on the full-size one; --live renders the
 //   guide frames once per session).
+//   --compare REF.pfm [--compare-eps E] (frame metrics of include/rt_amd.h: the frame the output stage is about to read, against a PFM of
+//   its size; one line `metrics: ...`), -l --live-stop X [--live-stop-min N] (the live loop ends once the frame's noise is at most X),
 //   --robust K [--robust-mode mean|trim|median|gini] [--robust-trim T] [--robust-gain X] (robust frames of include/rt_amd.h: K sub-frames
 //   of spp / K samples under seeds seed + k in one views launch, combined by the median of means; --denoise filters the result with
 //   samples = K, --bloom and --tonemap run behind it).
@@ -95,6 +97,12 @@ static void usage(const char *argv0) {
             "                         mapping, the light of the pixels whose luminance is above T, default 1, is blurred over K = 1..8 levels,\n"
             "                         default 5 (a glow of radius 2 * (2^K - 1) pixels), and added back STRENGTH >= 0 times, default 0.25; alone it\n"
             "                         implies --tonemap clamp; --orbit blooms each view on its own)\n"
+            "          [--compare REF.pfm [--compare-eps E]]   (one GPU, one pass; not with -l, --orbit or --progressive: the frame's means, behind\n"
+            "                         the filters and in front of bloom and the tone mapping, against the PFM of the same size; prints one line\n"
+            "                         metrics: count= mse= rmse= relmse= mae= bias= max= psnr=)\n"
+            "          [--live-stop X [--live-stop-min N]]   (with -l/--live: the noise of the running mean, the RMS relative standard error of the\n"
+            "                         pixel means, after every pass; the loop ends at the first pass with at least N samples, default 16, whose\n"
+            "                         noise is at most X, and prints live-stop: samples= noise=)\n"
             "          [--upsample F [--upsample-albedo] [--upsample-edges]]   (one GPU; a plain render, the --denoise family or --live: the frame is\n"
             "                         traced at 1/F of the width and height, F = 2, 3 or 4 — 1/F^2 of the paths — and brought to full size by a\n"
             "                         joint bilateral upsampler; --upsample-albedo multiplies the full-size first-hit albedo frame back in,\n"
@@ -124,7 +132,7 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     int scene = 0;
-    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false, robust_knob_given = false, panorama_knob_given = false;
+    bool live = false, output_given = false, live_spp_given = false, denoise_knob_given = false, albedo_knob_given = false, spatial_knob_given = false, edges_knob_given = false, tonemap_given = false, white_given = false, bloom_knob_given = false, robust_knob_given = false, panorama_knob_given = false, compare_eps_given = false, live_stop_min_given = false;
     std::string output = "output";
     SceneOptions so;
     so.earth_image = "assets/earth-large.jpg"; // the reference's default (src/main.rs:179,:591); --earth synthetic:WxH needs no file
@@ -313,6 +321,24 @@ int main(int argc, char **argv) {
             if (!ok) { fprintf(stderr, "--panorama-at needs a point x,y,z\n"); usage(argv[0]); return 2; }
             ro.panorama_at_given = true;
         }
+        else if (a == "--compare") ro.compare_file = need("--compare");
+        else if (a == "--compare-eps") {
+            char *end = nullptr;
+            const char *v = need("--compare-eps");
+            ro.compare_eps = strtod(v, &end);
+            compare_eps_given = true;
+            if (end == v || *end != 0 || !(ro.compare_eps > 0.0) || !(ro.compare_eps < 1e300)) { fprintf(stderr, "--compare-eps needs a number above 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--live-stop") {
+            char *end = nullptr;
+            const char *v = need("--live-stop");
+            ro.live_stop_noise = strtod(v, &end);
+            if (end == v || *end != 0 || !(ro.live_stop_noise >= 0.0)) { fprintf(stderr, "--live-stop needs a noise threshold of at least 0\n"); usage(argv[0]); return 2; }
+        }
+        else if (a == "--live-stop-min") {
+            ro.live_stop_min_samples = atoi(need("--live-stop-min")); live_stop_min_given = true;
+            if (ro.live_stop_min_samples < 1) { fprintf(stderr, "--live-stop-min needs a number of samples of at least 1\n"); usage(argv[0]); return 2; }
+        }
         else if (a == "--upsample-albedo") ro.upsample_albedo = true;
         else if (a == "--upsample-edges") ro.upsample_edges = true;
         else if (a == "--earth") so.earth_image = need("--earth");
@@ -448,6 +474,23 @@ int main(int argc, char **argv) {
         return 2;
     }
     if ((tonemap_given || ro.bloom >= 0.0) && ro.tonemap < 0) ro.tonemap = RT_TONEMAP_CLAMP; // an exposure or bloom alone: the stage with the plain clamp
+    if (!ro.compare_file.empty() && (live || ro.orbit > 0 || ro.progressive_spp > 0 || ro.gpus > 1)) {
+        const char *with = live ? "-l/--live" : ro.orbit > 0 ? "--orbit" : ro.progressive_spp > 0 ? "--progressive" : "--gpus > 1";
+        fprintf(stderr, "--compare measures the one frame of a one-GPU, one-pass route against a reference: it cannot be combined with %s\n", with);
+        return 2;
+    }
+    if (compare_eps_given && ro.compare_file.empty()) {
+        fprintf(stderr, "--compare-eps sets the relative error's eps of --compare: it needs --compare\n");
+        return 2;
+    }
+    if (ro.live_stop_noise >= 0.0 && !live) {
+        fprintf(stderr, "--live-stop ends the passes of --live: it needs -l/--live\n");
+        return 2;
+    }
+    if (live_stop_min_given && ro.live_stop_noise < 0.0) {
+        fprintf(stderr, "--live-stop-min sets the fewest samples of --live-stop: it needs --live-stop\n");
+        return 2;
+    }
     if (live_spp_given && !live) {
         fprintf(stderr, "--live-spp sets the samples per frame of --live: it needs -l/--live\n");
         return 2;

@@ -256,6 +256,85 @@ static std::vector<uint8_t> staged_device(int32_t width, int32_t height, const d
     return px;
 }
 
+// Frame metrics (include/rt_amd.h "frame metrics") on device 0: the output and the workspace are allocated here, the call is waited for
+// (the download of its doubles) and both are freed behind it.
+void frame_error_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const double *d_ref, int32_t ref_spp,
+                        double eps, double out8[8]) {
+    rt_frame_error_params ep;
+    if (rt_frame_error_params_init_sized(&ep, sizeof ep) != RT_OK) throw std::runtime_error(std::string("frame_error: ") + rt_last_error());
+    if (eps > 0.0) ep.eps = eps;
+    const int64_t work = rt_metrics_workspace_bytes(width, height);
+    if (work < 0) throw std::runtime_error("frame_error: no workspace for a frame of this size");
+    void *d_out = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_out); rt_device_free(0, d_work); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("frame_error: " + msg); } };
+    check(rt_device_malloc(0, 8 * (int64_t)sizeof(double), &d_out));
+    check(rt_device_malloc(0, work, &d_work));
+    check(rt_frame_error_device(width, height, d_values, spp, d_spp, d_ref, ref_spp, &ep, static_cast<double *>(d_out), d_work, nullptr));
+    check(rt_device_download(0, out8, d_out, 8 * (int64_t)sizeof(double), nullptr));
+    cleanup();
+}
+
+void frame_noise_device(int32_t width, int32_t height, int32_t form, const double *d_a, const double *d_b, int32_t n, const int32_t *d_spp, double eps,
+                        double out4[4]) {
+    rt_frame_noise_params np;
+    if (rt_frame_noise_params_init_sized(&np, sizeof np) != RT_OK) throw std::runtime_error(std::string("frame_noise: ") + rt_last_error());
+    if (eps > 0.0) np.eps = eps;
+    const int64_t work = rt_metrics_workspace_bytes(width, height);
+    if (work < 0) throw std::runtime_error("frame_noise: no workspace for a frame of this size");
+    void *d_out = nullptr, *d_work = nullptr;
+    auto cleanup = [&]() { rt_device_free(0, d_out); rt_device_free(0, d_work); };
+    auto check = [&](int rc) { if (rc != RT_OK) { const std::string msg = rt_last_error(); cleanup(); throw std::runtime_error("frame_noise: " + msg); } };
+    check(rt_device_malloc(0, 4 * (int64_t)sizeof(double), &d_out));
+    check(rt_device_malloc(0, work, &d_work));
+    check(rt_frame_noise_device(width, height, form, d_a, d_b, n, d_spp, &np, static_cast<double *>(d_out), d_work, nullptr));
+    check(rt_device_download(0, out4, d_out, 4 * (int64_t)sizeof(double), nullptr));
+    cleanup();
+}
+
+// opt.compare_file: the reference frame (means) of a w x h route, and the one line render() prints of a frame's eight values
+static bool compared(const RenderOptions &opt) { return !opt.compare_file.empty(); }
+static std::vector<double> compare_reference(int32_t width, int32_t height, const RenderOptions &opt) {
+    int32_t rw = 0, rh = 0;
+    std::vector<double> ref;
+    const std::string bad = read_pfm_rgb(opt.compare_file, rw, rh, &ref);
+    if (!bad.empty()) throw std::runtime_error("render: compare_file: " + bad);
+    if (rw != width || rh != height)
+        throw std::runtime_error("render: compare_file holds a " + std::to_string(rw) + " x " + std::to_string(rh) + " frame, the render a " +
+                                 std::to_string(width) + " x " + std::to_string(height) + " one");
+    return ref;
+}
+static void print_metrics(const double m[8]) {
+    printf("metrics: count=%.17g mse=%.17g rmse=%.17g relmse=%.17g mae=%.17g bias=%.17g max=%.17g psnr=%.17g\n", m[0], m[1], m[2], m[3], m[4], m[5], m[6],
+           m[7]);
+}
+// the values a route's output stage is about to read, against the reference: a HOST frame of sums through the mirror ...
+static void compare_host(const std::vector<double> &sums, int32_t width, int32_t height, int32_t spp, const RenderOptions &opt) {
+    if (!compared(opt)) return;
+    const std::vector<double> ref = compare_reference(width, height, opt);
+    rt_frame_error_params ep;
+    if (rt_frame_error_params_init_sized(&ep, sizeof ep) != RT_OK) throw std::runtime_error(std::string("render: ") + rt_last_error());
+    if (opt.compare_eps > 0.0) ep.eps = opt.compare_eps;
+    double m[8];
+    if (rth_frame_error(width, height, sums.data(), spp, nullptr, ref.data(), 1, &ep, m) != 0) throw std::runtime_error(std::string("render: ") + rth_last_error());
+    print_metrics(m);
+}
+// ... and a DEVICE frame (sums with spp or a device map; means with spp = 1) through rt_frame_error_device
+static void compare_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const RenderOptions &opt) {
+    if (!compared(opt)) return;
+    const std::vector<double> ref = compare_reference(width, height, opt);
+    const int64_t bytes = (int64_t)ref.size() * (int64_t)sizeof(double);
+    void *d_ref = nullptr;
+    if (rt_device_malloc(0, bytes, &d_ref) != RT_OK) throw std::runtime_error(std::string("render: ") + rt_last_error());
+    double m[8];
+    try {
+        if (rt_device_upload(0, d_ref, ref.data(), bytes, nullptr) != RT_OK) throw std::runtime_error(std::string("render: ") + rt_last_error());
+        frame_error_device(width, height, d_values, spp, d_spp, static_cast<const double *>(d_ref), 1, opt.compare_eps, m);
+    } catch (...) { rt_device_free(0, d_ref); throw; }
+    rt_device_free(0, d_ref);
+    print_metrics(m);
+}
+
 // The frame's file: NAME.png from RGB bytes, or with a film format NAME.hdr / NAME.pfm / NAME.png from the bytes the staging made in it.
 static void write_frame(const std::string &name, int32_t width, int32_t height, const std::vector<uint8_t> &px, const RenderOptions &opt) {
     const int64_t want = filmed(opt) ? rt_film_bytes(width, height, film_format(opt)) : (int64_t)width * height * 3;
@@ -416,6 +495,10 @@ static std::vector<uint8_t> run_denoise(const char *who, const DenoiseRequest &r
     if (!tonemapped(opt)) check(rt_device_malloc(0, n_pix * 4, &d_rgba8));
     check(rt_device_malloc(0, work, &d_work));
     check(denoise_into(r, opt, static_cast<double *>(d_mean), static_cast<uint8_t *>(d_rgba8), d_work));
+    if (compared(opt) && n_frames == 1) { // the filtered means, what the output stage reads
+        try { compare_device(width, height, static_cast<const double *>(d_mean), 1, nullptr, opt); }
+        catch (...) { cleanup(); throw; }
+    }
     if (tonemapped(opt)) {
         std::vector<uint8_t> rgb;
         try {
@@ -584,6 +667,7 @@ static std::vector<uint8_t> render_upsampled_rgb8(const Camera &camera, const Hi
     std::vector<uint8_t> px;
     try {
         upsample_device(w, h, d_low, low_spp, static_cast<const double *>(d_alb), spp, static_cast<const double *>(d_ids), spp, static_cast<double *>(d_out), opt);
+        compare_device(w, h, static_cast<const double *>(d_out), 1, nullptr, opt);
         if (tonemapped(opt)) {
             px = staged_device(w, h, static_cast<const double *>(d_out), 1, nullptr, false, opt);
         } else {
@@ -674,6 +758,7 @@ static std::vector<uint8_t> render_robust_rgb8(const Camera &camera, const Hitta
     std::vector<uint8_t> px;
     try {
         robust_device(w, h, K, static_cast<const double *>(d_stack), p.sample_end, static_cast<double *>(d_mean), static_cast<double *>(d_m2), opt);
+        if (!opt.denoise) compare_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, opt); // (filtered: behind the filter, in denoise_mean)
         if (opt.denoise) px = denoise_mean(w, h, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), K, opt);
         else if (tonemapped(opt)) px = staged_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, false, opt);
     } catch (...) { cleanup(); throw; }
@@ -736,6 +821,7 @@ static std::vector<uint8_t> render_panorama_rgb8(const Camera &camera, const Hit
     std::vector<uint8_t> px;
     try {
         panorama_device(w, h, static_cast<const double *>(d_faces), F, g, p.sample_end, static_cast<double *>(d_mean));
+        compare_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, opt);
         if (tonemapped(opt)) px = staged_device(w, h, static_cast<const double *>(d_mean), 1, nullptr, false, opt);
     } catch (...) { cleanup(); throw; }
     if (px.empty()) {
@@ -795,9 +881,13 @@ static std::vector<uint8_t> render_adaptive_rgb8(const Camera &camera, const Hit
                                static_cast<const int32_t *>(d_spp), opt);
         } catch (...) { cleanup(); throw; }
     } else if (tonemapped(opt)) { // each pixel's own spp is its n, through the map
+        try { compare_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), opt); }
+        catch (...) { cleanup(); throw; }
         try { px = staged_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), false, opt); }
         catch (...) { cleanup(); throw; }
     } else {
+        try { compare_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), 1, static_cast<const int32_t *>(d_spp), opt); }
+        catch (...) { cleanup(); throw; }
         check(rt_resolve_rgb8_spp_device(cam.image_width, cam.image_height, static_cast<const double *>(d_sum), static_cast<const int32_t *>(d_spp),
                                          static_cast<uint8_t *>(d_rgb8), nullptr));
         check(rt_device_download(0, px.data(), d_rgb8, n_pix * 3, nullptr));
@@ -851,13 +941,18 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const bool denoised = opt.live_denoise || opt.live_denoise_albedo || edges, guided = opt.live_denoise_albedo;
     if (opt.panorama_width != 0) throw std::runtime_error("live_render: panorama_width resamples the cube faces of one render() call: it cannot be combined with the live route");
     if (opt.robust_blocks != 0) throw std::runtime_error("live_render: robust_blocks combines the sub-frames of one render() call: it cannot be combined with the live route");
+    if (compared(opt)) throw std::runtime_error("live_render: compare_file measures the one frame of a render() call: it cannot be combined with the live route");
+    // opt.live_stop_noise >= 0: every pass keeps M2 (the moments route, whatever is shown), and the noise of (d_mean, d_m2) is reduced
+    // behind it into d_noise, four doubles that lie 8-byte aligned BEHIND the display bytes in d_rgba8's allocation
+    const bool stopping = opt.live_stop_noise >= 0.0;
+    if (opt.live_stop_noise != opt.live_stop_noise) throw std::runtime_error("live_render: live_stop_noise must be a number");
     if (edges && opt.upsample > 0) throw std::runtime_error("live_render: live_denoise_edges cannot be combined with upsample (the guide would have to be made at the low size)");
     const int32_t w = cam.image_width, h = cam.image_height;
     rt_scene *scene = nullptr, *albedo_scene = nullptr;
     void *d_mean = nullptr, *d_rgba8 = nullptr, *d_m2 = nullptr, *d_alb = nullptr, *d_shown = nullptr, *d_work = nullptr;
-    void *d_up_alb = nullptr, *d_up_ids = nullptr, *d_full = nullptr, *d_up_work = nullptr, *d_ids = nullptr;
+    void *d_up_alb = nullptr, *d_up_ids = nullptr, *d_full = nullptr, *d_up_work = nullptr, *d_ids = nullptr, *d_noise_work = nullptr;
     auto cleanup = [&]() {
-        rt_device_free(0, d_ids); rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
+        rt_device_free(0, d_noise_work); rt_device_free(0, d_ids); rt_device_free(0, d_mean); rt_device_free(0, d_rgba8); rt_device_free(0, d_m2); rt_device_free(0, d_alb); rt_device_free(0, d_shown);
         rt_device_free(0, d_work); rt_device_free(0, d_up_alb); rt_device_free(0, d_up_ids); rt_device_free(0, d_full); rt_device_free(0, d_up_work);
         rt_scene_destroy(scene); rt_scene_destroy(albedo_scene);
     };
@@ -865,7 +960,19 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
     const int64_t frame_bytes = n_pix * 3 * (int64_t)sizeof(double);
     check(rt_scene_create(&desc, 0, &scene));
     check(rt_device_malloc(0, frame_bytes, &d_mean));
-    check(rt_device_malloc(0, n_shown * 4, &d_rgba8));
+    const int64_t shown_bytes = n_shown * 4, noise_at = (shown_bytes + 7) / 8 * 8; // the four doubles' place behind the bytes
+    check(rt_device_malloc(0, stopping ? noise_at + 4 * (int64_t)sizeof(double) : shown_bytes, &d_rgba8));
+    double *const d_noise = stopping ? reinterpret_cast<double *>(static_cast<uint8_t *>(d_rgba8) + noise_at) : nullptr;
+    std::vector<uint8_t> handed; // the pass's one download where the bytes and the doubles come back together
+    rt_frame_noise_params noise_params;
+    if (stopping) {
+        const int64_t noise_work = rt_metrics_workspace_bytes(w, h);
+        if (noise_work < 0) { cleanup(); throw std::runtime_error("live_render: no metrics workspace for a frame of this size"); }
+        check(rt_frame_noise_params_init_sized(&noise_params, sizeof noise_params));
+        check(rt_device_malloc(0, noise_work, &d_noise_work));
+        if (!denoised) check(rt_device_malloc(0, frame_bytes, &d_m2));
+        handed.resize((size_t)noise_at + 4u * sizeof(double));
+    }
     rt_upsample_params up{};
     const int32_t guide_spp = last < LIVE_UPSAMPLE_GUIDE_SPP ? last : LIVE_UPSAMPLE_GUIDE_SPP;
     if (upsampled) {
@@ -905,7 +1012,9 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
         rt_render_params p{};
         p.seed = opt.seed; p.sample_begin = begin; p.sample_end = end; p.max_depth = cam.max_depth;
         p.shard_count = 1; p.out_layout = RT_OUT_FRAME;
-        if (!denoised) {
+        if (!denoised && stopping) { // the moments route: the same mean and the same bytes, with M2 beside them
+            check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), d_bytes, nullptr));
+        } else if (!denoised) {
             check(rt_render_mean_device(scene, &cam, &p, static_cast<double *>(d_mean), d_bytes, nullptr));
         } else {
             check(rt_render_mean_moments_device(scene, &cam, &p, static_cast<double *>(d_mean), static_cast<double *>(d_m2), nullptr, nullptr));
@@ -919,19 +1028,37 @@ std::vector<uint8_t> live_render(const Camera &camera, const Hittable &world, co
                                      &up, static_cast<double *>(d_full), tonemapped(opt) ? nullptr : static_cast<uint8_t *>(d_rgba8), d_up_work, nullptr));
             d_means = static_cast<const double *>(d_full);
         }
+        // the noise of the running frames, enqueued in front of the frame's hand-off: that hand-off's wait covers it
+        if (stopping)
+            check(rt_frame_noise_device(w, h, RT_METRICS_MEANS, static_cast<const double *>(d_mean), static_cast<const double *>(d_m2), end, nullptr, &noise_params,
+                                        d_noise, d_noise_work, nullptr));
+        double noise4[4] = {0.0, 0.0, 0.0, 0.0};
         if (tonemapped(opt)) {
             try { frame = staged_device(fw, fh, d_means, 1, nullptr, true, opt); }
             catch (...) { cleanup(); throw; }
+            // (the stage has its own output buffer and has waited for the stream: the doubles are ready, this copy waits for nothing)
+            if (stopping) check(rt_device_download(0, noise4, d_noise, (int64_t)sizeof noise4, nullptr));
+        } else if (stopping) { // one download: the bytes, and the four doubles behind them
+            check(rt_device_download(0, handed.data(), d_rgba8, (int64_t)handed.size(), nullptr));
+            memcpy(frame.data(), handed.data(), (size_t)shown_bytes);
+            memcpy(noise4, handed.data() + noise_at, sizeof noise4);
         } else {
             check(rt_device_download(0, frame.data(), d_rgba8, n_shown * 4, nullptr));
         }
         if (on_frame) {
             try { on_frame(frame, end); } catch (...) { cleanup(); throw; }
         }
-        if (end == last && final_film && filmed(asked)) { // the frame just shown, in the film format: bloom and the stage on the same means
+        bool stopped = false;
+        if (stopping) {
+            if (!opt.quiet) printf("live-stop-pass: samples=%d noise=%.17g\n", end, noise4[2]);
+            stopped = end >= opt.live_stop_min_samples && noise4[2] <= opt.live_stop_noise;
+            if (stopped || end == last) printf("live-stop: samples=%d noise=%.17g\n", end, noise4[2]);
+        }
+        if ((end == last || stopped) && final_film && filmed(asked)) { // the frame just shown, in the film format: bloom and the stage on the same means
             try { *final_film = staged_device(fw, fh, d_means, 1, nullptr, false, asked); }
             catch (...) { cleanup(); throw; }
         }
+        if (stopped) break;
     }
     cleanup();
     return frame;
@@ -1053,6 +1180,10 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     if (filmed(opt) && (opt.gpus > 1 || opt.progressive_spp > 0))
         throw std::runtime_error("render: a format other than png is written by the film stage of a one-GPU, one-pass route: it cannot be combined with "
                                  "gpus > 1 or progressive_spp (the gather and the passes carry 8-bit frames)");
+    if (compared(opt) && (opt.orbit > 0 || opt.gpus > 1 || opt.progressive_spp > 0))
+        throw std::runtime_error("render: compare_file measures the one frame of a one-GPU, one-pass route: it cannot be combined with orbit, gpus > 1 or "
+                                 "progressive_spp");
+    if (compared(opt) && !(opt.compare_eps >= 0.0 && opt.compare_eps < 1e300)) throw std::runtime_error("render: compare_eps must be a finite number >= 0 (0: the default)");
     if (opt.upsample != 0 && (opt.upsample < 2 || opt.upsample > 4)) throw std::runtime_error("render: upsample must be 0 (off), 2, 3 or 4");
     if (opt.upsample > 0 && (opt.orbit > 0 || opt.adaptive || opt.gpus > 1 || opt.progressive_spp > 0))
         throw std::runtime_error("render: upsample is a one-GPU, one-pass route: it cannot be combined with orbit, adaptive, gpus > 1 or progressive_spp");
@@ -1111,6 +1242,7 @@ void render(std::shared_ptr<Camera> camera, std::shared_ptr<Hittable> world, con
     }
 
     now = clock::now();
+    compare_host(sums, w, h, camera->samples_per_pixel, opt);
     const std::vector<uint8_t> px = tonemapped(opt) ? staged_rgb8(sums, w, h, camera->samples_per_pixel, opt) : resolve_rgb8(sums, camera->samples_per_pixel);
     write_frame(output_file_name, w, h, px, opt);
     if (!opt.quiet)

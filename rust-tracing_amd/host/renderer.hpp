@@ -134,7 +134,36 @@ struct RenderOptions {
     int panorama_guard = 1;
     bool panorama_at_given = false;
     double panorama_at[3] = {0.0, 0.0, 0.0};
+    // frame metrics (include/rt_amd.h "frame metrics"): compare_file names a colour PFM of the frame's size, a frame of means.  On every
+    // single-GPU, one-pass route that ends in one frame of sums or means — plain, adaptive, the denoise family, upsample, robust,
+    // panorama — render() measures the values the output stage is about to read (behind the filter, the combiner, the upsampler or the
+    // resampler; in front of bloom and the tone mapping) against it with rt_frame_error_device (a plain render, whose sums are on the
+    // host: its mirror rth_frame_error, the same bits) and prints one line,
+    //     metrics: count=… mse=… rmse=… relmse=… mae=… bias=… max=… psnr=…        (every double as %.17g)
+    // compare_eps is the call's eps; <= 0: the library's default.  It throws on a file the reader refuses and on a size mismatch.  Not
+    // with orbit, progressive_spp or gpus > 1 (render() throws), nor live_render (it throws).
+    std::string compare_file;
+    double compare_eps = 0.0;
+    // live_render: live_stop_noise >= 0 evaluates rt_frame_noise_device (means form) on the running mean and M2 after every pass and ends
+    // the loop at the first pass with samples >= live_stop_min_samples and noise <= live_stop_noise (or, as without it, at spp - 1
+    // samples).  The loop takes the moments route if it is not on it already (rt_render_mean_moments_device writes the same mean and
+    // bytes), so the frames shown before the stop are those of the same run without it.  Where the pass itself writes the display bytes,
+    // the four doubles lie behind them in one buffer and come back in the frame's own download; one line per pass (unless quiet),
+    //     live-stop-pass: samples=… noise=…
+    // and a final  live-stop: samples=… noise=…  (%.17g) are printed.  < 0: off.
+    double live_stop_noise = -1.0;
+    int live_stop_min_samples = 16;
 };
+
+// rt_frame_error_device on device 0 over DEVICE frames: d_values (sums with spp or, if d_spp is not null, a device map; means with
+// spp = 1) against d_ref (sums with ref_spp; means with 1); eps <= 0: the library's default.  Allocates the workspace and the output,
+// waits, and writes count, mse, rmse, rel_mse, mae, bias, max_abs, psnr to out8.  frame_noise_device: rt_frame_noise_device likewise
+// (form RT_METRICS_*; d_a, d_b the moments, n their count) into out4: count, mean_var, noise, max_noise.  Both throw std::runtime_error
+// on a library error.
+void frame_error_device(int32_t width, int32_t height, const double *d_values, int32_t spp, const int32_t *d_spp, const double *d_ref, int32_t ref_spp,
+                        double eps, double out8[8]);
+void frame_noise_device(int32_t width, int32_t height, int32_t form, const double *d_a, const double *d_b, int32_t n, const int32_t *d_spp, double eps,
+                        double out4[4]);
 
 // rt_denoise_device on device 0 over DEVICE frames of sums and sums of squares (3 * w * h doubles each) with the uniform sample count
 // `spp` or, if d_spp is not null, a device map of w * h int32: allocates the workspace and the outputs, runs the filter with
